@@ -9,9 +9,11 @@ One "step" = one pass of the hot path over one batch: `--replicates` independent
 `--events` recorded events each, from the single index case (the only initial condition the reference API can
 express), parameters of SURVEY.md §8(d) config 3.  Weak scaling: per-GPU work is fixed, replicates are sharded
 one wavefront each, no data-path collective; the only collective is one RCCL gather of the summary
-trajectories per step.  The JSON line also carries the roofline of the dominant kernel (device time from HIP
-events on the engine's stream) and the CPU baseline (the oracle = op-for-op port of the reference's dense
-algorithm, timed on this host, rank 0, N=1 only).
+trajectories per step.  A plain run sets up, warms up, times the `--steps` steps and prints one JSON line
+(`value`, `ms_per_step`, ...).  `--full` adds the roofline of the dominant kernel (device time from HIP events on
+the engine's stream), the CPU baseline (the oracle = op-for-op port of the reference's dense algorithm, timed on
+this host, rank 0, N=1 only), the tau-leap and config-5 legs and the extra legs.  `--dump-outputs DIR` writes
+what the last timed step computed to DIR/*.npy (see dump_outputs).
 """
 import argparse
 import contextlib
@@ -90,7 +92,7 @@ def cpu_baseline(seconds_target=45.0):
     from oracle import oracle
     oracle.build()
     cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
-    cores = max(1, min(cores, 64))
+    cores = max(1, min(cores, 16))      # at most 16 sampling processes: beyond that they only contend for the node's cores
     # the per-core processes start first (plain interpreters: nothing of this process' GPU state is inherited)
     code = ("import sys; sys.path.insert(0, %r); import bench; "
             "d, t, n = bench.cpu_sample(int(sys.argv[1]), %f); print(d, t)" % (ROOT, seconds_target * 0.6))
@@ -890,6 +892,47 @@ def memory_plan(R, N, T, world, rank, free_bytes, total_bytes):
     return plan
 
 
+DUMP_PART_BYTES = 24 * 2 ** 20       # --dump-outputs: trajectories and event chains each; counters at most 6 MiB: < 64 MB in all
+
+
+def dump_outputs(out_dir, ens, res, world=1, rank=0, seed=2020):
+    """--dump-outputs: what the last timed step handed its caller, as float64 .npy files in `out_dir` (identical from run to run
+    for the same arguments).  `events`, `loop_iterations`, `restarts`: the EnsembleResult counters per replicate; `trajectories`:
+    the summary trajectories [n, T, P, 2] of a fixed seeded sample of replicates (`trajectory_replicates`); `event_chain_<k>`: the
+    (6, n) event chain of replicate chain_replicates[k], the first four of that sample (at most 6 MiB each).  Ranks > 0 of a
+    multi-GPU run write the same names with a _rank<k> suffix."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    R = ens.R
+    order = np.random.default_rng(seed).permutation(R)
+    out = {}
+    keep = np.arange(R) if R <= 2 ** 18 else np.sort(order[:2 ** 18])
+    if len(keep) < R:
+        out["counter_replicates"] = keep
+    out.update(events=res.events[keep], loop_iterations=res.loop_iterations[keep], restarts=res.restarts[keep])
+    if ens.traj_shape is not None:
+        _, T, P, _ = ens.traj_shape
+        per = T * P * 2 * 8
+        picked = np.sort(order[:max(1, min(16, DUMP_PART_BYTES // per))])
+        t_keep = min(T, DUMP_PART_BYTES // (P * 2 * 8))
+        dev = torch.device("cuda", torch.cuda.current_device())
+        traj = ens.trajectories(torch.empty(ens.traj_shape, dtype=torch.float64, device=dev))
+        out["trajectory_replicates"] = picked
+        out["trajectories"] = traj[torch.from_numpy(picked).to(dev), :t_keep].cpu().numpy()
+        del traj
+    else:
+        picked = np.sort(order[:16])
+    chains = picked[:4]
+    out["chain_replicates"] = chains
+    cols = DUMP_PART_BYTES // (len(chains) * 6 * 8)
+    for k, r in enumerate(chains):
+        out["event_chain_%d" % k] = ens.replicate_events(int(r))[:, :cols]
+    suffix = "" if rank == 0 else "_rank%d" % rank
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: start N fresh ranks (torch.distributed.run, one per GPU) as a CHILD
     process and exit with its code.  Nothing in this parent has touched HIP or imported torch, and nothing is re-exec'ed."""
@@ -912,14 +955,22 @@ def main():
     ap.add_argument("--replicates", type=int, default=16384, help="replicates per GPU and step (four per wavefront)")
     ap.add_argument("--events", type=int, default=100000, help="recorded events per replicate and step")
     ap.add_argument("--traj-points", type=int, default=1001)
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float64; a fixed "
+                         "sample of replicates for the trajectories and event chains, under 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline and chain-bound figures, event-log copy-out, libm probe, CPU baselines, "
+                         "the tau-leap (config 4) and config-5 legs and every extra leg (the --no-* options below apply here)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-tau", action="store_true", help="skip the tau-leap (config 4) leg")
+    ap.add_argument("--no-tau", action="store_true", help="with --full: skip the tau-leap (config 4) leg")
     ap.add_argument("--no-tau-warmup-start", action="store_true", help="profiling: leave out tau_leap.warmup_start (6000 tau steps of warm-up: a quarter of a million launches in a trace)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the FAST-mode, spread-occupancy and config-2 legs")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the FAST-mode, spread-occupancy and config-2 legs")
     ap.add_argument("--only", default="", help="development/profiling: run only this extra leg (fast_mode, spread_occupancy, "
                                                "spread_occupancy_fast, config2, genealogy, single_trajectory, direct_config4_shape, config3_general, table3, tau_small, config5, propensity_scan, tau_leap) and print its JSON")
     ap.add_argument("--table3-cells", default="", help="profiling: restrict the table3 leg to these cells, e.g. 10:0.001,100:0.1")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     cells3 = {(int(c.split(":")[0]), float(c.split(":")[1])) for c in a.table3_cells.split(",") if c} or None
 
     # ---- ranks: one process per GPU.  Under a launcher (torch.distributed.run sets WORLD_SIZE) this process is one rank;
@@ -991,9 +1042,27 @@ def main():
     elapsed = time.perf_counter() - t0
     elapsed, total_events = loop.reduce(elapsed, events)
     events_per_rank = loop.per_rank(events)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, ens, res, world=world, rank=rank)
 
     if rank == 0:
         value = total_events / elapsed
+        li = float(res.loop_iterations.sum()) / max(float(res.events.sum()), 1.0)
+        line = {
+            # BASELINE.json's metric string; `value` is its direct-Gillespie leg on config 3, the tau-leap leg (config 4) is the
+            # `tau_leap` object of the same line (--full), the Cython-equivalent CPU path `cpu_baseline` (--full)
+            "metric": "simulated events/sec (direct + tau-leap) at 1/2/4/8 MI355X vs Cython CPU", "value": value, "unit": "events/s",
+            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / max(a.steps, 1),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"value_leg": "direct Gillespie (BASELINE config 3); tau-leap (config 4) in tau_leap",
+                       "workload": "BASELINE config 3: 65536 haplotypes (8 sites) x 64 populations x 1 susceptibility "
+                                   "group, direct Gillespie, bit-exact mode (PCG64 stream, reference summation order), "
+                                   "index-case start, b=2.5 d=0.9 s=0.1 m=0.01/site, total migration 0.01, N=1e7",
+                       "replicates_per_gpu": R, "events_per_replicate": N, "parallelism": "replicates x %d (one process per GPU, %d replicates each, no data-path collective)" % (world, R),
+                       "events_per_rank": events_per_rank,
+                       "trajectory_points": a.traj_points, "loop_iterations_per_event": li},
+        }
+    if rank == 0 and a.full:
         # ---- roofline of the dominant kernel (vgx_direct_kernel), this rank ----
         # Algorithmic bytes per recorded event of THIS engine's layout: the chosen population's
         # occupancy-list stream (16 B/entry, read once and kept in registers), the migration row (8P), the
@@ -1021,21 +1090,8 @@ def main():
         achieved = ev_per_launch * bytes_per_event / launch_s / 1e9
         dense_bytes = H * (84 + 16 * SUS) + 16 * POPS + 48   # the reference's dense layout
         traffic = pmc_traffic("headline", {"replicates_per_gpu": R, "events_per_replicate": N, "trajectory_points": a.traj_points})
-        li = float(res.loop_iterations.sum()) / max(float(res.events.sum()), 1.0)
-        line = {
-            # BASELINE.json's metric string; `value` is its direct-Gillespie leg on config 3, the tau-leap leg (config 4) is the
-            # `tau_leap` object of the same line, the Cython-equivalent CPU path `cpu_baseline`
-            "metric": "simulated events/sec (direct + tau-leap) at 1/2/4/8 MI355X vs Cython CPU", "value": value, "unit": "events/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / max(a.steps, 1),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "libm_probe_match": libm_probe_match(),
-            "config": {"value_leg": "direct Gillespie (BASELINE config 3); tau-leap (config 4) in tau_leap",
-                       "workload": "BASELINE config 3: 65536 haplotypes (8 sites) x 64 populations x 1 susceptibility "
-                                   "group, direct Gillespie, bit-exact mode (PCG64 stream, reference summation order), "
-                                   "index-case start, b=2.5 d=0.9 s=0.1 m=0.01/site, total migration 0.01, N=1e7",
-                       "replicates_per_gpu": R, "events_per_replicate": N, "parallelism": "replicates x %d (one process per GPU, %d replicates each, no data-path collective)" % (world, R),
-                       "events_per_rank": events_per_rank,
-                       "trajectory_points": a.traj_points, "loop_iterations_per_event": li},
+        line["libm_probe_match"] = libm_probe_match()
+        line.update({
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                          # what the memory system really moved (PMC bytes per launch / launch time / peak): `frac` above prices the
@@ -1057,7 +1113,7 @@ def main():
                             "achieved": ev_per_launch * (1.5 * nocc_w + 2.0 * POPS) / launch_s, "peak": CHAIN_STEPS_PER_S * 4,
                             "unit": "chain steps/s", "frac": ev_per_launch * (1.5 * nocc_w + 2.0 * POPS) / launch_s / (CHAIN_STEPS_PER_S * 4),
                             "chains_per_instruction": 4},
-        }
+        })
         # event log: resident in HBM per replicate (28 B/event); D2H through vgx_get_events on a sample
         t_d = time.perf_counter()
         nrep = min(R, 32)
@@ -1077,7 +1133,7 @@ def main():
     torch.cuda.empty_cache()
     # tau-leaping leg (BASELINE config 4): one independent replicate per GPU (replicas only, no collective on the path)
     tau = None
-    if not a.no_tau:
+    if a.full and not a.no_tau:
         try:
             tau = tau_leg(local, seed=2020 + rank, cpu=(rank == 0 and world == 1 and not a.no_cpu_baseline), warm=(world == 1 and not a.no_tau_warmup_start))
         except Exception as ex:  # never lose the headline line
@@ -1097,14 +1153,14 @@ def main():
                 tau["unit"] = "events/s (device time, %d replicas)" % world
                 tau.pop("roofline", None)
     c5 = None
-    if not a.no_extra:
+    if a.full and not a.no_extra:
         try:
             c5 = config5_leg(local, world=world, rank=rank)
         except Exception as ex:
             c5 = {"error": repr(ex)}
             if world > 1:
                 raise      # a rank that leaves a collective alone would hang the others: fail the run visibly
-    if rank == 0:
+    if rank == 0 and a.full:
         if c5 is not None:
             line["config5"] = c5
         if tau is not None:
@@ -1150,6 +1206,7 @@ def main():
             "propensity_scan_roofline_frac": pick(line, "propensity_scan", "roofline", "frac"),
             "cpu_baseline_events_per_s": pick(line, "cpu_baseline", "value"),
         }
+    if rank == 0:
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -8,7 +8,7 @@ TAG=${TAG:-r04}
 O=gpurun_out/prof_$TAG
 mkdir -p $O
 run() { name=$1; shift; echo "== $name" ; "$@" > $O/$name.log 2>&1; echo "   rc=$?"; find $O/$name -name "*kernel_trace.csv" -delete 2>/dev/null; }   # (gpurun copies back at most 64 MiB)
-HEAD="--no-cpu-baseline --no-tau --no-extra --steps 3 --warmup 1"
+HEAD="--full --no-cpu-baseline --no-tau --no-extra --steps 3 --warmup 1"
 LEGS=${LEGS:-"table3 single_trajectory tau_leap config3_general propensity_scan spread_occupancy tau_small"}
 if [ -z "${SKIP_HEAD:-}" ]; then
 run headline_stats rocprofv3 --kernel-trace --stats --output-format csv -d $O/headline_stats -- python3 bench.py $HEAD

@@ -86,7 +86,7 @@ except Exception:
 direct["source"] = ("rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE; raw rows in profiles/<round>_*_pmc_*.csv (each leg's entry names its round); "
                     "earlier rounds' values in git history")
 direct["correction"] = CORR
-HEAD = "python3 bench.py --no-cpu-baseline --no-tau --no-extra --steps 3 --warmup 1"
+HEAD = "python3 bench.py --full --no-cpu-baseline --no-tau --no-extra --steps 3 --warmup 1"
 for leg, kernel, cmd, cfg in (
         ("headline", "vgx_quad_kernel", HEAD, {"replicates_per_gpu": 16384, "events_per_replicate": 100000, "trajectory_points": 1001}),
         ("spread_occupancy", "vgx_quad_long_kernel", "python3 bench.py --only spread_occupancy",
