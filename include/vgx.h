@@ -241,6 +241,43 @@ int vgx_get_genealogy(vgx_genealogy_io *io, char *errbuf, int64_t errcap);
  * self.seed stands when GetGenealogy(seed=None) continues the simulation's stream (pyx:766-767). */
 void vgx_rng_position(int64_t seed, int64_t attempt, int64_t draws, uint64_t out[4]);
 
+/* The same backward pass for many replicates of the last vgx_simulate_direct call at once, on the device: one walk per
+ * replicate over the device event log in place (the log is not copied to the host), started from the replicate's final
+ * state; event times from the host clock (the times vgx_get_events gives).  For every selected replicate the result is
+ * what vgx_get_genealogy returns on that replicate's chain, state and start position: tree, tree_pop, times, the
+ * mutation and migration records, nodes_used and the final generator state.  Direct chains only (refused after
+ * vgx_simulate_tau or a call without an event log); every selected replicate's chain must start at log index 0
+ * (vgx_counters.ev_first_new == 0).  Two calls:
+ *   1. sizing: tree == NULL.  Fills node_off, mut_off, mig_off [n+1] with the capacities the walk needs, as offsets into
+ *      the concatenated outputs (2 sCounter - 1 nodes, or 0 when fewer than two cases were sampled; the log's MUTATION
+ *      events; its MIGRATION events + the nodes), counted on the device.
+ *   2. walk: the caller allocates the outputs by those offsets and calls again.  Outputs of replicate i start at its
+ *      offsets; status[i] = 0 or the reason its walk stopped (vgx_genealogy_message gives the text vgx_get_genealogy
+ *      reports for it); a failed replicate does not fail the call.
+ * Replicates whose workspace exceeds half of the free device memory (or VGX_GENEALOGY_CHUNK_BYTES) are walked in several
+ * passes. */
+typedef struct vgx_genealogies_io {
+    int64_t n;                               /* selected replicates */
+    const int64_t *replicates;               /* [n] */
+    const uint64_t *rng_state;               /* [n][4] PCG64 start: state hi, lo, increment hi, lo (walk call) */
+    int64_t *node_off, *mut_off, *mig_off;   /* [n+1] written by the sizing call, read by the walk call */
+    int64_t *tree, *tree_pop; double *times;                         /* [node_off[n]] */
+    int64_t *mut_node, *mut_AS, *mut_DS, *mut_site; double *mut_time; /* [mut_off[n]] */
+    int64_t *mig_node, *mig_old, *mig_new; double *mig_time;         /* [mig_off[n]] */
+    int64_t *status, *status_arg, *nodes_used, *mut_n, *mig_n;       /* [n] */
+    uint64_t *rng_out;                       /* [n][4] generator state after the walk */
+    int64_t layout;                          /* 0 = one replicate per lane (default), 1 = one replicate per wavefront */
+    int64_t passes;                          /* out: device passes the walk took */
+    double ms[3];                            /* out: walk kernels (device time), host clock and output conversion, whole call */
+} vgx_genealogies_io;
+int vgx_get_genealogies(vgx_engine *e, vgx_genealogies_io *io);
+/* Text of a walk status (vgx_genealogies_io.status, .status_arg) as vgx_get_genealogy reports the same condition; returns
+ * the status. */
+int vgx_genealogy_message(int64_t status, int64_t arg, char *errbuf, int64_t errcap);
+/* Test hook: the walk of vgx_get_genealogies (same code, compiled for the host) on the chain, state and generator of a
+ * vgx_genealogy_io; same outputs as vgx_get_genealogy.  Direct chains only: a MULTITYPE event with rows is refused. */
+int vgx_test_genealogy_walk(vgx_genealogy_io *io, char *errbuf, int64_t errcap);
+
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* Device time of the last simulate call's kernels, from HIP events on the engine's stream (ms). */
 double vgx_last_kernel_ms(const vgx_engine *e);

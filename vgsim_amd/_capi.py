@@ -63,6 +63,16 @@ class VgxGenealogyIO(C.Structure):
                 ("mig_time", _F), ("nodes_used", C.c_int64)]
 
 
+class VgxGenealogiesIO(C.Structure):
+    _fields_ = [("n", C.c_int64), ("replicates", _I), ("rng_state", C.POINTER(C.c_uint64)),
+                ("node_off", _I), ("mut_off", _I), ("mig_off", _I),
+                ("tree", _I), ("tree_pop", _I), ("times", _F),
+                ("mut_node", _I), ("mut_AS", _I), ("mut_DS", _I), ("mut_site", _I), ("mut_time", _F),
+                ("mig_node", _I), ("mig_old", _I), ("mig_new", _I), ("mig_time", _F),
+                ("status", _I), ("status_arg", _I), ("nodes_used", _I), ("mut_n", _I), ("mig_n", _I),
+                ("rng_out", C.POINTER(C.c_uint64)), ("layout", C.c_int64), ("passes", C.c_int64), ("ms", C.c_double * 3)]
+
+
 class VgxRowScan(C.Structure):
     _fields_ = [("rows", C.c_int64), ("H", C.c_int64), ("S", C.c_int64), ("infectious", _I), ("eventRates123", _F),
                 ("numToHap", _I), ("bRate", _F), ("susceptibility", _F), ("rowSusceptible", _F), ("rowContact", _F), ("u", _F),
@@ -102,6 +112,9 @@ SIGNATURES = {
     "vgx_get_profile": (C.c_int, [_H, C.c_int64, _I]),
     "vgx_get_list_counts_quad": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32), _I]),
     "vgx_get_genealogy": (C.c_int, [C.POINTER(VgxGenealogyIO), C.c_char_p, C.c_int64]),
+    "vgx_get_genealogies": (C.c_int, [_H, C.POINTER(VgxGenealogiesIO)]),
+    "vgx_genealogy_message": (C.c_int, [C.c_int64, C.c_int64, C.c_char_p, C.c_int64]),
+    "vgx_test_genealogy_walk": (C.c_int, [C.POINTER(VgxGenealogyIO), C.c_char_p, C.c_int64]),
     "vgx_rng_position": (None, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64 * 4)]),
     "vgx_propensity_scan": (C.c_int, [C.POINTER(VgxRowScan)]),
     "vgx_propensity_scan_bench": (C.c_int, [C.POINTER(VgxRowScan), C.c_int64, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -416,6 +429,23 @@ def get_genealogy(m, seed=None, rng_position=None, rng_raw=None):
     (``RndmWrapper(seed=(seed, 0))``, pyx:766-767); ``None`` continues from ``rng_position`` = (attempt, draws) of the
     simulation's stream, or from ``rng_raw`` = the raw generator state a previous pass returned (``out["rng_raw"]``).
     Walks ``m.infectious`` back in place; returns a dict of arrays."""
+    return _genealogy("vgx_get_genealogy", m, seed, rng_position, rng_raw)
+
+
+def genealogy_walk(m, seed=None, rng_position=None, rng_raw=None):
+    """``get_genealogy`` through ``vgx_test_genealogy_walk``: the walk of the device pass (vgx_gwalk.h) compiled for the
+    host, on the same arguments (direct chains only).  Same dict, same exceptions."""
+    return _genealogy("vgx_test_genealogy_walk", m, seed, rng_position, rng_raw)
+
+
+def genealogy_message(status, arg):
+    """The text ``vgx_get_genealogy`` reports for a walk status of ``vgx_get_genealogies``."""
+    buf = C.create_string_buffer(512)
+    load_library().vgx_genealogy_message(int(status), int(arg), buf, 512)
+    return buf.value.decode()
+
+
+def _genealogy(entry, m, seed, rng_position, rng_raw):
     lib = load_library()
     ev, mv = m.events, m.multievents
     io = VgxGenealogyIO()
@@ -461,9 +491,9 @@ def get_genealogy(m, seed=None, rng_position=None, rng_raw=None):
     out["mig_time"] = np.zeros(io.mig_cap)
     io.mig_time = _p(out["mig_time"])
     err = C.create_string_buffer(512)
-    rc = lib.vgx_get_genealogy(C.byref(io), err, 512)
+    rc = getattr(lib, entry)(C.byref(io), err, 512)
     if rc != 0:
-        raise RuntimeError(err.value.decode() or "vgx_get_genealogy failed (%d)" % rc)
+        raise RuntimeError(err.value.decode() or "%s failed (%d)" % (entry, rc))
     for k in list(out):
         if k.startswith("mut_"):
             out[k] = out[k][:io.mut_n]

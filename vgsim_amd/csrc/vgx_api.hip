@@ -23,6 +23,7 @@
 #include "vgx_solo.h"
 #include "vgx_lone.h"
 #include "vgx_rng.h"
+#include "vgx_gwalk.h"
 
 // launchers defined next to their kernels (vgx_direct.hip)
 extern "C" hipError_t vgxi_launch_direct(const VgxDirectArgs *a, size_t lds, hipStream_t stream);
@@ -42,6 +43,9 @@ extern "C" hipError_t vgxi_launch_taus(const VgxTausArgs *a, hipStream_t s);
 extern "C" hipError_t vgxi_launch_quadg(const VgxDirectArgs *a, const VgxQuadgArgs *qa, hipStream_t stream);
 extern "C" hipError_t vgxi_launch_solo(const VgxDirectArgs *a, const VgxSoloArgs *sa, int clock, hipStream_t stream);
 extern "C" hipError_t vgxi_launch_lone(const VgxDirectArgs *a, const VgxLoneArgs *la, int clock, hipStream_t stream);
+extern "C" hipError_t vgxi_gw_count(const int32_t *log, int64_t evcap, const int64_t *reps, const int64_t *n_ev, int64_t n, int64_t *out,
+                                    hipStream_t s);
+extern "C" hipError_t vgxi_gw_walk(const VgxGwLaunch *a, int wave, hipStream_t s);
 extern "C" hipError_t vgxi_launch_counts32(const int64_t *c64, int32_t *c32, int64_t n, hipStream_t stream);
 extern "C" hipError_t vgxi_launch_init_reps(const VgxDevRep *r, int P, int S, int64_t R, const int32_t *s_nocc,
                                             const int32_t *s_hap, const int32_t *s_cls, const int64_t *s_cnt,
@@ -2354,9 +2358,16 @@ struct ClockRun {      // accumulates one attempt's clock
     }
 };
 
-static int host_clock(vgx_engine *e, int64_t rep) {
-    vgx_engine::HostClock &hc = e->hc;
-    if (hc.rep == rep) return VGX_OK;
+// The clock of replicate `rep` into `hc` (re-entrant: reads the engine only; a failure's message goes to `err`).
+#define CLOCKCHECK(call)                                                                               \
+    do {                                                                                               \
+        hipError_t err__ = (call);                                                                     \
+        if (err__ != hipSuccess) {                                                                     \
+            err = std::string(#call) + ": " + hipGetErrorString(err__);                                \
+            return VGX_ERR_HIP;                                                                        \
+        }                                                                                              \
+    } while (0)
+static int clock_build(const vgx_engine *e, int64_t rep, vgx_engine::HostClock &hc, std::string &err) {
     const VgxRepScalars &s = e->sc_host[(size_t)rep];
     hc.rep = -1;
     hc.times.clear();
@@ -2369,8 +2380,8 @@ static int host_clock(vgx_engine *e, int64_t rep) {
     std::vector<double> loc_dev((size_t)nloc);
     std::vector<int64_t> loc_key((size_t)nloc);
     if (nloc > 0) {
-        HIPCHECK(e, hipMemcpy(loc_dev.data(), (double *)e->r_loctime.p + rep * e->loc_cap, (size_t)nloc * 8, hipMemcpyDeviceToHost));
-        HIPCHECK(e, hipMemcpy(loc_key.data(), (int64_t *)e->r_lociter.p + rep * e->loc_cap, (size_t)nloc * 8, hipMemcpyDeviceToHost));
+        CLOCKCHECK(hipMemcpy(loc_dev.data(), (double *)e->r_loctime.p + rep * e->loc_cap, (size_t)nloc * 8, hipMemcpyDeviceToHost));
+        CLOCKCHECK(hipMemcpy(loc_key.data(), (int64_t *)e->r_lociter.p + rep * e->loc_cap, (size_t)nloc * 8, hipMemcpyDeviceToHost));
     }
     hc.loc_times = loc_dev;
     hc.final_time = s.currentTime;
@@ -2390,8 +2401,8 @@ static int host_clock(vgx_engine *e, int64_t rep) {
     if (nfa > 0) {
         std::vector<double> fr((size_t)nfa);
         std::vector<int64_t> fk((size_t)nfa);
-        HIPCHECK(e, hipMemcpy(fr.data(), (double *)e->r_farate.p + rep * e->fa_cap, (size_t)nfa * 8, hipMemcpyDeviceToHost));
-        HIPCHECK(e, hipMemcpy(fk.data(), (int64_t *)e->r_fakey.p + rep * e->fa_cap, (size_t)nfa * 8, hipMemcpyDeviceToHost));
+        CLOCKCHECK(hipMemcpy(fr.data(), (double *)e->r_farate.p + rep * e->fa_cap, (size_t)nfa * 8, hipMemcpyDeviceToHost));
+        CLOCKCHECK(hipMemcpy(fk.data(), (int64_t *)e->r_fakey.p + rep * e->fa_cap, (size_t)nfa * 8, hipMemcpyDeviceToHost));
         int64_t k = 0;
         while (k < nfa) {
             const int64_t att = fk[(size_t)k] >> 40;
@@ -2412,12 +2423,12 @@ static int host_clock(vgx_engine *e, int64_t rep) {
         hc.final_time = 0.0;
     } else {
         const int64_t slot0 = hc.e0 - e->ev_base;
-        if (slot0 < 0 || slot0 + n > e->evcap) return fail(e, VGX_ERR_ARG, "host_clock: event range outside the device log");
+        if (slot0 < 0 || slot0 + n > e->evcap) { err = "host_clock: event range outside the device log"; return VGX_ERR_ARG; }
         std::vector<double> rate((size_t)n);
         std::vector<int32_t> cols((size_t)n * VGX_EV_COLS);
         if (n > 0) {
-            HIPCHECK(e, hipMemcpy(rate.data(), (double *)e->r_evrate.p + rep * e->evcap + slot0, (size_t)n * 8, hipMemcpyDeviceToHost));
-            HIPCHECK(e, hipMemcpy(cols.data(), (int32_t *)e->r_evcols.p + (rep * e->evcap + slot0) * VGX_EV_COLS,
+            CLOCKCHECK(hipMemcpy(rate.data(), (double *)e->r_evrate.p + rep * e->evcap + slot0, (size_t)n * 8, hipMemcpyDeviceToHost));
+            CLOCKCHECK(hipMemcpy(cols.data(), (int32_t *)e->r_evcols.p + (rep * e->evcap + slot0) * VGX_EV_COLS,
                                   (size_t)n * VGX_EV_COLS * 4, hipMemcpyDeviceToHost));
         }
         ClockRun c;
@@ -2453,10 +2464,22 @@ static int host_clock(vgx_engine *e, int64_t rep) {
         // the mismatch is kept for vgx_clock_mismatches().
         if (e->call_has_tlimit && (!limit_ok || ((s.currentTime < e->call_tlimit) != (hc.final_time < e->call_tlimit)))) {
             hc.limit_mismatch = true;
-            e->clock_mismatches += 1;
         }
     }
     hc.rep = rep;
+    return VGX_OK;
+}
+#undef CLOCKCHECK
+
+// the clock of one replicate, cached in e->hc (the getters of one replicate call it one after another)
+static int host_clock(vgx_engine *e, int64_t rep) {
+    vgx_engine::HostClock &hc = e->hc;
+    if (hc.rep == rep) return VGX_OK;
+    hc.rep = -1;
+    std::string err;
+    const int rc = clock_build(e, rep, hc, err);
+    if (rc) return fail(e, rc, err);
+    if (hc.limit_mismatch) e->clock_mismatches += 1;
     return VGX_OK;
 }
 
@@ -2742,5 +2765,218 @@ extern "C" int vgx_get_profile(vgx_engine *e, int64_t replicate, int64_t *out16)
     if (!e || !out16 || replicate < 0 || replicate >= e->R || !e->r_prof.p) return VGX_ERR_ARG;
     HIPCHECK(e, hipSetDevice(e->device));
     HIPCHECK(e, hipMemcpy(out16, (unsigned long long *)e->r_prof.p + replicate * VGX_PROF_SLOTS, VGX_PROF_SLOTS * 8, hipMemcpyDeviceToHost));
+    return VGX_OK;
+}
+
+// ---- backward pass of many replicates on the device (vgx_genealogies.hip, vgx_gwalk.h) -------------------------------------
+extern "C" int vgx_get_genealogies(vgx_engine *e, vgx_genealogies_io *io) {
+    if (!e || !io || io->n < 0 || (io->n > 0 && (!io->replicates || !io->node_off || !io->mut_off || !io->mig_off)))
+        return VGX_ERR_ARG;
+    const auto t_call = std::chrono::steady_clock::now();
+    io->passes = 0;
+    io->ms[0] = io->ms[1] = io->ms[2] = 0.0;
+    if (!e->sc_host_valid || !e->dev_state_valid) return fail(e, VGX_ERR_ARG, "vgx_get_genealogies: no direct simulate call yet");
+    if (e->last_was_tau) return fail(e, VGX_ERR_ARG, "vgx_get_genealogies: the last call was vgx_simulate_tau (direct chains only)");
+    if (!e->call_recorded) return fail(e, VGX_ERR_ARG, "vgx_get_genealogies: the last call did not record events");
+    const int64_t n = io->n, P = e->d.popNum, H = e->d.hapNum;
+    std::vector<int64_t> n_ev((size_t)n), sC((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t r = io->replicates[i];
+        if (r < 0 || r >= e->R) return fail(e, VGX_ERR_ARG, "vgx_get_genealogies: replicate index out of range");
+        const VgxRepScalars &s = e->sc_host[(size_t)r];
+        const int64_t first = s.restarts > 0 ? 0 : ((size_t)r < e->call_ev0.size() ? e->call_ev0[(size_t)r] : e->ev_ptr0);
+        if (first != 0 || e->ev_base != 0)
+            return fail(e, VGX_ERR_ARG, "vgx_get_genealogies: the chain of replicate " + std::to_string(r) +
+                                            " does not start in the last call's device log (events.ptr was not 0 at its start)");
+        if (s.ev_ptr < 0 || s.ev_ptr > e->evcap || s.ev_ptr >= ((int64_t)1 << 30))
+            return fail(e, VGX_ERR_ARG, "vgx_get_genealogies: event range of replicate " + std::to_string(r) + " outside the device log");
+        n_ev[(size_t)i] = s.ev_ptr;
+        sC[(size_t)i] = s.sCounter;
+    }
+    if (n == 0) return VGX_OK;
+    HIPCHECK(e, hipSetDevice(e->device));
+    const int32_t *log = (const int32_t *)e->r_evcols.p;
+
+    if (!io->tree) {   // sizing: the log's MUTATION / MIGRATION events, counted on the device
+        int64_t *d_rep = nullptr, *d_n = nullptr, *d_out = nullptr;
+        std::vector<int64_t> cnt((size_t)n * 2);
+        hipError_t er = hipMalloc(&d_rep, (size_t)n * 8 * 4);
+        if (er != hipSuccess) return fail(e, VGX_ERR_HIP, std::string("vgx_get_genealogies: hipMalloc: ") + hipGetErrorString(er));
+        d_n = d_rep + n;
+        d_out = d_rep + 2 * n;
+        er = hipMemcpy(d_rep, io->replicates, (size_t)n * 8, hipMemcpyHostToDevice);
+        if (er == hipSuccess) er = hipMemcpy(d_n, n_ev.data(), (size_t)n * 8, hipMemcpyHostToDevice);
+        if (er == hipSuccess) er = vgxi_gw_count(log, e->evcap, d_rep, d_n, n, d_out, e->stream);
+        if (er == hipSuccess) er = hipStreamSynchronize(e->stream);
+        if (er == hipSuccess) er = hipMemcpy(cnt.data(), d_out, (size_t)n * 16, hipMemcpyDeviceToHost);
+        (void)hipFree(d_rep);
+        if (er != hipSuccess) return fail(e, VGX_ERR_HIP, std::string("vgx_get_genealogies: counting pass: ") + hipGetErrorString(er));
+        io->node_off[0] = io->mut_off[0] = io->mig_off[0] = 0;
+        for (int64_t i = 0; i < n; i++) {
+            const int64_t nodes = sC[(size_t)i] >= 2 ? 2 * sC[(size_t)i] - 1 : 0;
+            io->node_off[i + 1] = io->node_off[i] + nodes;
+            io->mut_off[i + 1] = io->mut_off[i] + cnt[(size_t)(2 * i)];
+            io->mig_off[i + 1] = io->mig_off[i] + cnt[(size_t)(2 * i + 1)] + nodes;
+        }
+        io->ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+        return VGX_OK;
+    }
+
+    if (!io->rng_state || !io->tree_pop || !io->times || !io->status || !io->status_arg || !io->nodes_used || !io->mut_n || !io->mig_n ||
+        !io->rng_out || (io->mut_off[n] > 0 && (!io->mut_node || !io->mut_AS || !io->mut_DS || !io->mut_site || !io->mut_time)) ||
+        (io->mig_off[n] > 0 && (!io->mig_node || !io->mig_old || !io->mig_new || !io->mig_time)))
+        return fail(e, VGX_ERR_ARG, "vgx_get_genealogies: null output");
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t nodes = sC[(size_t)i] >= 2 ? 2 * sC[(size_t)i] - 1 : 0;
+        if (io->node_off[i + 1] - io->node_off[i] < nodes || io->mut_off[i + 1] < io->mut_off[i] || io->mig_off[i + 1] < io->mig_off[i])
+            return fail(e, VGX_ERR_ARG, "vgx_get_genealogies: output capacities smaller than the sizing call gave");
+    }
+    // the walk reads the 8-byte counts of the final occupancy lists
+    if (!e->counts64_valid) {
+        HIPCHECK(e, vgxi_launch_counts64(e->dr.lcnt32, e->dr.lcnt, e->R * P * e->cap, e->stream));
+        HIPCHECK(e, hipStreamSynchronize(e->stream));
+        e->counts64_valid = true;
+    }
+    // per-replicate workspace and outputs (elements), and the passes: every pass holds at most `share` bytes
+    std::vector<VgxGwDesc> desc((size_t)n);
+    std::vector<int64_t> bytes((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        VgxGwDesc &d = desc[(size_t)i];
+        d.rep = io->replicates[i];
+        d.n_ev = n_ev[(size_t)i];
+        d.sCounter = sC[(size_t)i];
+        d.tsize = d.sCounter >= 2 ? vgx_gw_table_size(d.n_ev, P * H) : 0;
+        d.arena_cap = d.sCounter >= 2 ? d.n_ev : 0;
+        d.mut_cap = io->mut_off[i + 1] - io->mut_off[i];
+        d.mig_cap = io->mig_off[i + 1] - io->mig_off[i];
+        for (int k = 0; k < 4; k++) d.rng[k] = io->rng_state[i * 4 + k];
+        const int64_t nodes = d.sCounter >= 2 ? 2 * d.sCounter - 1 : 0;
+        bytes[(size_t)i] = d.tsize * 28 + d.arena_cap * 4 + nodes * 12 + d.mut_cap * 20 + d.mig_cap * 16 + (int64_t)sizeof(VgxGwDesc) + 72;
+    }
+    size_t free_b = 0, total_b = 0;
+    HIPCHECK(e, hipMemGetInfo(&free_b, &total_b));
+    int64_t share = (int64_t)(free_b / 2);
+    if (const char *cb = getenv("VGX_GENEALOGY_CHUNK_BYTES")) share = std::min<int64_t>(share, std::max<int64_t>(atoll(cb), 1));
+    const bool wave = io->layout == 1;
+    std::vector<int64_t> mism((size_t)n, 0);
+    int64_t i0 = 0;
+    while (i0 < n) {
+        int64_t i1 = i0, sum = 0;
+        while (i1 < n && (i1 == i0 || sum + bytes[(size_t)i1] <= share)) sum += bytes[(size_t)i1++];
+        const int64_t m = i1 - i0;
+        // offsets of this pass (element counts relative to the pass)
+        int64_t T = 0, A = 0, N = 0, M = 0, G = 0;
+        std::vector<VgxGwDesc> dp(desc.begin() + i0, desc.begin() + i1);
+        for (int64_t j = 0; j < m; j++) {
+            VgxGwDesc &d = dp[(size_t)j];
+            d.tab_off = T; d.arena_off = A; d.node_off = N; d.mut_off = M; d.mig_off = G;
+            T += d.tsize; A += d.arena_cap; N += d.sCounter >= 2 ? 2 * d.sCounter - 1 : 0; M += d.mut_cap; G += d.mig_cap;
+        }
+        // one allocation: [desc | res | rng | key | cnt | base | len | lcap | arena | node x3 | mut x5 | mig x4]
+        auto up8 = [](int64_t b) { return (b + 255) / 256 * 256; };
+        const int64_t o_desc = 0, o_res = o_desc + up8(m * (int64_t)sizeof(VgxGwDesc)), o_rng = o_res + up8(m * 40),
+                      o_key = o_rng + up8(m * 32), o_cnt = o_key + up8(T * 8), o_base = o_cnt + up8(T * 8), o_len = o_base + up8(T * 4),
+                      o_lcap = o_len + up8(T * 4), o_arena = o_lcap + up8(T * 4), o_out = o_arena + up8(A * 4),
+                      out_bytes = up8((3 * N + 5 * M + 4 * G) * 4), total = o_out + out_bytes;
+        char *ws = nullptr;
+        hipError_t er = hipMalloc((void **)&ws, (size_t)total);
+        if (er != hipSuccess)
+            return fail(e, VGX_ERR_HIP, "vgx_get_genealogies: hipMalloc of " + std::to_string(total) + " bytes: " + hipGetErrorString(er));
+        std::unique_ptr<char, void (*)(char *)> hold(ws, [](char *p) { (void)hipFree(p); });
+        VgxGwLaunch a{};
+        a.n = m;
+        a.desc = (const VgxGwDesc *)(ws + o_desc);
+        a.log = log; a.evcap = e->evcap;
+        a.nocc = e->dr.nocc; a.lhap = e->dr.lhap; a.lcnt = e->dr.lcnt;
+        a.P = P; a.H = H; a.cap = e->cap;
+        a.key = (int64_t *)(ws + o_key); a.cnt = (int64_t *)(ws + o_cnt);
+        a.base = (int32_t *)(ws + o_base); a.len = (int32_t *)(ws + o_len); a.lcap = (int32_t *)(ws + o_lcap);
+        a.arena = (int32_t *)(ws + o_arena);
+        int32_t *o32 = (int32_t *)(ws + o_out);
+        a.tree = o32; a.tree_pop = o32 + N; a.node_ev = o32 + 2 * N;
+        int32_t *mu = o32 + 3 * N;
+        a.mut_node = mu; a.mut_AS = mu + M; a.mut_DS = mu + 2 * M; a.mut_site = mu + 3 * M; a.mut_ev = mu + 4 * M;
+        int32_t *mg = mu + 5 * M;
+        a.mig_node = mg; a.mig_old = mg + G; a.mig_new = mg + 2 * G; a.mig_ev = mg + 3 * G;
+        a.res = (int64_t *)(ws + o_res);
+        a.rng_out = (uint64_t *)(ws + o_rng);
+        HIPCHECK(e, hipMemcpyAsync(ws + o_desc, dp.data(), (size_t)m * sizeof(VgxGwDesc), hipMemcpyHostToDevice, e->stream));
+        if (T > 0) HIPCHECK(e, hipMemsetAsync(a.key, 0xFF, (size_t)T * 8, e->stream));   // every slot empty (-1)
+        HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
+        HIPCHECK(e, vgxi_gw_walk(&a, wave ? 1 : 0, e->stream));
+        HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
+        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)
+            return fail(e, VGX_ERR_HIP, std::string("vgx_get_genealogies: walk kernel failed: ") + hipGetErrorString(er));
+        float kms = 0.f;
+        HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
+        io->ms[0] += kms;
+        std::vector<int64_t> res((size_t)m * 5);
+        std::vector<uint64_t> rng((size_t)m * 4);
+        std::vector<int32_t> out((size_t)(3 * N + 5 * M + 4 * G));
+        HIPCHECK(e, hipMemcpy(res.data(), a.res, (size_t)m * 40, hipMemcpyDeviceToHost));
+        HIPCHECK(e, hipMemcpy(rng.data(), a.rng_out, (size_t)m * 32, hipMemcpyDeviceToHost));
+        if (!out.empty()) HIPCHECK(e, hipMemcpy(out.data(), o32, out.size() * 4, hipMemcpyDeviceToHost));
+        hold.reset();
+        // event indices -> times through every replicate's host clock (re-entrant form, one replicate per thread at a time)
+        const auto t_clock = std::chrono::steady_clock::now();
+        const int32_t *h_tree = out.data(), *h_pop = h_tree + N, *h_nev = h_tree + 2 * N, *h_mu = h_tree + 3 * N, *h_mg = h_mu + 5 * M;
+        std::vector<std::string> errs((size_t)m);
+        std::vector<int> rcs((size_t)m, 0);
+        int64_t work = 0;
+        for (int64_t j = 0; j < m; j++) work += dp[(size_t)j].n_ev;
+        for_parts(m, [&](int64_t j0, int64_t j1, unsigned) {
+            if (hipSetDevice(e->device) != hipSuccess) { for (int64_t j = j0; j < j1; j++) { rcs[(size_t)j] = VGX_ERR_HIP; errs[(size_t)j] = "hipSetDevice"; } return; }
+            vgx_engine::HostClock hc;
+            for (int64_t j = j0; j < j1; j++) {
+                const VgxGwDesc &d = dp[(size_t)j];
+                const int64_t gi = i0 + j;
+                int rc = clock_build(e, d.rep, hc, errs[(size_t)j]);
+                if (rc) { rcs[(size_t)j] = rc; continue; }
+                mism[(size_t)gi] = hc.limit_mismatch ? 1 : 0;
+                const int64_t *r5 = res.data() + j * 5;
+                io->status[gi] = r5[0]; io->status_arg[gi] = r5[1]; io->nodes_used[gi] = r5[2];
+                io->mut_n[gi] = r5[0] == VGX_GW_OK ? r5[3] : 0;
+                io->mig_n[gi] = r5[0] == VGX_GW_OK ? r5[4] : 0;
+                for (int k = 0; k < 4; k++) io->rng_out[gi * 4 + k] = rng[(size_t)(j * 4 + k)];
+                if (r5[0] != VGX_GW_OK) continue;
+                auto time_of = [&](int32_t ev, double &t) {
+                    if (ev < 0) { t = 0.0; return true; }
+                    const int64_t k = (int64_t)ev - hc.e0;
+                    if (k < 0 || k >= (int64_t)hc.times.size()) return false;
+                    t = hc.times[(size_t)k];
+                    return true;
+                };
+                bool ok = true;
+                const int64_t nodes = 2 * d.sCounter - 1, no = io->node_off[gi];
+                for (int64_t k = 0; k < nodes; k++) {
+                    io->tree[no + k] = h_tree[d.node_off + k];
+                    io->tree_pop[no + k] = h_pop[d.node_off + k];
+                    ok &= time_of(h_nev[d.node_off + k], io->times[no + k]);
+                }
+                const int64_t mo = io->mut_off[gi];
+                for (int64_t k = 0; k < r5[3]; k++) {
+                    const int64_t q = d.mut_off + k;
+                    io->mut_node[mo + k] = h_mu[q]; io->mut_AS[mo + k] = h_mu[M + q]; io->mut_DS[mo + k] = h_mu[2 * M + q];
+                    io->mut_site[mo + k] = h_mu[3 * M + q];
+                    ok &= time_of(h_mu[4 * M + q], io->mut_time[mo + k]);
+                }
+                const int64_t go = io->mig_off[gi];
+                for (int64_t k = 0; k < r5[4]; k++) {
+                    const int64_t q = d.mig_off + k;
+                    io->mig_node[go + k] = h_mg[q]; io->mig_old[go + k] = h_mg[G + q]; io->mig_new[go + k] = h_mg[2 * G + q];
+                    ok &= time_of(h_mg[3 * G + q], io->mig_time[go + k]);
+                }
+                if (!ok) { rcs[(size_t)j] = VGX_ERR_ARG; errs[(size_t)j] = "vgx_get_genealogies: an event index outside the host clock's range"; }
+            }
+        }, std::max<int64_t>(work / std::max<int64_t>(m, 1), 1) * 64);
+        for (int64_t j = 0; j < m; j++)
+            if (rcs[(size_t)j]) return fail(e, rcs[(size_t)j], errs[(size_t)j]);
+        io->ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_clock).count();
+        io->passes += 1;
+        i0 = i1;
+    }
+    // every replicate's clock was built once, as when the replicates are fetched one by one
+    for (int64_t i = 0; i < n; i++) e->clock_mismatches += mism[(size_t)i];
+    io->ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
     return VGX_OK;
 }

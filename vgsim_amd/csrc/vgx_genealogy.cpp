@@ -12,11 +12,13 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "../../include/vgx.h"
+#include "vgx_gwalk.h"
 #include "vgx_logfact.h"
 #include "vgx_rng.h"
 
@@ -375,4 +377,94 @@ extern "C" void vgx_rng_position(int64_t seed, int64_t attempt, int64_t draws, u
     vgx_mul128(acc_mh, acc_ml, g.sh, g.sl, sh, sl);
     vgx_add128(sh, sl, acc_ph, acc_pl);
     out[0] = sh; out[1] = sl; out[2] = g.ih; out[3] = g.il;
+}
+
+// ---- the shared walk (vgx_gwalk.h) ---------------------------------------------------------------------------------------
+// What vgx_get_genealogy reports for each walk status (the device pass's statuses become the host pass's messages).
+static std::string walk_message(int64_t status, int64_t arg) {
+    switch (status) {
+    case VGX_GW_OK: return "";
+    case VGX_GW_FEW_SAMPLES: return "Less than two cases were sampled...";
+    case VGX_GW_EXTRA_SAMPLING: return "vgx_get_genealogy: more sampling events than sCounter";
+    case VGX_GW_TREE_OVERFLOW: return "vgx_get_genealogy: tree overflow (event log and sCounter disagree)";
+    case VGX_GW_NOT_COALESCED: return "vgx_get_genealogy: lineage " + std::to_string(arg) + " never coalesced (several roots)";
+    case VGX_GW_UNKNOWN_TYPE: return "vgx_get_genealogy: unknown event type " + std::to_string(arg);
+    case VGX_GW_MULTITYPE: return "vgx_get_genealogy: MULTITYPE event without a multievent log";
+    case VGX_GW_MUT_CAP: return "vgx_get_genealogy: mutation record capacity exceeded";
+    case VGX_GW_MIG_CAP: return "vgx_get_genealogy: migration record capacity exceeded";
+    case VGX_GW_WORKSPACE: return "vgx_get_genealogy: walk workspace exhausted";
+    default: return "vgx_get_genealogy: walk status " + std::to_string(status);
+    }
+}
+
+extern "C" int vgx_genealogy_message(int64_t status, int64_t arg, char *errbuf, int64_t errcap) {
+    if (errbuf && errcap > 0) std::snprintf(errbuf, (size_t)errcap, "%s", walk_message(status, arg).c_str());
+    return (int)status;
+}
+
+extern "C" int vgx_test_genealogy_walk(vgx_genealogy_io *io, char *errbuf, int64_t errcap) {
+    auto fail = [&](const std::string &m) {
+        if (errbuf && errcap > 0) std::snprintf(errbuf, (size_t)errcap, "%s", m.c_str());
+        return VGX_ERR_ARG;
+    };
+    if (!io || !io->infectious || !io->tree || !io->tree_pop || !io->times) return fail("vgx_test_genealogy_walk: null argument");
+    if (io->sCounter < 2) return fail(walk_message(VGX_GW_FEW_SAMPLES, 0));
+    const int64_t n = io->ev_ptr, PH = io->popNum * io->hapNum;
+    if (n < 0 || n >= ((int64_t)1 << 30) || 2 * io->sCounter > ((int64_t)1 << 31)) return fail("vgx_test_genealogy_walk: chain too long");
+    // the chain in the device log's record layout
+    std::vector<int32_t> log((size_t)n * 6);
+    for (int64_t e = 0; e < n; e++) {
+        const int64_t v[5] = {io->ev_types[e], io->ev_haplotypes[e], io->ev_populations[e], io->ev_newHaplotypes[e], io->ev_newPopulations[e]};
+        for (int c = 0; c < 5; c++) {
+            if (v[c] < INT32_MIN || v[c] > INT32_MAX) return fail("vgx_test_genealogy_walk: log value outside 32 bits");
+            log[(size_t)(e * 6 + c)] = (int32_t)v[c];
+        }
+    }
+    const int64_t nodes = 2 * io->sCounter - 1;
+    const int64_t tsize = vgx_gw_table_size(n, PH);
+    std::vector<int64_t> key((size_t)tsize, -1), cnt((size_t)tsize);
+    // (the table's fields other than the key are left as the device leaves them: uninitialised until a slot is taken)
+    std::unique_ptr<int32_t[]> base(new int32_t[(size_t)tsize]), len(new int32_t[(size_t)tsize]), lcap(new int32_t[(size_t)tsize]);
+    std::vector<int32_t> arena((size_t)std::max<int64_t>(n, 1));
+    std::vector<int32_t> tree((size_t)nodes), tree_pop((size_t)nodes), node_ev((size_t)nodes);
+    const int64_t mut_cap = std::max<int64_t>(io->mut_cap, 0), mig_cap = std::max<int64_t>(io->mig_cap, 0);
+    std::vector<int32_t> mu((size_t)mut_cap * 5 + 1), mg((size_t)mig_cap * 4 + 1);
+    VgxGwRep w;
+    w.n_ev = n; w.sCounter = io->sCounter; w.H = io->hapNum; w.tsize = tsize;
+    w.key = key.data(); w.cnt = cnt.data(); w.base = base.get(); w.len = len.get(); w.lcap = lcap.get();
+    w.arena = arena.data(); w.arena_cap = n;
+    w.tree = tree.data(); w.tree_pop = tree_pop.data(); w.node_ev = node_ev.data();
+    w.mut_cap = mut_cap;
+    w.mut_node = mu.data(); w.mut_AS = w.mut_node + mut_cap; w.mut_DS = w.mut_AS + mut_cap; w.mut_site = w.mut_DS + mut_cap;
+    w.mut_ev = w.mut_site + mut_cap;
+    w.mig_cap = mig_cap;
+    w.mig_node = mg.data(); w.mig_old = w.mig_node + mig_cap; w.mig_new = w.mig_old + mig_cap; w.mig_ev = w.mig_new + mig_cap;
+    VgxGwFlatReader rd{log.data()};
+    VgxGwResult res{};
+    res.status = vgx_gw_prepass(w, rd);
+    if (res.status != VGX_GW_OK) return fail(walk_message(res.status, res.arg));
+    for (int64_t s = 0; s < tsize; s++)   // the counts of the touched compartments
+        if (key[(size_t)s] >= 0 && key[(size_t)s] < PH) cnt[(size_t)s] = io->infectious[key[(size_t)s]];
+    VgxPcg64 g{io->rng_state[0], io->rng_state[1], io->rng_state[2], io->rng_state[3]};
+    vgx_gw_walk(w, rd, g, res);
+    for (int64_t s = 0; s < tsize; s++)   // walked back in place, as the host pass does
+        if (key[(size_t)s] >= 0 && key[(size_t)s] < PH) io->infectious[key[(size_t)s]] = cnt[(size_t)s];
+    if (res.status != VGX_GW_OK) return fail(walk_message(res.status, res.arg));
+    auto time_of = [&](int32_t e) { return e < 0 ? 0.0 : io->ev_times[e]; };
+    for (int64_t i = 0; i < nodes; i++) {
+        io->tree[i] = tree[(size_t)i]; io->tree_pop[i] = tree_pop[(size_t)i]; io->times[i] = time_of(node_ev[(size_t)i]);
+    }
+    io->mut_n = res.mut_n;
+    for (int64_t k = 0; k < res.mut_n; k++) {
+        io->mut_node[k] = w.mut_node[k]; io->mut_AS[k] = w.mut_AS[k]; io->mut_DS[k] = w.mut_DS[k]; io->mut_site[k] = w.mut_site[k];
+        io->mut_time[k] = time_of(w.mut_ev[k]);
+    }
+    io->mig_n = res.mig_n;
+    for (int64_t k = 0; k < res.mig_n; k++) {
+        io->mig_node[k] = w.mig_node[k]; io->mig_old[k] = w.mig_old[k]; io->mig_new[k] = w.mig_new[k];
+        io->mig_time[k] = time_of(w.mig_ev[k]);
+    }
+    io->nodes_used = res.nodes_used;
+    io->rng_state[0] = g.sh; io->rng_state[1] = g.sl; io->rng_state[2] = g.ih; io->rng_state[3] = g.il;
+    return VGX_OK;
 }

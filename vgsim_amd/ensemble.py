@@ -41,6 +41,7 @@ class Ensemble:
             else np.ascontiguousarray(seeds, dtype=np.int64)
         assert self.seeds.shape == (self.R,)
         self.traj_shape = None
+        self._last_call = None   # ('direct' | 'tau', record_events) of the last simulate call
 
     def close(self):
         self.engine.close()
@@ -78,7 +79,9 @@ class Ensemble:
         o.kernel = {'auto': 0, 'wave': 1, 'lane': 2, 'quad': 3, 'quadg': 4, 'solo': 5, 'lone': 6}[kernel]
         rc = eng.lib.vgx_simulate_direct(eng.handle, int(iterations), int(sample_size), float(np.float32(epidemic_time)),
                                          int(attempts), C.byref(o))
+        self._last_call = None
         eng._check(rc)
+        self._last_call = ('direct', bool(record_events))
         res = EnsembleResult(self.R)
         call = eng.counters_all()
         res.events[:], res.loop_iterations[:], res.restarts[:] = call[:, 0], call[:, 1], call[:, 2]
@@ -112,7 +115,9 @@ class Ensemble:
         o.record_events = 1 if record_events else 0
         rc = eng.lib.vgx_simulate_tau(eng.handle, int(iterations), int(sample_size), float(np.float32(epidemic_time)),
                                       int(attempts), C.byref(o))
+        self._last_call = None
         eng._check(rc)
+        self._last_call = ('tau', bool(record_events))
         res = EnsembleResult(self.R)
         call = eng.counters_all()
         res.events[:], res.loop_iterations[:], res.restarts[:] = call[:, 0], call[:, 1], call[:, 2]
@@ -158,6 +163,74 @@ class Ensemble:
         pos = (int(c.reserved[1]), 2 * int(c.reserved[2])) if c.reserved[1] >= 0 else None
         m.user_seed = int(self.seeds[replicate])
         return _capi.get_genealogy(m, seed, rng_position=pos)
+
+    def genealogies(self, seed=None, replicates=None, layout='wave'):
+        """The backward pass of every selected replicate of the last direct ``simulate(record_events=True)`` call at once,
+        on the device (``vgx_get_genealogies``): one walk per replicate over its log where the kernel left it.  Returns a
+        :class:`GenealogyBatch` whose ``replicate(r)`` is bit-identical to ``genealogy(r, seed_r)``.
+
+        ``seed``: None (every replicate continues its own simulation stream), an int (every replicate reseeded with
+        ``(seed, 0)``), or one seed per selected replicate.  ``replicates``: indices (default all, in order).  A replicate
+        whose walk fails (fewer than two samples, lineages that never coalesce, ...) gets a nonzero status and does not
+        fail the call.  ``layout``: 'wave' (one replicate per wavefront, the faster one measured) or 'lane'
+        (one replicate per lane)."""
+        if self._last_call is None:
+            raise ValueError("genealogies() needs a direct simulate(record_events=True) call first")
+        if self._last_call[0] != 'direct':
+            raise ValueError("genealogies() walks direct chains only: the last call was simulate_tau")
+        if not self._last_call[1]:
+            raise ValueError("genealogies() needs the event log: the last call had record_events=False")
+        if layout not in ('lane', 'wave'):
+            raise ValueError("layout must be 'lane' or 'wave'")
+        eng, lib = self.engine, self.engine.lib
+        reps = np.arange(self.R, dtype=np.int64) if replicates is None else np.ascontiguousarray(replicates, dtype=np.int64).ravel()
+        n = len(reps)
+        if n and (reps.min() < 0 or reps.max() >= self.R):
+            raise ValueError("replicate index out of range")
+        if len(np.unique(reps)) != n:
+            raise ValueError("replicates must be distinct")
+        counters = [eng.counters(int(r)) for r in reps]
+        for r, c in zip(reps, counters):
+            if c.ev_first_new != 0:
+                raise ValueError("replicate %d: its chain does not start in the last call's device log (the model held %d events "
+                                 "when the ensemble started); use genealogy(r, seed)" % (r, c.ev_first_new))
+        if seed is not None and not np.isscalar(seed):
+            seeds = np.ascontiguousarray(seed, dtype=np.int64).ravel()
+            if len(seeds) != n:
+                raise ValueError("one seed per selected replicate: got %d for %d" % (len(seeds), n))
+        rng = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        pos = (C.c_uint64 * 4)()
+        for i, (r, c) in enumerate(zip(reps, counters)):   # the start of every walk, as genealogy(r, seed) finds it
+            if seed is None:
+                att, draws = (int(c.reserved[1]), 2 * int(c.reserved[2])) if c.reserved[1] >= 0 else (0, 0)
+                lib.vgx_rng_position(int(self.seeds[r]), att, draws, C.byref(pos))
+            else:
+                lib.vgx_rng_position(int(seed) if np.isscalar(seed) else int(seeds[i]), 0, 0, C.byref(pos))
+            rng[i] = list(pos)
+        b = GenealogyBatch(reps)
+        io = _capi.VgxGenealogiesIO()
+        io.n = n
+        io.replicates = _capi._p(reps)
+        off = {k: np.zeros(n + 1, dtype=np.int64) for k in ("node", "mut", "mig")}
+        io.node_off, io.mut_off, io.mig_off = _capi._p(off["node"]), _capi._p(off["mut"]), _capi._p(off["mig"])
+        eng._check(lib.vgx_get_genealogies(eng.handle, C.byref(io)))          # sizing
+        io.rng_state = rng.ctypes.data_as(C.POINTER(C.c_uint64))
+        cap = {}
+        for keys, o in ((GenealogyBatch.NODE_KEYS, off["node"]), (GenealogyBatch.MUT_KEYS, off["mut"]), (GenealogyBatch.MIG_KEYS, off["mig"])):
+            for k in keys:
+                cap[k] = np.zeros(max(int(o[-1]), 1), dtype=np.float64 if k.endswith("times") or k.endswith("_time") else np.int64)
+        for k, a in cap.items():
+            setattr(io, k, _capi._p(a))
+        per = {k: np.zeros(max(n, 1), dtype=np.int64) for k in ("status", "status_arg", "nodes_used", "mut_n", "mig_n")}
+        for k, a in per.items():
+            setattr(io, k, _capi._p(a))
+        rng_out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        io.rng_out = rng_out.ctypes.data_as(C.POINTER(C.c_uint64))
+        io.layout = 1 if layout == 'wave' else 0
+        eng._check(lib.vgx_get_genealogies(eng.handle, C.byref(io)))          # walk
+        b._fill(off, cap, {k: v[:n] for k, v in per.items()}, rng_out[:n])
+        b.passes, b.kernel_ms, b.clock_ms, b.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
+        return b
 
     def trajectories(self, out=None):
         """Summary trajectories of the last call, ``[R, T, P, 2]`` float64 (infectious, susceptible per population).
@@ -225,6 +298,65 @@ class Ensemble:
             out = None
             work = dist.gather(mine, None, dst=dst, async_op=async_op)
         return PendingGather(work, out, mine) if async_op else out
+
+
+class GenealogyBatch:
+    """Genealogies of many replicates (``Ensemble.genealogies``), as flat arrays with per-replicate offsets.
+
+    ``replicates[i]`` is the replicate of row i; ``status[i]`` is 0 or why its walk stopped (``message(i)``).  Nodes of row i
+    are ``tree`` / ``tree_pop`` / ``times``[node_offsets[i]:node_offsets[i+1]] (node ids local to the replicate, 0 ..
+    2 sCounter - 2), its mutation records ``mut_*``[mut_offsets[i]:mut_offsets[i+1]], its migration records likewise
+    ``mig_*``; failed rows hold none.  ``nodes_used[i]``, ``rng_raw[i]`` (the generator after the walk)."""
+
+    NODE_KEYS = ("tree", "tree_pop", "times")
+    MUT_KEYS = ("mut_node", "mut_AS", "mut_DS", "mut_site", "mut_time")
+    MIG_KEYS = ("mig_node", "mig_time", "mig_old", "mig_new")
+
+    def __init__(self, replicates):
+        self.replicates = np.asarray(replicates, dtype=np.int64).copy()
+        self._row = {int(r): i for i, r in enumerate(self.replicates)}
+
+    def _fill(self, off, cap, per, rng_out):
+        n = len(self.replicates)
+        self.status, self.status_arg = per["status"].copy(), per["status_arg"].copy()
+        ok = self.status == 0
+        self.nodes_used = per["nodes_used"].copy()
+        self.rng_raw = np.zeros((n, 6), dtype=np.uint64)
+        self.rng_raw[:, :4] = rng_out
+
+        def compact(o, keep, keys):   # row i keeps the first keep[i] entries of its capacity
+            lens = np.diff(o)
+            pos = np.arange(int(o[-1]), dtype=np.int64) - np.repeat(o[:-1], lens)
+            mask = pos < np.repeat(keep, lens)
+            for k in keys:
+                setattr(self, k, cap[k][:len(mask)][mask])
+            return np.concatenate(([0], np.cumsum(keep))).astype(np.int64)
+        self.node_offsets = compact(off["node"], np.where(ok, np.diff(off["node"]), 0), self.NODE_KEYS)
+        self.mut_offsets = compact(off["mut"], np.where(ok, per["mut_n"], 0), self.MUT_KEYS)
+        self.mig_offsets = compact(off["mig"], np.where(ok, per["mig_n"], 0), self.MIG_KEYS)
+
+    def __len__(self):
+        return len(self.replicates)
+
+    def message(self, i):
+        """Text of row i's status: what ``Ensemble.genealogy`` raises for that replicate ('' when it succeeded)."""
+        return _capi.genealogy_message(int(self.status[i]), int(self.status_arg[i]))
+
+    def replicate(self, r):
+        """The genealogy of replicate ``r`` as ``Ensemble.genealogy(r, seed_r)`` returns it; raises what that raises when
+        the walk of ``r`` failed."""
+        i = self._row.get(int(r))
+        if i is None:
+            raise KeyError("replicate %d is not in this batch" % r)
+        if self.status[i] != 0:
+            raise RuntimeError(self.message(i))
+        out = {}
+        for keys, o in ((self.NODE_KEYS, self.node_offsets), (self.MUT_KEYS, self.mut_offsets), (self.MIG_KEYS, self.mig_offsets)):
+            for k in keys:
+                out[k] = getattr(self, k)[o[i]:o[i + 1]].copy()
+        out["nodes_used"] = int(self.nodes_used[i])
+        out["rng_raw"] = tuple(int(x) for x in self.rng_raw[i])
+        return out
 
 
 class PendingGather:
