@@ -93,7 +93,8 @@ typedef struct vgx_state {
 typedef struct vgx_run_opts {
     int64_t record_events;   /* 1: keep the event log (default for the classic API); 0: counters/trajectories only */
     int64_t max_loop_factor; /* loop guard: at most max_loop_factor*iterations + 2^20 loop iterations (0 = 1024) */
-    int64_t traj_points;     /* >0: bin totalInfectious/totalSusceptible[P] at this many uniform time points */
+    int64_t traj_points;     /* >0: bin totalInfectious/totalSusceptible[P] at this many uniform time points (direct and tau calls;
+                                a grid point gets the totals before the event / step that takes the time past it) */
     double traj_t0, traj_t1; /* time window of the trajectory grid */
     int64_t mode;            /* direct path: 0 = EXACT (the reference's floating-point summation order, bit-exact log);
                                 1 = FAST (order-free sums: class-aggregated infection rate, integer prefix search,
@@ -199,7 +200,8 @@ int vgx_get_tau_tries(vgx_engine *e, int64_t replicate, int64_t first, int64_t c
 int vgx_get_multievents(vgx_engine *e, int64_t replicate, int64_t cap, int64_t *num, double *times, int64_t *types,
                         int64_t *haplotypes, int64_t *populations, int64_t *newHaplotypes,
                         int64_t *newPopulations, int64_t *n);
-/* Summary trajectories of the last call: out[replicate][point][population][0=infectious,1=susceptible], f64.
+/* Summary trajectories of the last call (direct or tau; an error when it recorded none): out[replicate][point][population][0=infectious,
+ * 1=susceptible], f64.
  * `out` is a host pointer, or a device pointer when out_is_device != 0 (e.g. a torch tensor for an RCCL gather). */
 int vgx_get_trajectories(vgx_engine *e, double *out, int out_is_device);
 /* The same trajectories as 32-bit integers written to a DEVICE buffer of the same shape (compartment totals are whole numbers;

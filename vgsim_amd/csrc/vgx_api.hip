@@ -55,6 +55,7 @@ extern "C" hipError_t vgxi_launch_init_reps(const VgxDevRep *r, int P, int S, in
 #define TAU_DECL(name) extern "C" hipError_t vgxi_##name(const VgxTauArgs *a, hipStream_t s);
 TAU_DECL(tau_eff) TAU_DECL(tau_scatter) TAU_DECL(tau_prep) TAU_DECL(tau_drift) TAU_DECL(tau_choose) TAU_DECL(tau_draw)
 TAU_DECL(tau_conv8) TAU_DECL(tau_sync8) TAU_DECL(tau_arrivals) TAU_DECL(tau_verdict) TAU_DECL(tau_apply) TAU_DECL(tau_check) TAU_DECL(tau_decide) TAU_DECL(tau_commit) TAU_DECL(tau_finish) TAU_DECL(tau_draw_big) TAU_DECL(tau_suspect)
+extern "C" hipError_t vgxi_tau_traj(const VgxTauArgs *a, int64_t rep0, int64_t n, int fill, hipStream_t s);
 
 static std::string g_create_error;
 
@@ -110,7 +111,7 @@ struct vgx_engine {
         r_evrate, r_evcols, r_locrec, r_loctime, r_lociter, r_farate, r_fakey, r_traj, r_prof, r_qeff, r_qmebm, r_qflag;
     // tau-leaping (dense compartments)
     DevBuf t_I, t_S, t_dChk, t_dApp, t_dSi, t_dTot, t_totInf, t_gI, t_cd, t_lock, t_F, t_eff, t_Aeff, t_Gout, t_dS,
-        t_taubits, t_tau, t_time, t_flags, t_counters, t_cnttry, t_cntpop, t_front, t_frontn, t_occ, t_occn, t_occpop, t_tIpt, t_d8spk, t_d8sbc, t_d8stile, t_d8sovf, t_d8smax, t_mev, t_mevn, t_mevbase, t_locn, t_mutcum, t_migcdf, t_migIn, t_mutHi, t_colT, t_colTW, t_inc, t_incn, t_sieve, t_sievepop, t_sieveskip, t_big, t_bign, t_res, t_susp, t_suspn, t_stkey, t_stval, t_dChkTot, t_q, t_qn, t_hist, t_I8, t_dSpart, t_tmax8, t_iI, t_iS, t_slog, t_sres;
+        t_taubits, t_tau, t_time, t_flags, t_counters, t_cnttry, t_cntpop, t_front, t_frontn, t_occ, t_occn, t_occpop, t_tIpt, t_d8spk, t_d8sbc, t_d8stile, t_d8sovf, t_d8smax, t_mev, t_mevn, t_mevbase, t_locn, t_mutcum, t_migcdf, t_migIn, t_mutHi, t_colT, t_colTW, t_inc, t_incn, t_sieve, t_sievepop, t_sieveskip, t_big, t_bign, t_res, t_susp, t_suspn, t_stkey, t_stval, t_dChkTot, t_q, t_qn, t_hist, t_I8, t_dSpart, t_tmax8, t_iI, t_iS, t_slog, t_sres, t_trajpre, t_trajn;
     std::vector<int64_t> tau_sieve_skipped;   // [R] tries left out by the sieve in the last tau call
     bool last_was_tau = false;
     bool tau_staged = false;              // vgx_stage_tau put the current start state on the device in the tau kernels' layout
@@ -1391,6 +1392,7 @@ extern "C" int vgx_stage_tau(vgx_engine *e) {
 extern "C" int vgx_simulate_tau(vgx_engine *e, int64_t iterations, int64_t sample_size, float time, int64_t attempts,
                                 const vgx_run_opts *opts) {
     if (!e) return VGX_ERR_ARG;
+    e->traj_points = 0;    // (until this call has written its own: vgx_get_trajectories never returns the bins of an earlier call)
     if (!e->have_params || !e->have_state) return fail(e, VGX_ERR_ARG, "vgx_simulate_tau: set params and state first");
     HIPCHECK(e, hipSetDevice(e->device));
     const int64_t H = e->d.hapNum, P = e->d.popNum, S = e->d.susNum, R = e->R;
@@ -1575,6 +1577,13 @@ extern "C" int vgx_simulate_tau(vgx_engine *e, int64_t iterations, int64_t sampl
     rc |= ensure(e, e->t_mevn, (size_t)R * 8);
     rc |= ensure(e, e->t_mevbase, (size_t)R * 8);
     rc |= ensure(e, e->t_locn, (size_t)R * 8);
+    // summary trajectories [R][T][P][2] as the direct calls bin them (direct_core), the step kernels' copy of the totals before a step
+    if (o.traj_points > 0) {
+        rc |= ensure(e, e->r_traj, (size_t)(R * o.traj_points * P * 2) * 8);
+        rc |= ensure(e, e->t_trajpre, (size_t)(R * P * 2) * 8);
+        rc |= ensure(e, e->t_trajn, (size_t)R * 8);
+    }
+    const double traj_dt = o.traj_points > 1 ? (o.traj_t1 - o.traj_t0) / (double)(o.traj_points - 1) : 0.0;
     if (e->h_has_mig && !e->h_mig_uniform) rc |= ensure(e, e->t_migIn, (size_t)(R * P * H) * 8);
     if (e->h_mig_uniform) { rc |= ensure(e, e->t_colT, (size_t)(R * H) * 8); rc |= ensure(e, e->t_colTW, (size_t)(R * H) * 8); }
     rc |= ensure(e, e->t_mutHi, (size_t)(e->d.sites > 6 ? R * P * H : 1) * 8);   // tiled drift, first pass (vgx_tau_muthigh_kernel)
@@ -1772,6 +1781,10 @@ extern "C" int vgx_simulate_tau(vgx_engine *e, int64_t iterations, int64_t sampl
     e->tau_mev_cap = mev_cap;
     a.mev_n = (unsigned long long *)e->t_mevn.p; a.mev_base = (unsigned long long *)e->t_mevbase.p;
     a.loc_n = (unsigned long long *)e->t_locn.p; a.loc_rec = (int32_t *)e->r_locrec.p; a.loc_time = (double *)e->r_loctime.p;
+    if (o.traj_points > 0) {
+        a.traj = (double *)e->r_traj.p; a.traj_points = o.traj_points; a.traj_t0 = o.traj_t0; a.traj_dt = traj_dt;
+        a.traj_pre = (double *)e->t_trajpre.p; a.traj_next = (int64_t *)e->t_trajn.p;
+    }
 
     // ---- per-replicate host bookkeeping ----
     std::vector<double> tnow((size_t)R, h.currentTime), tau_h;
@@ -1834,6 +1847,10 @@ extern "C" int vgx_simulate_tau(vgx_engine *e, int64_t iterations, int64_t sampl
             e->C <= VGX_TAUS_MAX_C && e->CB <= VGX_TAUS_MAX_CB && vgx_taus_lds_bytes(P, H, S, e->C, e->CB) <= 150 * 1024)
             use_small = true;      // (VGX_TAU_STEP_KERNELS=0: the on-device loop wherever it can run, for tests and comparisons)
     }
+    if (!use_small && a.traj) {   // the step kernels' trajectories start from the uploaded state
+        HIPCHECK(e, vgxi_tau_traj(&a, 0, R, 0, e->stream));
+        launches += 1;
+    }
     if (use_small) {
         std::vector<int32_t> i32((size_t)(P * H));
         for (int64_t i = 0; i < P * H; i++) i32[(size_t)i] = (int32_t)h.initial_infectious[(size_t)i];
@@ -1858,6 +1875,7 @@ extern "C" int vgx_simulate_tau(vgx_engine *e, int64_t iterations, int64_t sampl
         ta.slog = (int64_t *)e->t_slog.p; ta.slog_cap = slog_cap;
         ta.loc_rec = a.loc_rec; ta.loc_time = a.loc_time; ta.loc_n = a.loc_n;
         ta.res = (int64_t *)e->t_sres.p;
+        ta.traj = a.traj; ta.traj_points = a.traj_points; ta.traj_t0 = a.traj_t0; ta.traj_dt = a.traj_dt;
         HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
         HIPCHECK(e, vgxi_launch_taus(&ta, e->stream));
         HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
@@ -1917,6 +1935,7 @@ extern "C" int vgx_simulate_tau(vgx_engine *e, int64_t iterations, int64_t sampl
                 restarts[(size_t)r] += 1;
                 rc = tau_upload_state(e, r, h.initial_infectious, h.initial_susceptible);
                 if (rc) return rc;
+                if (a.traj) { HIPCHECK(e, vgxi_tau_traj(&a, r, 1, 0, e->stream)); launches += 1; }   // (its bins start again, on the restored state)
                 i8_dirty = true;
                 occ_est = occupied;   // (the start state again)
                 {   // the lockdown records of the failed attempt stay (Restart does not clear `loc`); then CheckLockdown for
@@ -2264,6 +2283,11 @@ extern "C" int vgx_simulate_tau(vgx_engine *e, int64_t iterations, int64_t sampl
         }
     }
 
+    if (!use_small && a.traj) {   // the grid points after the last step: the final state
+        HIPCHECK(e, vgxi_tau_traj(&a, 0, R, 1, e->stream));
+        HIPCHECK(e, hipStreamSynchronize(e->stream));
+        launches += 1;
+    }
     lap("step loop");
     if (timing) {
         int64_t st_all = 0;
@@ -2318,6 +2342,7 @@ extern "C" int vgx_simulate_tau(vgx_engine *e, int64_t iterations, int64_t sampl
     e->last_launches = launches;
     e->last_ev_size = ev_size;
     e->ev_ptr0 = ev_ptr_start;
+    e->traj_points = o.traj_points > 0 ? o.traj_points : 0;
     h.ev_ptr = ev_ptr[0];
     return VGX_OK;
 }

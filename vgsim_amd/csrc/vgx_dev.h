@@ -292,4 +292,11 @@ struct VgxTauArgs {
     long long *st_val;               // [R][st_size] infectious + own delta + arrivals
     int64_t st_size;                 // power of two >= 2 * suspect_cap
     int64_t *dChkTot;                // [R][P] sum over the population's compartments of the deltas as the check books them
+    // summary trajectories (null: none): grid point j = traj_t0 + j traj_dt.  The apply / commit kernels move totInf and S to the state
+    // after the step before vgx_tau_finish_kernel learns the step's new time, so the totals before the step are kept aside
+    double *traj;                    // [R][traj_points][P][2] infectious, susceptible totals per population
+    int64_t traj_points;
+    double traj_t0, traj_dt;
+    double *traj_pre;                // [R][P][2] the totals before the current step (vgx_tau_traj_kernel, then every step's finish kernel)
+    int64_t *traj_next;              // [R] next grid point to write
 };

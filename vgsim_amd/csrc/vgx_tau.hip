@@ -3620,6 +3620,13 @@ extern "C" __global__ void __launch_bounds__(TB) vgx_tau_commit_kernel(VgxTauArg
     }
 }
 
+// grid point j of the summary trajectories, t0 + j dt, as the direct kernels form it: no FMA contraction (allowed in the rest of this
+// file), so that the bins of every path and of a replay on the host fall at the same times
+static __device__ __forceinline__ double tau_traj_grid(const VgxTauArgs &a, int64_t j) {
+#pragma clang fp contract(off)
+    return a.traj_t0 + (double)j * a.traj_dt;
+}
+
 // End of a step (pyx:2322-2329): globalInfectious, CheckLockdown for every population (contact density
 // only: the step kernels rebuild what they need from it).  grid = R, block = 64.
 extern "C" __global__ void __launch_bounds__(64) vgx_tau_finish_kernel(VgxTauArgs a) {
@@ -3658,7 +3665,44 @@ extern "C" __global__ void __launch_bounds__(64) vgx_tau_finish_kernel(VgxTauArg
             }
         }
     }
-    __syncthreads();   // the lockdown records above use time_now + tau
+    if (a.traj) {
+        // summary trajectories: the grid points before the step's new time (that of its record, pyx:2322) get the totals before the step,
+        // kept aside since the apply / commit kernels moved totInf and S on; then the totals after it are kept for the next step
+        const double t_new = a.time_now[rep] + a.tau[rep];
+        const int S = p.S;
+        const int64_t j0 = a.traj_next[rep];
+        int64_t j1 = j0;
+        while (j1 < a.traj_points && tau_traj_grid(a, j1) < t_new) ++j1;
+        double2 *pre = (double2 *)a.traj_pre + (int64_t)rep * P;
+        double2 *o = (double2 *)a.traj + (int64_t)rep * a.traj_points * P;
+        // Four populations per lane at a time, every load issued before the first store: the compiler cannot tell the grid from the copy,
+        // and loads behind a bin's stores cost a round trip per bin (+50 us per config-4 step at 50 bins a step).  Named registers: an
+        // array indexed in a loop went to LDS and was read back per bin (+13 us).  Lanes past P read population P - 1: no branch between
+        // the loads, only the stores are guarded.
+        struct Cell { int pn; bool mine; double2 was; long long inf, sus; };
+        auto load = [&](int pn) {
+            Cell c;
+            c.mine = pn < P;
+            c.pn = c.mine ? pn : P - 1;
+            c.was = pre[c.pn];
+            c.inf = a.totInf[(int64_t)rep * P + c.pn];
+            c.sus = 0;
+            return c;
+        };
+        auto sus_of = [&](const Cell &c, int sn) { return a.S[((int64_t)rep * P + c.pn) * S + sn]; };
+        auto store = [&](const Cell &c) {
+            if (!c.mine) return;
+            for (int64_t j = j0; j < j1; ++j) o[j * P + c.pn] = c.was;
+            pre[c.pn] = make_double2((double)c.inf, (double)c.sus);
+        };
+        for (int base = 0; base < P; base += 4 * 64) {
+            Cell c0 = load(base + lane), c1 = load(base + 64 + lane), c2 = load(base + 128 + lane), c3 = load(base + 192 + lane);
+            for (int sn = 0; sn < S; ++sn) { c0.sus += sus_of(c0, sn); c1.sus += sus_of(c1, sn); c2.sus += sus_of(c2, sn); c3.sus += sus_of(c3, sn); }
+            store(c0); store(c1); store(c2); store(c3);
+        }
+        if (lane == 0) a.traj_next[rep] = j1;
+    }
+    __syncthreads();   // the lockdown records and the trajectories above use time_now + tau
     for (int i = lane; i < a.inc_shards; i += 64) a.inc_n[(int64_t)rep * VGX_INC_SHARDS + i] = 0;   // (sparse mode: applied by now)
     long long occ_sum = 0;
     if (a.occ_pop) {
@@ -3686,6 +3730,26 @@ extern "C" __global__ void __launch_bounds__(64) vgx_tau_finish_kernel(VgxTauArg
     }
 }
 
+// Summary trajectories of the step kernels outside the steps, replicates rep0, rep0 + 1, ...: fill = 0: the totals of the state as it
+// stands become the copy "before the step" and the replicate's grid starts again at point 0 (start of the call, after a Restart: the
+// bins then describe the final attempt, as its log does); fill = 1: every grid point not yet written gets the final totals (a time limit,
+// extinction, a stop, a call that never starts).  grid = replicates, block = 64.
+extern "C" __global__ void __launch_bounds__(64) vgx_tau_traj_kernel(VgxTauArgs a, int64_t rep0, int fill) {
+    const int64_t rep = rep0 + blockIdx.x;
+    const int P = a.p.P, S = a.p.S, lane = threadIdx.x;
+    const int64_t j0 = a.traj_next[rep];
+    double2 *o = (double2 *)a.traj + rep * a.traj_points * P;
+    for (int pn = lane; pn < P; pn += 64) {
+        long long sus = 0;
+        for (int sn = 0; sn < S; ++sn) sus += a.S[(rep * P + pn) * S + sn];
+        const double2 v = make_double2((double)a.totInf[rep * P + pn], (double)sus);
+        if (fill) for (int64_t j = j0; j < a.traj_points; ++j) o[j * P + pn] = v;
+        else ((double2 *)a.traj_pre)[rep * P + pn] = v;
+    }
+    __syncthreads();
+    if (lane == 0) a.traj_next[rep] = fill ? a.traj_points : 0;
+}
+
 // ---- launchers -----------------------------------------------------------------------------------
 #define TAU_LAUNCH(name, grid, block)                                                            \
     extern "C" __attribute__((visibility("hidden"))) hipError_t vgxi_##name(const VgxTauArgs *a, \
@@ -3707,6 +3771,10 @@ extern "C" __attribute__((visibility("hidden"))) int vgxi_tau_drift_blocks(const
     }
     const unsigned tiles = (unsigned)((a->p.H + TB - 1) / TB);
     return (int)(tiles < 32u ? tiles : 32u);
+}
+extern "C" __attribute__((visibility("hidden"))) hipError_t vgxi_tau_traj(const VgxTauArgs *a, int64_t rep0, int64_t n, int fill, hipStream_t s) {
+    hipLaunchKernelGGL(vgx_tau_traj_kernel, dim3((unsigned)n), dim3(64), 0, s, *a, rep0, fill);
+    return hipGetLastError();
 }
 extern "C" __attribute__((visibility("hidden"))) hipError_t vgxi_tau_conv8(const VgxTauArgs *a, hipStream_t s) {
     hipLaunchKernelGGL(vgx_tau_conv8_kernel, dim3((unsigned)((a->p.H + 4 * TB - 1) / (4 * TB)), (unsigned)a->p.P, (unsigned)a->R), dim3(TB), 0, s, *a);

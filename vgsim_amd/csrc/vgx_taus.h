@@ -40,6 +40,10 @@ struct VgxTausArgs {
     double *loc_time;                 // [R][VGX_LOC_CAP]
     unsigned long long *loc_n;        // [R]
     int64_t *res;                     // [R][24] what the host reads after the call (see vgx_taus.hip)
+    // summary trajectories (null: none): grid point j = traj_t0 + j traj_dt, [R][traj_points][P][2] infectious, susceptible totals
+    double *traj;
+    int64_t traj_points;
+    double traj_t0, traj_dt;
 };
 
 enum { TS_TAU = 0, TS_GI, TS_CNT0, TS_EVPTR = 10, TS_ATT, TS_GOOD, TS_RESTARTS, TS_STEPS, TS_MEVROWS, TS_ERROR, TS_TIME, TS_EVPTR0, TS_TRIES };

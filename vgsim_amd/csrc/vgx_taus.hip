@@ -44,6 +44,13 @@ extern "C" int vgx_taus_get_profile(unsigned long long *out, int clear) {
 #else
 #define TSPROF(i)
 #endif
+// grid point j of the summary trajectories, t0 + j dt, as the direct kernels form it: no FMA contraction (this translation unit allows
+// it, vgx_tau_rng.h), so that the bins of the two paths and of a replay on the host fall at the same times
+static __device__ __forceinline__ double taus_traj_grid(double t0, double dt, int64_t j) {
+#pragma clang fp contract(off)
+    return t0 + (double)j * dt;
+}
+
 // TT = threads of the workgroup.  One trajectory (or a few) wants many lanes per step (512: two rounds of the 528 channels of the 16 x 3
 // model); ensembles that fill the chip want many small workgroups per CU instead — measured (tools/probe_taus_threads.py, steps/s of all
 // replicates): 16 x 3, 2048 replicates: 6.2e7 at 64 threads, 3.6e7 at 256, 2.2e7 at 512; 512 replicates: 1.8e7 / 3.5e7 / 2.2e7; 64:
@@ -113,6 +120,24 @@ static __device__ __forceinline__ void taus_body() {
     bool running = a.attempts > 0 && a.start_ok;
     bool fresh = true, finished = a.attempts <= 0;
     int64_t guard = 0;
+    // summary trajectories (as vgx_direct.hip's traj_emit): every grid point not yet written that lies before t_new gets the totals
+    // in LDS (the state before the step that moves the time to t_new); final_fill: every remaining one
+    double *const trajr = a.traj ? a.traj + (int64_t)rep * a.traj_points * P * 2 : nullptr;
+    int64_t traj_next = 0;
+    auto traj_emit = [&](double t_new, bool final_fill) {
+        while (traj_next < a.traj_points) {
+            const double tg = taus_traj_grid(a.traj_t0, a.traj_dt, traj_next);
+            if (!final_fill && !(tg < t_new)) break;
+            double *o = trajr + traj_next * P * 2;
+            for (int pn = tid; pn < P; pn += TT) {
+                long long sus = 0;
+                for (int sn = 0; sn < S; ++sn) sus += Sv[pn * S + sn];
+                o[pn * 2 + 0] = (double)tot[pn];
+                o[pn * 2 + 1] = (double)sus;
+            }
+            traj_next += 1;
+        }
+    };
 
     // CheckLockdown for every population (pyx:698-710), by one thread in population order; `t` = the time the records carry
     auto check_lockdowns = [&](double t) {
@@ -176,6 +201,7 @@ static __device__ __forceinline__ void taus_body() {
                 for (int pn = 0; pn < P; ++pn) g0 += tot[pn];
                 gI = g0;
                 tnow = 0.0; ev_ptr = 0; ev_ptr_start = 0; mev_base = 0; steps = 0;
+                traj_next = 0;      // (the bins describe the final attempt, as its log does)
                 att += 1;
                 if (att < a.attempts && err == 0) { running = g0 != 0 && a.rates_nonzero_initial; fresh = true; }
                 else finished = true;
@@ -452,6 +478,14 @@ static __device__ __forceinline__ void taus_body() {
         }
         if (err) break;
 
+        // ---- summary trajectories: the grid points before the step's new time (tnow + tau_l, the time its record carries) get the
+        // totals of tot and Sv, still the state before the step (a condition uniform over the block: the barrier orders these reads of
+        // Sv before the update below) ----
+        if (trajr && traj_next < a.traj_points && taus_traj_grid(a.traj_t0, a.traj_dt, traj_next) < tnow + tau_l) {
+            traj_emit(tnow + tau_l, false);
+            __syncthreads();
+        }
+
         // ---- UpdateCompartmentCounts_tau (pyx:2536-2593), the MULTITYPE record (pyx:2325) ----
         for (int i = tid; i < PH; i += TT) I[i] += dApp[i];
         for (int i = tid; i < P * S; i += TT) Sv[i] += dS[i];
@@ -500,6 +534,7 @@ static __device__ __forceinline__ void taus_body() {
 #endif
     // ---- state and results back ----
     __syncthreads();
+    if (trajr) traj_emit(0.0, true);     // the remaining grid points: the final state (time limit, extinction, a stop, no start)
     for (int i = tid; i < PH; i += TT) gIr[i] = I[i];
     for (int i = tid; i < P * S; i += TT) a.S[(int64_t)rep * P * S + i] = Sv[i];
     for (int i = tid; i < P; i += TT) {

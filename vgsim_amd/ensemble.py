@@ -89,10 +89,13 @@ class Ensemble:
         self.traj_shape = (self.R, int(traj_points), m.popNum, 2) if traj_points > 0 else None
         return res
 
-    def simulate_tau(self, iterations, sample_size=None, epidemic_time=-1, attempts=200, record_events=False, seeds=None):
+    def simulate_tau(self, iterations, sample_size=None, epidemic_time=-1, attempts=200, record_events=False, seeds=None,
+                     traj_points=0, traj_window=(0.0, 1.0)):
         """Poisson tau-leaping for every replicate from the model's current state (``SimulatePopulation_tau``
         semantics per replicate, pyx:2293-2346).  ``EnsembleResult.events`` counts MULTITYPE records (steps);
-        ``events_drawn`` the sum of the drawn channel multiplicities."""
+        ``events_drawn`` the sum of the drawn channel multiplicities.  ``traj_points`` / ``traj_window``: summary
+        trajectories as ``simulate`` bins them (a grid point gets the totals before the step that takes the time past it),
+        with or without the event log; read with ``trajectories()`` / ``gather_trajectories()``."""
         m, eng = self.model, self.engine
         if seeds is not None:
             self.seeds = np.ascontiguousarray(seeds, dtype=np.int64)
@@ -113,6 +116,8 @@ class Ensemble:
         eng.set_seeds(self.seeds)
         o = _capi.VgxRunOpts()
         o.record_events = 1 if record_events else 0
+        o.traj_points = int(traj_points)
+        o.traj_t0, o.traj_t1 = float(traj_window[0]), float(traj_window[1])
         rc = eng.lib.vgx_simulate_tau(eng.handle, int(iterations), int(sample_size), float(np.float32(epidemic_time)),
                                       int(attempts), C.byref(o))
         self._last_call = None
@@ -123,7 +128,7 @@ class Ensemble:
         res.events[:], res.loop_iterations[:], res.restarts[:] = call[:, 0], call[:, 1], call[:, 2]
         res.events_drawn = call[:, 3].copy()
         res.kernel_ms = eng.last_kernel_ms
-        self.traj_shape = None
+        self.traj_shape = (self.R, int(traj_points), m.popNum, 2) if traj_points > 0 else None
         return res
 
     def replicate_state(self, replicate):
