@@ -200,6 +200,13 @@ int vgx_get_tau_tries(vgx_engine *e, int64_t replicate, int64_t first, int64_t c
 int vgx_get_multievents(vgx_engine *e, int64_t replicate, int64_t cap, int64_t *num, double *times, int64_t *types,
                         int64_t *haplotypes, int64_t *populations, int64_t *newHaplotypes,
                         int64_t *newPopulations, int64_t *n);
+/* The rows of ALL replicates of the last tau call in one read-out: offsets[r] .. offsets[r + 1] are the rows of replicate r in `rows`
+ * ([.][6]: num, type, haplotype, population, newHaplotype, newPopulation, in the order the device appended them) and `steps` (the step
+ * of the call, 0-based, a row belongs to; may be NULL).  rows == NULL: only `offsets` ([R + 1]) is filled (sizing); cap: rows there is room for. */
+int vgx_get_multievents_all(vgx_engine *e, int64_t cap, int64_t *offsets, int64_t *rows, int64_t *steps);
+/* The states of ALL replicates after the last tau call: infectious [R][P][H], susceptible [R][P][S], counters [R][8] (bCounter, dCounter,
+ * sCounter, mCounter, iCounter, migPlus, globalInfectious, ev_ptr), times [R] (currentTime); each may be NULL. */
+int vgx_get_tau_states_all(vgx_engine *e, int64_t *infectious, int64_t *susceptible, int64_t *counters, double *times);
 /* Summary trajectories of the last call (direct or tau; an error when it recorded none): out[replicate][point][population][0=infectious,
  * 1=susceptible], f64.
  * `out` is a host pointer, or a device pointer when out_is_device != 0 (e.g. a torch tensor for an RCCL gather). */

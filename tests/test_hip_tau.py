@@ -9,7 +9,10 @@ distributional, as BASELINE.json asks ("within a stated distributional tolerance
   * from ONE common warm-up state, N_ENSEMBLE seeded tau runs per engine (the device's as one ensemble launch): mean,
     variance and the two quartiles of every counter, of the epidemic time, of the infectious total of every population
     and of every haplotype agree within 4.5 standard errors of the respective estimator (stated in the test);
-  * bookkeeping invariants hold exactly on every run (compartment sums, counters vs multievent rows)."""
+  * bookkeeping invariants hold exactly on every run (compartment sums, counters vs multievent rows).
+These are comparisons of aggregates of whole runs between two samples: a channel that carries a per cent of the events can be wrong
+by tens of per cent without moving them.  The law of every single channel (one step from one common state against the analytic
+product of Poissons, per draw path and mean regime) is tested by tests/test_hip_tau_step_law.py with tests/tau_law.py."""
 import numpy as np
 import pytest
 

@@ -102,6 +102,8 @@ SIGNATURES = {
     "vgx_get_lockdowns": (C.c_int, [_H, C.c_int64, C.c_int64, _I, _I, _F, _I]),
     "vgx_get_tau_tries": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32)]),
     "vgx_get_multievents": (C.c_int, [_H, C.c_int64, C.c_int64, _I, _F, _I, _I, _I, _I, _I, _I]),
+    "vgx_get_multievents_all": (C.c_int, [_H, C.c_int64, _I, _I, _I]),
+    "vgx_get_tau_states_all": (C.c_int, [_H, _I, _I, _I, _F]),
     "vgx_get_trajectories": (C.c_int, [_H, C.c_void_p, C.c_int]),
     "vgx_get_trajectories_int": (C.c_int, [_H, C.c_void_p]),
     "vgx_clock_mismatches": (C.c_int64, [_H]),
@@ -315,6 +317,31 @@ class HipEngine:
                                                      _p(cols["newPopulations"]), C.byref(n)))
         cols["times"] = times
         return cols
+
+    def multievents_all(self):
+        """The rows of every replicate of the last tau call in one read-out (``vgx_get_multievents_all``): ``offsets`` [R + 1] and a dict
+        of arrays (num, types, haplotypes, populations, newHaplotypes, newPopulations, steps) in which rows offsets[r]:offsets[r + 1]
+        are replicate r's, in the device's order (``canonical_multievents`` gives the reference's)."""
+        off = np.zeros(self.R + 1, dtype=np.int64)
+        self._check(self.lib.vgx_get_multievents_all(self.handle, 0, _p(off), None, None))
+        n = int(off[-1])
+        rows = np.zeros((max(n, 1), 6), dtype=np.int64)
+        steps = np.zeros(max(n, 1), dtype=np.int64)
+        if n:
+            self._check(self.lib.vgx_get_multievents_all(self.handle, n, _p(off), _p(rows), _p(steps)))
+        cols = {name: np.ascontiguousarray(rows[:n, j]) for j, name in enumerate(("num", "types", "haplotypes", "populations", "newHaplotypes", "newPopulations"))}
+        cols["steps"] = steps[:n]
+        return off, cols
+
+    def tau_states_all(self):
+        """infectious [R, P, H], susceptible [R, P, S], counters [R, 8] (bCounter, dCounter, sCounter, mCounter, iCounter, migPlus,
+        globalInfectious, ev_ptr) and currentTime [R] of every replicate after the last tau call (``vgx_get_tau_states_all``)."""
+        inf = np.zeros((self.R, self.P, self.H), dtype=np.int64)
+        sus = np.zeros((self.R, self.P, self.S), dtype=np.int64)
+        cnt = np.zeros((self.R, 8), dtype=np.int64)
+        t = np.zeros(self.R, dtype=np.float64)
+        self._check(self.lib.vgx_get_tau_states_all(self.handle, _p(inf), _p(sus), _p(cnt), _p(t)))
+        return inf, sus, cnt, t
 
     def counters_all(self):
         """``[R, 4]`` int64: ev_ptr, loop_iterations, restarts, tau events drawn of every replicate."""

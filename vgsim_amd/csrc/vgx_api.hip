@@ -2653,6 +2653,77 @@ extern "C" int vgx_get_multievents(vgx_engine *e, int64_t replicate, int64_t cap
     return VGX_OK;
 }
 
+extern "C" int vgx_get_multievents_all(vgx_engine *e, int64_t cap, int64_t *offsets /* [R + 1] */, int64_t *rows /* [cap][6] */,
+                                       int64_t *steps /* [cap] */) {
+    if (!e || !offsets || cap < 0) return VGX_ERR_ARG;
+    const int64_t R = e->R;
+    for (int64_t r = 0; r <= R; r++) offsets[r] = 0;
+    if (!e->last_was_tau || e->tau_mev_cap <= 0 || (int64_t)e->tau_log.size() < R) return VGX_OK;   // no rows recorded
+    int64_t most = 0;
+    for (int64_t r = 0; r < R; r++) {
+        const auto &lg = e->tau_log[(size_t)r];
+        const int64_t n = lg.empty() ? 0 : lg.back().m1;
+        offsets[r + 1] = offsets[r] + n;
+        most = std::max(most, n);
+    }
+    if (!rows) return VGX_OK;                                                                       // sizing call
+    if (cap < offsets[R]) return fail(e, VGX_ERR_ARG, "vgx_get_multievents_all: room for fewer rows than the call recorded");
+    if (most == 0) return VGX_OK;
+    HIPCHECK(e, hipSetDevice(e->device));
+    const int64_t mev_cap = e->tau_mev_cap;
+    if (most > mev_cap) return fail(e, VGX_ERR_ARG, "vgx_get_multievents_all: a replicate logged more rows than its block holds");
+    // the replicates' row blocks lie mev_cap rows apart on the device: strided copies of the widest block, a batch of replicates at a time
+    const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(R, ((int64_t)1 << 28) / (most * 48)));
+    std::vector<int64_t> buf((size_t)(batch * most * 6));
+    for (int64_t r0 = 0; r0 < R; r0 += batch) {
+        const int64_t nr = std::min(batch, R - r0);
+        HIPCHECK(e, hipMemcpy2D(buf.data(), (size_t)most * 48, (int64_t *)e->t_mev.p + r0 * mev_cap * 6, (size_t)mev_cap * 48, (size_t)most * 48,
+                                (size_t)nr, hipMemcpyDeviceToHost));
+        for (int64_t r = r0; r < r0 + nr; r++) {
+            const int64_t n = offsets[r + 1] - offsets[r];
+            if (n <= 0) continue;
+            memcpy(rows + offsets[r] * 6, buf.data() + (r - r0) * most * 6, (size_t)n * 48);
+            if (steps) {
+                const auto &lg = e->tau_log[(size_t)r];
+                size_t st = 0;
+                for (int64_t i = 0; i < n; i++) {
+                    while (st + 1 < lg.size() && i >= lg[st].m1) st++;
+                    steps[offsets[r] + i] = (int64_t)st;
+                }
+            }
+        }
+    }
+    return VGX_OK;
+}
+
+extern "C" int vgx_get_tau_states_all(vgx_engine *e, int64_t *infectious /* [R][P][H] */, int64_t *susceptible /* [R][P][S] */,
+                                      int64_t *counters /* [R][8] */, double *times /* [R] */) {
+    if (!e) return VGX_ERR_ARG;
+    if (!e->last_was_tau || !e->sc_host_valid) return fail(e, VGX_ERR_ARG, "vgx_get_tau_states_all: the last call was not vgx_simulate_tau");
+    HIPCHECK(e, hipSetDevice(e->device));
+    const int64_t R = e->R, H = e->d.hapNum, P = e->d.popNum, S = e->d.susNum;
+    if (susceptible) HIPCHECK(e, hipMemcpy(susceptible, e->t_S.p, (size_t)(R * P * S) * 8, hipMemcpyDeviceToHost));
+    if (infectious) {
+        const int64_t n = R * P * H, part = std::min<int64_t>(n, (int64_t)1 << 26);
+        std::unique_ptr<int32_t[]> inf32(new int32_t[(size_t)part]);
+        for (int64_t i0 = 0; i0 < n; i0 += part) {
+            const int64_t k = std::min(part, n - i0);
+            HIPCHECK(e, hipMemcpy(inf32.get(), (int32_t *)e->t_I.p + i0, (size_t)k * 4, hipMemcpyDeviceToHost));
+            for (int64_t i = 0; i < k; i++) infectious[i0 + i] = inf32[(size_t)i];
+        }
+    }
+    for (int64_t r = 0; r < R; r++) {
+        const VgxRepScalars &s = e->sc_host[(size_t)r];
+        if (counters) {
+            int64_t *c = counters + r * 8;
+            c[0] = s.bCounter; c[1] = s.dCounter; c[2] = s.sCounter; c[3] = s.mCounter; c[4] = s.iCounter; c[5] = s.migPlus;
+            c[6] = s.globalInfectious; c[7] = s.ev_ptr;
+        }
+        if (times) times[r] = s.currentTime;
+    }
+    return VGX_OK;
+}
+
 extern "C" int vgx_get_trajectories(vgx_engine *e, double *out, int out_is_device) {
     if (!e || !out) return VGX_ERR_ARG;
     if (e->traj_points <= 0) return fail(e, VGX_ERR_ARG, "vgx_get_trajectories: the last call recorded none");

@@ -141,6 +141,20 @@ class Ensemble:
         self.engine.get_state(m, replicate)
         return m
 
+    def replicate_multievents(self):
+        """The multievent rows of every replicate of the last ``simulate_tau(record_events=True)`` call in one read-out:
+        ``(offsets, rows)`` of ``HipEngine.multievents_all`` (rows offsets[r]:offsets[r + 1] are replicate r's)."""
+        if self._last_call != ('tau', True):
+            raise ValueError("replicate_multievents() needs a simulate_tau(record_events=True) call first")
+        return self.engine.multievents_all()
+
+    def replicate_states_tau(self):
+        """infectious, susceptible, counters and currentTime of every replicate after the last ``simulate_tau`` call in one read-out
+        (``HipEngine.tau_states_all``)."""
+        if self._last_call is None or self._last_call[0] != 'tau':
+            raise ValueError("replicate_states_tau() needs a simulate_tau call first")
+        return self.engine.tau_states_all()
+
     def replicate_events(self, replicate):
         """(6, n) float64 event chain of one replicate (needs ``record_events=True``)."""
         from ._model import Events
