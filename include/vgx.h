@@ -26,6 +26,9 @@
  *   VGX_TAU_NO_OCCLIST=1           tau: a try's scan and front pass always stream all compartments (no lists of the occupied ones)
  *   VGX_TAU_NO_FRONT_ALONE=1       tau, one replicate: the front pass is enqueued together with the try proper, not ahead of it
  *   VGX_TAU_LARGE_MODEL_THRESHOLDS=1  tau: the draw thresholds of large models on a small one
+ *   VGX_GENEALOGY_CHUNK_BYTES=n    vgx_get_genealogies: device bytes of workspace per pass (several passes)
+ *   VGX_TIMELINES_LDS_BYTES=n      vgx_get_timelines: LDS budget of a replay workgroup (default 65536, at most 163840; the queries are split over launches)
+ *   VGX_TIMELINES_CHUNK_BYTES=n    vgx_get_timelines: device bytes of staging and outputs per chunk of replicates
  */
 #ifndef VGX_H
 #define VGX_H
@@ -286,6 +289,71 @@ int vgx_genealogy_message(int64_t status, int64_t arg, char *errbuf, int64_t err
 /* Test hook: the walk of vgx_get_genealogies (same code, compiled for the host) on the chain, state and generator of a
  * vgx_genealogy_io; same outputs as vgx_get_genealogy.  Direct chains only: a MULTITYPE event with rows is refused. */
 int vgx_test_genealogy_walk(vgx_genealogy_io *io, char *errbuf, int64_t errcap);
+
+/* ---- log replays ---------------------------------------------------------------------------- */
+/* Replaces BirthDeathModel.get_data_infectious(pop, hap, step_num) / get_data_susceptible(pop, group, step_num) (pyx:1967-2045)
+ * for many replicates of the last vgx_simulate_direct call and many compartments at once, on the device: one pass per
+ * replicate over the device event log in place (the log is not copied to the host).  Event times do not exist on the
+ * device; the host clock (the times vgx_get_events gives) decides only at which event the grid index advances, from the
+ * packed (iteration, rate) logs: 12 bytes per event reach the host, in pinned memory.  Direct chains only: refused after
+ * vgx_simulate_tau (MULTITYPE rows are not replayed here) or a call without an event log; every selected replicate's chain
+ * must start at log index 0 (vgx_counters.ev_first_new == 0).  T = step_num + 1.
+ *   semantics 0 (reference): the reference's replay to the letter, including the operator precedence of pyx:1982 (a DEATH or
+ *     SAMPLING in ANY compartment decrements every infectious series and every SAMPLING counts in every Sample); entries after
+ *     last_point stay 0 as upstream leaves them.
+ *   semantics 1 (compartment): the series of the compartment itself.  Infectious (p, h): BIRTH at (p, h) +1; DEATH / SAMPLING
+ *     at (p, h) -1; MUTATION from (p, h) -1, to (p, newHaplotype) +1; MIGRATION with newPopulation == p, haplotype == h +1;
+ *     Sample: SAMPLING at (p, h).  Susceptible: as the reference.  Entries after last_point repeat the value at last_point.
+ * Every series starts from initial_infectious[pop][hap] / initial_susceptible[pop][group] as the engine holds it (the state an
+ * attempt restarts from).  A query may be given once only.  Two calls:
+ *   1. sizing: time_points == NULL.  Sets loc_cap to the most lockdown records any selected replicate holds (at least 1).
+ *   2. replay: the caller allocates the outputs and calls again with that loc_cap (or a larger one).
+ * The per-bin counters of a launch live in a workgroup's LDS: 4 (step_num + 2 T + (2 n_inf + n_sus) T) bytes and a small
+ * table.  The budget is 64 KiB per workgroup (VGX_TIMELINES_LDS_BYTES changes it, up to the 160 KiB a workgroup may declare);
+ * a call whose queries need more is split over several launches, each re-reading the log.  step_num must leave room for one
+ * query (step_num <= 8000 is safe).  Replicates whose staging and outputs exceed half of the free device memory or 1 GiB (or
+ * VGX_TIMELINES_CHUNK_BYTES) are replayed in several chunks.  vgx_clock_mismatches counts every selected replicate once, as
+ * vgx_get_genealogies does.
+ * The pinned (page-locked) host staging of the packed logs, 12 bytes per event of the largest chunk (up to about 1 GiB at the
+ * default chunk size), is kept by the engine for the next call and freed by vgx_destroy.
+ * A model that had been simulated before (first_simulation != 0) and whose event log was empty when the call started passes the
+ * ev_first_new == 0 condition, but its chain starts from the model's state at that time, not from initial_*: 'reference' still
+ * equals the reference's replay (which starts from initial_* too), 'compartment' then does not end in the final state.
+ * Refusals (VGX_ERR_ARG) carry the wording of Ensemble.timelines' ValueErrors behind "vgx_get_timelines: ". */
+typedef struct vgx_timelines_io {
+    int64_t n;                               /* selected replicates */
+    const int64_t *replicates;               /* [n] */
+    int64_t step_num, semantics;
+    int64_t n_inf; const int64_t *inf_pop, *inf_hap;    /* infectious queries (population, haplotype) */
+    int64_t n_sus; const int64_t *sus_pop, *sus_grp;    /* susceptible queries (population, group) */
+    double *time_points;                     /* [n][T] i * currentTime / step_num of every replicate's own final time */
+    double *inf_data, *inf_sample;           /* [n][n_inf][T] */
+    double *sus_data;                        /* [n][n_sus][T] */
+    int64_t *last_point;                     /* [n] last grid index the replay reached */
+    int64_t loc_cap;                         /* in (replay) / out (sizing): lockdown records per replicate there is room for */
+    int64_t *loc_n, *loc_state, *loc_pop;    /* [n], [n][loc_cap], [n][loc_cap] lockdown records (models.pxi:52-66) */
+    double *loc_time;                        /* [n][loc_cap] their host-clock times */
+    int64_t passes;                          /* out: launches of the replay kernel */
+    double ms[3];                            /* out: pack and replay kernels (device time), host clock, whole call */
+} vgx_timelines_io;
+int vgx_get_timelines(vgx_engine *e, vgx_timelines_io *io);
+/* Test hook: the replay of vgx_get_timelines (same classification, cut rule and query table, compiled for the host) on one
+ * chain given as arrays: no device, no engine.  Direct chains only: a MULTITYPE event with rows is refused. */
+typedef struct vgx_timelines_chain {
+    int64_t popNum, hapNum, susNum;
+    int64_t ev_ptr;
+    const double *ev_times;
+    const int64_t *ev_types, *ev_haplotypes, *ev_populations, *ev_newHaplotypes, *ev_newPopulations;
+    double currentTime;
+    int64_t step_num, semantics;
+    int64_t n_inf; const int64_t *inf_pop, *inf_hap, *inf_start;   /* inf_start[k] = initial_infectious[pop][hap] */
+    int64_t n_sus; const int64_t *sus_pop, *sus_grp, *sus_start;
+    double *time_points;                     /* [T] */
+    double *inf_data, *inf_sample;           /* [n_inf][T] */
+    double *sus_data;                        /* [n_sus][T] */
+    int64_t last_point;
+} vgx_timelines_chain;
+int vgx_test_timelines(vgx_timelines_chain *io, char *errbuf, int64_t errcap);
 
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* Device time of the last simulate call's kernels, from HIP events on the engine's stream (ms). */

@@ -73,6 +73,27 @@ class VgxGenealogiesIO(C.Structure):
                 ("rng_out", C.POINTER(C.c_uint64)), ("layout", C.c_int64), ("passes", C.c_int64), ("ms", C.c_double * 3)]
 
 
+class VgxTimelinesIO(C.Structure):
+    _fields_ = [("n", C.c_int64), ("replicates", _I), ("step_num", C.c_int64), ("semantics", C.c_int64),
+                ("n_inf", C.c_int64), ("inf_pop", _I), ("inf_hap", _I), ("n_sus", C.c_int64), ("sus_pop", _I), ("sus_grp", _I),
+                ("time_points", _F), ("inf_data", _F), ("inf_sample", _F), ("sus_data", _F), ("last_point", _I),
+                ("loc_cap", C.c_int64), ("loc_n", _I), ("loc_state", _I), ("loc_pop", _I), ("loc_time", _F),
+                ("passes", C.c_int64), ("ms", C.c_double * 3)]
+
+
+class VgxTimelinesChain(C.Structure):
+    _fields_ = [("popNum", C.c_int64), ("hapNum", C.c_int64), ("susNum", C.c_int64), ("ev_ptr", C.c_int64),
+                ("ev_times", _F), ("ev_types", _I), ("ev_haplotypes", _I), ("ev_populations", _I),
+                ("ev_newHaplotypes", _I), ("ev_newPopulations", _I),
+                ("currentTime", C.c_double), ("step_num", C.c_int64), ("semantics", C.c_int64),
+                ("n_inf", C.c_int64), ("inf_pop", _I), ("inf_hap", _I), ("inf_start", _I),
+                ("n_sus", C.c_int64), ("sus_pop", _I), ("sus_grp", _I), ("sus_start", _I),
+                ("time_points", _F), ("inf_data", _F), ("inf_sample", _F), ("sus_data", _F), ("last_point", C.c_int64)]
+
+
+TIMELINE_SEMANTICS = {'reference': 0, 'compartment': 1}
+
+
 class VgxRowScan(C.Structure):
     _fields_ = [("rows", C.c_int64), ("H", C.c_int64), ("S", C.c_int64), ("infectious", _I), ("eventRates123", _F),
                 ("numToHap", _I), ("bRate", _F), ("susceptibility", _F), ("rowSusceptible", _F), ("rowContact", _F), ("u", _F),
@@ -117,6 +138,8 @@ SIGNATURES = {
     "vgx_get_genealogies": (C.c_int, [_H, C.POINTER(VgxGenealogiesIO)]),
     "vgx_genealogy_message": (C.c_int, [C.c_int64, C.c_int64, C.c_char_p, C.c_int64]),
     "vgx_test_genealogy_walk": (C.c_int, [C.POINTER(VgxGenealogyIO), C.c_char_p, C.c_int64]),
+    "vgx_get_timelines": (C.c_int, [_H, C.POINTER(VgxTimelinesIO)]),
+    "vgx_test_timelines": (C.c_int, [C.POINTER(VgxTimelinesChain), C.c_char_p, C.c_int64]),
     "vgx_rng_position": (None, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64 * 4)]),
     "vgx_propensity_scan": (C.c_int, [C.POINTER(VgxRowScan)]),
     "vgx_propensity_scan_bench": (C.c_int, [C.POINTER(VgxRowScan), C.c_int64, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -230,12 +253,14 @@ class HipEngine:
             setattr(s, c, int(getattr(m, c)))
         s.currentTime, s.totalRate, s.totalMigrationRate, s.tau_l = m.currentTime, m.totalRate, m.totalMigrationRate, m.tau_l
         s.ev_ptr, s.ev_size = m.events.ptr, m.events.size
-        self._first_call = bool(m.first_simulation)     # (the call after this snapshots the initial state: get_state reads it back then only)
+        # upstream's first_simulation is False until the first simulation (pyx:76, 435-448): the call after this one snapshots the
+        # initial state exactly then, and get_state reads it back after that call only
+        self._snapshot_call = not bool(m.first_simulation)
         self._check(self.lib.vgx_set_state(self.handle, C.byref(s)))
 
     def get_state(self, m, replicate=0):
         s = self._state_struct(m)
-        if not getattr(self, "_first_call", True):
+        if not getattr(self, "_snapshot_call", True):
             # the initial state is written by the first simulation's snapshot alone (pyx:419-424): at config 4's size copying it back
             # after every call is 2 GB of memcpy for nothing
             s.initial_susceptible = None
@@ -529,6 +554,54 @@ def _genealogy(entry, m, seed, rng_position, rng_raw):
     out["nodes_used"] = int(io.nodes_used)
     out["rng_raw"] = tuple(int(io.rng_state[i]) for i in range(4)) + (int(io.rng_has_uint32), int(io.rng_uinteger))
     return out
+
+
+def unique_queries(pairs):
+    """(unique pairs as an (k, 2) int64 array in first-seen order, index of every given pair among them)."""
+    seen, uniq, index = {}, [], []
+    for a, b in pairs:
+        key = (int(a), int(b))
+        if key not in seen:
+            seen[key] = len(uniq)
+            uniq.append(key)
+        index.append(seen[key])
+    return np.asarray(uniq, dtype=np.int64).reshape(-1, 2), np.asarray(index, dtype=np.int64)
+
+
+def replay_timelines(m, infectious=(), susceptible=(), step_num=100, semantics='reference'):
+    """The log replays of ``Ensemble.timelines`` for one host model through ``vgx_test_timelines``: the device replay's code
+    (vgx_tline.h) compiled for the host, on ``m.events``, ``m.currentTime`` and ``m.initial_*`` (direct chains only; no GPU).
+    Returns a dict: ``time_points`` [T], ``infectious`` / ``samples`` [Ki, T], ``susceptible`` [Ks, T], ``last_point``."""
+    if semantics not in TIMELINE_SEMANTICS:
+        raise ValueError("semantics must be 'reference' or 'compartment'")
+    lib = load_library()
+    ev = m.events
+    qi, ii = unique_queries(infectious)
+    qs, si = unique_queries(susceptible)
+    T = int(step_num) + 1
+    io = VgxTimelinesChain()
+    io.popNum, io.hapNum, io.susNum, io.ev_ptr = m.popNum, m.hapNum, m.susNum, int(ev.ptr)
+    io.ev_times, io.ev_types, io.ev_haplotypes = _p(ev.times), _p(ev.types), _p(ev.haplotypes)
+    io.ev_populations, io.ev_newHaplotypes, io.ev_newPopulations = _p(ev.populations), _p(ev.newHaplotypes), _p(ev.newPopulations)
+    io.currentTime, io.step_num, io.semantics = float(m.currentTime), int(step_num), TIMELINE_SEMANTICS[semantics]
+
+    def start(q, table, width):
+        ok = (q[:, 0] >= 0) & (q[:, 0] < m.popNum) & (q[:, 1] >= 0) & (q[:, 1] < width)   # (the library refuses the others)
+        out = np.zeros(len(q), dtype=np.int64)
+        out[ok] = np.asarray(table, dtype=np.int64)[q[ok, 0], q[ok, 1]]
+        return out
+    keep = [np.ascontiguousarray(qi[:, 0]), np.ascontiguousarray(qi[:, 1]), start(qi, m.initial_infectious, m.hapNum),
+            np.ascontiguousarray(qs[:, 0]), np.ascontiguousarray(qs[:, 1]), start(qs, m.initial_susceptible, m.susNum)]
+    io.n_inf, io.inf_pop, io.inf_hap, io.inf_start = len(qi), _p(keep[0]), _p(keep[1]), _p(keep[2])
+    io.n_sus, io.sus_pop, io.sus_grp, io.sus_start = len(qs), _p(keep[3]), _p(keep[4]), _p(keep[5])
+    tp = np.zeros(T)
+    inf, smp, sus = np.zeros((max(len(qi), 1), T)), np.zeros((max(len(qi), 1), T)), np.zeros((max(len(qs), 1), T))
+    io.time_points, io.inf_data, io.inf_sample, io.sus_data = _p(tp), _p(inf), _p(smp), _p(sus)
+    err = C.create_string_buffer(512)
+    if lib.vgx_test_timelines(C.byref(io), err, 512) != 0:
+        raise ValueError(err.value.decode() or "vgx_test_timelines failed")
+    return {"time_points": tp, "infectious": inf[:len(qi)][ii], "samples": smp[:len(qi)][ii], "susceptible": sus[:len(qs)][si],
+            "last_point": int(io.last_point)}
 
 
 def propensity_scan(infectious, rates123, numToHap, bRate, susceptibility, rowSusceptible, rowContact, u, bench_rows=0, repeats=3):

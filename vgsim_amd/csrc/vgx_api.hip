@@ -24,6 +24,8 @@
 #include "vgx_lone.h"
 #include "vgx_rng.h"
 #include "vgx_gwalk.h"
+#include "vgx_tline.h"
+#include "vgx_timelines.h"
 
 // launchers defined next to their kernels (vgx_direct.hip)
 extern "C" hipError_t vgxi_launch_direct(const VgxDirectArgs *a, size_t lds, hipStream_t stream);
@@ -46,6 +48,9 @@ extern "C" hipError_t vgxi_launch_lone(const VgxDirectArgs *a, const VgxLoneArgs
 extern "C" hipError_t vgxi_gw_count(const int32_t *log, int64_t evcap, const int64_t *reps, const int64_t *n_ev, int64_t n, int64_t *out,
                                     hipStream_t s);
 extern "C" hipError_t vgxi_gw_walk(const VgxGwLaunch *a, int wave, hipStream_t s);
+extern "C" hipError_t vgxi_tl_pack(const int32_t *log, const double *evrate, int64_t evcap, const int64_t *rep, const int32_t *n_ev,
+                                   const int64_t *off, int64_t m, int64_t max_n, int32_t *iter_out, double *rate_out, hipStream_t s);
+extern "C" hipError_t vgxi_tl_replay(const VgxTlLaunch *a, hipStream_t s);
 extern "C" hipError_t vgxi_launch_counts32(const int64_t *c64, int32_t *c32, int64_t n, hipStream_t stream);
 extern "C" hipError_t vgxi_launch_init_reps(const VgxDevRep *r, int P, int S, int64_t R, const int32_t *s_nocc,
                                             const int32_t *s_hap, const int32_t *s_cls, const int64_t *s_cnt,
@@ -87,6 +92,8 @@ struct vgx_engine {
     int64_t start_max_nocc = 0;    // longest occupancy list of the state last uploaded
     int64_t start_lone_rows = 0;   // heap rows of vgx_lone.hip that state (and the Restart snapshot) needs at least
     void *pin[2] = {nullptr, nullptr};   // pinned staging buffers of large uploads (VGX_PIN_BYTES each), allocated on first use
+    void *pin_tl = nullptr;               // pinned staging of vgx_get_timelines (packed iteration and rate logs), kept between calls
+    size_t pin_tl_bytes = 0;
     void *pin_tau = nullptr;              // pinned mirror of what the tau step loop reads after every try and step (flags, the finish kernel's record)
     size_t pin_tau_bytes = 0;
     hipEvent_t pin_ev[2] = {nullptr, nullptr};
@@ -276,6 +283,7 @@ extern "C" void vgx_destroy(vgx_engine *e) {
         if (e->pin_ev[i]) (void)hipEventDestroy(e->pin_ev[i]);
     }
     if (e->pin_tau) (void)hipHostFree(e->pin_tau);
+    if (e->pin_tl) (void)hipHostFree(e->pin_tl);
     if (e->ev0) (void)hipEventDestroy(e->ev0);
     if (e->ev1) (void)hipEventDestroy(e->ev1);
     if (e->stream) (void)hipStreamDestroy(e->stream);
@@ -2392,7 +2400,10 @@ struct ClockRun {      // accumulates one attempt's clock
             return VGX_ERR_HIP;                                                                        \
         }                                                                                              \
     } while (0)
-static int clock_build(const vgx_engine *e, int64_t rep, vgx_engine::HostClock &hc, std::string &err) {
+// `staged`: the replicate's rate log and iteration indices already on the host (vgx_get_timelines packs them on the device and
+// copies them to pinned memory); without it they are copied out of the device log here.
+struct ClockStaged { const double *rate; const int32_t *iter; };
+static int clock_build(const vgx_engine *e, int64_t rep, vgx_engine::HostClock &hc, std::string &err, const ClockStaged *staged = nullptr) {
     const VgxRepScalars &s = e->sc_host[(size_t)rep];
     hc.rep = -1;
     hc.times.clear();
@@ -2449,9 +2460,18 @@ static int clock_build(const vgx_engine *e, int64_t rep, vgx_engine::HostClock &
     } else {
         const int64_t slot0 = hc.e0 - e->ev_base;
         if (slot0 < 0 || slot0 + n > e->evcap) { err = "host_clock: event range outside the device log"; return VGX_ERR_ARG; }
-        std::vector<double> rate((size_t)n);
-        std::vector<int32_t> cols((size_t)n * VGX_EV_COLS);
-        if (n > 0) {
+        std::vector<double> rate;
+        std::vector<int32_t> cols;
+        const double *rate_p = staged ? staged->rate : nullptr;
+        const int32_t *iter_p = staged ? staged->iter : nullptr;   // the iteration index of event k is iter_p[k * iter_stride]
+        const int64_t iter_stride = staged ? 1 : VGX_EV_COLS;
+        if (!staged) {
+            rate.resize((size_t)n);
+            cols.resize((size_t)n * VGX_EV_COLS);
+            rate_p = rate.data();
+            iter_p = cols.data() + 5;
+        }
+        if (n > 0 && !staged) {
             CLOCKCHECK(hipMemcpy(rate.data(), (double *)e->r_evrate.p + rep * e->evcap + slot0, (size_t)n * 8, hipMemcpyDeviceToHost));
             CLOCKCHECK(hipMemcpy(cols.data(), (int32_t *)e->r_evcols.p + (rep * e->evcap + slot0) * VGX_EV_COLS,
                                   (size_t)n * VGX_EV_COLS * 4, hipMemcpyDeviceToHost));
@@ -2466,14 +2486,14 @@ static int clock_build(const vgx_engine *e, int64_t rep, vgx_engine::HostClock &
         int64_t it = 0;
         for (int64_t k = 0; k < n; k++) {
             // iteration index: 32 bits logged, strictly increasing
-            const uint32_t lo = (uint32_t)cols[(size_t)(k * VGX_EV_COLS + 5)];
+            const uint32_t lo = (uint32_t)iter_p[(size_t)(k * iter_stride)];
             it += (int64_t)(uint32_t)(lo - (uint32_t)it);
             if (e->call_has_tlimit && it > c.iter + 1) {   // loop condition of the iterations without a record (pyx:407)
                 ClockRun probe = c;
-                probe.advance(it - 1, rate[(size_t)k]);
+                probe.advance(it - 1, rate_p[(size_t)k]);
                 if (!(probe.t < e->call_tlimit)) limit_ok = false;
             }
-            c.advance(it, rate[(size_t)k]);
+            c.advance(it, rate_p[(size_t)k]);
             hc.times[(size_t)k] = c.t;
             if (e->call_has_tlimit && k + 1 < n && !(c.t < e->call_tlimit)) limit_ok = false;
             while (li < nloc && (loc_key[(size_t)li] >> 40) == s.last_attempt && (loc_key[(size_t)li] & IT) == it) {
@@ -3069,6 +3089,256 @@ extern "C" int vgx_get_genealogies(vgx_engine *e, vgx_genealogies_io *io) {
             if (rcs[(size_t)j]) return fail(e, rcs[(size_t)j], errs[(size_t)j]);
         io->ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_clock).count();
         io->passes += 1;
+        i0 = i1;
+    }
+    // every replicate's clock was built once, as when the replicates are fetched one by one
+    for (int64_t i = 0; i < n; i++) e->clock_mismatches += mism[(size_t)i];
+    io->ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+    return VGX_OK;
+}
+
+// ---- log replays of many replicates on the device (vgx_timelines.hip, vgx_tline.h) ------------------------------------------
+// The split of vgx_get_genealogies: the host runs every replicate's clock, here from the packed (iteration, rate)
+// logs in pinned memory, and turns the times into step_num event indices per replicate; the device does the rest over the log
+// in place.
+extern "C" int vgx_get_timelines(vgx_engine *e, vgx_timelines_io *io) {
+    if (!e || !io || io->n < 0 || (io->n > 0 && !io->replicates) || io->n_inf < 0 || io->n_sus < 0) return VGX_ERR_ARG;
+    const auto t_call = std::chrono::steady_clock::now();
+    io->passes = 0;
+    io->ms[0] = io->ms[1] = io->ms[2] = 0.0;
+    if (!e->sc_host_valid || !e->dev_state_valid) return fail(e, VGX_ERR_ARG, "vgx_get_timelines: needs a direct vgx_simulate_direct call with the event log first");
+    if (e->last_was_tau) return fail(e, VGX_ERR_ARG, "vgx_get_timelines: the last call was vgx_simulate_tau (replays direct chains only)");
+    if (!e->call_recorded) return fail(e, VGX_ERR_ARG, "vgx_get_timelines: the last call did not record events");
+    const int64_t n = io->n, P = e->d.popNum, H = e->d.hapNum, S = e->d.susNum, step = io->step_num, T = step + 1;
+    const int64_t n_inf = io->n_inf, n_sus = io->n_sus;
+    if (step < 1) return fail(e, VGX_ERR_ARG, "vgx_get_timelines: step_num must be at least 1");
+    if (io->semantics != VGX_TL_REFERENCE && io->semantics != VGX_TL_COMPARTMENT)
+        return fail(e, VGX_ERR_ARG, "vgx_get_timelines: semantics must be 0 (reference) or 1 (compartment)");
+    if ((n_inf > 0 && (!io->inf_pop || !io->inf_hap)) || (n_sus > 0 && (!io->sus_pop || !io->sus_grp)) || n_inf + n_sus >= ((int64_t)1 << 20))
+        return fail(e, VGX_ERR_ARG, "vgx_get_timelines: bad query list");
+    {
+        std::vector<std::pair<int64_t, int64_t>> qi, qs;
+        for (int64_t k = 0; k < n_inf; k++) {
+            if (io->inf_pop[k] < 0 || io->inf_pop[k] >= P) return fail(e, VGX_ERR_ARG, "vgx_get_timelines: population index out of range");
+            if (io->inf_hap[k] < 0 || io->inf_hap[k] >= H) return fail(e, VGX_ERR_ARG, "vgx_get_timelines: haplotype index out of range");
+            qi.emplace_back(io->inf_pop[k], io->inf_hap[k]);
+        }
+        for (int64_t k = 0; k < n_sus; k++) {
+            if (io->sus_pop[k] < 0 || io->sus_pop[k] >= P) return fail(e, VGX_ERR_ARG, "vgx_get_timelines: population index out of range");
+            if (io->sus_grp[k] < 0 || io->sus_grp[k] >= S) return fail(e, VGX_ERR_ARG, "vgx_get_timelines: susceptibility group index out of range");
+            qs.emplace_back(io->sus_pop[k], io->sus_grp[k]);
+        }
+        std::sort(qi.begin(), qi.end());
+        std::sort(qs.begin(), qs.end());
+        if (std::adjacent_find(qi.begin(), qi.end()) != qi.end() || std::adjacent_find(qs.begin(), qs.end()) != qs.end())
+            return fail(e, VGX_ERR_ARG, "vgx_get_timelines: a query is given twice");
+    }
+    std::vector<int32_t> n_ev((size_t)n);
+    int64_t loc_need = 1;
+    {
+        std::vector<char> seen((size_t)e->R, 0);
+        for (int64_t i = 0; i < n; i++) {
+            const int64_t r = io->replicates[i];
+            if (r < 0 || r >= e->R) return fail(e, VGX_ERR_ARG, "vgx_get_timelines: replicate index out of range");
+            if (seen[(size_t)r]) return fail(e, VGX_ERR_ARG, "vgx_get_timelines: replicates must be distinct");
+            seen[(size_t)r] = 1;
+            const VgxRepScalars &s = e->sc_host[(size_t)r];
+            const int64_t first = s.restarts > 0 ? 0 : ((size_t)r < e->call_ev0.size() ? e->call_ev0[(size_t)r] : e->ev_ptr0);
+            if (first != 0 || e->ev_base != 0)
+                return fail(e, VGX_ERR_ARG, "vgx_get_timelines: replicate " + std::to_string(r) + ": its chain does not start in the last call's device log (the model held " +
+                                                std::to_string(e->ev_base != 0 ? e->ev_base : first) + " events when the ensemble started)");
+            if (s.ev_ptr < 0 || s.ev_ptr > e->evcap || s.ev_ptr >= ((int64_t)1 << 30))
+                return fail(e, VGX_ERR_ARG, "vgx_get_timelines: event range of replicate " + std::to_string(r) + " outside the device log");
+            n_ev[(size_t)i] = (int32_t)s.ev_ptr;
+            loc_need = std::max(loc_need, std::min<int64_t>(s.loc_n, e->loc_cap));
+        }
+    }
+    if (!io->time_points) {   // sizing
+        io->loc_cap = loc_need;
+        io->ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+        return VGX_OK;
+    }
+    if (n == 0) {
+        io->ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+        return VGX_OK;
+    }
+    if (!io->last_point || !io->loc_n || !io->loc_state || !io->loc_pop || !io->loc_time || (n_inf > 0 && (!io->inf_data || !io->inf_sample)) ||
+        (n_sus > 0 && !io->sus_data))
+        return fail(e, VGX_ERR_ARG, "vgx_get_timelines: null output");
+    if (io->loc_cap < loc_need) return fail(e, VGX_ERR_ARG, "vgx_get_timelines: loc_cap smaller than the sizing call gave");
+    const int64_t loc_cap = io->loc_cap;
+
+    // the queries of every launch: as many as the LDS budget holds, infectious ones first
+    int64_t budget = VGX_TL_LDS_DEFAULT;
+    if (const char *lb = getenv("VGX_TIMELINES_LDS_BYTES")) budget = std::min<int64_t>(std::max<int64_t>(atoll(lb), 1), VGX_TL_LDS_MAX);
+    const int64_t need1 = std::max(n_inf > 0 ? vgx_tl_lds_bytes(step, 1, 0) : 0, n_sus > 0 ? vgx_tl_lds_bytes(step, 0, 1) : vgx_tl_lds_bytes(step, 0, 0));
+    if (need1 > VGX_TL_LDS_MAX)
+        return fail(e, VGX_ERR_ARG, "vgx_get_timelines: step_num " + std::to_string(step) + " is too large: the counters of one query exceed a workgroup's LDS");
+    budget = std::max(budget, need1);
+    struct Group { int64_t i0, ni, s0, ns, tab_off, start_off; };
+    std::vector<Group> groups;
+    std::vector<int32_t> h_tab;
+    std::vector<int64_t> h_start;
+    for (int64_t i = 0, s = 0; i < n_inf || s < n_sus;) {
+        Group g{i, 0, s, 0, (int64_t)h_tab.size(), (int64_t)h_start.size()};
+        while (i + g.ni < n_inf && vgx_tl_lds_bytes(step, g.ni + 1, g.ns) <= budget) g.ni++;
+        while (s + g.ns < n_sus && vgx_tl_lds_bytes(step, g.ni, g.ns + 1) <= budget) g.ns++;
+        const int ts = vgx_tl_table_size((int)(g.ni + g.ns));
+        h_tab.resize(h_tab.size() + (size_t)(3 * ts), -1);
+        int32_t *tab = h_tab.data() + g.tab_off;
+        for (int64_t k = 0; k < g.ni; k++) {
+            vgx_tl_insert(tab, ts, 0, (int32_t)io->inf_pop[i + k], (int32_t)io->inf_hap[i + k], (int32_t)k);
+            h_start.push_back(e->hs.initial_infectious[(size_t)(io->inf_pop[i + k] * H + io->inf_hap[i + k])]);
+        }
+        for (int64_t k = 0; k < g.ns; k++) {
+            vgx_tl_insert(tab, ts, 1, (int32_t)io->sus_pop[s + k], (int32_t)io->sus_grp[s + k], (int32_t)(2 * g.ni + k));
+            h_start.push_back(e->hs.initial_susceptible[(size_t)(io->sus_pop[s + k] * S + io->sus_grp[s + k])]);
+        }
+        groups.push_back(g);
+        i += g.ni;
+        s += g.ns;
+    }
+    HIPCHECK(e, hipSetDevice(e->device));
+    auto up8 = [](int64_t b) { return (b + 255) / 256 * 256; };
+    auto dev_free = [](char *p) { (void)hipFree(p); };
+    char *qws = nullptr;
+    const int64_t q_tab = 0, q_start = up8((int64_t)h_tab.size() * 4 + 8), q_total = q_start + up8((int64_t)h_start.size() * 8 + 8);
+    hipError_t er = hipMalloc((void **)&qws, (size_t)q_total);
+    if (er != hipSuccess) return fail(e, VGX_ERR_HIP, std::string("vgx_get_timelines: hipMalloc: ") + hipGetErrorString(er));
+    std::unique_ptr<char, void (*)(char *)> qhold(qws, dev_free);
+    if (!h_tab.empty()) HIPCHECK(e, hipMemcpy(qws + q_tab, h_tab.data(), h_tab.size() * 4, hipMemcpyHostToDevice));
+    if (!h_start.empty()) HIPCHECK(e, hipMemcpy(qws + q_start, h_start.data(), h_start.size() * 8, hipMemcpyHostToDevice));
+
+    // chunks of replicates: packed logs, cuts and outputs of a chunk fit `share` bytes of device memory (and 12 bytes per event
+    // of pinned host memory)
+    size_t free_b = 0, total_b = 0;
+    HIPCHECK(e, hipMemGetInfo(&free_b, &total_b));
+    int64_t share = std::min<int64_t>((int64_t)(free_b / 2), (int64_t)1 << 30);
+    if (const char *cb = getenv("VGX_TIMELINES_CHUNK_BYTES")) share = std::min<int64_t>(share, std::max<int64_t>(atoll(cb), 1));
+    const int64_t out_row = (2 * n_inf + n_sus) * T * 8;
+    std::vector<int64_t> mism((size_t)n, 0);
+    int64_t i0 = 0;
+    while (i0 < n) {
+        int64_t i1 = i0, sum = 0, E = 0, max_n = 0;
+        while (i1 < n && i1 - i0 < ((int64_t)1 << 20)) {
+            const int64_t b = (int64_t)n_ev[(size_t)i1] * 12 + step * 4 + out_row + 64;
+            if (i1 > i0 && sum + b > share) break;
+            sum += b;
+            E += n_ev[(size_t)i1];
+            max_n = std::max<int64_t>(max_n, n_ev[(size_t)i1]);
+            i1++;
+        }
+        const int64_t m = i1 - i0;
+        std::vector<int64_t> off((size_t)m), reps(io->replicates + i0, io->replicates + i1);
+        for (int64_t j = 0, o = 0; j < m; j++) { off[(size_t)j] = o; o += n_ev[(size_t)(i0 + j)]; }
+        // one allocation: [rep | n_ev | last | off | cut | iter | rate | inf | smp | sus]
+        const int64_t o_rep = 0, o_nev = o_rep + up8(m * 8), o_last = o_nev + up8(m * 4), o_off = o_last + up8(m * 4), o_cut = o_off + up8(m * 8),
+                      o_iter = o_cut + up8(m * step * 4), o_rate = o_iter + up8(E * 4), o_inf = o_rate + up8(E * 8),
+                      o_smp = o_inf + up8(m * n_inf * T * 8), o_sus = o_smp + up8(m * n_inf * T * 8), total = o_sus + up8(m * n_sus * T * 8);
+        char *ws = nullptr;
+        er = hipMalloc((void **)&ws, (size_t)total);
+        if (er != hipSuccess)
+            return fail(e, VGX_ERR_HIP, "vgx_get_timelines: hipMalloc of " + std::to_string(total) + " bytes: " + hipGetErrorString(er));
+        std::unique_ptr<char, void (*)(char *)> hold(ws, dev_free);
+        const int64_t pin_iter = 0, pin_rate = up8(E * 4), pin_need = pin_rate + up8(E * 8);
+        if ((int64_t)e->pin_tl_bytes < pin_need) {
+            if (e->pin_tl) (void)hipHostFree(e->pin_tl);
+            e->pin_tl = nullptr; e->pin_tl_bytes = 0;
+            HIPCHECK(e, hipHostMalloc(&e->pin_tl, (size_t)pin_need, hipHostMallocDefault));
+            e->pin_tl_bytes = (size_t)pin_need;
+        }
+        const int32_t *h_iter = (const int32_t *)((char *)e->pin_tl + pin_iter);
+        const double *h_rate = (const double *)((char *)e->pin_tl + pin_rate);
+        HIPCHECK(e, hipMemcpyAsync(ws + o_rep, reps.data(), (size_t)m * 8, hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(ws + o_nev, n_ev.data() + i0, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(ws + o_off, off.data(), (size_t)m * 8, hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
+        HIPCHECK(e, vgxi_tl_pack((const int32_t *)e->r_evcols.p, (const double *)e->r_evrate.p, e->evcap, (const int64_t *)(ws + o_rep),
+                                 (const int32_t *)(ws + o_nev), (const int64_t *)(ws + o_off), m, max_n, (int32_t *)(ws + o_iter),
+                                 (double *)(ws + o_rate), e->stream));
+        HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
+        if (E > 0) {
+            HIPCHECK(e, hipMemcpyAsync(e->pin_tl, ws + o_iter, (size_t)E * 4, hipMemcpyDeviceToHost, e->stream));
+            HIPCHECK(e, hipMemcpyAsync((char *)e->pin_tl + pin_rate, ws + o_rate, (size_t)E * 8, hipMemcpyDeviceToHost, e->stream));
+        }
+        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)
+            return fail(e, VGX_ERR_HIP, std::string("vgx_get_timelines: pack kernel failed: ") + hipGetErrorString(er));
+        float kms = 0.f;
+        HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
+        io->ms[0] += kms;
+        // host: every replicate's clock -> time_points, cuts, last_point, lockdown times (one replicate per thread at a time)
+        const auto t_clock = std::chrono::steady_clock::now();
+        std::vector<int32_t> cuts((size_t)(m * step)), last((size_t)m);
+        std::vector<std::string> errs((size_t)m);
+        std::vector<int> rcs((size_t)m, 0);
+        for_parts(m, [&](int64_t j0, int64_t j1, unsigned) {
+            if (hipSetDevice(e->device) != hipSuccess) { for (int64_t j = j0; j < j1; j++) { rcs[(size_t)j] = VGX_ERR_HIP; errs[(size_t)j] = "hipSetDevice"; } return; }
+            vgx_engine::HostClock hc;
+            std::vector<int32_t> rec;
+            for (int64_t j = j0; j < j1; j++) {
+                const int64_t gi = i0 + j, r = reps[(size_t)j], ne = n_ev[(size_t)gi];
+                const ClockStaged st{h_rate + off[(size_t)j], h_iter + off[(size_t)j]};
+                int rc = clock_build(e, r, hc, errs[(size_t)j], &st);
+                if (rc) { rcs[(size_t)j] = rc; continue; }
+                if ((int64_t)hc.times.size() != ne) {
+                    rcs[(size_t)j] = VGX_ERR_ARG;
+                    errs[(size_t)j] = "vgx_get_timelines: the host clock of replicate " + std::to_string(r) + " does not cover its chain";
+                    continue;
+                }
+                mism[(size_t)gi] = hc.limit_mismatch ? 1 : 0;
+                double *tp = io->time_points + gi * T;
+                vgx_tl_time_points(hc.final_time, step, tp);
+                VgxTlCutter ct{tp, step, cuts.data() + j * step};
+                for (int64_t k = 0; k < ne; k++) ct.event(k, hc.times[(size_t)k]);
+                const int64_t lp = ct.finish(ne);
+                last[(size_t)j] = (int32_t)lp;
+                io->last_point[gi] = lp;
+                const int64_t nloc = std::min<int64_t>(std::min<int64_t>(e->sc_host[(size_t)r].loc_n, e->loc_cap), (int64_t)hc.loc_times.size());
+                io->loc_n[gi] = nloc;
+                if (nloc > 0) {
+                    rec.resize((size_t)nloc * 2);
+                    hipError_t he = hipMemcpy(rec.data(), (int32_t *)e->r_locrec.p + r * e->loc_cap * 2, (size_t)nloc * 8, hipMemcpyDeviceToHost);
+                    if (he != hipSuccess) { rcs[(size_t)j] = VGX_ERR_HIP; errs[(size_t)j] = std::string("vgx_get_timelines: lockdown records: ") + hipGetErrorString(he); continue; }
+                    for (int64_t k = 0; k < nloc; k++) {
+                        io->loc_state[gi * loc_cap + k] = rec[(size_t)(2 * k)];
+                        io->loc_pop[gi * loc_cap + k] = rec[(size_t)(2 * k + 1)];
+                        io->loc_time[gi * loc_cap + k] = hc.loc_times[(size_t)k];
+                    }
+                }
+            }
+        }, std::max<int64_t>(E / std::max<int64_t>(m, 1), 1) * 64);
+        for (int64_t j = 0; j < m; j++)
+            if (rcs[(size_t)j]) return fail(e, rcs[(size_t)j], errs[(size_t)j]);
+        io->ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_clock).count();
+        // device: the replay, one launch per group of queries
+        HIPCHECK(e, hipMemcpyAsync(ws + o_cut, cuts.data(), (size_t)(m * step) * 4, hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(ws + o_last, last.data(), (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
+        for (const Group &g : groups) {
+            VgxTlLaunch a{};
+            a.m = m;
+            a.log = (const int32_t *)e->r_evcols.p; a.evcap = e->evcap;
+            a.rep = (const int64_t *)(ws + o_rep); a.n_ev = (const int32_t *)(ws + o_nev); a.last = (const int32_t *)(ws + o_last);
+            a.cut = (const int32_t *)(ws + o_cut);
+            a.step = (int)step; a.semantics = (int)io->semantics;
+            a.ni = (int)g.ni; a.ns = (int)g.ns; a.i0 = (int)g.i0; a.s0 = (int)g.s0; a.n_inf = (int)n_inf; a.n_sus = (int)n_sus;
+            a.tsize = vgx_tl_table_size((int)(g.ni + g.ns));
+            a.tab = (const int32_t *)(qws + q_tab) + g.tab_off;
+            a.start = (const int64_t *)(qws + q_start) + g.start_off;
+            a.inf = (double *)(ws + o_inf); a.smp = (double *)(ws + o_smp); a.sus = (double *)(ws + o_sus);
+            HIPCHECK(e, vgxi_tl_replay(&a, e->stream));
+            io->passes += 1;
+        }
+        HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
+        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)
+            return fail(e, VGX_ERR_HIP, std::string("vgx_get_timelines: replay kernel failed: ") + hipGetErrorString(er));
+        HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
+        io->ms[0] += kms;
+        if (n_inf > 0) {
+            HIPCHECK(e, hipMemcpy(io->inf_data + i0 * n_inf * T, ws + o_inf, (size_t)(m * n_inf * T) * 8, hipMemcpyDeviceToHost));
+            HIPCHECK(e, hipMemcpy(io->inf_sample + i0 * n_inf * T, ws + o_smp, (size_t)(m * n_inf * T) * 8, hipMemcpyDeviceToHost));
+        }
+        if (n_sus > 0) HIPCHECK(e, hipMemcpy(io->sus_data + i0 * n_sus * T, ws + o_sus, (size_t)(m * n_sus * T) * 8, hipMemcpyDeviceToHost));
         i0 = i1;
     }
     // every replicate's clock was built once, as when the replicates are fetched one by one

@@ -251,6 +251,84 @@ class Ensemble:
         b.passes, b.kernel_ms, b.clock_ms, b.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
         return b
 
+    def timelines(self, infectious=(), susceptible=(), step_num=100, replicates=None, semantics='reference'):
+        """The log replays ``get_data_infectious(pop, hap, step_num)`` / ``get_data_susceptible(pop, group, step_num)``
+        (pyx:1967-2045) of every selected replicate of the last direct ``simulate(record_events=True)`` call for a list of
+        compartments at once, on the device (``vgx_get_timelines``): one pass per replicate over its log where the kernel left
+        it.  Returns a :class:`TimelineBatch`.
+
+        ``infectious``: ``(population, haplotype)`` pairs; ``susceptible``: ``(population, group)`` pairs (either may be empty;
+        a pair given twice gets the same row twice).  ``replicates``: indices (default all, in order).  ``semantics``:
+        'reference' is the reference's replay to the letter, including the operator precedence of pyx:1982 (a recovery or
+        sampling in ANY compartment decrements every infectious series, every sampling counts in every ``Sample``) and zeros
+        after the last grid index the replay reached; 'compartment' is the series of the compartment itself (births,
+        recoveries, samplings, mutations out of and into it, migrations into it; ``Sample`` its own samplings), the value at
+        the last reached index repeated after it: its ``Data[last_point]`` is the replicate's final state.  Every series
+        starts from the replicate's ``initial_infectious`` / ``initial_susceptible``: for a model that had been simulated before and
+        whose event log was empty when the ensemble started, that is not where the chain starts ('reference' still equals the
+        reference's replay, 'compartment' then does not end in the final state).  Direct chains only: tau chains (MULTITYPE rows)
+        are not replayed here."""
+        if self._last_call is None:
+            raise ValueError("timelines() needs a direct simulate(record_events=True) call first")
+        if self._last_call[0] != 'direct':
+            raise ValueError("timelines() replays direct chains only: the last call was simulate_tau")
+        if not self._last_call[1]:
+            raise ValueError("timelines() needs the event log: the last call had record_events=False")
+        if semantics not in _capi.TIMELINE_SEMANTICS:
+            raise ValueError("semantics must be 'reference' or 'compartment'")
+        step_num = int(step_num)
+        if step_num < 1:
+            raise ValueError("step_num must be at least 1")
+        m, eng, lib = self.model, self.engine, self.engine.lib
+        qi, ii = _capi.unique_queries(infectious)
+        qs, si = _capi.unique_queries(susceptible)
+        for q, width, what in ((qi, m.hapNum, "haplotype"), (qs, m.susNum, "susceptibility group")):
+            if len(q) and (q[:, 0].min() < 0 or q[:, 0].max() >= m.popNum):
+                raise ValueError("population index out of range")
+            if len(q) and (q[:, 1].min() < 0 or q[:, 1].max() >= width):
+                raise ValueError("%s index out of range" % what)
+        reps = np.arange(self.R, dtype=np.int64) if replicates is None else np.ascontiguousarray(replicates, dtype=np.int64).ravel()
+        n = len(reps)
+        if n and (reps.min() < 0 or reps.max() >= self.R):
+            raise ValueError("replicate index out of range")
+        if len(np.unique(reps)) != n:
+            raise ValueError("replicates must be distinct")
+        for r in reps:
+            c = eng.counters(int(r))
+            if c.ev_first_new != 0:
+                raise ValueError("replicate %d: its chain does not start in the last call's device log (the model held %d events "
+                                 "when the ensemble started)" % (r, c.ev_first_new))
+        T = step_num + 1
+        io = _capi.VgxTimelinesIO()
+        io.n, io.replicates, io.step_num, io.semantics = n, _capi._p(reps), step_num, _capi.TIMELINE_SEMANTICS[semantics]
+        keep = [np.ascontiguousarray(q[:, j]) for q in (qi, qs) for j in (0, 1)]
+        io.n_inf, io.inf_pop, io.inf_hap = len(qi), _capi._p(keep[0]), _capi._p(keep[1])
+        io.n_sus, io.sus_pop, io.sus_grp = len(qs), _capi._p(keep[2]), _capi._p(keep[3])
+        eng._check(lib.vgx_get_timelines(eng.handle, C.byref(io)))            # sizing
+        cap = int(io.loc_cap)
+        tp = np.zeros((max(n, 1), T))
+        inf, smp = np.zeros((max(n, 1), max(len(qi), 1), T)), np.zeros((max(n, 1), max(len(qi), 1), T))
+        sus = np.zeros((max(n, 1), max(len(qs), 1), T))
+        if len(qi) == 0:
+            inf, smp = inf[:, :0], smp[:, :0]
+        if len(qs) == 0:
+            sus = sus[:, :0]
+        last, loc_n = np.zeros(max(n, 1), dtype=np.int64), np.zeros(max(n, 1), dtype=np.int64)
+        loc_state, loc_pop = np.zeros((max(n, 1), cap), dtype=np.int64), np.zeros((max(n, 1), cap), dtype=np.int64)
+        loc_time = np.zeros((max(n, 1), cap))
+        io.time_points, io.last_point = _capi._p(tp), _capi._p(last)
+        io.inf_data = _capi._p(inf) if len(qi) else None
+        io.inf_sample = _capi._p(smp) if len(qi) else None
+        io.sus_data = _capi._p(sus) if len(qs) else None
+        io.loc_n, io.loc_state, io.loc_pop, io.loc_time = _capi._p(loc_n), _capi._p(loc_state), _capi._p(loc_pop), _capi._p(loc_time)
+        eng._check(lib.vgx_get_timelines(eng.handle, C.byref(io)))            # replay
+        b = TimelineBatch(reps, qi[ii], qs[si], step_num, semantics)
+        b.time_points, b.last_point = tp[:n], last[:n]
+        b.infectious, b.samples, b.susceptible = inf[:n][:, ii], smp[:n][:, ii], sus[:n][:, si]
+        b._loc = (loc_n[:n], loc_state[:n], loc_pop[:n], loc_time[:n])
+        b.passes, b.kernel_ms, b.clock_ms, b.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
+        return b
+
     def trajectories(self, out=None):
         """Summary trajectories of the last call, ``[R, T, P, 2]`` float64 (infectious, susceptible per population).
         ``out`` may be a CUDA torch tensor (filled on the device, no host round trip) or None (numpy)."""
@@ -376,6 +454,50 @@ class GenealogyBatch:
         out["nodes_used"] = int(self.nodes_used[i])
         out["rng_raw"] = tuple(int(x) for x in self.rng_raw[i])
         return out
+
+
+class TimelineBatch:
+    """Compartment series of many replicates (``Ensemble.timelines``) as flat arrays; T = step_num + 1.
+
+    ``replicates[i]`` is the replicate of row i; ``time_points[i]`` its grid (``k * currentTime / step_num`` of its own final
+    time); ``infectious[i, k]`` / ``samples[i, k]`` the ``Data`` / ``Sample`` series of ``infectious_queries[k]`` = (population,
+    haplotype); ``susceptible[i, k]`` the series of ``susceptible_queries[k]`` = (population, group); ``last_point[i]`` the last
+    grid index the replay reached.  All series are float64 whole numbers."""
+
+    def __init__(self, replicates, infectious_queries, susceptible_queries, step_num, semantics):
+        self.replicates = np.asarray(replicates, dtype=np.int64).copy()
+        self._row = {int(r): i for i, r in enumerate(self.replicates)}
+        self.infectious_queries = np.asarray(infectious_queries, dtype=np.int64).reshape(-1, 2)
+        self.susceptible_queries = np.asarray(susceptible_queries, dtype=np.int64).reshape(-1, 2)
+        self.step_num, self.semantics = int(step_num), semantics
+
+    def __len__(self):
+        return len(self.replicates)
+
+    def _index(self, r):
+        i = self._row.get(int(r))
+        if i is None:
+            raise KeyError("replicate %d is not in this batch" % r)
+        return i
+
+    def lockdowns(self, r, pop):
+        """``[[state, time], ...]`` of population ``pop`` of replicate ``r`` (times from the host clock)."""
+        i = self._index(r)
+        n, st, pp, tt = self._loc
+        return [[bool(st[i, k]), float(tt[i, k])] for k in range(int(n[i])) if pp[i, k] == pop]
+
+    def data_infectious(self, r, k):
+        """``(Data, Sample, time_points, lockdowns)`` as ``BirthDeathModel.get_data_infectious(pop, hap, step_num)`` returns
+        them for replicate ``r`` and infectious query ``k``."""
+        i = self._index(r)
+        return (self.infectious[i, k].copy(), self.samples[i, k].copy(), [float(t) for t in self.time_points[i]],
+                self.lockdowns(r, int(self.infectious_queries[k, 0])))
+
+    def data_susceptible(self, r, k):
+        """``(Data, time_points, lockdowns)`` as ``BirthDeathModel.get_data_susceptible(pop, group, step_num)`` returns them."""
+        i = self._index(r)
+        return (self.susceptible[i, k].copy(), [float(t) for t in self.time_points[i]],
+                self.lockdowns(r, int(self.susceptible_queries[k, 0])))
 
 
 class PendingGather:
