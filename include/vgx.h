@@ -17,7 +17,8 @@
  * Environment switches read by the library (diagnostics and tests; none is needed in production):
  *   VGX_LIST_CAP=n                 caps the capacity of every occupancy list at n entries (exercises the kernels' overflow paths)
  *   VGX_TIMING=1                   vgx_simulate_tau prints its host-side phases on stderr
- *   VGX_SOLO_PLAIN_DIV=1           single-trajectory kernel: x / actualSizes by the compiler's division instead of the reciprocal sequence
+ *   VGX_SOLO_PLAIN_DIV=1           single-trajectory kernels and the exact row kernel: x / actualSizes by the compiler's division instead of
+ *                                  the reciprocal sequence
  *   VGX_SOLO_GENERAL=1             ... its general BirthRate layout where the compact one would be taken
  *   VGX_SOLO_NO_UNIT=1             ... no one-haplotype / one-population instantiation
  *   VGX_TAU_STEP_KERNELS=1 / 0     tau: always / never the step kernels (default: the on-device step loop for small models)
@@ -410,6 +411,11 @@ int vgx_test_poisson(double lam, int64_t n, uint64_t seed, int64_t *out);
  * corrections (how the single-trajectory kernel divides BirthRate's terms by actualSizes, pyx:390), q_lean = its division sequence
  * without range scaling and special-case fix-up (fastChoose's rescalings, fast_choose.pxi:31), q_div = the division. */
 int vgx_test_div_by_const(const double *n, const double *b, int64_t count, double *q_seq, double *q_lean, double *q_div);
+
+/* the serial prefix chains of the row kernels on `rows` rows of 64 weights w[row][0..63] (finite, >= +0.0) from carry[row], formed on
+ * the device: pre16[row][l] = carry + w[0] + ... + w[l] for l < 16 and tot16[row][l] = pre16[row][15] in every lane (row_scan16),
+ * pre64[row][k] = carry + w[0] + ... + w[k] for k < 64 (row_scan64), every sum left to right. */
+int vgx_test_row_scans(const double *w, const double *carry, int64_t rows, double *pre16, double *tot16, double *pre64);
 
 #ifdef __cplusplus
 }

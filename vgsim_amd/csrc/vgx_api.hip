@@ -36,7 +36,7 @@ extern "C" int vgxi_tau_drift_blocks(const VgxTauArgs *a);
 extern "C" hipError_t vgxi_tau_sieve(const VgxTauArgs *a, hipStream_t s);
 extern "C" hipError_t vgxi_launch_lanes(const VgxDirectArgs *a, const VgxLaneWs *w, hipStream_t stream);
 extern "C" hipError_t vgxi_launch_quad(const VgxDirectArgs *a, const double *cd, double *effMig, double *maxEBM, int32_t *has_mig, int long_lists,
-                                       hipStream_t stream);
+                                       int plain_div, hipStream_t stream);
 extern "C" size_t vgxi_direct_lds_bytes(int P, int S, int C, int CB);
 extern "C" hipError_t vgxi_launch_counts64(const int32_t *c32, int64_t *c64, int64_t n, hipStream_t stream);
 extern "C" hipError_t vgxi_launch_quad_prep(const VgxDevParams *p, const double *cd, double *effMig, double *maxEBM, int32_t *has_mig, hipStream_t stream);
@@ -1071,6 +1071,11 @@ static int direct_core(vgx_engine *e, int64_t iterations, int64_t sample_size, f
                       e->cap <= ((int64_t)1 << 24);   // (the 64-ary lower bound of vgx_rowlist.h descends from stride 64^3: lists of up to 2^24 entries)
     for (int64_t pn = 0; pn < P && quad_shape; pn++)
         if (e->sizes[(size_t)pn] >= ((int64_t)1 << 31)) quad_shape = false;   // its streaming passes read 4-byte counts
+    {   // vgx_quad_kernel keeps the per-population totals and globalInfectious as doubles: exact while the model's host count is below 2^53
+        double hosts = 0.0;
+        for (int64_t pn = 0; pn < P; pn++) hosts += (double)e->sizes[(size_t)pn];
+        if (!(hosts < 9007199254740992.0)) quad_shape = false;
+    }
     for (int64_t pn = 0; pn < P && quad_shape; pn++)
         if (h.totalSusceptible[(size_t)pn] != h.susceptible[(size_t)pn]) quad_shape = false;
     const bool quad_ok = o.mode == 0 && !philox_remapped && quad_shape;
@@ -1241,7 +1246,8 @@ static int direct_core(vgx_engine *e, int64_t iterations, int64_t sample_size, f
     }
     else if (use_lanes) HIPCHECK(e, vgxi_launch_lanes(&a, &ws, e->stream));
     else if (use_quad) HIPCHECK(e, vgxi_launch_quad(&a, (const double *)e->s_cd.p, (double *)e->r_qeff.p, (double *)e->r_qmebm.p,
-                                                    (int32_t *)e->r_qflag.p, e->start_max_nocc > 64 ? 1 : 0, e->stream));
+                                                    (int32_t *)e->r_qflag.p, e->start_max_nocc > 64 ? 1 : 0,
+                                                    getenv("VGX_SOLO_PLAIN_DIV") ? 1 : 0, e->stream));
     else if (use_quadf) HIPCHECK(e, vgxi_launch_quadf(&a, (const double *)e->s_cd.p, (double *)e->r_qeff.p, (double *)e->r_qmebm.p,
                                                       (int32_t *)e->r_qflag.p, e->stream));
     else if (use_quadg) {

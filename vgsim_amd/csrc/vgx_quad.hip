@@ -28,6 +28,7 @@
 #include "vgx_wave.h"
 #include "vgx_rowprim.h"
 #include "vgx_rowlist.h"
+#include "vgx_flat.h"
 
 #ifndef VGX_QUAD_WAVES
 #define VGX_QUAD_WAVES 2     // waves per SIMD the register allocation aims at (measured: 3 spills into the hot loop and is slower)
@@ -53,12 +54,13 @@ enum { QEV_BIRTH = 0, QEV_DEATH, QEV_SAMPLING, QEV_MUTATION, QEV_SUSCCHANGE, QEV
 enum { ST_REBUILD = 0, ST_RUN = 1, ST_DONE = 2 };
 
 // ---- LDS layout (bytes), one wavefront per workgroup ---------------------------------------------------------
-// model constants [64] f64: cd, as, smul (= sRate * samplingMultiplier), maxEBM                      2048
+// model constants [64] f64: cd, as, smul (= sRate * samplingMultiplier), maxEBM, 1 / as                2560
 // PCG64 jump-ahead [16][4] u64: a^(l+1), 1 + a + ... + a^l (high, low words) for l = 0..15            512
-// per replicate   infect[64], birthC[64] f64; totS[64], totI[64] i64; nocc[64] i32; cc[4] f64 (serial prefix sum of
+// per replicate   infect[64], birthC[64] f64; totS[64], totI[64] f64 (whole numbers below 2^53: the host admits no larger model,
+//                 so every total and every difference of totals is exact, and the rates take them without a conversion); nocc[64] i32; cc[4] f64 (serial prefix sum of
 //                 popRate at the end of each 16-population slot); counters[8] i64 (births, deaths, mutations,
 //                 accepted / rejected migrations)                                                     4 x 2400
-#define Q_CONST_BYTES 2048
+#define Q_CONST_BYTES 2560
 #define Q_RNG_BYTES 512
 #define Q_REP_BYTES 2912     // ... + the stage of eight event records (256 bytes)
 #define Q_LDS_BYTES (Q_CONST_BYTES + Q_RNG_BYTES + 4 * Q_REP_BYTES)
@@ -80,20 +82,25 @@ static __device__ __forceinline__ double row_sum64(double w0, double w1, double 
     return acc;
 }
 // the serial prefix of every entry of a tile: p[j] of lane l = carry + (all entries before 4l + j) + its own.  The chain is the one
-// of row_sum64; lane K keeps the running sum as it stands before its own four entries (one select per group of four steps) and
-// forms its four prefixes from it afterwards — the same additions on the same operands in the same order as the chain made.
-#define QCAP4(K)                                                                                                   \
-    st = rl_ == K ? acc : st;                                                                                      \
-    asm volatile(QFM4(K) : "+v"(acc) : "v"(w0), "v"(w1), "v"(w2), "v"(w3), "v"(one));
+// of row_sum64 with the per-lane multiplier of row_scan16 (vgx_rowprim.h), here 1.0 while the chain is below the lane's own four
+// entries and +0.0 from them on, moved up the row once per group of four steps: lane l ends with the running sum as it stands
+// before its entries and forms its four prefixes from it afterwards — the same additions on the same operands in the same order
+// as the chain made.  (No lane is above lane 15: its group is not run.)
+#define QSG4(K, NOP, M)                                                                                                         \
+    asm volatile(NOP QFM4(K) : "+v"(acc) : "v"(w0), "v"(w1), "v"(w2), "v"(w3), "v"(__hiloint2double(M, 0)));
+#define QSG12(K0, K1, K2) QSG4(K0, "", ma) ma = QMUL_SHR(ma, 3); QSG4(K1, "", mb) mb = QMUL_SHR(mb, 3); QSG4(K2, "", mc) mc = QMUL_SHR(mc, 3);
 static __device__ __forceinline__ void row_scan64(double w0, double w1, double w2, double w3, double carry, double &p0, double &p1,
                                                   double &p2, double &p3) {
-    const double one = 1.0;
-    const int rl_ = threadIdx.x & 15;
-    double acc = carry, st = carry;
-    asm volatile("s_nop 1" ::: );
-    QCAP4(0) QCAP4(1) QCAP4(2) QCAP4(3) QCAP4(4) QCAP4(5) QCAP4(6) QCAP4(7) QCAP4(8) QCAP4(9) QCAP4(10) QCAP4(11)
-    QCAP4(12) QCAP4(13) QCAP4(14) QCAP4(15)
-    p0 = st + w0; p1 = p0 + w1; p2 = p1 + w2; p3 = p2 + w3;
+    double acc = carry;
+    int one_hi = 0x3FF00000;
+    asm volatile("" : "+v"(one_hi));
+    int ma = QMUL_SHR(one_hi, 1), mb = QMUL_SHR(one_hi, 2), mc = QMUL_SHR(one_hi, 3);
+    QSG4(0, "s_nop 1\n\t", ma) ma = QMUL_SHR(ma, 3);
+    QSG4(1, "", mb) mb = QMUL_SHR(mb, 3);
+    QSG4(2, "", mc) mc = QMUL_SHR(mc, 3);
+    QSG12(3, 4, 5) QSG12(6, 7, 8) QSG12(9, 10, 11)
+    QSG4(12, "", ma) QSG4(13, "", mb) QSG4(14, "", mc)
+    p0 = acc + w0; p1 = p0 + w1; p2 = p1 + w2; p3 = p2 + w3;
 }
 // QT = tiles of 64 four-byte counts a row keeps in flight ahead of its summation chain: 1 in vgx_quad_kernel, 5 in
 // vgx_quad_long_kernel (start states with lists longer than one tile).  The event loop is sensitive to its CODE SIZE (46 to
@@ -345,11 +352,21 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t vgxi_launch_quad_pre
     return hipGetLastError();
 }
 
-template <int QT>
-static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const QArgs &qa) {
+// RCPDIV: BirthRate's terms are divided by actualSizes through its reciprocal (vgx_flat.h div_by_const: the IEEE quotient in five
+// operations instead of the division's eleven); false: the division itself (validation, VGX_SOLO_PLAIN_DIV=1).
+// The kernel's arguments are read through the kernarg segment pointer (constant address space: scalar loads where and when a value is
+// needed), as in vgx_solo.hip and vgx_quadg.hip: by-value parameters referenced all over the loop are kept in scalar registers for the
+// whole kernel, and the ones that do not fit are spilled to lanes of vector registers, every reload an instruction in the event loop.
+struct VgxQuadKArgs { VgxDirectArgs a; QArgs qa; };
+typedef const VgxQuadKArgs __attribute__((address_space(4))) *QuadKA;
+template <int QT, bool RCPDIV>
+static __device__ __forceinline__ void quad_body() {
+    const QuadKA ka = (QuadKA)__builtin_amdgcn_kernarg_segment_ptr();
+    const auto &a = ka->a;
+    const auto &qa = ka->qa;
     const int lane = threadIdx.x, row = lane >> 4, rl = lane & 15;
-    const VgxDevParams &p = a.p;
-    const VgxDevRep &r = a.r;
+    const auto &p = a.p;
+    const auto &r = a.r;
     const int P = p.P, sites = p.sites, H = p.H;
     const int64_t R = a.n_replicates;
     const int64_t rep_raw = (int64_t)blockIdx.x * 4 + row;
@@ -359,11 +376,11 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
     const bool has_mig = qa.has_mig[0] != 0;
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *k_cd = (double *)smem, *k_as = k_cd + 64, *k_smul = k_as + 64, *k_mebm = k_smul + 64;
+    double *k_cd = (double *)smem, *k_as = k_cd + 64, *k_smul = k_as + 64, *k_mebm = k_smul + 64, *k_rcp = k_mebm + 64;
     uint64_t *k_jump = (uint64_t *)(smem + Q_CONST_BYTES) + rl * 4;
     unsigned char *blk = smem + Q_CONST_BYTES + Q_RNG_BYTES + row * Q_REP_BYTES;
     double *s_inf = (double *)blk, *s_bc = s_inf + 64;
-    int64_t *s_ts = (int64_t *)(s_bc + 64), *s_ti = s_ts + 64;
+    double *s_ts = s_bc + 64, *s_ti = s_ts + 64;
     int32_t *s_nocc = (int32_t *)(s_ti + 64);
     double *s_cc = (double *)(s_nocc + 64);
     int64_t *s_cnt = (int64_t *)(s_cc + 4);
@@ -402,6 +419,7 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
         const int pn = lane;
         k_cd[pn] = pn < P ? gD[PD_CD * P + pn] : 0.0;   // identical in every replicate (no lockdown switches)
         k_as[pn] = pn < P ? p.actualSizes[pn] : 1.0;
+        k_rcp[pn] = pn < P ? 1.0 / p.actualSizes[pn] : 1.0;     // the correctly rounded reciprocal (the division is IEEE)
         k_smul[pn] = pn < P ? c_s * p.sampMult[pn] : 0.0;
         k_mebm[pn] = pn < P ? qa.maxEBM[pn] : 0.0;
         for (int s = 0; s < 4; ++s) {
@@ -409,8 +427,8 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
             const bool ok = pq < P;
             s_inf[pq] = 0.0; s_bc[pq] = 0.0;
             if (rl < 4) s_cc[rl] = 0.0;
-            s_ts[pq] = ok ? gI64[PI_TOTSUS * P + pq] : 0;
-            s_ti[pq] = ok ? gI64[PI_TOTINF * P + pq] : 0;
+            s_ts[pq] = ok ? (double)gI64[PI_TOTSUS * P + pq] : 0.0;
+            s_ti[pq] = ok ? (double)gI64[PI_TOTINF * P + pq] : 0.0;
             s_nocc[pq] = ok ? gN[pq] : 0;
             s_zero[pq] = 0;                 // (the lists arrive settled)
         }
@@ -434,7 +452,8 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
     }
 
     double t_now = sc->currentTime, totalRate = 0.0, totalMig = 0.0;
-    int64_t gI = sc->globalInfectious, ev_ptr = sc->ev_ptr;
+    double gI = (double)sc->globalInfectious;     // a whole number, like the totals
+    int64_t ev_ptr = sc->ev_ptr;
     int64_t cS = sc->sCounter;
     if (rl == 0) {
         s_cnt[QC_B] = sc->bCounter; s_cnt[QC_D] = sc->dCounter; s_cnt[QC_M] = sc->mCounter;
@@ -497,7 +516,7 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
                     pos = 8;
                     open = true;
                     last_att = att; att_loops = 0;
-                    if (!(totalRate + totalMig != 0.0 && gI != 0)) end_attempt = true;   // pyx:404
+                    if (!(totalRate + totalMig != 0.0 && gI != 0.0)) end_attempt = true;   // pyx:404
                 }
             }
             if (st == ST_RUN && !end_attempt &&
@@ -551,7 +570,7 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
                         double *o = r.traj + (rep * r.traj_points + traj_next) * (int64_t)P * 2;
                         for (int s = 0; s < nslot; ++s) {
                             const int pn = s * 16 + rl;
-                            if (pn < P) { o[pn * 2 + 0] = (double)s_ti[pn]; o[pn * 2 + 1] = (double)s_ts[pn]; }
+                            if (pn < P) { o[pn * 2 + 0] = s_ti[pn]; o[pn * 2 + 1] = s_ts[pn]; }
                         }
                         traj_next += 1;
                     }
@@ -709,13 +728,13 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
                 rn = (r3 - (total - wi)) / wi;
             }
             const bool go = evn && err == 0;
-            const int64_t ts_pi = s_ts[pi], ti_pi = s_ti[pi];
+            const double ts_pi = s_ts[pi], ti_pi = s_ti[pi];
             const bool isB = go && ei == 0, isD = go && (ei == 1 || ei == 2), isM = go && ei == 3;
             if (isB) {
                 // ---- Birth (pyx:568-605; one susceptibility group: si = 0, its weight susceptHapPopRate = S * sigma) ----
-                if ((double)ts_pi * c_sig == 0.0) err = Q_ERR_ZERO_WEIGHT + 256 * 6;
-                if (rl == 0) { s_ts[pi] = ts_pi - 1; s_ti[pi] = ti_pi + 1; }
-                gI += 1; QBUMP(QC_B);
+                if (ts_pi * c_sig == 0.0) err = Q_ERR_ZERO_WEIGHT + 256 * 6;
+                if (rl == 0) { s_ts[pi] = ts_pi - 1.0; s_ti[pi] = ti_pi + 1.0; }
+                gI += 1.0; QBUMP(QC_B);
                 if (live && rl == 0) { if (QT < 4) ln[k_hit] = cnt_hit + 1; l3[k_hit] = (int32_t)(cnt_hit + 1); if (QT >= 4) L8(pi)[k_hit] = B8(cnt_hit + 1); if (n_sel > 64) lt[k_hit >> 6] += 1; }
 #pragma unroll
                 for (int c = 0; c < 4; ++c)
@@ -725,8 +744,8 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
             }
             if (isD) {
                 // ---- Death / Sampling (pyx:616-635): recovery into group suscType = 0 ----
-                if (rl == 0) { s_ts[pi] = ts_pi + 1; s_ti[pi] = ti_pi - 1; }
-                gI -= 1;
+                if (rl == 0) { s_ts[pi] = ts_pi + 1.0; s_ti[pi] = ti_pi - 1.0; }
+                gI -= 1.0;
                 if (ei == 2) { cS += 1; e_type = QEV_SAMPLING; } else { QBUMP(QC_D); e_type = QEV_DEATH; }
                 // (the long-list kernel leaves a count of 0 in the list: vgx_rowlist.h)
                 if (QT < 4 && cnt_hit == 1) { op_n = 1; op_pi = pi; op_h0 = hap_hit; op_d0 = -1; ch_pi = -1; }
@@ -792,7 +811,7 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
                     int cand = 64;
                     for (int s = 0; s < nslot; ++s) {
                         const int pn = s * 16 + rl;
-                        const double w = pn < P ? k_mebm[pn] * (double)s_ts[pn] * (double)(gI - s_ti[pn]) : 0.0;
+                        const double w = pn < P ? k_mebm[pn] * s_ts[pn] * (gI - s_ti[pn]) : 0.0;
                         double tot_;
                         const double pre = row_scan16(w, carry, tot_);
                         const int q = row_min(cand == 64 && pn < P && !(pre < rr_) ? rl : 16);
@@ -810,20 +829,20 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
                 // source population: fastChoose_skip(totalInfectious, globalInfectious - totalInfectious[tpi], rn, skip = tpi)
                 int spi = -1;
                 {
-                    const double rr_ = (double)(gI - s_ti[tpi]) * rm;
+                    const double rr_ = (gI - s_ti[tpi]) * rm;
                     const int start = tpi == 0 ? 1 : 0;
                     int64_t carry = 0, total = 0;
                     for (int s = 0; s < nslot; ++s) {
                         const int pn = s * 16 + rl;
                         const bool in = pn < P && pn != tpi && pn >= start;
-                        const int64_t w = in ? s_ti[pn] : 0;
+                        const int64_t w = in ? (int64_t)s_ti[pn] : 0;
                         const int64_t pre = row_iscan(w) + carry;
                         const int q = row_min(spi < 0 && in && !((double)pre < rr_) ? rl : 16);
                         if (spi < 0 && q < 16) { spi = s * 16 + q; total = rowget_i64(pre, q); }
                         carry = rowget_i64(pre, 15);
                     }
                     if (spi < 0) { spi = P - 1; total = carry; }   // clamp at n-1 (may equal skip only then)
-                    const int64_t wi = s_ti[spi];
+                    const int64_t wi = (int64_t)s_ti[spi];
                     if (evm && wi == 0) err = Q_ERR_ZERO_WEIGHT + 256 * 10;
                     rm = (rr_ - (double)(total - wi)) / (double)wi;
                 }
@@ -837,7 +856,7 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
                     const int32_t *l32 = lcnt32 + (int64_t)spi * cap;
 #define CN2(k) (QT >= 4 ? (int64_t)l32[k] : ln2[k])      /* (the long-list kernel keeps the 4-byte counts only) */
                     const int64_t *lt2 = ltsum + (int64_t)spi * capT;
-                    const double rr_ = (double)s_ti[spi] * rm;
+                    const double rr_ = s_ti[spi] * rm;
                     int64_t before = 0;
                     int base = 0;
                     bool none = false;
@@ -879,8 +898,8 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
                             err = Q_ERR_ZERO_WEIGHT + 256 * 11;
                             if (rl == 0 && r.prof) {
                                 unsigned long long *d = r.prof + rep * VGX_PROF_SLOTS;
-                                d[0] = n; d[1] = spi; d[2] = tpi; d[3] = s_ti[spi]; d[4] = __double_as_longlong(rr_); d[5] = __double_as_longlong(rm);
-                                d[6] = total; d[7] = before; d[8] = maxn2; d[9] = gI; d[10] = s_ti[tpi]; d[11] = n > 0 ? CN2(0) : -1;
+                                d[0] = n; d[1] = spi; d[2] = tpi; d[3] = (int64_t)s_ti[spi]; d[4] = __double_as_longlong(rr_); d[5] = __double_as_longlong(rm);
+                                d[6] = total; d[7] = before; d[8] = maxn2; d[9] = (int64_t)gI; d[10] = (int64_t)s_ti[tpi]; d[11] = n > 0 ? CN2(0) : -1;
                                 d[12] = ev_ptr; d[13] = loops; d[14] = __double_as_longlong(totalMig); d[15] = __double_as_longlong(choose);
                             }
                             kq = 0; wi = 1;
@@ -892,17 +911,17 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
                 }
                 // susceptibility group of the target (one group): fastChoose(susceptible[tpi, :], totalSusceptible[tpi], rn)
                 {
-                    const int64_t wi = s_ts[tpi];
-                    const double rr_ = (double)wi * rm;
-                    if (evm && wi == 0 && err == 0) err = Q_ERR_ZERO_WEIGHT + 256 * 12;
-                    rm = (rr_ - (double)(wi - wi)) / (double)wi;
+                    const double wi = s_ts[tpi];
+                    const double rr_ = wi * rm;
+                    if (evm && wi == 0.0 && err == 0) err = Q_ERR_ZERO_WEIGHT + 256 * 12;
+                    rm = (rr_ - (wi - wi)) / wi;
                 }
                 const bool mgo = evm && err == 0;
                 if (mgo) {
                     const double p_accept = qa.effMig[(int64_t)spi * P + tpi] * p.bRate[hi] * p.susc[hi] / k_mebm[tpi];
                     if (rm < p_accept) {
-                        if (rl == 0) { s_ts[tpi] -= 1; s_ti[tpi] += 1; }     // NewInfections (pyx:246-251)
-                        gI += 1; QBUMP(QC_MIGP);
+                        if (rl == 0) { s_ts[tpi] -= 1.0; s_ti[tpi] += 1.0; }     // NewInfections (pyx:246-251)
+                        gI += 1.0; QBUMP(QC_MIGP);
                         op_n = 1; op_pi = tpi; op_h0 = hi; op_d0 = +1; ch_pi = -1;
                         e_type = QEV_MIGRATION; e_hap = hi; e_pop = spi; e_nh = 0; e_np = tpi;
                         u_lo = tpi; u_hi = tpi + 1;
@@ -1109,7 +1128,7 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
                 const bool act = pn0 < u_hi;
                 const int pi = act ? pn0 : 0;
                 // BirthRate of the class (pyx:382-392): ps += ((x*m)*m*cd)/as over the source populations, in order
-                const double x = (double)s_ts[pi] * c_sig;
+                const double x = s_ts[pi] * c_sig;
                 const double *mrow = p.mig + (int64_t)pi * P;
                 const bool mhave = act && pi == pm_pi;
                 double tv4[4], ps = 0.0;
@@ -1119,7 +1138,10 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
                     if (s < nslot) {
                         const int pn = s * 16 + rl;
                         const double m = mhave ? m_pre[s] : mrow[min(pn, P - 1)];
-                        tv4[s] = x * m * m * k_cd[pn] / k_as[pn];        // lanes beyond P: cd = +0.0, as = 1.0
+                        // lanes beyond P: cd = +0.0, as = 1.0.  The terms are susceptible counts times rates below the population
+                        // size: no overflow or underflow inside the reciprocal sequence (the latency kernels' range: vgx_flat.h)
+                        const double t = x * m * m * k_cd[pn];
+                        tv4[s] = RCPDIV ? div_by_const(t, k_as[pn], k_rcp[pn]) : t / k_as[pn];
                         if (pn >= P) tv4[s] = 0.0;
                     }
                 }
@@ -1185,7 +1207,7 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
                     w4[s] = 0.0;
                     if (s < nslot) {
                         const int pn = s * 16 + rl;     // lanes beyond P: maxEBM = +0.0, counts 0
-                        w4[s] = k_mebm[pn] * (double)s_ts[pn] * (double)(gI - s_ti[pn]);
+                        w4[s] = k_mebm[pn] * s_ts[pn] * (gI - s_ti[pn]);
                         if (pn >= P) w4[s] = 0.0;
                     }
                 }
@@ -1200,7 +1222,7 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
         // ================= after the pass =================
         if (rebuild && st == ST_REBUILD) st = err ? ST_DONE : ST_RUN;
         if (err != 0) st = ST_DONE;
-        if (ev && st == ST_RUN && (totalRate == 0.0 || gI == 0)) end_attempt = true;   // pyx:410-411
+        if (ev && st == ST_RUN && (totalRate == 0.0 || gI == 0.0)) end_attempt = true;   // pyx:410-411
         if (st == ST_RUN && end_attempt) {
             // end of an attempt (pyx:414-418)
             open = false;
@@ -1247,10 +1269,10 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
                 if (rs)
                     for (int j = (n + 63) / 64 + rl; j <= n_old / 64 && j < capT; j += 16) ltsum[(int64_t)pn * capT + j] = 0;
                 if (QT < 4) q_zero_tail(lcnt32 + (int64_t)pn * cap, n, cap, rs);
-                if (rs && rl == 0) { s_nocc[pn] = n; s_zero[pn] = 0; s_ts[pn] = r.i_sus[pn]; s_ti[pn] = ti; }
+                if (rs && rl == 0) { s_nocc[pn] = n; s_zero[pn] = 0; s_ts[pn] = (double)r.i_sus[pn]; s_ti[pn] = (double)ti; }
                 g += ti;
             }
-            if (rs) gI = g;
+            if (rs) gI = (double)g;
             WSYNC();
         }
     }
@@ -1264,7 +1286,7 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
                 double *o = r.traj + (rep * r.traj_points + traj_next) * (int64_t)P * 2;
                 for (int s = 0; s < nslot; ++s) {
                     const int pn = s * 16 + rl;
-                    if (pn < P) { o[pn * 2 + 0] = (double)s_ti[pn]; o[pn * 2 + 1] = (double)s_ts[pn]; }
+                    if (pn < P) { o[pn * 2 + 0] = s_ti[pn]; o[pn * 2 + 1] = s_ts[pn]; }
                 }
                 traj_next += 1;
             }
@@ -1295,18 +1317,18 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
                 gD[PD_POPRATE * P + pn] = s_inf[pn];
                 gD[PD_INFECT * P + pn] = s_inf[pn];
                 gD[PD_IMMUNE * P + pn] = 0.0;
-                gD[PD_MIG * P + pn] = k_mebm[pn] * (double)s_ts[pn] * (double)(gI - s_ti[pn]);
+                gD[PD_MIG * P + pn] = k_mebm[pn] * s_ts[pn] * (gI - s_ti[pn]);
                 gD[PD_MAXEBM * P + pn] = k_mebm[pn];
-                gI64[PI_TOTSUS * P + pn] = s_ts[pn];
-                gI64[PI_TOTINF * P + pn] = s_ti[pn];
+                gI64[PI_TOTSUS * P + pn] = (int64_t)s_ts[pn];
+                gI64[PI_TOTINF * P + pn] = (int64_t)s_ti[pn];
                 gN[pn] = s_nocc[pn];
-                r.sus[rep * P + pn] = s_ts[pn];
+                r.sus[rep * P + pn] = (int64_t)s_ts[pn];
                 r.immSrc[rep * P + pn] = 0.0;
             }
         }
         if (rl == 0) {
             sc->currentTime = t_now; sc->totalRate = totalRate; sc->totalMig = totalMig;
-            sc->globalInfectious = gI;
+            sc->globalInfectious = (int64_t)gI;
             sc->bCounter = s_cnt[QC_B]; sc->dCounter = s_cnt[QC_D]; sc->sCounter = cS; sc->mCounter = s_cnt[QC_M];
             sc->migPlus = s_cnt[QC_MIGP]; sc->migNonPlus = s_cnt[QC_MIGN];
             sc->good_attempt = good_attempt;
@@ -1321,11 +1343,14 @@ static __device__ __forceinline__ void quad_body(const VgxDirectArgs &a, const Q
 #ifndef VGX_QT_SHORT
 #define VGX_QT_SHORT 1   // measured at the headline workload: 3 -> 7.9e8, 2 -> 8.2e8, 1 -> 8.6e8 events/s (8.8e8 with the branch hints)
 #endif
-extern "C" __global__ void __launch_bounds__(64, VGX_QUAD_WAVES) vgx_quad_kernel(VgxDirectArgs a, QArgs qa) { quad_body<VGX_QT_SHORT>(a, qa); }
+extern "C" __global__ void __launch_bounds__(64, VGX_QUAD_WAVES) vgx_quad_kernel(VgxQuadKArgs) { quad_body<VGX_QT_SHORT, true>(); }
 #ifndef VGX_QT_LONG
 #define VGX_QT_LONG 7     // (254 VGPRs, no spill; 5: 1.31e8, 7: 1.33e8 events/s at 4096-entry lists)
 #endif
-extern "C" __global__ void __launch_bounds__(64, VGX_QUAD_WAVES) vgx_quad_long_kernel(VgxDirectArgs a, QArgs qa) { quad_body<VGX_QT_LONG>(a, qa); }
+extern "C" __global__ void __launch_bounds__(64, VGX_QUAD_WAVES) vgx_quad_long_kernel(VgxQuadKArgs) { quad_body<VGX_QT_LONG, true>(); }
+// validation: BirthRate's terms by the compiler's division instead of the reciprocal sequence (VGX_SOLO_PLAIN_DIV=1)
+extern "C" __global__ void __launch_bounds__(64, VGX_QUAD_WAVES) vgx_quad_kernel_plaindiv(VgxQuadKArgs) { quad_body<VGX_QT_SHORT, false>(); }
+extern "C" __global__ void __launch_bounds__(64, VGX_QUAD_WAVES) vgx_quad_long_kernel_plaindiv(VgxQuadKArgs) { quad_body<VGX_QT_LONG, false>(); }
 
 // The 4-byte copy of the counts after another kernel changed the lists (the copy is kept by vgx_quad_kernel only).
 extern "C" __global__ void __launch_bounds__(256) vgx_quad_counts32_kernel(const int64_t *c64, int32_t *c32, int64_t n) {
@@ -1358,21 +1383,63 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t vgxi_launch_traj_i32
 extern "C" __attribute__((visibility("hidden"))) hipError_t vgxi_launch_lists_settle(const VgxDirectArgs *a, hipStream_t stream);
 extern "C" __attribute__((visibility("hidden"))) hipError_t vgxi_launch_quad(const VgxDirectArgs *a, const double *cd,
                                                                             double *effMig, double *maxEBM, int32_t *has_mig,
-                                                                            int long_lists, hipStream_t stream) {
+                                                                            int long_lists, int plain_div, hipStream_t stream) {
     hipLaunchKernelGGL(vgx_quad_prep_kernel, dim3(1), dim3(64), 0, stream, a->p, cd, effMig, maxEBM, has_mig);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
-    QArgs qa;
-    qa.effMig = effMig; qa.maxEBM = maxEBM; qa.has_mig = has_mig;
+    VgxQuadKArgs ka;
+    ka.a = *a;
+    ka.qa.effMig = effMig; ka.qa.maxEBM = maxEBM; ka.qa.has_mig = has_mig;
     const unsigned grid = (unsigned)((a->n_replicates + 3) / 4);
     if (long_lists) {
         const int64_t n = (int64_t)a->n_replicates * a->p.P * a->r.cap;      // (list capacities are multiples of 4 from one site on)
         hipLaunchKernelGGL(vgx_quad_counts8_kernel, dim3(4096), dim3(256), 0, stream, a->r.lcnt32, (uint8_t *)(a->r.lcnt32 + n), (n + 3) / 4);
-        hipLaunchKernelGGL(vgx_quad_long_kernel, dim3(grid), dim3(64), Q_LDS_BYTES, stream, *a, qa);
+        hipLaunchKernelGGL(plain_div ? vgx_quad_long_kernel_plaindiv : vgx_quad_long_kernel, dim3(grid), dim3(64), Q_LDS_BYTES, stream, ka);
         // its lists hold zero-count entries and 4-byte counts only: squeeze, tile sums, 8-byte counts (vgx_quadf.hip)
         hipError_t e2 = vgxi_launch_lists_settle(a, stream);
         if (e2 != hipSuccess) return e2;
     }
-    else hipLaunchKernelGGL(vgx_quad_kernel, dim3(grid), dim3(64), Q_LDS_BYTES, stream, *a, qa);
+    else hipLaunchKernelGGL(plain_div ? vgx_quad_kernel_plaindiv : vgx_quad_kernel, dim3(grid), dim3(64), Q_LDS_BYTES, stream, ka);
     return hipGetLastError();
+}
+
+// ---- test hook: the serial prefix chains of the row kernels on their own ----
+// Block b runs rows 4b .. 4b+3, one per 16-lane DPP row as the kernels do: row_scan16 over the first sixteen weights of a row,
+// row_scan64 over all 64 in the tile layout (lane l holds entries 4l .. 4l+3), both from the row's carry.
+extern "C" __global__ void __launch_bounds__(64) vgx_quad_scantest_kernel(const double *w, const double *carry, int64_t rows, double *pre16,
+                                                                         double *tot16, double *pre64) {
+    const int rl = threadIdx.x & 15;
+    const int64_t row_raw = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 4);
+    const int64_t row = row_raw < rows ? row_raw : rows - 1;      // (rows beyond the last repeat it: the chains need all 64 lanes)
+    const double c = carry[row];
+    double tot;
+    const double p = row_scan16(w[row * 64 + rl], c, tot);
+    const double *w4 = w + row * 64 + 4 * rl;
+    double p0, p1, p2, p3;
+    row_scan64(w4[0], w4[1], w4[2], w4[3], c, p0, p1, p2, p3);
+    if (row_raw < rows) {
+        pre16[row * 16 + rl] = p; tot16[row * 16 + rl] = tot;
+        double *o = pre64 + row * 64 + 4 * rl;
+        o[0] = p0; o[1] = p1; o[2] = p2; o[3] = p3;
+    }
+}
+extern "C" int vgx_test_row_scans(const double *w, const double *carry, int64_t rows, double *pre16, double *tot16, double *pre64) {
+    if (!w || !carry || !pre16 || !tot16 || !pre64 || rows < 0) return 1;
+    if (rows == 0) return 0;
+    double *d = nullptr;
+    const size_t n = (size_t)rows;
+    if (hipMalloc((void **)&d, n * (64 + 1 + 16 + 16 + 64) * 8) != hipSuccess) return 2;
+    double *dw = d, *dc = dw + n * 64, *d16 = dc + n, *dt = d16 + n * 16, *d64 = dt + n * 16;
+    int rc = 0;
+    if (hipMemcpy(dw, w, n * 64 * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dc, carry, n * 8, hipMemcpyHostToDevice) != hipSuccess) rc = 2;
+    if (!rc) {
+        hipLaunchKernelGGL(vgx_quad_scantest_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(64), 0, nullptr, dw, dc, rows, d16, dt, d64);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(pre16, d16, n * 16 * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(tot16, dt, n * 16 * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(pre64, d64, n * 64 * 8, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = 2;
+    }
+    (void)hipFree(d);
+    return rc;
 }

@@ -45,6 +45,13 @@ static __device__ __forceinline__ int rows_max(int v) {
     return max(max(a, b), max(c, d));
 }
 
+// value of lane 15 of each row in all its lanes (DPP row broadcast)
+static __device__ __forceinline__ double rowget15_f64(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), 0x15F, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), 0x15F, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
 // acc + v[0] + ... + v[15] of each row, in lane order: 16 dependent v_fmac_f64 (acc = fma(v[k], 1.0, acc) rounds like
 // acc + v[k]), every one of them serving the four rows.  acc row-uniform in and out; all 64 lanes active.
 #define QFM(K) "v_fmac_f64_dpp %0, %1, %2 row_newbcast:" #K " row_mask:0xf bank_mask:0xf\n\t"
@@ -56,21 +63,32 @@ static __device__ __forceinline__ double row_sum16(double v, double acc) {
                  : "v"(v), "v"(one));
     return acc;
 }
-// lane l of each row gets carry + v[0] + ... + v[l] (the serial prefix): the same chain, each lane keeping the running
-// sum of its own step (the selects are off the chain's critical path); `total` receives carry + v[0] + ... + v[15].
-#define QSTEP(K)                                                                                        \
-    asm volatile(QFM(K) : "+v"(acc) : "v"(v), "v"(one));                                                 \
-    res = rl_ == K ? acc : res;
+// lane l of each row gets carry + v[0] + ... + v[l] (the serial prefix): the same chain with a per-lane multiplier that is 1.0
+// through the lane's own step and +0.0 afterwards (v >= +0.0 and finite: x + v * 0.0 = x), so no select and no lane mask sits
+// between the steps.  The multipliers are not sixteen registers: the high dword of 1.0 moves up the row behind the chain (32-bit
+// DPP row_shr, lanes without a source receive 0; the low dword is 0 either way).  Three registers take the steps in turn, each
+// shifted by three lanes after its step: the DPP read of a shift then has the two other shifts between it and the write before it
+// (two wait states are needed, and the compiler's hazard recogniser counts none for an asm statement: with two registers it puts
+// a s_nop into every other step).  The starting value passes through an empty asm statement: without it every multiplier is a
+// loop invariant the compiler keeps in a register of its own across the event loop.
+// `total` receives carry + v[0] + ... + v[15] in every lane (lane 15's prefix).
+#define QMUL_SHR(m, d) __builtin_amdgcn_update_dpp(0, (m), 0x110 + (d), 0xf, 0xf, true)
+#define QSC(K, NOP, M)                                                                                                      \
+    asm volatile(NOP "v_fmac_f64_dpp %0, %1, %2 row_newbcast:" #K " row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(v), "v"(__hiloint2double(M, 0)));
+#define QSC3(K0, K1, K2) QSC(K0, "", ma) ma = QMUL_SHR(ma, 3); QSC(K1, "", mb) mb = QMUL_SHR(mb, 3); QSC(K2, "", mc) mc = QMUL_SHR(mc, 3);
 static __device__ __forceinline__ double row_scan16(double v, double carry, double &total) {
-    const double one = 1.0;
-    const int rl_ = threadIdx.x & 15;
-    double acc = carry, res = carry;
-    asm volatile("s_nop 1\n\t" QFM(0) : "+v"(acc) : "v"(v), "v"(one));
-    res = rl_ == 0 ? acc : res;
-    QSTEP(1) QSTEP(2) QSTEP(3) QSTEP(4) QSTEP(5) QSTEP(6) QSTEP(7) QSTEP(8) QSTEP(9) QSTEP(10) QSTEP(11) QSTEP(12)
-    QSTEP(13) QSTEP(14) QSTEP(15)
-    total = acc;
-    return res;
+    double acc = carry;
+    int ma = 0x3FF00000;
+    asm volatile("" : "+v"(ma));
+    int mb = QMUL_SHR(ma, 1), mc = QMUL_SHR(ma, 2);
+    QSC(0, "s_nop 1\n\t", ma) ma = QMUL_SHR(ma, 3);
+    QSC(1, "", mb) mb = QMUL_SHR(mb, 3);
+    QSC(2, "", mc) mc = QMUL_SHR(mc, 3);
+    QSC3(3, 4, 5) QSC3(6, 7, 8) QSC3(9, 10, 11)
+    QSC(12, "", ma) ma = QMUL_SHR(ma, 3);
+    QSC(13, "", mb) QSC(14, "", mc) QSC(15, "", ma)
+    total = rowget15_f64(acc);
+    return acc;
 }
 
 }  // namespace
