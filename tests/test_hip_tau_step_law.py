@@ -32,7 +32,7 @@ pytestmark = pytest.mark.gpu
 
 PATHS = {"loop": {}, "steps": {"VGX_TAU_STEP_KERNELS": "1"}, "large": {"VGX_TAU_LARGE_MODEL_THRESHOLDS": "1"}}
 SWITCHES = ("VGX_TAU_STEP_KERNELS", "VGX_TAU_LARGE_MODEL_THRESHOLDS", "VGX_TAU_NO_OCCLIST", "VGX_TAU_NO_FRONT")
-SMALL_MODEL_CELLS = 1 << 18      # P H R up to which the step kernels switch to the channel-by-channel kernel at a mean of 16 (vgx_api.hip)
+SMALL_MODEL_CELLS = 1 << 18      # P H R up to which the step kernels switch to the channel-by-channel kernel at a mean of 16 (vgx_tau_run.hip)
 LAUNCH = 1 << 10                 # replicates per launch: a tau call sizes its cross-compartment list at 2^22 entries (32 MB) per replicate
 
 

@@ -1,4 +1,4 @@
-// vgx_dev.h — structures shared by the host side of libvgx (vgx_api.hip) and the gfx950 kernels.
+// vgx_dev.h — structures shared by the host side of libvgx (vgx_api.hip, vgx_tau_run.hip) and the gfx950 kernels.
 //
 // HBM layout.  Parameters are one read-only copy shared by all replicates.  Each
 // replicate (= one seeded trajectory) owns:
@@ -152,6 +152,20 @@ struct VgxLaneWs {
     // [P], [P*H], [P*H], [P*H], [P*H*S], [P*S], [P] x 5, [P*P]
 };
 
+// Words of the record vgx_tau_finish_kernel packs per replicate and step (VgxTauArgs::res, host_res)
+enum TauRecord {
+    TR_TAU = 0,        // the step's tau (bit pattern)
+    TR_GI,             // globalInfectious after the step
+    TR_CNT0,           // counters[8]
+    TR_MEVBASE = 10,   // multievent rows of this step: [TR_MEVBASE, TR_MEVN)
+    TR_MEVN,
+    TR_ERROR,
+    TR_OCC,            // occupied compartments at the start of this step (drift pass on the bytes), else -1
+    TR_RETRY,          // rejected tries of this step
+    TR_FORMED,         // compartments whose empty neighbours the sparse drift pass formed, else -1 (res only: the pinned copy ends before it)
+    TR_WORDS
+};
+
 // Tau-leaping (vgx_tau.hip): dense compartment arrays per replicate, [R][P][H] / [R][P][S].
 struct VgxTauArgs {
     VgxDevParams p;
@@ -207,10 +221,9 @@ struct VgxTauArgs {
     int64_t *big;        // [R][big_cap] pn * H + hn
     int64_t big_cap;
     unsigned long long *big_n;  // [R]
-    int64_t *res;        // [R][16] what the host reads after a step, packed by vgx_tau_finish_kernel: tau (bits),
-                         // globalInfectious, counters[8], multievent row range of the step, error
+    int64_t *res;        // [R][TR_WORDS] what the host reads after a step, packed by vgx_tau_finish_kernel: the words of TauRecord
     int32_t *host_flags; // [3 R] accepted, grow as the decide kernel left them, and "the front pass alone found nothing", in pinned HOST memory (or null)
-    int64_t *host_res;   // [R][16] the finish kernel's record per replicate, in pinned host memory (or null)
+    int64_t *host_res;   // [R][TR_WORDS] the finish kernel's record per replicate, in pinned host memory (or null)
     int32_t *grow;       // [R] the try overflowed the cross-compartment list: the host enlarges it and the SAME try runs again
     int32_t *attempt;    // [R]
     const int64_t *seeds;  // [R]
@@ -242,7 +255,7 @@ struct VgxTauArgs {
     int64_t *front;      // [R][P][front_cap] the front pass's lists: compartments that can fall below zero on their own in this try (vgx_tau_front_kernel)
     unsigned int *front_n;   // [R][P] their counts (may exceed front_cap: the rest is found by the try proper); cleared by vgx_tau_decide_kernel
     int32_t front_cap, front_on;
-    // A whole ROUND of a step enqueued without the host in between (one replicate, vgx_api.hip): several tries' front passes back to
+    // A whole ROUND of a step enqueued without the host in between (one replicate, vgx_tau_run.hip): several tries' front passes back to
     // back, the try proper of the first one that finds nothing, the end of the step.  `spec` says on the device how far the round is:
     // 0 = front passes still look for a try that can succeed, 1 = one found nothing: its try proper runs, 2 = over (accepted, an error,
     // or the host has to enlarge a list).  `gate` (set per launch by the host) says which of these states a launch belongs to: 0 = none
@@ -251,7 +264,7 @@ struct VgxTauArgs {
     int32_t *spec;              // [R]
     int32_t gate, gate_pad;
     int32_t phase, phase_pad;   // of a try: 0 = front pass and try proper in one go; 1 = the front pass alone (the decide kernel rejects the try or
-                                // reports that the pass found nothing); 2 = the try proper after such a front pass (one replicate: vgx_api.hip)
+                                // reports that the pass found nothing); 2 = the try proper after such a front pass (one replicate: vgx_tau_run.hip)
     unsigned long long *cnt_pop;   // [R][P][8] the events kernel's share of them per population, folded into cnt_try by vgx_tau_decide_kernel
     int64_t *mev;        // [R][mev_cap][6]  num, type, hap, pop, newHap, newPop (rows with num > 0 only)
     int64_t mev_cap;

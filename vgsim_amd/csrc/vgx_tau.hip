@@ -1309,7 +1309,7 @@ extern "C" __global__ void __launch_bounds__(D8_TB, 4) vgx_tau_drift8_kernel(Vgx
 // is the same bit pattern; the susceptible compartments' drift (in the dense form a sum over ALL compartments of a tile) comes from exact
 // integer sums per (population, tile) and differs from the dense form's by rounding only
 // (tests/test_hip_tau.py::test_drift_over_the_lists_equals_the_dense_pass).  Where the empty neighbours of too many compartments have
-// to be formed (a high mutation rate) the host goes back to the dense pass (vgx_api.hip: sparse_ban).
+// to be formed (a high mutation rate) the host goes back to the dense pass (vgx_tau_run.hip: sparse_ban).
 struct D8S {
     const uint8_t *I8row;
     const int32_t *Irow;
@@ -1514,7 +1514,7 @@ extern "C" __global__ void __launch_bounds__(256) vgx_tau_drift8s_heavy_kernel(V
         }
     }
     d8s_commit(a, rep, cand_min, ad_max);
-    // how many compartments took this path: the host goes back to the dense pass where it is no longer the few (vgx_api.hip)
+    // how many compartments took this path: the host goes back to the dense pass where it is no longer the few (vgx_tau_run.hip)
     if (lane == 0 && nheavy != 0) atomicAdd(&a.d8s_bc[(int64_t)rep * 8 + 3], (unsigned long long)nheavy);
 }
 
@@ -3712,18 +3712,18 @@ extern "C" __global__ void __launch_bounds__(64) vgx_tau_finish_kernel(VgxTauArg
     if (lane == 0) {
         a.gI[rep] = g;
         // one packed record per replicate for the host, and the bookkeeping it used to upload before every step
-        int64_t *o = a.res + (int64_t)rep * 16;
-        o[0] = __double_as_longlong(a.tau[rep]);
-        o[1] = g;
-        for (int i = 0; i < 8; ++i) o[2 + i] = a.counters[(int64_t)rep * 8 + i];
-        o[10] = (int64_t)a.mev_base[rep];        // multievent rows of this step: [o[10], o[11])
-        o[11] = (int64_t)a.mev_n[rep];
-        o[12] = a.error[rep];
-        o[13] = (a.occ_pop && a.use8) ? occ_sum : -1;   // occupied compartments at the start of this step (drift pass on the bytes), else -1
-        o[14] = a.retry[rep];                            // rejected tries of this step
-        o[15] = (a.drift_sparse && a.d8s_bc) ? (int64_t)a.d8s_bc[(int64_t)rep * 8 + 3] : -1;   // compartments whose empty neighbours the sparse drift pass formed
+        int64_t *o = a.res + (int64_t)rep * TR_WORDS;
+        o[TR_TAU] = __double_as_longlong(a.tau[rep]);
+        o[TR_GI] = g;
+        for (int i = 0; i < 8; ++i) o[TR_CNT0 + i] = a.counters[(int64_t)rep * 8 + i];
+        o[TR_MEVBASE] = (int64_t)a.mev_base[rep];
+        o[TR_MEVN] = (int64_t)a.mev_n[rep];
+        o[TR_ERROR] = a.error[rep];
+        o[TR_OCC] = (a.occ_pop && a.use8) ? occ_sum : -1;
+        o[TR_RETRY] = a.retry[rep];
+        o[TR_FORMED] = (a.drift_sparse && a.d8s_bc) ? (int64_t)a.d8s_bc[(int64_t)rep * 8 + 3] : -1;
         if (a.host_res)
-            for (int i = 0; i < 15; ++i) a.host_res[(int64_t)rep * 16 + i] = o[i];   // the host's (pinned) copy
+            for (int i = 0; i < TR_FORMED; ++i) a.host_res[(int64_t)rep * TR_WORDS + i] = o[i];   // the host's (pinned) copy: every word before TR_FORMED
         a.mev_base[rep] = a.mev_n[rep];          // rows of the accepted step stay (pyx:2325)
         a.time_now[rep] += a.tau[rep];           // pyx:2322
         a.step[rep] += 1;

@@ -1,4 +1,4 @@
-// vgx_taus.h — arguments of the on-device tau-leaping step loop of small models (vgx_taus.hip), shared with vgx_api.hip.
+// vgx_taus.h — arguments of the on-device tau-leaping step loop of small models (vgx_taus.hip), shared with vgx_tau_run.hip.
 #pragma once
 #include <stdint.h>
 #include "vgx_dev.h"
