@@ -107,22 +107,30 @@ typedef struct vgx_run_opts {
                                 (Philox4x32-10 keyed by the seed, counter = (draw index, attempt): every draw can be formed
                                 on its own; other numbers than PCG64's, so another trajectory of the same law).  Ignored by
                                 vgx_simulate_tau. */
-    int64_t kernel;          /* direct path: 0 = automatic, 1 = one replicate per wavefront (vgx_direct.hip), 2 = one replicate
-                                per lane (vgx_lanes.hip; small models: popNum <= 16, popNum*hapNum <= 1024, susNum <= 8, EXACT),
-                                3 = four replicates per wavefront, one per 16-lane row (EXACT): vgx_quad.hip
-                                for popNum <= 64, one susceptibility group, one rate class and no possible lockdown switch,
-                                else the general form vgx_quadg.hip (popNum <= 128, susNum <= 8, <= 64 rate classes, <= 16
-                                transmission/susceptibility classes; also models with a recombination probability); 4 = the general
-                                form even where 3 would take the other;
+    int64_t kernel;          /* direct path: 0 = automatic, 1 = one replicate per wavefront (vgx_direct.hip: every model, every mode),
+                                2 = one replicate per lane (vgx_lanes.hip; small models: popNum <= 16, popNum*hapNum <= 1024,
+                                susNum <= 8, mode 0),
+                                3 = four replicates per wavefront, one per 16-lane row: for popNum <= 64, one susceptibility group,
+                                one rate class, no possible lockdown switch and no recombination vgx_quad.hip in mode 0 and the FAST
+                                row kernel vgx_quadf.hip in modes 1 and 2, else the general form vgx_quadg.hip (popNum <= 128,
+                                susNum <= 8, <= 64 rate classes, <= 16 transmission/susceptibility classes; also models with a
+                                recombination probability; mode 0, and mode 2 as exact arithmetic on the counter-based stream);
+                                4 = the general form even where 3 would take another (mode 0; mode 2 only for models outside the
+                                one-class scope);
                                 5 = one replicate per wavefront with the whole DENSE model in LDS and registers (vgx_solo.hip: the
-                                latency kernel of single trajectories; EXACT, hapNum <= 64, popNum <= 128, susNum <= 16).
+                                latency kernel of single trajectories; hapNum <= 64, popNum <= 128, susNum <= 16; modes 0 and 2).
                                 Automatic: 5 for fewer than 2048 replicates of a model it takes (and for more where it beats 3 / 4:
-                                small models with several classes, one-class models below 8192 replicates);
+                                small models with several classes, one-class models below 8192 replicates — in mode 2 at every size);
                                 6 = one replicate per wavefront with the occupancy LISTS in LDS (vgx_lone.hip: single trajectories of
-                                large haplotype spaces; EXACT, popNum <= 64; automatic up to 1536 replicates of models 5 does not take);
-                                mode 1 on a model the FAST row kernel does not take runs the exact kernels 3 / 4 / 5 / 6 (their output
-                                is what FAST promises), mode 2 likewise with those kernels' exact arithmetic on the counter-based
-                                stream (4, 5 and 6 take it); 2 for P*H*S <= 4 from 131072 replicates, or when asked for */
+                                large haplotype spaces; popNum <= 64; modes 0 and 2, both of its forms; automatic up to 1536 replicates
+                                of models 5 does not take, on a state that came through vgx_set_state);
+                                2 automatically for P*H*S <= 4 from 131072 replicates in mode 0.
+                                Where an exact kernel serves the request, the call runs in mode 0 whatever was asked for: mode 1 with
+                                kernel 0 on a model outside the one-class scope that 4 takes (4, 5 or 6 then runs it: their output
+                                is what FAST promises); mode 2 with kernel 0, 5 or 6 on every model without recombination, and with 3 or 4 on a model
+                                outside the one-class scope that 4 takes — exact arithmetic on the counter-based stream.  A request
+                                that then lands on 1 or on the FAST row kernel keeps its own mode.  Recombination: mode 0 only.
+                                tests/test_direct_plan.py has the table. */
     int64_t reserved[2];     /* [0] tau path: 1 = run every try of the halving loop (pyx:2316-2321) instead of starting at the
                                 first try that is not certain to be rejected (same accepted steps either way);
                                 [1] tau path, how a try's deltas are kept and checked (same draws and decisions in every mode):
@@ -356,10 +364,50 @@ typedef struct vgx_timelines_chain {
 } vgx_timelines_chain;
 int vgx_test_timelines(vgx_timelines_chain *io, char *errbuf, int64_t errcap);
 
+/* ---- kernel choice of the direct path ------------------------------------------------------- */
+/* What the choice of a direct call's kernel reads: the model's dimensions, the state the call starts from and two diagnostic
+ * switches.  vgx_simulate_direct fills one from the engine; the choice itself is a pure function of it and of the options. */
+typedef struct vgx_direct_shape {
+    int64_t P, H, S, sites;          /* popNum, hapNum, susNum, sites */
+    int64_t R;                       /* replicates */
+    int64_t C, CB;                   /* rate classes; birth classes (transmission rate x susceptibility row) */
+    int64_t cap;                     /* entries an occupancy list can hold */
+    int64_t n_seg, n_solo_seg;       /* chain segments of the BirthRate program; (group, non-zero susceptibility) pairs */
+    int64_t solo_npass0, solo_npass1;   /* passes of the single-trajectory kernel without / with the migration sum (< 0: too many) */
+    int64_t solo_ncls, solo_maxnnz;  /* susceptibility classes; most non-zero groups of one class */
+    int64_t start_lone_rows;         /* heap rows of vgx_lone.hip the start state needs */
+    int64_t start_max_nocc;          /* longest occupancy list of the start state */
+    int64_t max_size;                /* largest population size */
+    int64_t hosts_below_2p53;        /* the population sizes, summed as doubles, stay below 2^53 */
+    int64_t ld_possible;             /* some population can switch its lockdown state */
+    int64_t recomb;                  /* recombination probability != 0 */
+    int64_t fresh_state;             /* the call starts from the state of vgx_set_state (it does not continue the device's) */
+    int64_t suscep_cumul0_zero;      /* no immunity loss from group 0: suscepCumulTransition[0] == 0 */
+    int64_t have_counts32;           /* the device state keeps the 4-byte copy of the counts */
+    int64_t tot_sus_is_sus;          /* one group, and totalSusceptible == susceptible in every population */
+    int64_t no_lone, solo_general;   /* diagnostics: VGX_NO_LONE, VGX_SOLO_GENERAL are set */
+} vgx_direct_shape;
+/* What the rest of the call needs from the choice.  The fields of a kernel that was not chosen are 0. */
+typedef struct vgx_direct_plan {
+    int64_t kernel;                  /* a value of vgx_run_opts.kernel, 1 .. 6, or 7: the FAST row kernel (vgx_quadf.hip) */
+    int64_t mode;                    /* the mode the call runs in: 0 where an exact kernel serves a FAST request */
+    int64_t fast, philox;            /* order-free arithmetic; counter-based stream */
+    int64_t solo_mig_in_lds;         /* 5: migrationRates fit the LDS budget */
+    int64_t solo_compact;            /* 5: 0 general layout, 1 / 2 compact layout with one / two registers of terms */
+    int64_t lone_general;            /* 6: its general form */
+    int64_t lone_lds_bytes;          /* 6: dynamic LDS of the launch */
+    int64_t long_lists;              /* 3: the exact row kernel's form for lists beyond one tile */
+    int64_t leaves32;                /* the kernel leaves only the 4-byte counts current */
+    int64_t fallback_kernel, fallback_mode;   /* 6 as the automatic choice: the request the call repeats when the LDS heap fills up */
+} vgx_direct_plan;
+/* Test hook: the choice for a shape and options given as numbers: no device, no engine.  Returns the code vgx_simulate_direct would
+ * return for a refused request, with that call's vgx_last_error text in errbuf. */
+int vgx_test_direct_plan(const vgx_direct_shape *shape, const vgx_run_opts *opts, vgx_direct_plan *plan, char *errbuf, int64_t errcap);
+
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* Device time of the last simulate call's kernels, from HIP events on the engine's stream (ms). */
 double vgx_last_kernel_ms(const vgx_engine *e);
-/* The kernel the last vgx_simulate_direct call ran on, as a value of vgx_run_opts.kernel (1 .. 5; 3 also for the FAST row kernel). */
+/* The kernel the last vgx_simulate_direct call ran on, as a value of vgx_run_opts.kernel (1 .. 6; 3 also for the FAST row kernel). */
 int vgx_last_direct_kernel(const vgx_engine *e);
 /* Number of kernel launches timed by the last simulate call. */
 int64_t vgx_last_kernel_launches(const vgx_engine *e);

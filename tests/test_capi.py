@@ -36,7 +36,8 @@ def test_struct_layouts_match_header():
     src = open(os.path.join(ROOT, "include", "vgx.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     for cname, ctype in (("vgx_dims", _capi.VgxDims), ("vgx_params", _capi.VgxParams), ("vgx_state", _capi.VgxState),
-                         ("vgx_run_opts", _capi.VgxRunOpts), ("vgx_counters", _capi.VgxCounters)):
+                         ("vgx_run_opts", _capi.VgxRunOpts), ("vgx_counters", _capi.VgxCounters),
+                         ("vgx_direct_shape", _capi.VgxDirectShape), ("vgx_direct_plan", _capi.VgxDirectPlan)):
         body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cname, cname), src, flags=re.S).group(1)
         names = []
         for decl in body.split(";"):

@@ -130,7 +130,7 @@ def test_continued_calls_keep_the_host_clock(oracle_mod, kernel):
     """Time-sliced runs through the C ABI: a second vgx_simulate_direct on the device-resident state (no vgx_set_state in between)
     continues every replicate where IT stopped — its own events.ptr, and its own clock: the event times of the second slice are the
     reference's libm sums continued from the first slice's last event, bit for bit what the oracle gives when one model runs both
-    slices (the host clock of the first slice is rebuilt before its logs are overwritten; vgx_api.hip direct_core)."""
+    slices (the host clock of the first slice is rebuilt before its logs are overwritten; vgx_direct_run.hip continue_clock)."""
     import ctypes as C
     from vgsim_amd import Simulator, _capi
     ctor, phases = models.CASES["g5_short"]

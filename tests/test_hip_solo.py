@@ -148,7 +148,7 @@ def test_solo_replicates_equal_single_runs(oracle_mod, name, n_events):
 
 @pytest.mark.parametrize("name,n_events", [("g1", 800), ("g5", 800), ("g6_short", 800)])
 def test_one_class_ensembles_below_8192_replicates_take_the_latency_kernel(oracle_mod, name, n_events):
-    """The automatic choice (vgx_api.hip, direct dispatch): a one-class model both this kernel and the one-class row kernel take
+    """The automatic choice (vgx_direct_run.hip, vgx_choose_direct): a one-class model both this kernel and the one-class row kernel take
     runs here below 8192 replicates; a few replicates out of 4096 against single oracle runs, and the row kernel from 8192 on."""
     from vgsim_amd import Simulator
     from vgsim_amd.ensemble import Ensemble

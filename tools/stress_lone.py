@@ -81,7 +81,7 @@ def check(seed):
         return False, tag + ": oracle rc %d, engine ran" % rc
     try:
         helpers.assert_models_equal(hip.simulation, m, tag)
-        # a continued call on the same engine state (vgx_api.hip runs it on the row kernels: the lists are no longer fresh) must go on
+        # a continued call on the same engine state (vgx_direct_run.hip runs it on the row kernels: the lists are no longer fresh) must go on
         # from where the first one ended
         rc = oracle.run_direct(m, n // 2 + 1, 10 ** 9, -1, 200)
         if rc == 0:

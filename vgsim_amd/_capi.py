@@ -94,6 +94,19 @@ class VgxTimelinesChain(C.Structure):
 TIMELINE_SEMANTICS = {'reference': 0, 'compartment': 1}
 
 
+class VgxDirectShape(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in (
+        "P", "H", "S", "sites", "R", "C", "CB", "cap", "n_seg", "n_solo_seg", "solo_npass0", "solo_npass1", "solo_ncls",
+        "solo_maxnnz", "start_lone_rows", "start_max_nocc", "max_size", "hosts_below_2p53", "ld_possible", "recomb",
+        "fresh_state", "suscep_cumul0_zero", "have_counts32", "tot_sus_is_sus", "no_lone", "solo_general")]
+
+
+class VgxDirectPlan(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in (
+        "kernel", "mode", "fast", "philox", "solo_mig_in_lds", "solo_compact", "lone_general", "lone_lds_bytes", "long_lists",
+        "leaves32", "fallback_kernel", "fallback_mode")]
+
+
 class VgxRowScan(C.Structure):
     _fields_ = [("rows", C.c_int64), ("H", C.c_int64), ("S", C.c_int64), ("infectious", _I), ("eventRates123", _F),
                 ("numToHap", _I), ("bRate", _F), ("susceptibility", _F), ("rowSusceptible", _F), ("rowContact", _F), ("u", _F),
@@ -140,6 +153,7 @@ SIGNATURES = {
     "vgx_test_genealogy_walk": (C.c_int, [C.POINTER(VgxGenealogyIO), C.c_char_p, C.c_int64]),
     "vgx_get_timelines": (C.c_int, [_H, C.POINTER(VgxTimelinesIO)]),
     "vgx_test_timelines": (C.c_int, [C.POINTER(VgxTimelinesChain), C.c_char_p, C.c_int64]),
+    "vgx_test_direct_plan": (C.c_int, [C.POINTER(VgxDirectShape), C.POINTER(VgxRunOpts), C.POINTER(VgxDirectPlan), C.c_char_p, C.c_int64]),
     "vgx_rng_position": (None, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64 * 4)]),
     "vgx_propensity_scan": (C.c_int, [C.POINTER(VgxRowScan)]),
     "vgx_propensity_scan_bench": (C.c_int, [C.POINTER(VgxRowScan), C.c_int64, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -603,6 +617,20 @@ def replay_timelines(m, infectious=(), susceptible=(), step_num=100, semantics='
         raise ValueError(err.value.decode() or "vgx_test_timelines failed")
     return {"time_points": tp, "infectious": inf[:len(qi)][ii], "samples": smp[:len(qi)][ii], "susceptible": sus[:len(qs)][si],
             "last_point": int(io.last_point)}
+
+
+def direct_plan(shape, mode=0, kernel=0):
+    """The kernel choice of a direct call through ``vgx_test_direct_plan``: ``shape`` maps the fields of ``vgx_direct_shape`` to
+    integers (missing ones are 0).  Returns the fields of ``vgx_direct_plan`` as a dict; a refused request raises ``VgxError``
+    with the library's message."""
+    lib = load_library()
+    s, o, plan = VgxDirectShape(**{k: int(v) for k, v in shape.items()}), VgxRunOpts(), VgxDirectPlan()
+    o.record_events, o.mode, o.kernel = 1, int(mode), int(kernel)
+    err = C.create_string_buffer(1024)
+    rc = lib.vgx_test_direct_plan(C.byref(s), C.byref(o), C.byref(plan), err, 1024)
+    if rc != 0:
+        raise VgxError(rc, err.value.decode())
+    return {name: int(getattr(plan, name)) for name, _ in VgxDirectPlan._fields_}
 
 
 def propensity_scan(infectious, rates123, numToHap, bRate, susceptibility, rowSusceptible, rowContact, u, bench_rows=0, repeats=3):

@@ -1,4 +1,4 @@
-// vgx_dev.h — structures shared by the host side of libvgx (vgx_api.hip, vgx_tau_run.hip) and the gfx950 kernels.
+// vgx_dev.h — structures shared by the host side of libvgx (vgx_api.hip, vgx_direct_run.hip, vgx_tau_run.hip) and the gfx950 kernels.
 //
 // HBM layout.  Parameters are one read-only copy shared by all replicates.  Each
 // replicate (= one seeded trajectory) owns:

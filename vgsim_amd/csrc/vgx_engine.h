@@ -1,6 +1,7 @@
 // vgx_engine.h — the engine behind the C ABI of include/vgx.h, as the host drivers of libvgx.so share it: the engine structure,
 // its device buffers and error helpers, the launchers defined next to their kernels.  Host-only; included by the host drivers
-// (vgx_api.hip, vgx_tau_run.hip) alone.  Helpers used by both are `inline` here; direct_core has its one definition in vgx_api.hip.
+// (vgx_api.hip, vgx_direct_run.hip, vgx_tau_run.hip) alone.  Helpers that several of them use are `inline` here; direct_core and the
+// choice of its kernel have their one definition in vgx_direct_run.hip, host_clock in vgx_api.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -59,6 +60,9 @@ extern "C" hipError_t vgxi_launch_init_reps(const VgxDevRep *r, int P, int S, in
 TAU_DECL(tau_eff) TAU_DECL(tau_scatter) TAU_DECL(tau_prep) TAU_DECL(tau_drift) TAU_DECL(tau_choose) TAU_DECL(tau_draw)
 TAU_DECL(tau_conv8) TAU_DECL(tau_sync8) TAU_DECL(tau_arrivals) TAU_DECL(tau_verdict) TAU_DECL(tau_apply) TAU_DECL(tau_check) TAU_DECL(tau_decide) TAU_DECL(tau_commit) TAU_DECL(tau_finish) TAU_DECL(tau_draw_big) TAU_DECL(tau_suspect)
 extern "C" hipError_t vgxi_tau_traj(const VgxTauArgs *a, int64_t rep0, int64_t n, int fill, hipStream_t s);
+
+// vgx_direct_plan.kernel
+enum { VGX_K_WAVE = 1, VGX_K_LANES = 2, VGX_K_QUAD = 3, VGX_K_QUADG = 4, VGX_K_SOLO = 5, VGX_K_LONE = 6, VGX_K_QUADF = 7 };
 
 struct HostState {
     std::vector<int64_t> susceptible, infectious, initial_susceptible, initial_infectious;
@@ -152,7 +156,7 @@ struct vgx_engine {
         bool limit_mismatch = false;      // device and host clock disagreed on a time-limit stop (see host_clock)
     } hc;
     int64_t clock_mismatches = 0;
-    bool last_used_lanes = false, last_used_quad = false, last_used_quadg = false, last_used_quadf = false;
+    int64_t last_kernel = VGX_K_WAVE;   // vgx_direct_plan.kernel of the last direct call
     // BirthRate program of the general row kernel (vgx_quadg.h)
     std::vector<int32_t> h_seg_par, h_seg_sn, h_cb_seg;
     std::vector<double> h_seg_sig;
@@ -164,8 +168,6 @@ struct vgx_engine {
     DevBuf so_sn, so_sig, so_rcp, so_hapcls, so_nnz, so_tsn, so_tsig, so_clssig, so_pass;
     std::vector<int32_t> h_so_pass;
     int h_so_npass0 = 0, h_so_npass1 = 0;
-    bool last_used_solo = false;
-    bool last_used_lone = false;
     int64_t lone_fallbacks = 0;       // calls that ran again on the row kernel because the LDS heap of vgx_lone.hip was full
     bool dev_clock_stale = false;     // the last direct call ran without the device clock (vgx_solo.hip, CLOCK = false): r_sc[].currentTime is the
                                       // time at that call's START; a continued call must take the host clock's final time instead
@@ -283,7 +285,12 @@ inline void prepare_first(vgx_engine *e) {
     }
 }
 
-// the direct Gillespie driver (vgx_api.hip); the tau driver runs it with zero attempts for PrepareParameters
+// the direct Gillespie driver (vgx_direct_run.hip); the tau driver runs it with zero attempts for PrepareParameters
 int direct_core(vgx_engine *e, int64_t iterations, int64_t sample_size, float time, int64_t attempts, const vgx_run_opts *opts);
+// the clock of one replicate of the last direct call, rebuilt on the host into e->hc (vgx_api.hip); a continued call starts from it
+int host_clock(vgx_engine *e, int64_t rep);
+// The kernel of a direct call and what goes with it, from numbers alone: no engine, no HIP call, no environment.  Returns VGX_OK, or the
+// code of a refused request with its message in err.
+int vgx_choose_direct(const vgx_direct_shape *s, const vgx_run_opts *o, vgx_direct_plan *plan, std::string &err);
 
 #pragma GCC visibility pop

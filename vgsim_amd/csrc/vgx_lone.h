@@ -8,7 +8,7 @@
 #define VGX_LONE_COLD 16
 #define VGX_LONE_ROW 16            // list slots per heap row (one DPP row); a tile of the chains = four rows
 #define VGX_LONE_FULL_SITE 77      // error = capacity | this << 8: the LDS heap cannot hold the lists any longer (the host runs the call again
-                                   // on the four-replicates-per-wavefront kernel, vgx_api.hip)
+                                   // on the four-replicates-per-wavefront kernel, vgx_direct_run.hip)
 
 struct VgxLoneArgs {
     const double *effMig;      // [P][P] effectiveMigration (vgx_quad_prep_kernel: no population can switch its lockdown state)

@@ -1,4 +1,4 @@
-// vgx_quadg.h — what the host (vgx_api.hip) and the general row-per-replicate kernel (vgx_quadg.hip) share: the kernel's
+// vgx_quadg.h — what the host (vgx_direct_run.hip) and the general row-per-replicate kernel (vgx_quadg.hip) share: the kernel's
 // extra arguments, the limits of the shapes it takes and its LDS layout.
 #pragma once
 #include <stdint.h>

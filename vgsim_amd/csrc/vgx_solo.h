@@ -1,4 +1,4 @@
-// vgx_solo.h — what the host (vgx_api.hip) and the latency kernel of small models (vgx_solo.hip) share: the kernel's extra
+// vgx_solo.h — what the host (vgx_direct_run.hip) and the latency kernel of small models (vgx_solo.hip) share: the kernel's extra
 // arguments, the limits of the shapes it takes and its LDS layout.
 #pragma once
 #include <stdint.h>
