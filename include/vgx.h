@@ -28,8 +28,9 @@
  *   VGX_TAU_NO_FRONT_ALONE=1       tau, one replicate: the front pass is enqueued together with the try proper, not ahead of it
  *   VGX_TAU_LARGE_MODEL_THRESHOLDS=1  tau: the draw thresholds of large models on a small one
  *   VGX_GENEALOGY_CHUNK_BYTES=n    vgx_get_genealogies: device bytes of workspace per pass (several passes)
- *   VGX_TIMELINES_LDS_BYTES=n      vgx_get_timelines: LDS budget of a replay workgroup (default 65536, at most 163840; the queries are split over launches)
- *   VGX_TIMELINES_CHUNK_BYTES=n    vgx_get_timelines: device bytes of staging and outputs per chunk of replicates
+ *   VGX_TIMELINES_LDS_BYTES=n      vgx_get_timelines, vgx_get_tau_timelines: LDS budget of a replay workgroup (default 65536, at most 163840; the
+ *                                  queries are split over launches)
+ *   VGX_TIMELINES_CHUNK_BYTES=n    vgx_get_timelines, vgx_get_tau_timelines: device bytes of staging and outputs per chunk of replicates
  */
 #ifndef VGX_H
 #define VGX_H
@@ -363,6 +364,44 @@ typedef struct vgx_timelines_chain {
     int64_t last_point;
 } vgx_timelines_chain;
 int vgx_test_timelines(vgx_timelines_chain *io, char *errbuf, int64_t errcap);
+
+/* The same replays for many replicates of the last vgx_simulate_tau call (with the event log), on the device: one pass per
+ * replicate over its multievent rows where the tau kernels left them (48 bytes each; nothing is copied to the host or compacted).
+ * A tau call normally continues a chain, and the reference replays the WHOLE chain: the events the model held when the call
+ * started (`prefix`, shared by all replicates; NULL or empty when there were none), then the replicate's own steps, on the grid
+ * i * currentTime_r / step_num of the replicate's own final time.  The prefix is flattened once per call into rows of the same
+ * layout (a direct event = a row with num 1, a MULTITYPE event of an earlier tau call = its multievent rows), uploaded once,
+ * and replayed in front of every replicate's own rows.  A replicate that restarted (vgx_counters.restarts > 0) starts from
+ * time 0 without the prefix.  Multievent rows take the rule of the reference's MULTITYPE branch, which differs from the direct
+ * one in its susceptible MIGRATION clause (pyx:2037 tests `haplotypes`, pyx:2023 `newHaplotypes`); the order of a step's rows
+ * does not matter (they share a bin and every update is an integer sum).  No host clock runs: step times are host doubles.
+ * Same structure, two-call protocol, semantics, outputs and environment switches as vgx_get_timelines, with these differences:
+ *   - counters are 64-bit in LDS (a bin sums `num` over many steps): 8 (2 T + (2 n_inf + n_sus) T) + 4 step_num bytes and the table;
+ *   - every series is exact while its values stay below 2^53 in magnitude (the reference accumulates in float64 and is exact in
+ *     the same range);
+ *   - lockdown records of a replicate: the prefix's, then the call's (a restarted replicate: the call's only);
+ *   - ms[1] is the host's cut search (no clock), ms[0] the replay kernel.
+ * Refusals (VGX_ERR_ARG): the last call was not vgx_simulate_tau; it recorded no rows (record_events = 0); a replicate that
+ * did not restart continues a log of another length than prefix->ev_ptr; prefix plus own rows reach 2^31. */
+typedef struct vgx_timelines_prefix {
+    int64_t ev_ptr;                          /* events of the model's chain before the call */
+    const double *ev_times;
+    const int64_t *ev_types, *ev_haplotypes, *ev_populations, *ev_newHaplotypes, *ev_newPopulations;
+    int64_t mev_rows;                        /* multievent rows its MULTITYPE events index as [haplotypes, populations) */
+    const int64_t *mev_num, *mev_types, *mev_haplotypes, *mev_populations, *mev_newHaplotypes, *mev_newPopulations;
+    int64_t loc_n;                           /* lockdown records before the call */
+    const int64_t *loc_state, *loc_pop; const double *loc_time;
+} vgx_timelines_prefix;
+int vgx_get_tau_timelines(vgx_engine *e, vgx_timelines_io *io, const vgx_timelines_prefix *prefix);
+/* Test hook: the replay of vgx_get_tau_timelines (same classification, flattening, cut search and query table, compiled for the
+ * host) on one chain given as arrays, multievent rows included (dense logs with num == 0 rows are accepted): no device, no
+ * engine.  The chain's trailing MULTITYPE events play the replicate's own steps, everything before them the prefix. */
+typedef struct vgx_tau_timelines_chain {
+    vgx_timelines_chain chain;
+    int64_t mev_rows;
+    const int64_t *mev_num, *mev_types, *mev_haplotypes, *mev_populations, *mev_newHaplotypes, *mev_newPopulations;
+} vgx_tau_timelines_chain;
+int vgx_test_tau_timelines(vgx_tau_timelines_chain *io, char *errbuf, int64_t errcap);
 
 /* ---- kernel choice of the direct path ------------------------------------------------------- */
 /* What the choice of a direct call's kernel reads: the model's dimensions, the state the call starts from and two diagnostic

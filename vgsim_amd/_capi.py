@@ -91,6 +91,19 @@ class VgxTimelinesChain(C.Structure):
                 ("time_points", _F), ("inf_data", _F), ("inf_sample", _F), ("sus_data", _F), ("last_point", C.c_int64)]
 
 
+class VgxTimelinesPrefix(C.Structure):
+    _fields_ = [("ev_ptr", C.c_int64), ("ev_times", _F), ("ev_types", _I), ("ev_haplotypes", _I), ("ev_populations", _I),
+                ("ev_newHaplotypes", _I), ("ev_newPopulations", _I),
+                ("mev_rows", C.c_int64), ("mev_num", _I), ("mev_types", _I), ("mev_haplotypes", _I), ("mev_populations", _I),
+                ("mev_newHaplotypes", _I), ("mev_newPopulations", _I),
+                ("loc_n", C.c_int64), ("loc_state", _I), ("loc_pop", _I), ("loc_time", _F)]
+
+
+class VgxTauTimelinesChain(C.Structure):
+    _fields_ = [("chain", VgxTimelinesChain), ("mev_rows", C.c_int64), ("mev_num", _I), ("mev_types", _I), ("mev_haplotypes", _I),
+                ("mev_populations", _I), ("mev_newHaplotypes", _I), ("mev_newPopulations", _I)]
+
+
 TIMELINE_SEMANTICS = {'reference': 0, 'compartment': 1}
 
 
@@ -153,6 +166,8 @@ SIGNATURES = {
     "vgx_test_genealogy_walk": (C.c_int, [C.POINTER(VgxGenealogyIO), C.c_char_p, C.c_int64]),
     "vgx_get_timelines": (C.c_int, [_H, C.POINTER(VgxTimelinesIO)]),
     "vgx_test_timelines": (C.c_int, [C.POINTER(VgxTimelinesChain), C.c_char_p, C.c_int64]),
+    "vgx_get_tau_timelines": (C.c_int, [_H, C.POINTER(VgxTimelinesIO), C.POINTER(VgxTimelinesPrefix)]),
+    "vgx_test_tau_timelines": (C.c_int, [C.POINTER(VgxTauTimelinesChain), C.c_char_p, C.c_int64]),
     "vgx_test_direct_plan": (C.c_int, [C.POINTER(VgxDirectShape), C.POINTER(VgxRunOpts), C.POINTER(VgxDirectPlan), C.c_char_p, C.c_int64]),
     "vgx_rng_position": (None, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64 * 4)]),
     "vgx_propensity_scan": (C.c_int, [C.POINTER(VgxRowScan)]),
@@ -583,13 +598,10 @@ def unique_queries(pairs):
     return np.asarray(uniq, dtype=np.int64).reshape(-1, 2), np.asarray(index, dtype=np.int64)
 
 
-def replay_timelines(m, infectious=(), susceptible=(), step_num=100, semantics='reference'):
-    """The log replays of ``Ensemble.timelines`` for one host model through ``vgx_test_timelines``: the device replay's code
-    (vgx_tline.h) compiled for the host, on ``m.events``, ``m.currentTime`` and ``m.initial_*`` (direct chains only; no GPU).
-    Returns a dict: ``time_points`` [T], ``infectious`` / ``samples`` [Ki, T], ``susceptible`` [Ks, T], ``last_point``."""
+def _timelines_chain(m, infectious, susceptible, step_num, semantics):
+    """A ``VgxTimelinesChain`` for host model ``m`` with its outputs allocated: (io, finish) where ``finish()`` gives the result dict."""
     if semantics not in TIMELINE_SEMANTICS:
         raise ValueError("semantics must be 'reference' or 'compartment'")
-    lib = load_library()
     ev = m.events
     qi, ii = unique_queries(infectious)
     qs, si = unique_queries(susceptible)
@@ -612,11 +624,49 @@ def replay_timelines(m, infectious=(), susceptible=(), step_num=100, semantics='
     tp = np.zeros(T)
     inf, smp, sus = np.zeros((max(len(qi), 1), T)), np.zeros((max(len(qi), 1), T)), np.zeros((max(len(qs), 1), T))
     io.time_points, io.inf_data, io.inf_sample, io.sus_data = _p(tp), _p(inf), _p(smp), _p(sus)
+
+    def finish(chain=io, _alive=keep):   # (the query arrays live as long as this closure)
+        return {"time_points": tp, "infectious": inf[:len(qi)][ii], "samples": smp[:len(qi)][ii], "susceptible": sus[:len(qs)][si],
+                "last_point": int(chain.last_point)}
+    return io, finish
+
+
+def replay_timelines(m, infectious=(), susceptible=(), step_num=100, semantics='reference'):
+    """The log replays of ``Ensemble.timelines`` for one host model through ``vgx_test_timelines``: the device replay's code
+    (vgx_tline.h) compiled for the host, on ``m.events``, ``m.currentTime`` and ``m.initial_*`` (direct chains only; no GPU).
+    Returns a dict: ``time_points`` [T], ``infectious`` / ``samples`` [Ki, T], ``susceptible`` [Ks, T], ``last_point``."""
+    io, finish = _timelines_chain(m, infectious, susceptible, step_num, semantics)
     err = C.create_string_buffer(512)
-    if lib.vgx_test_timelines(C.byref(io), err, 512) != 0:
+    if load_library().vgx_test_timelines(C.byref(io), err, 512) != 0:
         raise ValueError(err.value.decode() or "vgx_test_timelines failed")
-    return {"time_points": tp, "infectious": inf[:len(qi)][ii], "samples": smp[:len(qi)][ii], "susceptible": sus[:len(qs)][si],
-            "last_point": int(io.last_point)}
+    return finish()
+
+
+MEV_COLUMNS = ("num", "types", "haplotypes", "populations", "newHaplotypes", "newPopulations")
+
+
+def replay_tau_timelines(m, infectious=(), susceptible=(), step_num=100, semantics='reference', mev=None):
+    """The log replays of ``Ensemble.tau_timelines`` for one host model through ``vgx_test_tau_timelines``: the device replay's
+    code (weighted rows, flattening, cut search; vgx_tline.h, vgx_tau_timelines.hip) compiled for the host, on ``m.events`` with
+    the multievent rows its MULTITYPE events index (no GPU).  ``mev``: a dict of the columns num, types, haplotypes, populations,
+    newHaplotypes, newPopulations (dense logs with ``num == 0`` rows are fine); default ``m.multievents``.  Same dict as
+    ``replay_timelines``."""
+    io, finish = _timelines_chain(m, infectious, susceptible, step_num, semantics)
+    tio = VgxTauTimelinesChain()
+    tio.chain = io
+    if mev is None:
+        mv = m.multievents
+        mev = {c: getattr(mv, c)[:mv.ptr] for c in MEV_COLUMNS}
+    cols = [np.ascontiguousarray(mev[c], dtype=np.int64) for c in MEV_COLUMNS]
+    if len({len(c) for c in cols}) != 1:
+        raise ValueError("multievent columns of different lengths")
+    tio.mev_rows = len(cols[0])
+    for name, col in zip(MEV_COLUMNS, cols):
+        setattr(tio, "mev_" + name, _p(col))
+    err = C.create_string_buffer(512)
+    if load_library().vgx_test_tau_timelines(C.byref(tio), err, 512) != 0:
+        raise ValueError(err.value.decode() or "vgx_test_tau_timelines failed")
+    return finish(tio.chain)
 
 
 def direct_plan(shape, mode=0, kernel=0):

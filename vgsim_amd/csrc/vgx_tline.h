@@ -2,6 +2,8 @@
 // DIRECT event chain, written once for the host and the device: which counters an event moves, the rule that turns event
 // times into bins, and the query table.  vgx_timelines.hip runs it one workgroup per replicate over the device log
 // (vgx_get_timelines) and, compiled for the host, behind vgx_test_timelines.
+// vgx_tau_timelines.hip runs the same rule on weighted rows (a tau replicate's chain: the model's events before the call, then
+// its multievent rows) behind vgx_get_tau_timelines / vgx_test_tau_timelines.
 //
 // The replay depends on time for one thing only: at which event the grid index `point` advances (pyx:1978-1981).  `point`
 // never decreases, so the whole time dependence of a chain is step_num event indices:
@@ -59,6 +61,21 @@ VGX_HD void vgx_tl_classify(int semantics, const int32_t c[5], VgxTlMoves &m) {
         m.op[0] = VgxTlOp{0, np, hap, 1, 0};
         m.op[1] = VgxTlOp{1, np, nh, -1, 0};
     }
+}
+
+// ---- weighted rows (vgx_tau_timelines.hip): the chain of a tau replicate as ONE list of rows (num, type, haplotype, population,
+// newHaplotype, newPopulation).  A direct event is a row with num = 1 under the DIRECT rule (vgx_tl_classify as it stands); a
+// multievent row moves the same counters num times under the MULTIEVENT rule, the MULTITYPE branch of the reference's replays
+// (pyx:1993-2003, 2030-2040), which differs from the direct rule in one place: its susceptible MIGRATION clause tests the row's
+// `haplotypes` field against the group (pyx:2037) where the direct one tests `newHaplotypes` (pyx:2023).  The tau kernels write
+// the migrant's group into newHaplotypes (as direct MIGRATION events carry it), so the `compartment` semantics key it there under
+// both rules.  Returns the weight of the row's moves (0: the row moves nothing).
+enum { VGX_TL_RULE_DIRECT = 0, VGX_TL_RULE_MULTIEVENT = 1 };
+#define VGX_TL_ROW_DIRECT 0x100   // set in the type field of a flattened row that takes the direct rule
+VGX_HD int64_t vgx_tl_classify_row(int semantics, int rule, int64_t num, const int32_t c[5], VgxTlMoves &m) {
+    vgx_tl_classify(semantics, c, m);
+    if (rule == VGX_TL_RULE_MULTIEVENT && semantics == VGX_TL_REFERENCE && c[0] == VGX_TL_MIGRATION) m.op[1].minor = c[1];
+    return num > 0 ? num : 0;
 }
 
 // ---- the query table: open addressing over (major, minor'), minor' = haplotype for an infectious query and ~group for a
@@ -145,5 +162,40 @@ VGX_HD int64_t vgx_tl_lds_bytes(int64_t step, int64_t ni, int64_t ns) {
     const int64_t T = step + 1;
     return 4 * (step + 3 * (int64_t)vgx_tl_table_size((int)(ni + ns)) + 2 * T + (2 * ni + ns) * T);
 }
-#define VGX_TL_LDS_DEFAULT (64 * 1024)     // a workgroup's LDS budget unless VGX_TIMELINES_LDS_BYTES says otherwise
+// ... of the weighted-row replay (vgx_tau_timelines.hip): the same rows with int64 counters (a bin sums `num` over many steps), the
+// counters first so that they are 8-byte aligned, then the cuts and the table.
+VGX_HD int64_t vgx_ttl_lds_bytes(int64_t step, int64_t ni, int64_t ns) {
+    const int64_t T = step + 1;
+    return 8 * (2 * T + (2 * ni + ns) * T) + 4 * (step + 3 * (int64_t)vgx_tl_table_size((int)(ni + ns)));
+}
+
+// host: the cuts of a chain made of a PREFIX of events shared by many chains and the chain's OWN events, as ROW indices of the
+// flattened list (prefix rows, then own rows).  The event loop is VgxTlCutter's; the prefix part does not walk the prefix:
+// time_points never decrease, so the first prefix event with `time_points[p] < t` is the first one whose RUNNING MAXIMUM of the
+// times exceeds time_points[p] — a binary search in pre_max per grid point, equal to the literal loop whatever the times do.
+// pre_row[i] = first row of prefix event i (pre_row[n_pre] = prefix rows); own event k starts at row own_row0 + own_m0(k); an
+// event without rows still advances `point`, and its cut is the first row after it.  Returns last_point.
+template <class OwnTime, class OwnRow>
+static inline int64_t vgx_tl_row_cuts(const double *tp, int64_t step, int64_t n_pre, const double *pre_max, const int64_t *pre_row,
+                                      int64_t n_own, OwnTime own_time, OwnRow own_m0, int64_t own_row0, int64_t n_rows, int32_t *cut) {
+    int64_t point = 0, lo = 0;
+    while (point != step && lo < n_pre) {
+        int64_t a = lo, b = n_pre;                       // first i in [lo, n_pre) with pre_max[i] > tp[point]
+        while (a < b) {
+            const int64_t mid = (a + b) >> 1;
+            if (tp[point] < pre_max[mid]) b = mid; else a = mid + 1;
+        }
+        if (a == n_pre) break;
+        cut[point++] = (int32_t)pre_row[a];
+        lo = a;
+    }
+    for (int64_t k = 0; k < n_own; k++) {
+        const double t = own_time(k);
+        while (point != step && tp[point] < t) cut[point++] = (int32_t)(own_row0 + own_m0(k));
+    }
+    for (int64_t p = point; p < step; p++) cut[p] = (int32_t)n_rows;
+    return point;
+}
+
+#define VGX_TL_LDS_DEFAULT (64 * 1024)    // a workgroup's LDS budget unless VGX_TIMELINES_LDS_BYTES says otherwise
 #define VGX_TL_LDS_MAX (160 * 1024)        // what one workgroup may declare on gfx950

@@ -42,6 +42,7 @@ class Ensemble:
         assert self.seeds.shape == (self.R,)
         self.traj_shape = None
         self._last_call = None   # ('direct' | 'tau', record_events) of the last simulate call
+        self._tau_prefix = None  # events, multievent rows and lockdown records of the model when the last recorded tau call started
 
     def close(self):
         self.engine.close()
@@ -114,6 +115,13 @@ class Ensemble:
         finally:
             m.events.ptr, m.events.size = saved
         eng.set_seeds(self.seeds)
+        self._tau_prefix = None
+        if record_events:   # the model's chain as it is now: what tau_timelines() replays in front of every replicate's steps
+            ev, mv = m.events, m.multievents
+            self._tau_prefix = ([ev.times[:ev.ptr].copy()] + [getattr(ev, c)[:ev.ptr].copy() for c in ev.COLUMNS],
+                                [getattr(mv, c)[:mv.ptr].copy() for c in mv.COLUMNS],
+                                [np.asarray(m.loc.states, dtype=np.int64), np.asarray(m.loc.populationsId, dtype=np.int64),
+                                 np.asarray(m.loc.times, dtype=np.float64)])
         o = _capi.VgxRunOpts()
         o.record_events = 1 if record_events else 0
         o.traj_points = int(traj_points)
@@ -274,12 +282,57 @@ class Ensemble:
             raise ValueError("timelines() replays direct chains only: the last call was simulate_tau")
         if not self._last_call[1]:
             raise ValueError("timelines() needs the event log: the last call had record_events=False")
+        step_num, qi, ii, qs, si, reps = self._timeline_arguments(infectious, susceptible, step_num, replicates, semantics)
+        eng = self.engine
+        for r in reps:
+            c = eng.counters(int(r))
+            if c.ev_first_new != 0:
+                raise ValueError("replicate %d: its chain does not start in the last call's device log (the model held %d events "
+                                 "when the ensemble started)" % (r, c.ev_first_new))
+        return self._timeline_batch(lambda io: eng.lib.vgx_get_timelines(eng.handle, C.byref(io)), step_num, qi, ii, qs, si, reps, semantics)
+
+    def tau_timelines(self, infectious=(), susceptible=(), step_num=100, replicates=None, semantics='reference'):
+        """``timelines()`` for the replicates of the last ``simulate_tau(record_events=True)`` call (``vgx_get_tau_timelines``):
+        the same queries, semantics, validation and :class:`TimelineBatch`, one pass per replicate over its multievent rows
+        where the tau kernels left them.
+
+        The reference replays the WHOLE chain of a model, so every replicate's series run over the events the model held when
+        the tau call started (``model.events`` / ``model.multievents`` as they were then; shared by all replicates and uploaded
+        once), followed by the replicate's own steps, on the grid ``i * currentTime_r / step_num`` of its own final time.  A
+        replicate that restarted (``restarts > 0``) starts again at time 0 without that prefix.  Lockdown records: the model's
+        before the call, then the replicate's (a restarted replicate: its own only).  Multievent rows take the rule of the
+        reference's MULTITYPE branch (its susceptible MIGRATION clause tests ``haplotypes``, pyx:2037); 'compartment' keys the
+        migrant's group where the tau kernels write it, so its ``Data[last_point]`` is ``replicate_states_tau()``'s state.  Series
+        are exact while their values stay below 2^53 in magnitude."""
+        if self._last_call is None:
+            raise ValueError("tau_timelines() needs a simulate_tau(record_events=True) call first")
+        if self._last_call[0] != 'tau':
+            raise ValueError("tau_timelines() replays tau chains only: the last call was a direct simulate()")
+        if not self._last_call[1]:
+            raise ValueError("tau_timelines() needs the multievent rows: the last call had record_events=False")
+        step_num, qi, ii, qs, si, reps = self._timeline_arguments(infectious, susceptible, step_num, replicates, semantics)
+        eng = self.engine
+        pre = _capi.VgxTimelinesPrefix()
+        ev, mv, loc = self._tau_prefix
+        pre.ev_ptr, pre.ev_times = len(ev[0]), _capi._p(ev[0])
+        for name, col in zip(("types", "haplotypes", "populations", "newHaplotypes", "newPopulations"), ev[1:]):
+            setattr(pre, "ev_" + name, _capi._p(col))
+        pre.mev_rows = len(mv[0])
+        for name, col in zip(_capi.MEV_COLUMNS, mv):
+            setattr(pre, "mev_" + name, _capi._p(col))
+        pre.loc_n, pre.loc_state, pre.loc_pop, pre.loc_time = len(loc[0]), _capi._p(loc[0]), _capi._p(loc[1]), _capi._p(loc[2])
+        return self._timeline_batch(lambda io: eng.lib.vgx_get_tau_timelines(eng.handle, C.byref(io), C.byref(pre)),
+                                    step_num, qi, ii, qs, si, reps, semantics)
+
+    def _timeline_arguments(self, infectious, susceptible, step_num, replicates, semantics):
+        """The checks ``timelines()`` and ``tau_timelines()`` share: (step_num, unique infectious queries and the index of every given
+        one among them, the same for the susceptible ones, replicates)."""
         if semantics not in _capi.TIMELINE_SEMANTICS:
             raise ValueError("semantics must be 'reference' or 'compartment'")
         step_num = int(step_num)
         if step_num < 1:
             raise ValueError("step_num must be at least 1")
-        m, eng, lib = self.model, self.engine, self.engine.lib
+        m = self.model
         qi, ii = _capi.unique_queries(infectious)
         qs, si = _capi.unique_queries(susceptible)
         for q, width, what in ((qi, m.hapNum, "haplotype"), (qs, m.susNum, "susceptibility group")):
@@ -293,18 +346,17 @@ class Ensemble:
             raise ValueError("replicate index out of range")
         if len(np.unique(reps)) != n:
             raise ValueError("replicates must be distinct")
-        for r in reps:
-            c = eng.counters(int(r))
-            if c.ev_first_new != 0:
-                raise ValueError("replicate %d: its chain does not start in the last call's device log (the model held %d events "
-                                 "when the ensemble started)" % (r, c.ev_first_new))
-        T = step_num + 1
+        return step_num, qi, ii, qs, si, reps
+
+    def _timeline_batch(self, call, step_num, qi, ii, qs, si, reps, semantics):
+        """The two-call protocol of ``vgx_get_timelines`` / ``vgx_get_tau_timelines`` (``call(io)`` returns the library's code)."""
+        eng, n, T = self.engine, len(reps), step_num + 1
         io = _capi.VgxTimelinesIO()
         io.n, io.replicates, io.step_num, io.semantics = n, _capi._p(reps), step_num, _capi.TIMELINE_SEMANTICS[semantics]
         keep = [np.ascontiguousarray(q[:, j]) for q in (qi, qs) for j in (0, 1)]
         io.n_inf, io.inf_pop, io.inf_hap = len(qi), _capi._p(keep[0]), _capi._p(keep[1])
         io.n_sus, io.sus_pop, io.sus_grp = len(qs), _capi._p(keep[2]), _capi._p(keep[3])
-        eng._check(lib.vgx_get_timelines(eng.handle, C.byref(io)))            # sizing
+        eng._check(call(io))                                                  # sizing
         cap = int(io.loc_cap)
         tp = np.zeros((max(n, 1), T))
         inf, smp = np.zeros((max(n, 1), max(len(qi), 1), T)), np.zeros((max(n, 1), max(len(qi), 1), T))
@@ -321,7 +373,7 @@ class Ensemble:
         io.inf_sample = _capi._p(smp) if len(qi) else None
         io.sus_data = _capi._p(sus) if len(qs) else None
         io.loc_n, io.loc_state, io.loc_pop, io.loc_time = _capi._p(loc_n), _capi._p(loc_state), _capi._p(loc_pop), _capi._p(loc_time)
-        eng._check(lib.vgx_get_timelines(eng.handle, C.byref(io)))            # replay
+        eng._check(call(io))                                                  # replay
         b = TimelineBatch(reps, qi[ii], qs[si], step_num, semantics)
         b.time_points, b.last_point = tp[:n], last[:n]
         b.infectious, b.samples, b.susceptible = inf[:n][:, ii], smp[:n][:, ii], sus[:n][:, si]
