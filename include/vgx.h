@@ -27,7 +27,7 @@
  *   VGX_TAU_NO_OCCLIST=1           tau: a try's scan and front pass always stream all compartments (no lists of the occupied ones)
  *   VGX_TAU_NO_FRONT_ALONE=1       tau, one replicate: the front pass is enqueued together with the try proper, not ahead of it
  *   VGX_TAU_LARGE_MODEL_THRESHOLDS=1  tau: the draw thresholds of large models on a small one
- *   VGX_GENEALOGY_CHUNK_BYTES=n    vgx_get_genealogies: device bytes of workspace per pass (several passes)
+ *   VGX_GENEALOGY_CHUNK_BYTES=n    vgx_get_genealogies, vgx_get_tau_genealogies: device bytes of workspace per pass (several passes)
  *   VGX_TIMELINES_LDS_BYTES=n      vgx_get_timelines, vgx_get_tau_timelines: LDS budget of a replay workgroup (default 65536, at most 163840; the
  *                                  queries are split over launches)
  *   VGX_TIMELINES_CHUNK_BYTES=n    vgx_get_timelines, vgx_get_tau_timelines: device bytes of staging and outputs per chunk of replicates
@@ -299,6 +299,68 @@ int vgx_genealogy_message(int64_t status, int64_t arg, char *errbuf, int64_t err
 /* Test hook: the walk of vgx_get_genealogies (same code, compiled for the host) on the chain, state and generator of a
  * vgx_genealogy_io; same outputs as vgx_get_genealogy.  Direct chains only: a MULTITYPE event with rows is refused. */
 int vgx_test_genealogy_walk(vgx_genealogy_io *io, char *errbuf, int64_t errcap);
+
+/* The backward pass for many replicates of the last vgx_simulate_tau call (with the event log), on the device.  For every selected
+ * replicate the result is what vgx_get_genealogy returns on that replicate's WHOLE chain in the reference's layout, from its final
+ * state: the events and multievent rows the model held when the call started (`prefix`, shared by all replicates; NULL or empty
+ * when there were none), then the replicate's own steps with their rows in the reference's order and granularity (one row per
+ * channel: the tau kernels append a row per drawn transmission, mutant or migrant, in scheduling order).  A replicate that
+ * restarted (vgx_counters.restarts > 0) has no prefix.  A canonicalise kernel (one workgroup per replicate) sorts every step's
+ * rows by the reference's channel order in LDS and merges equal channels into compact rows in the pass's workspace — the
+ * multievent log itself is only read — and a walk kernel (one replicate per wavefront) takes the rows from the last step back,
+ * then the prefix, then the closing pass.  Prefix events of direct type take the single-event rule of vgx_get_genealogies.
+ * The two-call protocol, the outputs and the passes are those of vgx_get_genealogies (VGX_GENEALOGY_CHUNK_BYTES included), with
+ * these differences:
+ *   - rng_state / rng_out are [n][6]: the PCG64 words, then numpy's buffered 32-bit half (rng_has_uint32, rng_uinteger of
+ *     vgx_genealogy_io): the hypergeometric sampler draws 32-bit halves;
+ *   - capacities of the sizing call: 2 sCounter - 1 nodes; mutation records: the sum of min(num, sCounter) over the replicate's
+ *     MUTATION rows as the device holds them, plus the prefix's (an event counts 1); migration records likewise, plus the nodes;
+ *   - THE STEP BOUND: the sort of a step holds a 16-byte key and a 2-byte row index per raw row in the 160 KiB of LDS a workgroup
+ *     may declare: at most 8192 raw rows per step.  A replicate with a longer step gets status 10 (VGX_GW_STEP_ROWS, status_arg =
+ *     the step of the call, 0-based) and fails nothing else;
+ *   - status 12: a row with an index outside the model, or with more events than the counts of its compartment allow (numpy's
+ *     hypergeometric raises on those; vgx_get_genealogy does not check them and must not be given such a chain: tau steps at very
+ *     small counts can write one);
+ *   - THE LOGARITHM: numpy's hypergeometric sampler (HRUA, from 10 draws on) calls log() in Stirling's ln k! (k >= 126) and in its
+ *     acceptance test 2 log U <= T.  The device's library log and the host's are different functions, so the walk uses the
+ *     engine's own logarithm (fdlibm's algorithm in +, -, *, / on binary64, no contraction; below 1 ulp): the device and its host
+ *     instance (vgx_test_tau_genealogy_walk, vgx_test_hypergeometric) are identical by construction.  vgx_get_genealogy keeps
+ *     libm's log: against it a draw — and the tree after it — can differ only where one of HRUA's comparisons is decided within
+ *     the last ulp of a logarithm;
+ *   - ms[0] is the device time of both kernels, ms[1] the host's conversion of the outputs.
+ * Refusals (VGX_ERR_ARG): the last call was not vgx_simulate_tau; it recorded no rows (record_events = 0); a replicate that did
+ * not restart continues a log of another length than prefix->ev_ptr; a prefix row with an index outside the model. */
+typedef struct vgx_tau_genealogy_prefix {
+    int64_t ev_ptr;                          /* events of the model's chain before the call */
+    const double *ev_times;
+    const int64_t *ev_types, *ev_haplotypes, *ev_populations, *ev_newHaplotypes, *ev_newPopulations;
+    int64_t mev_rows;                        /* multievent rows its MULTITYPE events index as [haplotypes, populations) */
+    const int64_t *mev_num; const double *mev_times;   /* mev_times may be NULL: the event's time then */
+    const int64_t *mev_types, *mev_haplotypes, *mev_populations, *mev_newHaplotypes, *mev_newPopulations;
+} vgx_tau_genealogy_prefix;
+typedef struct vgx_tau_genealogies_io {
+    int64_t n;                               /* selected replicates */
+    const int64_t *replicates;               /* [n] */
+    const uint64_t *rng_state;               /* [n][6] start of every walk (walk call) */
+    int64_t *node_off, *mut_off, *mig_off;   /* [n+1] written by the sizing call, read by the walk call */
+    int64_t *tree, *tree_pop; double *times;                         /* [node_off[n]] */
+    int64_t *mut_node, *mut_AS, *mut_DS, *mut_site; double *mut_time; /* [mut_off[n]] */
+    int64_t *mig_node, *mig_old, *mig_new; double *mig_time;         /* [mig_off[n]] */
+    int64_t *status, *status_arg, *nodes_used, *mut_n, *mig_n;       /* [n] */
+    uint64_t *rng_out;                       /* [n][6] generator state after the walk */
+    int64_t passes;                          /* out: device passes the walk took */
+    double ms[3];                            /* out: kernels (device time), output conversion, whole call */
+} vgx_tau_genealogies_io;
+int vgx_get_tau_genealogies(vgx_engine *e, vgx_tau_genealogies_io *io, const vgx_tau_genealogy_prefix *prefix);
+/* Test hook: the walk of vgx_get_tau_genealogies (same key, merge rule, row rule and sampler, compiled for the host) on the
+ * chain, state and generator of a vgx_genealogy_io; same outputs as vgx_get_genealogy.  The chain's trailing MULTITYPE events
+ * play the replicate's own steps: their rows may come in any order and granularity (they are brought into the reference's by
+ * the device's key; a step of more than 8192 rows is refused with the text of status 10).  Everything before them plays the
+ * prefix: its rows are taken as they are.  `sites`: the model's number of sites (hapNum = 4^sites). */
+int vgx_test_tau_genealogy_walk(vgx_genealogy_io *io, int64_t sites, char *errbuf, int64_t errcap);
+/* Test hook: n draws of numpy's random_hypergeometric(good, bad, sample) as the walk makes them, by the host build of the sampler
+ * or the device's; state = PCG64 state hi, lo, increment hi, lo, has_uint32, uinteger (in / out). */
+int vgx_test_hypergeometric(int on_device, int64_t good, int64_t bad, int64_t sample, int64_t n, uint64_t state[6], int64_t *out);
 
 /* ---- log replays ---------------------------------------------------------------------------- */
 /* Replaces BirthDeathModel.get_data_infectious(pop, hap, step_num) / get_data_susceptible(pop, group, step_num) (pyx:1967-2045)

@@ -73,6 +73,27 @@ class VgxGenealogiesIO(C.Structure):
                 ("rng_out", C.POINTER(C.c_uint64)), ("layout", C.c_int64), ("passes", C.c_int64), ("ms", C.c_double * 3)]
 
 
+class VgxTauGenealogyPrefix(C.Structure):
+    _fields_ = [("ev_ptr", C.c_int64), ("ev_times", _F), ("ev_types", _I), ("ev_haplotypes", _I), ("ev_populations", _I),
+                ("ev_newHaplotypes", _I), ("ev_newPopulations", _I),
+                ("mev_rows", C.c_int64), ("mev_num", _I), ("mev_times", _F), ("mev_types", _I), ("mev_haplotypes", _I),
+                ("mev_populations", _I), ("mev_newHaplotypes", _I), ("mev_newPopulations", _I)]
+
+
+class VgxTauGenealogiesIO(C.Structure):
+    _fields_ = [("n", C.c_int64), ("replicates", _I), ("rng_state", C.POINTER(C.c_uint64)),
+                ("node_off", _I), ("mut_off", _I), ("mig_off", _I),
+                ("tree", _I), ("tree_pop", _I), ("times", _F),
+                ("mut_node", _I), ("mut_AS", _I), ("mut_DS", _I), ("mut_site", _I), ("mut_time", _F),
+                ("mig_node", _I), ("mig_old", _I), ("mig_new", _I), ("mig_time", _F),
+                ("status", _I), ("status_arg", _I), ("nodes_used", _I), ("mut_n", _I), ("mig_n", _I),
+                ("rng_out", C.POINTER(C.c_uint64)), ("passes", C.c_int64), ("ms", C.c_double * 3)]
+
+
+TAU_STEP_ROWS_MAX = 8192   # raw multievent rows of one step the device pass sorts (vgx.h: the step bound)
+GW_STEP_ROWS = 10          # the status of a replicate with a longer step
+
+
 class VgxTimelinesIO(C.Structure):
     _fields_ = [("n", C.c_int64), ("replicates", _I), ("step_num", C.c_int64), ("semantics", C.c_int64),
                 ("n_inf", C.c_int64), ("inf_pop", _I), ("inf_hap", _I), ("n_sus", C.c_int64), ("sus_pop", _I), ("sus_grp", _I),
@@ -164,6 +185,9 @@ SIGNATURES = {
     "vgx_get_genealogies": (C.c_int, [_H, C.POINTER(VgxGenealogiesIO)]),
     "vgx_genealogy_message": (C.c_int, [C.c_int64, C.c_int64, C.c_char_p, C.c_int64]),
     "vgx_test_genealogy_walk": (C.c_int, [C.POINTER(VgxGenealogyIO), C.c_char_p, C.c_int64]),
+    "vgx_get_tau_genealogies": (C.c_int, [_H, C.POINTER(VgxTauGenealogiesIO), C.POINTER(VgxTauGenealogyPrefix)]),
+    "vgx_test_tau_genealogy_walk": (C.c_int, [C.POINTER(VgxGenealogyIO), C.c_int64, C.c_char_p, C.c_int64]),
+    "vgx_test_hypergeometric": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64 * 6), _I]),
     "vgx_get_timelines": (C.c_int, [_H, C.POINTER(VgxTimelinesIO)]),
     "vgx_test_timelines": (C.c_int, [C.POINTER(VgxTimelinesChain), C.c_char_p, C.c_int64]),
     "vgx_get_tau_timelines": (C.c_int, [_H, C.POINTER(VgxTimelinesIO), C.POINTER(VgxTimelinesPrefix)]),
@@ -520,6 +544,25 @@ def genealogy_walk(m, seed=None, rng_position=None, rng_raw=None):
     return _genealogy("vgx_test_genealogy_walk", m, seed, rng_position, rng_raw)
 
 
+def tau_genealogy_walk(m, seed=None, rng_position=None, rng_raw=None):
+    """``get_genealogy`` through ``vgx_test_tau_genealogy_walk``: the walk of the device pass for tau chains (vgx_gwalk_tau.h)
+    compiled for the host, on the same arguments.  The chain's trailing MULTITYPE events play a replicate's own steps: their
+    rows may come in any order and granularity; everything before them is taken as it is.  Same dict, same exceptions."""
+    return _genealogy("vgx_test_tau_genealogy_walk", m, seed, rng_position, rng_raw, extra=(int(m.sites),))
+
+
+def hypergeometric(good, bad, sample, n, state, on_device=False):
+    """``n`` draws of numpy's ``random_hypergeometric(good, bad, sample)`` by the sampler of the tau walk (``vgx_test_hypergeometric``;
+    the host build, or the device's).  ``state``: PCG64 state hi, lo, increment hi, lo, has_uint32, uinteger.  Returns (draws, state
+    after them)."""
+    st = (C.c_uint64 * 6)(*[int(x) for x in state])
+    out = np.zeros(max(int(n), 1), dtype=np.int64)
+    rc = load_library().vgx_test_hypergeometric(1 if on_device else 0, int(good), int(bad), int(sample), int(n), C.byref(st), _p(out))
+    if rc != VGX_OK:
+        raise VgxError(rc, "vgx_test_hypergeometric failed")
+    return out[:n], tuple(int(x) for x in st)
+
+
 def genealogy_message(status, arg):
     """The text ``vgx_get_genealogy`` reports for a walk status of ``vgx_get_genealogies``."""
     buf = C.create_string_buffer(512)
@@ -527,7 +570,7 @@ def genealogy_message(status, arg):
     return buf.value.decode()
 
 
-def _genealogy(entry, m, seed, rng_position, rng_raw):
+def _genealogy(entry, m, seed, rng_position, rng_raw, extra=()):
     lib = load_library()
     ev, mv = m.events, m.multievents
     io = VgxGenealogyIO()
@@ -573,7 +616,7 @@ def _genealogy(entry, m, seed, rng_position, rng_raw):
     out["mig_time"] = np.zeros(io.mig_cap)
     io.mig_time = _p(out["mig_time"])
     err = C.create_string_buffer(512)
-    rc = getattr(lib, entry)(C.byref(io), err, 512)
+    rc = getattr(lib, entry)(C.byref(io), *extra, err, 512)
     if rc != 0:
         raise RuntimeError(err.value.decode() or "%s failed (%d)" % (entry, rc))
     for k in list(out):

@@ -19,6 +19,7 @@
 
 #include "../../include/vgx.h"
 #include "vgx_gwalk.h"
+#include "vgx_gwalk_tau.h"
 #include "vgx_logfact.h"
 #include "vgx_rng.h"
 
@@ -393,6 +394,12 @@ static std::string walk_message(int64_t status, int64_t arg) {
     case VGX_GW_MUT_CAP: return "vgx_get_genealogy: mutation record capacity exceeded";
     case VGX_GW_MIG_CAP: return "vgx_get_genealogy: migration record capacity exceeded";
     case VGX_GW_WORKSPACE: return "vgx_get_genealogy: walk workspace exhausted";
+    case VGX_GW_STEP_ROWS:
+        return "vgx_get_tau_genealogies: step " + std::to_string(arg) + " of the call has more multievent rows than the device sorts (" +
+               std::to_string(VGX_GT_STEP_ROWS_MAX) + ")";
+    case VGX_GW_UNKNOWN_ROW_TYPE: return "vgx_get_genealogy: unknown multievent type " + std::to_string(arg);
+    case VGX_GW_BAD_ROW:
+        return "vgx_get_tau_genealogies: a multievent row of event " + std::to_string(arg) + " does not fit the model or the compartment counts";
     default: return "vgx_get_genealogy: walk status " + std::to_string(status);
     }
 }

@@ -122,6 +122,7 @@ class Ensemble:
                                 [getattr(mv, c)[:mv.ptr].copy() for c in mv.COLUMNS],
                                 [np.asarray(m.loc.states, dtype=np.int64), np.asarray(m.loc.populationsId, dtype=np.int64),
                                  np.asarray(m.loc.times, dtype=np.float64)])
+            self._tau_prefix_mev_times = mv.times[:mv.ptr].copy()   # (tau_genealogies: nodes of a prefix row carry the row's time)
         o = _capi.VgxRunOpts()
         o.record_events = 1 if record_events else 0
         o.traj_points = int(traj_points)
@@ -255,6 +256,132 @@ class Ensemble:
         io.rng_out = rng_out.ctypes.data_as(C.POINTER(C.c_uint64))
         io.layout = 1 if layout == 'wave' else 0
         eng._check(lib.vgx_get_genealogies(eng.handle, C.byref(io)))          # walk
+        b._fill(off, cap, {k: v[:n] for k, v in per.items()}, rng_out[:n])
+        b.passes, b.kernel_ms, b.clock_ms, b.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
+        return b
+
+    def _check_tau_genealogy_call(self, what):
+        if self._last_call is None:
+            raise ValueError("%s needs a simulate_tau(record_events=True) call first" % what)
+        if self._last_call[0] != 'tau':
+            raise ValueError("%s walks tau chains only: the last call was a direct simulate()" % what)
+        if not self._last_call[1]:
+            raise ValueError("%s needs the multievent rows: the last call had record_events=False" % what)
+
+    def tau_genealogy(self, replicate, seed):
+        """Backward pass (``GetGenealogy``, pyx:743-1000) over the WHOLE chain of one replicate of the last
+        ``simulate_tau(record_events=True)`` call, on the host: the events and multievent rows the model held when the call
+        started (none for a replicate that restarted), then the replicate's own steps with their rows in the reference's order
+        (``_capi.canonical_multievents``), from the replicate's final state.  ``seed``: an int reseeds the stream with
+        ``(seed, 0)``; None starts at ``(seeds[replicate], attempt 0, 0 draws)``, where the model's ``genealogy()`` starts after a
+        tau call.  Returns the dict of ``_capi.get_genealogy``; a chain with a row the reference's pass cannot take (numpy's
+        hypergeometric would raise on it) raises the text of the device pass's status 12 instead."""
+        import copy
+        from ._model import Events, MultiEvents
+        self._check_tau_genealogy_call("tau_genealogy()")
+        eng = self.engine
+        r = int(replicate)
+        m = self.replicate_state(r)
+        c = eng.counters(r)
+        ev0, mv0, _ = self._tau_prefix
+        if c.restarts > 0:
+            n_pre, k_pre = 0, 0
+        else:
+            n_pre, k_pre = len(ev0[0]), len(mv0[0])
+            if c.ev_first_new != n_pre:
+                raise ValueError("replicate %d: its chain continues a log of %d events, the prefix holds %d" % (r, c.ev_first_new, n_pre))
+        own = self.replicate_events(r)[:, int(c.ev_first_new):]
+        starts, ends = own[2].astype(np.int64), own[3].astype(np.int64)
+        if m.sCounter >= 2 and len(starts) and int((ends - starts).max()) > _capi.TAU_STEP_ROWS_MAX:   # what the device pass reports
+            raise RuntimeError(_capi.genealogy_message(_capi.GW_STEP_ROWS, int(np.argmax(ends - starts > _capi.TAU_STEP_ROWS_MAX))))
+        rows = _capi.canonical_multievents(eng.multievents(r), starts, ends, m.sites, m.susNum)
+        n = n_pre + own.shape[1]
+        ev = Events()
+        ev.CreateEvents(max(n, 1))
+        ev.times[:n] = np.concatenate((ev0[0][:n_pre], own[0]))
+        for k, name in enumerate(ev.COLUMNS):
+            col = own[k + 1].astype(np.int64)
+            if name == "haplotypes":
+                col = starts + k_pre                 # the MULTITYPE records' row ranges, behind the prefix's rows
+            elif name == "populations":
+                col = ends + k_pre
+            getattr(ev, name)[:n] = np.concatenate((ev0[k + 1][:n_pre], col))
+        ev.ptr = n
+        mv = MultiEvents()
+        mv.extend(np.concatenate((self._tau_prefix_mev_times[:k_pre], rows["times"])),
+                  **{name: np.concatenate((mv0[j][:k_pre], rows[name])) for j, name in enumerate(mv.COLUMNS)})
+        m.events, m.multievents = ev, mv
+        m.user_seed = int(self.seeds[r])
+        # vgx_get_genealogy trusts its rows as the reference does: where numpy's hypergeometric would raise (more migrants than the
+        # source compartment holds, ...) or a transmission row draws more pairs than there are lineages, it reads and writes outside
+        # its lists.  Tau steps at very small counts write such rows.  The guarded walk of the device pass (its host instance) goes
+        # first on a copy of the counts: what it refuses is raised here with the device's text, and never reaches the host pass.
+        probe = copy.copy(m)
+        probe.infectious = m.infectious.copy()
+        try:
+            _capi.tau_genealogy_walk(probe, seed, rng_position=(0, 0))
+        except RuntimeError as e:
+            if str(e).startswith("vgx_get_tau_genealogies:"):
+                raise
+        return _capi.get_genealogy(m, seed, rng_position=(0, 0))
+
+    def tau_genealogies(self, seed=None, replicates=None):
+        """The backward pass of every selected replicate of the last ``simulate_tau(record_events=True)`` call at once, on the
+        device (``vgx_get_tau_genealogies``): every step's rows are brought into the reference's order and granularity where the
+        tau kernels left them (they are only read), then one walk per replicate over its whole chain: the model's chain before the
+        call (shared, uploaded once; none for a replicate that restarted), then its own steps.  Returns a :class:`GenealogyBatch`
+        whose ``replicate(r)`` equals ``tau_genealogy(r, seed_r)`` on every key, all six words of ``rng_raw`` included (the
+        hypergeometric sampler's logarithm is the engine's own on the device and libm's on the host: a draw can differ only where
+        a comparison is decided within the last ulp of a logarithm, include/vgx.h).
+
+        ``seed`` and ``replicates`` as in ``genealogies()``; ``seed=None`` starts every walk at ``(seeds[r], attempt 0, 0
+        draws)``.  A replicate whose walk fails (fewer than two samples, a step of more than 8192 raw rows, ...) gets a nonzero
+        status and does not fail the call."""
+        self._check_tau_genealogy_call("tau_genealogies()")
+        eng, lib = self.engine, self.engine.lib
+        reps = np.arange(self.R, dtype=np.int64) if replicates is None else np.ascontiguousarray(replicates, dtype=np.int64).ravel()
+        n = len(reps)
+        if n and (reps.min() < 0 or reps.max() >= self.R):
+            raise ValueError("replicate index out of range")
+        if len(np.unique(reps)) != n:
+            raise ValueError("replicates must be distinct")
+        if seed is not None and not np.isscalar(seed):
+            seeds = np.ascontiguousarray(seed, dtype=np.int64).ravel()
+            if len(seeds) != n:
+                raise ValueError("one seed per selected replicate: got %d for %d" % (len(seeds), n))
+        rng = np.zeros((max(n, 1), 6), dtype=np.uint64)
+        pos = (C.c_uint64 * 4)()
+        for i, r in enumerate(reps):
+            lib.vgx_rng_position(int(self.seeds[r]) if seed is None else int(seed) if np.isscalar(seed) else int(seeds[i]), 0, 0, C.byref(pos))
+            rng[i, :4] = list(pos)
+        pre = _capi.VgxTauGenealogyPrefix()
+        ev, mv, _ = self._tau_prefix
+        pre.ev_ptr, pre.ev_times = len(ev[0]), _capi._p(ev[0])
+        for name, col in zip(("types", "haplotypes", "populations", "newHaplotypes", "newPopulations"), ev[1:]):
+            setattr(pre, "ev_" + name, _capi._p(col))
+        pre.mev_rows, pre.mev_times = len(mv[0]), _capi._p(self._tau_prefix_mev_times)
+        for name, col in zip(_capi.MEV_COLUMNS, mv):
+            setattr(pre, "mev_" + name, _capi._p(col))
+        b = GenealogyBatch(reps)
+        io = _capi.VgxTauGenealogiesIO()
+        io.n = n
+        io.replicates = _capi._p(reps)
+        off = {k: np.zeros(n + 1, dtype=np.int64) for k in ("node", "mut", "mig")}
+        io.node_off, io.mut_off, io.mig_off = _capi._p(off["node"]), _capi._p(off["mut"]), _capi._p(off["mig"])
+        eng._check(lib.vgx_get_tau_genealogies(eng.handle, C.byref(io), C.byref(pre)))          # sizing
+        io.rng_state = rng.ctypes.data_as(C.POINTER(C.c_uint64))
+        cap = {}
+        for keys, o in ((GenealogyBatch.NODE_KEYS, off["node"]), (GenealogyBatch.MUT_KEYS, off["mut"]), (GenealogyBatch.MIG_KEYS, off["mig"])):
+            for k in keys:
+                cap[k] = np.zeros(max(int(o[-1]), 1), dtype=np.float64 if k.endswith("times") or k.endswith("_time") else np.int64)
+        for k, a in cap.items():
+            setattr(io, k, _capi._p(a))
+        per = {k: np.zeros(max(n, 1), dtype=np.int64) for k in ("status", "status_arg", "nodes_used", "mut_n", "mig_n")}
+        for k, a in per.items():
+            setattr(io, k, _capi._p(a))
+        rng_out = np.zeros((max(n, 1), 6), dtype=np.uint64)
+        io.rng_out = rng_out.ctypes.data_as(C.POINTER(C.c_uint64))
+        eng._check(lib.vgx_get_tau_genealogies(eng.handle, C.byref(io), C.byref(pre)))          # walk
         b._fill(off, cap, {k: v[:n] for k, v in per.items()}, rng_out[:n])
         b.passes, b.kernel_ms, b.clock_ms, b.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
         return b
@@ -471,7 +598,7 @@ class GenealogyBatch:
         ok = self.status == 0
         self.nodes_used = per["nodes_used"].copy()
         self.rng_raw = np.zeros((n, 6), dtype=np.uint64)
-        self.rng_raw[:, :4] = rng_out
+        self.rng_raw[:, :rng_out.shape[1]] = rng_out   # (tau batches: the buffered 32-bit half too)
 
         def compact(o, keep, keys):   # row i keeps the first keep[i] entries of its capacity
             lens = np.diff(o)
