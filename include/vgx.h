@@ -521,6 +521,10 @@ int vgx_get_profile(vgx_engine *e, int64_t replicate, int64_t *out16);
  * four-replicates-per-wavefront kernel left it (list order = haplotype order), and the capacity of every list in *list_cap
  * (0 without device state).  count = 0 asks for the capacity alone; VGX_ERR_ARG when that copy is not current. */
 int vgx_get_list_counts_quad(vgx_engine *e, int64_t replicate, int64_t population, int64_t count, int32_t *out, int64_t *list_cap);
+/* Diagnostics / tests: the first `count` tile sums of one occupancy list as the last direct call left them: the sum of the counts of
+ * every 64-entry tile of a list longer than one tile, 0 behind the list (what the kernels choose a migrant's haplotype by), and the
+ * number of tile sums every list has room for in *tile_cap (0 without device state).  count = 0 asks for that number alone. */
+int vgx_get_list_tile_sums(vgx_engine *e, int64_t replicate, int64_t population, int64_t count, int64_t *out, int64_t *tile_cap);
 
 /* ---- the dense propensity row pass (K3) ------------------------------------------------------- */
 /* For callers that hold the reference's dense per-population arrays: the infect branch of UpdateRates (pyx:518-528:
@@ -565,6 +569,15 @@ int vgx_test_div_by_const(const double *n, const double *b, int64_t count, doubl
  * the device: pre16[row][l] = carry + w[0] + ... + w[l] for l < 16 and tot16[row][l] = pre16[row][15] in every lane (row_scan16),
  * pre64[row][k] = carry + w[0] + ... + w[k] for k < 64 (row_scan64), every sum left to right. */
 int vgx_test_row_scans(const double *w, const double *carry, int64_t rows, double *pre16, double *tot16, double *pre64);
+
+/* the haplotype choice of the four-replicates-per-wavefront kernel over lists longer than one 64-entry tile, on its own: `rows` lists
+ * (counts[row][0 .. n[row]-1] >= 0 and haps[row][..] ascending, rows of `maxlen` entries), one per 16-lane row and four to a wavefront.
+ * Each row's rate refresh sums tE[row] * count left to right and keeps the running sum at the end of every tile; the choice for
+ * r[row] then runs twice, [0][row] from those kept sums and [1][row] streaming the tiles again: the list index chosen (the first k
+ * whose prefix sum is not below r; none: n - 1 if that entry is haplotype H - 1, else -1), the prefix sum at that index (none: the
+ * list's total), its weight tE * count and its count.  All outputs are [2][rows]. */
+int vgx_test_quad_tile_choice(const int32_t *counts, const int32_t *haps, const int32_t *n, const double *tE, const double *r, int64_t rows,
+                              int64_t maxlen, int H, int32_t *k_hit, double *pre_hit, double *w_hit, int64_t *cnt_hit);
 
 #ifdef __cplusplus
 }

@@ -34,3 +34,6 @@ if tl[3] > 0:
                                                                           tl[2] / (4 * long_iters), tl[3] / (4 * long_iters), 100 * tl[2] / tl[3]))
 if tl[6] > 0:
     print("long rate refresh, per row: own list %.2f tiles, streamed %.2f (%.0f %% own)" % (tl[4] / tl[6], tl[5] / tl[6], 100 * tl[4] / tl[5]))
+if tl[7] + tl[8] > 0:
+    print("choices over a multi-tile list: %.2f %% took the tile from the row's end-of-tile sums, %.2f %% streamed; long-form iterations in which "
+          "no row streamed: %.2f %%" % (100 * tl[7] / (tl[7] + tl[8]), 100 * tl[8] / (tl[7] + tl[8]), 100 * tl[9] / long_iters))

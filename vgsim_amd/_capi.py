@@ -181,6 +181,7 @@ SIGNATURES = {
     "vgx_device_bytes": (C.c_int64, [_H]),
     "vgx_get_profile": (C.c_int, [_H, C.c_int64, _I]),
     "vgx_get_list_counts_quad": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32), _I]),
+    "vgx_get_list_tile_sums": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_int64, _I, _I]),
     "vgx_get_genealogy": (C.c_int, [C.POINTER(VgxGenealogyIO), C.c_char_p, C.c_int64]),
     "vgx_get_genealogies": (C.c_int, [_H, C.POINTER(VgxGenealogiesIO)]),
     "vgx_genealogy_message": (C.c_int, [C.c_int64, C.c_int64, C.c_char_p, C.c_int64]),
@@ -201,6 +202,8 @@ SIGNATURES = {
     "vgx_test_poisson": (C.c_int, [C.c_double, C.c_int64, C.c_uint64, _I]),
     "vgx_test_div_by_const": (C.c_int, [_F, _F, C.c_int64, _F, _F, _F]),
     "vgx_test_row_scans": (C.c_int, [_F, _F, C.c_int64, _F, _F, _F]),
+    "vgx_test_quad_tile_choice": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F, _F, C.c_int64, C.c_int64, C.c_int,
+                                            C.POINTER(C.c_int32), _F, _F, _I]),
 }
 
 _lib = None

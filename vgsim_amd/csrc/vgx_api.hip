@@ -977,6 +977,17 @@ extern "C" int vgx_get_list_counts_quad(vgx_engine *e, int64_t replicate, int64_
     return VGX_OK;
 }
 
+extern "C" int vgx_get_list_tile_sums(vgx_engine *e, int64_t replicate, int64_t population, int64_t count, int64_t *out, int64_t *tile_cap) {
+    if (!e || replicate < 0 || replicate >= e->R || population < 0 || population >= e->d.popNum || count < 0) return VGX_ERR_ARG;
+    if (tile_cap) *tile_cap = e->dev_state_valid ? e->dr.capT : 0;
+    if (count == 0) return VGX_OK;
+    if (!out || !e->dev_state_valid || !e->dr.ltsum || count > e->dr.capT) return VGX_ERR_ARG;
+    HIPCHECK(e, hipSetDevice(e->device));
+    HIPCHECK(e, hipStreamSynchronize(e->stream));
+    HIPCHECK(e, hipMemcpy(out, e->dr.ltsum + (replicate * e->d.popNum + population) * e->dr.capT, (size_t)count * 8, hipMemcpyDeviceToHost));
+    return VGX_OK;
+}
+
 extern "C" int vgx_get_profile(vgx_engine *e, int64_t replicate, int64_t *out16) {
     if (!e || !out16 || replicate < 0 || replicate >= e->R || !e->r_prof.p) return VGX_ERR_ARG;
     HIPCHECK(e, hipSetDevice(e->device));

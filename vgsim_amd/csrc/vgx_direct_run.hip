@@ -619,9 +619,12 @@ struct __attribute__((visibility("hidden"))) DirectRun {
     }
 
     // the copy of the counts the kernel reads: the 4-byte one is kept by the one-class row kernels alone
+    // (both forms of the exact row kernel work on the 4-byte counts alone, like the kernels the plan marks leaves32: the 8-byte counts
+    // are widened on demand, by the next kernel that reads them or by vgx_get_state)
+    bool on_counts32() const { return plan.leaves32 || plan.kernel == VGX_K_QUAD; }
     int sync_counts() {
         const bool row32 = plan.kernel == VGX_K_QUAD || plan.kernel == VGX_K_QUADF;
-        if (!e->counts64_valid && !(plan.leaves32 && e->counts32_valid)) {
+        if (!e->counts64_valid && !(on_counts32() && e->counts32_valid)) {
             HIPCHECK(e, vgxi_launch_counts64(e->dr.lcnt32, e->dr.lcnt, R * P * e->cap, e->stream));
             e->counts64_valid = true;
         }
@@ -655,7 +658,7 @@ struct __attribute__((visibility("hidden"))) DirectRun {
         default: HIPCHECK(e, vgxi_launch_direct(&a, lds, e->stream)); break;
         }
         e->counts32_valid = plan.kernel == VGX_K_QUAD || plan.kernel == VGX_K_QUADF;
-        if (plan.leaves32) e->counts64_valid = false;
+        if (on_counts32()) e->counts64_valid = false;
         e->dev_clock_stale = (plan.kernel == VGX_K_SOLO || plan.kernel == VGX_K_LONE) && !dev_clock;
         HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
         if (hipStreamSynchronize(e->stream) != hipSuccess) {

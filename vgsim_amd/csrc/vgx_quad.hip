@@ -23,6 +23,7 @@
 // parameters only and come from vgx_quad_prep_kernel, shared by all replicates.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <vector>
 #include "vgx_dev.h"
 #include "vgx_rng.h"
 #include "vgx_wave.h"
@@ -137,20 +138,19 @@ struct QSel { int k_hit, hap_hit, err; double pre_hit, w_hit; int64_t cnt_hit; }
 // Called with all lanes active.
 template <int QT>
 static __device__ __forceinline__ void q_long_select(const int32_t *ln, const int32_t *lh, int n_sel, int maxn, double tE,
-                                                               double r2, bool evn, int H, QSel &o, const double *ltp) {
+                                                               double r2, bool evn, int H, QSel &o, const double *ltp, int pi, double tc,
+                                                               int tc_pi) {
     const int rl = threadIdx.x & 15;
     o.k_hit = -1; o.err = 0;
-    // long lists: the running sum advances one tile of 64 entries per step; the tile in which it first reaches r is
-    // then scanned entry by entry — same additions, same order.  Loads run QT tiles ahead (unconditional: a row
-    // that is through, or has its hit, re-reads its tile 0; every list is followed by 64 entries of padding).
+    // long lists: the tile of 64 entries in which the running sum first reaches r is found first and then scanned entry by
+    // entry — same additions, same order.  Where the tiles are streamed, loads run QT tiles ahead (unconditional: a row
+    // that is through, has its hit or does not stream re-reads its tile 0; every list is followed by 64 entries of padding).
     QTile buf[QT];
-    QTile kc = {0, 0, 0, 0};      // QT < 4: the counts of the tile the refine scans (the hit tile, else the list's last), kept from the stream
     double carry = 0.0, carry_hit = 0.0;
     int t_hit = -1;
-    const int nt = (n_sel + 63) >> 6, maxt = (maxn + 63) >> 6;
-    // tiles that lie inside the list of EVERY row that has one: no bounds to look at (a row without a list adds zeros)
-    const int full = QT >= 4 ? -rows_max(n_sel > 0 ? -n_sel : -0x7fffffff) >> 6 : 0;
+    const int nt = (n_sel + 63) >> 6;
     const double tEz = n_sel > 0 ? tE : 0.0;
+    (void)maxn;
     if (QT >= 4) {
         // The tile by the running sums the last refresh of this population left at the end of every tile (q_long_sum: the same
         // additions in the same order as the loop below would make, on the same counts and the same tE): lane l looks at tiles
@@ -181,40 +181,43 @@ static __device__ __forceinline__ void q_long_select(const int32_t *ln, const in
         if (ntc > 0) carry = ltp[lastc];                   // no hit: the total of the whole list
         else if (n_sel > 0) { t_hit = 0; carry_hit = 0.0; }
     } else {
+        // QT < 4.  A row whose list fits one tile has nothing to stream: its tile is scanned below.  A row whose last long-form
+        // refresh was of this population (tag tc_pi) holds the running sum at the end of tile t in lane t of tc (q_long_sum: the
+        // same additions in the same order as the stream below makes, on the same counts and the same tE): one compare per lane
+        // names the tile.  The stream runs only while a row with more than one tile has no such register.
+        const bool multi = nt > 1;
+        const bool hitc = multi && tc_pi == pi;
+        const int qc = row_min(hitc && rl < nt && !(tc < r2) ? rl : 16);
+        const double cs = rowget_f64(tc, (qc < 16 ? max(qc - 1, 0) : max(nt - 1, 0)) & 15);   // the sum before the hit tile / of the whole list
+        if (hitc) {
+            if (qc < 16) { t_hit = qc; carry_hit = qc > 0 ? cs : 0.0; } else carry = cs;
+        } else if (!multi && n_sel > 0) t_hit = 0;
+        const bool need = multi && !hitc;
+        const int maxs = rows_max(need ? nt : 0);
+        if (__builtin_expect(maxs > 0, 0)) {
 #pragma unroll
-    for (int d = 0; d < QT; ++d) buf[d] = tile_load(ln, d < nt ? d : 0, rl);
-    for (int tb = 0; tb < maxt; tb += QT) {
+            for (int d = 0; d < QT; ++d) buf[d] = tile_load(ln, need && d < nt ? d : 0, rl);
+            for (int tb = 0; tb < maxs; tb += QT) {
 #pragma unroll
-        for (int d = 0; d < QT; ++d) {
-            const int t = tb + d;
-            const QTile c = buf[d];
-            buf[d] = tile_load(ln, (t + QT < nt && t_hit < 0) ? t + QT : 0, rl);
-            double w0, w1, w2, w3;
-            if (QT < 4) {
-                // the short-list kernel's lists hold count 0 from n to the end of n's tile (q_zero_tail): a tile of the list needs no
-                // bounds, a tile past it is weighted by +0.0 as a whole (tEz * count = +0.0 or -0.0: either adds nothing to a sum >= +0.0)
-                const double tEt = t < nt ? tEz : 0.0;
-                w0 = tEt * (double)c.c0; w1 = tEt * (double)c.c1; w2 = tEt * (double)c.c2; w3 = tEt * (double)c.c3;
-            } else if (t < full) {
-                w0 = tEz * (double)c.c0; w1 = tEz * (double)c.c1; w2 = tEz * (double)c.c2; w3 = tEz * (double)c.c3;
-            } else {
-                const int e0 = t * 64 + 4 * rl;
-                w0 = e0 + 0 < n_sel ? tE * (double)c.c0 : 0.0; w1 = e0 + 1 < n_sel ? tE * (double)c.c1 : 0.0;
-                w2 = e0 + 2 < n_sel ? tE * (double)c.c2 : 0.0; w3 = e0 + 3 < n_sel ? tE * (double)c.c3 : 0.0;
+                for (int d = 0; d < QT; ++d) {
+                    const int t = tb + d;
+                    const QTile c = buf[d];
+                    buf[d] = tile_load(ln, (need && t + QT < nt && t_hit < 0) ? t + QT : 0, rl);
+                    // the short-list kernel's lists hold count 0 from n to the end of n's tile (q_zero_tail): a tile of the list needs no
+                    // bounds; a tile past it, and every tile of a row that does not stream, is weighted by +0.0 as a whole (adds nothing
+                    // to a sum >= +0.0)
+                    const double tEt = need && t < nt ? tEz : 0.0;
+                    const double acc = row_sum64(tEt * (double)c.c0, tEt * (double)c.c1, tEt * (double)c.c2, tEt * (double)c.c3, carry);
+                    if (need && t_hit < 0 && t < nt && !(acc < r2)) { t_hit = t; carry_hit = carry; }      // still inside its list without a hit
+                    carry = acc;
+                }
+                if (!__ballot(need && nt > tb + QT && t_hit < 0)) break;
             }
-            const double acc = row_sum64(w0, w1, w2, w3, carry);
-            const bool own = t_hit < 0 && t < nt;      // the row is still inside its list without a hit
-            if (QT < 4 && own) kc = c;
-            if (own && !(acc < r2)) { t_hit = t; carry_hit = carry; }
-            carry = acc;
         }
-        if (!__ballot(nt > tb + QT && t_hit < 0)) break;
-    }
     }
     // refine inside the hit tile (rows without a hit look at their last tile for the H-1 rule)
     const int tt = t_hit >= 0 ? t_hit : max((n_sel - 1) >> 6, 0);
-    // QT < 4: the counts come from the stream, the haplotype words' load runs under the scan (no round trip after the choice)
-    const QTile c = QT < 4 ? kc : tile_load(ln, tt, rl);
+    const QTile c = tile_load(ln, tt, rl);
     const int4 hv = *(const int4 *)(lh + (int64_t)tt * 64 + 4 * rl);     // the haplotypes with the counts (every list is followed by a tile of padding)
     const int e0 = tt * 64 + 4 * rl;
     double w0, w1, w2, w3;
@@ -240,7 +243,7 @@ static __device__ __forceinline__ void q_long_select(const int32_t *ln, const in
     const double wsel = qj == 0 ? w0 : qj == 1 ? w1 : qj == 2 ? w2 : w3;
     const int64_t csel = (int64_t)(qj == 0 ? c.c0 : qj == 1 ? c.c1 : qj == 2 ? c.c2 : c.c3);
     // no hit: the total of the whole list (a one-tile list of the cached form: the end of this scan)
-    o.pre_hit = q < 64 ? rowget_f64(psel, ql) : (QT >= 4 && nt <= 1) ? rowget_f64(p3, 15) : carry;
+    o.pre_hit = q < 64 ? rowget_f64(psel, ql) : nt <= 1 ? rowget_f64(p3, 15) : carry;
     o.w_hit = rowget_f64(wsel, ql);
     o.cnt_hit = rowget_i64(csel, ql);
     o.hap_hit = rowget_i32(qj == 0 ? hv.x : qj == 1 ? hv.y : qj == 2 ? hv.z : hv.w, ql);
@@ -248,7 +251,6 @@ static __device__ __forceinline__ void q_long_select(const int32_t *ln, const in
     else if (evn) {
         if (n_sel > 0 && o.hap_hit == H - 1 && (QT < 4 || o.cnt_hit != 0)) o.k_hit = n_sel - 1; else o.err = Q_ERR_ZERO_WEIGHT + 256 * 3;
     }
-            
 }
 
 // infectPopRate over a list longer than 64 entries (pyx:519-528)
@@ -258,7 +260,8 @@ static __device__ __forceinline__ void q_long_select(const int32_t *ln, const in
 // of every tile is left in ltp for the next haplotype choice in this population (q_long_select).
 #define VGX_QB8 6      // (tiles in flight; 4: 1.88e8, 6: 2.00e8, 8: 1.92e8 events/s at 4096-entry lists: the unrolled chains are code)
 template <int QT>
-static __device__ __forceinline__ double q_long_sum(const int32_t *ln, const uint8_t *l8, int n, int maxn, double tE, double *ltp) {
+static __device__ __forceinline__ double q_long_sum(const int32_t *ln, const uint8_t *l8, int n, int maxn, double tE, double *ltp, bool act,
+                                                    int pi, double &tc, int &tc_pi) {
     const int rl = threadIdx.x & 15;
     double acc = 0.0;
     const int nt = (n + 63) >> 6, maxt = (maxn + 63) >> 6;
@@ -296,6 +299,11 @@ static __device__ __forceinline__ double q_long_sum(const int32_t *ln, const uin
         }
         return acc;
     }
+    // The short-list instantiation leaves the running sum at the end of tile t in lane t of the row's register tc, tagged with the
+    // population (tc_pi), for the next haplotype choice there (q_long_select): lists of 2 to 16 tiles.  Only a row that refreshes
+    // (act) touches its register: the others pass through with n = 0 and keep what they hold, and so does a row whose list here
+    // fits one tile (its choice needs no sums), unless the register is this population's: then it is out of date.
+    const bool fill = act && nt > 1 && nt <= 16;
     QTile buf[QT];
 #pragma unroll
     for (int d = 0; d < QT; ++d) buf[d] = tile_load(ln, d < nt ? d : 0, rl);
@@ -308,8 +316,10 @@ static __device__ __forceinline__ double q_long_sum(const int32_t *ln, const uin
             // count 0 from n to the end of its tile (q_zero_tail); a tile past the row's list is weighted by +0.0 as a whole
             const double tEt = t < nt ? tEz : 0.0;
             acc = row_sum64(tEt * (double)c.c0, tEt * (double)c.c1, tEt * (double)c.c2, tEt * (double)c.c3, acc);
+            if (fill && rl == t) tc = acc;
         }
     }
+    if (act) tc_pi = fill ? pi : tc_pi == pi ? -1 : tc_pi;
     return acc;
 }
 
@@ -385,7 +395,8 @@ static __device__ __forceinline__ void quad_body() {
     double *s_cc = (double *)(s_nocc + 64);
     int64_t *s_cnt = (int64_t *)(s_cc + 4);
     uint64_t *s_inc = (uint64_t *)(s_cnt + 6);         // counters use 5 of their 8 slots; the last two hold the PCG64 increment
-    int32_t *s_zero = (int32_t *)(s_inc + 2);           // long-list kernel: zero-count entries in every population's list (vgx_rowlist.h)
+    int32_t *s_zero = (int32_t *)(s_inc + 2);           // long-list kernel: zero-count entries in every population's list (vgx_rowlist.h);
+                                                        // short-list kernel: the longest every list has been since the launch
     // Event records are staged here, eight per replicate, and written out together: 192 contiguous bytes of columns + 64 of rates
     // instead of eight lone 24 + 8 byte stores per stream (16 384 streams: every lone store cost a 64-byte memory transaction).
     // Dwords 0..47: the six columns of records 0..7; dwords 48..63: their rates.
@@ -430,7 +441,7 @@ static __device__ __forceinline__ void quad_body() {
             s_ts[pq] = ok ? (double)gI64[PI_TOTSUS * P + pq] : 0.0;
             s_ti[pq] = ok ? (double)gI64[PI_TOTINF * P + pq] : 0.0;
             s_nocc[pq] = ok ? gN[pq] : 0;
-            s_zero[pq] = 0;                 // (the lists arrive settled)
+            s_zero[pq] = QT < 4 && ok ? gN[pq] : 0;     // (long-list kernel: the lists arrive settled; short-list kernel: the longest the list has been)
         }
     }
     WSYNC();
@@ -487,14 +498,22 @@ static __device__ __forceinline__ void quad_body() {
     int pos = 8;                                       // iterations consumed from the row's batch (8 = empty)
     // a list of up to 64 entries read for the haplotype choice stays in registers for the rate refresh
     int32_t ch_cn[4] = {0, 0, 0, 0};
+    // QT < 4: the running sums at the end of the tiles of ONE multi-tile list of the row (lane t: tile t), as its last long-form
+    // refresh made them, and the population they belong to (-1: none).  They stand while no count and no rate of that population
+    // changes: every change of a list is followed by UpdateRates of its population, which rewrites the register (long form) or
+    // drops the tag (register path, below); UpdateRates of another population leaves this one's tE alone (no lockdown switches).
+    double tc = 0.0;
+    int tc_pi = -1;
 
 #ifdef VGX_PROFILE
     unsigned long long prof_acc[VGX_PROF_SLOTS], prof_t0 = __builtin_readcyclecounter();
     for (int i = 0; i < VGX_PROF_SLOTS; ++i) prof_acc[i] = 0;
     // tile work of the long-list forms, row-uniform: [0] the row's own tiles, [1] the wave's longest list in tiles, [2] the tiles
     // the row needs up to its hit, [3] the most any row of the wave needs (= tiles streamed) — per haplotype choice that took the
-    // long form; [4] / [5] the same pair for the rate refresh; [6] refreshes that took the long form
-    int prof_tiles[7] = {0, 0, 0, 0, 0, 0, 0};
+    // long form; [4] / [5] the same pair for the rate refresh; [6] refreshes that took the long form; [7] / [8] choices over a
+    // multi-tile list that found / did not find the row's end-of-tile sums in its register; [9] long-form choices (per wavefront:
+    // row 0 counts) in which no row streamed
+    int prof_tiles[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
     while (true) {
         QPROF(0);
@@ -616,9 +635,8 @@ static __device__ __forceinline__ void quad_body() {
             const double tE = ((bC + c_d) + smul) + c_tm;          // tEventHapPopRate (pyx:522-526)
             const int n_sel = evn ? s_nocc[pi] : 0;
             const int32_t *lh = lhap + (int64_t)pi * cap;
-            int64_t *ln = lcnt + (int64_t)pi * cap;
             int32_t *l3 = lcnt32 + (int64_t)pi * cap;
-            int64_t *lt = ltsum + (int64_t)pi * capT;
+            int64_t *lt = ltsum + (int64_t)pi * capT;          // (kept per event by the long-list kernel alone)
             {   // row pi of the migration matrix for the BirthRate refresh: in flight together with the list
                 const double *mrow = p.mig + (int64_t)pi * P;
 #pragma unroll
@@ -700,8 +718,16 @@ static __device__ __forceinline__ void quad_body() {
 #ifdef VGX_PROFILE
                 prof_acc[15] += 1;       // (diagnostic build: iterations whose haplotype choice took the long-list form)
 #endif
+#ifdef VGX_PROFILE
+                if (QT < 4) {
+                    const bool hit_ = n_sel > 64 && tc_pi == pi, miss_ = n_sel > 64 && tc_pi != pi;
+                    prof_tiles[7] += hit_; prof_tiles[8] += miss_;
+                    if (!__ballot(miss_) && row == 0) prof_tiles[9] += 1;
+                }
+#endif
                 QSel sel;
-                q_long_select<QT>(l3, lh, n_sel, maxn, tE, r2, evn, H, sel, (double *)(ltsum + (int64_t)pi * capT + R * P * capT))   /* the cached running sums lie behind the tile sums (vgx_dev.h) */;
+                q_long_select<QT>(l3, lh, n_sel, maxn, tE, r2, evn, H, sel, (double *)(ltsum + (int64_t)pi * capT + R * P * capT) /* the long-list kernel's running sums lie behind the tile sums (vgx_dev.h) */,
+                                  pi, tc, tc_pi);
                 k_hit = sel.k_hit; pre_hit = sel.pre_hit; w_hit = sel.w_hit; hap_hit = sel.hap_hit; cnt_hit = sel.cnt_hit;
                 if (sel.err) err = sel.err;
 #ifdef VGX_PROFILE
@@ -735,7 +761,7 @@ static __device__ __forceinline__ void quad_body() {
                 if (ts_pi * c_sig == 0.0) err = Q_ERR_ZERO_WEIGHT + 256 * 6;
                 if (rl == 0) { s_ts[pi] = ts_pi - 1.0; s_ti[pi] = ti_pi + 1.0; }
                 gI += 1.0; QBUMP(QC_B);
-                if (live && rl == 0) { if (QT < 4) ln[k_hit] = cnt_hit + 1; l3[k_hit] = (int32_t)(cnt_hit + 1); if (QT >= 4) L8(pi)[k_hit] = B8(cnt_hit + 1); if (n_sel > 64) lt[k_hit >> 6] += 1; }
+                if (live && rl == 0) { l3[k_hit] = (int32_t)(cnt_hit + 1); if (QT >= 4) { L8(pi)[k_hit] = B8(cnt_hit + 1); if (n_sel > 64) lt[k_hit >> 6] += 1; } }
 #pragma unroll
                 for (int c = 0; c < 4; ++c)
                     if (c == (k_hit >> 4) && rl == (k_hit & 15)) ch_cn[c] += 1;
@@ -750,7 +776,7 @@ static __device__ __forceinline__ void quad_body() {
                 // (the long-list kernel leaves a count of 0 in the list: vgx_rowlist.h)
                 if (QT < 4 && cnt_hit == 1) { op_n = 1; op_pi = pi; op_h0 = hap_hit; op_d0 = -1; ch_pi = -1; }
                 else {
-                    if (live && rl == 0) { if (QT < 4) ln[k_hit] = cnt_hit - 1; l3[k_hit] = (int32_t)(cnt_hit - 1); if (QT >= 4) L8(pi)[k_hit] = B8(cnt_hit - 1); if (n_sel > 64) lt[k_hit >> 6] -= 1; }
+                    if (live && rl == 0) { l3[k_hit] = (int32_t)(cnt_hit - 1); if (QT >= 4) { L8(pi)[k_hit] = B8(cnt_hit - 1); if (n_sel > 64) lt[k_hit >> 6] -= 1; } }
                     if (QT >= 4 && cnt_hit == 1 && rl == 0) s_zero[pi] += 1;
 #pragma unroll
                     for (int c = 0; c < 4; ++c)
@@ -852,9 +878,8 @@ static __device__ __forceinline__ void quad_body() {
                 {
                     const int n = evm ? s_nocc[spi] : 0;
                     const int32_t *lh2 = lhap + (int64_t)spi * cap;
-                    const int64_t *ln2 = lcnt + (int64_t)spi * cap;
                     const int32_t *l32 = lcnt32 + (int64_t)spi * cap;
-#define CN2(k) (QT >= 4 ? (int64_t)l32[k] : ln2[k])      /* (the long-list kernel keeps the 4-byte counts only) */
+#define CN2(k) ((int64_t)l32[k])      /* (the row kernels keep the 4-byte counts only) */
                     const int64_t *lt2 = ltsum + (int64_t)spi * capT;
                     const double rr_ = s_ti[spi] * rm;
                     int64_t before = 0;
@@ -866,6 +891,18 @@ static __device__ __forceinline__ void quad_body() {
                         const int maxt = rows_max(nt);
                         int jt = -1;
                         int64_t carry = 0;
+                        if (QT < 4) {
+                            // the short-list kernel keeps no tile sums while it runs: a tile's sum from its 4-byte counts (count 0 from n to
+                            // the end of n's tile, q_zero_tail), tile by tile until every row has its tile
+                            for (int t = 0; t < maxt; ++t) {
+                                const QTile c = tile_load(l32, t < nt ? t : 0, rl);
+                                const int64_t w = t < nt ? (int64_t)c.c0 + (int64_t)c.c1 + (int64_t)c.c2 + (int64_t)c.c3 : 0;
+                                const int64_t pre = rowget_i64(row_iscan(w), 15) + carry;
+                                if (jt < 0 && t < nt && !((double)pre < rr_)) { jt = t; before = carry; }
+                                carry = pre;
+                                if (!__ballot(jt < 0 && t + 1 < nt)) break;
+                            }
+                        } else
                         for (int tb = 0; tb < maxt; tb += 16) {
                             const int j = tb + rl;
                             const int64_t w = j < nt ? lt2[j] : 0;
@@ -977,13 +1014,11 @@ static __device__ __forceinline__ void quad_body() {
             const int n = act ? s_nocc[op_pi] : 0;
             int32_t *lh = lhap + (int64_t)op_pi * cap;
             int32_t *lc = lcls + (int64_t)op_pi * cap;
-            int64_t *ln = lcnt + (int64_t)op_pi * cap;
-            int32_t *l3 = lcnt32 + (int64_t)op_pi * cap;
-            int64_t *lt = ltsum + (int64_t)op_pi * capT;
+            int32_t *l3 = lcnt32 + (int64_t)op_pi * cap;      // (this kernel shifts and writes the 4-byte counts alone)
             // ---- lower bound: first index whose haplotype is >= hap ----
             int posn = 0;
             bool found = false;
-            int64_t cur = 0;
+            int32_t cur = 0;
             {
                 int lo = 0;             // first entry of the 16^k-aligned window known to contain the bound
                 const int maxn = rows_max(n);
@@ -1005,37 +1040,14 @@ static __device__ __forceinline__ void quad_body() {
                         lo = lo + (nle > 0 ? (nle - 1) * stride : 0);
                     }
                 }
-                if (act && found) cur = ln[posn];
+                if (act && found) cur = l3[posn];
             }
             const bool bump = act && found && cur + delta != 0;       // count changes in place
             const bool rem = act && found && cur + delta == 0;        // the entry disappears
             const bool ins = act && !found;                           // a new entry (delta = +1)
             if (ins && n >= cap) { err = Q_ERR_CAPACITY; }
             const bool ins_ok = ins && err == 0;
-            if (bump && rl == 0) { ln[posn] = cur + delta; l3[posn] = (int32_t)(cur + delta); if (QT >= 4) L8(op_pi)[posn] = B8(cur + delta); if (n > 64) lt[posn >> 6] += delta; }
-            // ---- tile sums of lists longer than one tile (vgx_direct.hip list_insert_at / list_remove_at) ----
-            if (__builtin_expect(__ballot((ins_ok || rem) && n > 64) != 0, 0)) {
-                const bool tt = (ins_ok || rem) && n > 64;
-                const int jp = posn >> 6, jl = ins_ok ? (n >> 6) : ((n - 1) >> 6);
-                const int maxj = rows_max(tt ? jl + 1 : 0);
-                for (int tb = 0; tb < maxj; tb += 16) {
-                    const int j = tb + rl;
-                    if (tt && j >= jp && j <= jl) {
-                        int64_t in_, out_;
-                        if (ins_ok) {
-                            in_ = j == jp ? (int64_t)delta : ln[(int64_t)j * 64 - 1];
-                            const int kout = j * 64 + 63;
-                            out_ = kout < n ? ln[kout] : 0;
-                        } else {
-                            out_ = j == jp ? ln[posn] : ln[(int64_t)j * 64];
-                            const int kin = j * 64 + 64;
-                            in_ = kin < n ? ln[kin] : 0;
-                        }
-                        lt[j] += in_ - out_;
-                    }
-                }
-                WSYNC();
-            }
+            if (bump && rl == 0) l3[posn] = cur + delta;
             // ---- shift: insertion moves [posn, n) one slot up (highest block first), removal (posn, n) one slot down ----
             if (__builtin_expect(__ballot(ins_ok) != 0, 0)) {
                 enum { SU = 4 };
@@ -1044,30 +1056,25 @@ static __device__ __forceinline__ void quad_body() {
                 while (__ballot(hi_ > lo_)) {
                     const int blo = max(lo_, hi_ - SU * 16);
                     int h[SU];
-                    int64_t ct[SU];
+                    int32_t ct[SU];
 #pragma unroll
                     for (int u = 0; u < SU; ++u) {
                         const int k = blo + u * 16 + rl;
                         h[u] = 0; ct[u] = 0;
-                        if (k < hi_) { h[u] = lh[k]; ct[u] = ln[k]; }
+                        if (k < hi_) { h[u] = lh[k]; ct[u] = l3[k]; }
                     }
                     WSYNC();
 #pragma unroll
                     for (int u = 0; u < SU; ++u) {
                         const int k = blo + u * 16 + rl;
-                        if (k < hi_) { lh[k + 1] = h[u]; lc[k + 1] = 0; ln[k + 1] = ct[u]; l3[k + 1] = (int32_t)ct[u]; if (QT >= 4) L8(op_pi)[k + 1] = B8(ct[u]); }
+                        if (k < hi_) { lh[k + 1] = h[u]; lc[k + 1] = 0; l3[k + 1] = ct[u]; }
                     }
                     WSYNC();
                     hi_ = blo;
                 }
-                if (ins_ok && rl == 0) { lh[posn] = hap; lc[posn] = 0; ln[posn] = delta; l3[posn] = delta; if (QT >= 4) L8(op_pi)[posn] = B8(delta); s_nocc[op_pi] = n + 1; }
-                q_zero_tail(l3, n + 1, cap, QT < 4 && ins_ok && ((n + 1) & 63) == 0);     // the list fills its last tile: the next one holds 0
-                WSYNC();
-                if (ins_ok && n == 64) {   // the list outgrows one tile: start its tile sums
-                    int64_t s0 = 0;
-                    for (int c4 = 0; c4 < 4; ++c4) s0 += rowget_i64(row_iscan(ln[c4 * 16 + rl]), 15);
-                    if (rl == 0) { lt[0] = s0; lt[1] = ln[64]; }
-                }
+                // (s_zero: the longest the list has been since the launch — the tile sums the kernel has to rewrite when it leaves)
+                if (ins_ok && rl == 0) { lh[posn] = hap; lc[posn] = 0; l3[posn] = delta; s_nocc[op_pi] = n + 1; if (n + 1 > s_zero[op_pi]) s_zero[op_pi] = n + 1; }
+                q_zero_tail(l3, n + 1, cap, ins_ok && ((n + 1) & 63) == 0);     // the list fills its last tile: the next one holds 0
                 WSYNC();
             }
             if (__builtin_expect(__ballot(rem) != 0, 0)) {
@@ -1076,23 +1083,23 @@ static __device__ __forceinline__ void quad_body() {
                 const int hi_ = rem ? n : 0;
                 while (__ballot(lo_ < hi_)) {
                     int h[SU];
-                    int64_t ct[SU];
+                    int32_t ct[SU];
 #pragma unroll
                     for (int u = 0; u < SU; ++u) {
                         const int k = lo_ + u * 16 + rl;
                         h[u] = 0; ct[u] = 0;
-                        if (k < hi_) { h[u] = lh[k]; ct[u] = ln[k]; }
+                        if (k < hi_) { h[u] = lh[k]; ct[u] = l3[k]; }
                     }
                     WSYNC();
 #pragma unroll
                     for (int u = 0; u < SU; ++u) {
                         const int k = lo_ + u * 16 + rl;
-                        if (k < hi_) { lh[k - 1] = h[u]; ln[k - 1] = ct[u]; l3[k - 1] = (int32_t)ct[u]; if (QT >= 4) L8(op_pi)[k - 1] = B8(ct[u]); }
+                        if (k < hi_) { lh[k - 1] = h[u]; l3[k - 1] = ct[u]; }
                     }
                     WSYNC();
                     lo_ += SU * 16;
                 }
-                if (rem && rl == 0) { s_nocc[op_pi] = n - 1; if (QT < 4) l3[n - 1] = 0; }    // (the vacated entry: q_zero_tail)
+                if (rem && rl == 0) { s_nocc[op_pi] = n - 1; l3[n - 1] = 0; }    // (the vacated entry: q_zero_tail)
                 WSYNC();
             }
         }
@@ -1159,6 +1166,7 @@ static __device__ __forceinline__ void quad_body() {
                 if (__builtin_expect(maxn <= 64, QT < 4)) {
                     const int nch = (maxn + 15) >> 4;
                     const bool chave = act && pi == ch_pi;     // the list read for the haplotype choice, event applied
+                    if (QT < 4 && act && pi == tc_pi) tc_pi = -1;      // (the list fell back to one tile: its end-of-tile sums are out of date)
                     const double tEz = n > 0 ? tE : 0.0;
                     int32_t cn4[4];
 #pragma unroll
@@ -1176,7 +1184,7 @@ static __device__ __forceinline__ void quad_body() {
 #ifdef VGX_PROFILE
                     prof_tiles[4] += (n + 63) >> 6; prof_tiles[5] += (maxn + 63) >> 6; prof_tiles[6] += 1;
 #endif
-                    acc = q_long_sum<QT>(l3, L8(pi), n, maxn, tE, (double *)(ltsum + (int64_t)pi * capT + R * P * capT));   // (the cached running sums lie behind the tile sums, vgx_dev.h)
+                    acc = q_long_sum<QT>(l3, L8(pi), n, maxn, tE, (double *)(ltsum + (int64_t)pi * capT + R * P * capT), act, pi, tc, tc_pi);   // (the long-list kernel's running sums lie behind the tile sums, vgx_dev.h)
                 }
                 if (act && rl == 0) { s_bc[pi] = bC; s_inf[pi] = acc; }
                 WSYNC();
@@ -1234,6 +1242,7 @@ static __device__ __forceinline__ void quad_body() {
                 t_now = 0.0; traj_next = 0;
                 restarts += 1; att += 1;
                 st = ST_REBUILD;
+                tc_pi = -1;
             } else {
                 good_attempt = (int64_t)att + 1;
                 st = ST_DONE;
@@ -1256,7 +1265,7 @@ static __device__ __forceinline__ void quad_body() {
                             if (rs) {
                                 lhap[(int64_t)pn * cap + k] = r.i_hap[(int64_t)pn * r.i_cap + k];
                                 lcls[(int64_t)pn * cap + k] = r.i_cls[(int64_t)pn * r.i_cap + k];
-                                lcnt[(int64_t)pn * cap + k] = ct;
+                                if (QT >= 4) lcnt[(int64_t)pn * cap + k] = ct;
                                 lcnt32[(int64_t)pn * cap + k] = (int32_t)ct;
                                 if (QT >= 4) L8(pn)[k] = B8(ct);
                             }
@@ -1269,7 +1278,7 @@ static __device__ __forceinline__ void quad_body() {
                 if (rs)
                     for (int j = (n + 63) / 64 + rl; j <= n_old / 64 && j < capT; j += 16) ltsum[(int64_t)pn * capT + j] = 0;
                 if (QT < 4) q_zero_tail(lcnt32 + (int64_t)pn * cap, n, cap, rs);
-                if (rs && rl == 0) { s_nocc[pn] = n; s_zero[pn] = 0; s_ts[pn] = (double)r.i_sus[pn]; s_ti[pn] = (double)ti; }
+                if (rs && rl == 0) { s_nocc[pn] = n; if (QT >= 4) s_zero[pn] = 0; else if (n > s_zero[pn]) s_zero[pn] = n; s_ts[pn] = (double)r.i_sus[pn]; s_ti[pn] = (double)ti; }
                 g += ti;
             }
             if (rs) gI = (double)g;
@@ -1297,7 +1306,7 @@ static __device__ __forceinline__ void quad_body() {
     if (lane == 0 && r.prof)
         for (int i = 0; i < VGX_PROF_SLOTS; ++i) r.prof[rep * VGX_PROF_SLOTS + i] = prof_acc[i];
     // the tile counters, summed over the four rows, in the buffer of the wavefront's second replicate
-    for (int i = 0; i < 7; ++i) {
+    for (int i = 0; i < 10; ++i) {
         const long long t4 = (long long)__builtin_amdgcn_readlane(prof_tiles[i], 0) + __builtin_amdgcn_readlane(prof_tiles[i], 16) +
                              __builtin_amdgcn_readlane(prof_tiles[i], 32) + __builtin_amdgcn_readlane(prof_tiles[i], 48);
         if (lane == 0 && r.prof && rep_raw + 1 < R) r.prof[(rep_raw + 1) * VGX_PROF_SLOTS + i] = (unsigned long long)t4;
@@ -1306,6 +1315,26 @@ static __device__ __forceinline__ void quad_body() {
     // ---- state back to HBM ----
     stage_flush(stage_n > 0);
     WSYNC();
+    if (QT < 4) {
+        // The short-list kernel kept the 4-byte counts alone (the host widens them for whoever reads the 8-byte ones).  The integer
+        // tile sums the other kernels choose by: the sum of every 64-entry tile of every list (count 0 from n to the end of n's
+        // tile), 0 behind the list as far as it ever reached since the launch — what a Restart leaves (above).
+        for (int pn = 0; pn < P; ++pn) {
+            const int n = live ? s_nocc[pn] : 0, top = live ? s_zero[pn] : 0;
+            const int32_t *l3 = lcnt32 + (int64_t)pn * cap;
+            const int jmax = rows_max(top >> 6);
+            for (int j = 0; j <= jmax && j < capT; ++j) {
+                int64_t w = 0;            // (entry by entry inside the list: a capacity may be smaller than a tile)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int k = j * 64 + 4 * rl + i;
+                    if (k < n) w += (int64_t)l3[k];
+                }
+                const int64_t tsum = rowget_i64(row_iscan(w), 15);
+                if (live && rl == 0 && j <= (top >> 6)) ltsum[(int64_t)pn * capT + j] = tsum;
+            }
+        }
+    }
     if (live) {
         double *gD = r.popD + rep * PD_COUNT * P;
         int64_t *gI64 = r.popI + rep * PI_COUNT * P;
@@ -1438,6 +1467,75 @@ extern "C" int vgx_test_row_scans(const double *w, const double *carry, int64_t 
             hipMemcpy(pre16, d16, n * 16 * 8, hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(tot16, dt, n * 16 * 8, hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(pre64, d64, n * 64 * 8, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = 2;
+    }
+    (void)hipFree(d);
+    return rc;
+}
+
+// ---- test hook: the haplotype choice over multi-tile lists of the short-list kernel on its own ----
+// Block b runs rows 4b .. 4b+3, one per 16-lane DPP row, each with a list of its own (4-byte counts, count 0 behind the list to the
+// end of its tile, a tile of padding behind every list, as the kernel keeps them): q_long_sum<1> as the rate refresh runs it, which
+// leaves the end-of-tile sums in the row's register; a second pass in which rows 1 and 3 of the wavefront are idle (n = 0) while rows
+// 0 and 2 refresh again — the idle rows must keep what they hold; then q_long_select<1> twice: from the register, and with the
+// tag dropped, which streams the tiles.
+extern "C" __global__ void __launch_bounds__(64) vgx_quad_tilechoice_kernel(const int32_t *cnt, const int32_t *hap, const int32_t *n,
+                                                                           const double *tE, const double *r, int64_t rows, int64_t stride,
+                                                                           int H, int32_t *k_hit, double *pre_hit, double *w_hit, int64_t *cnt_hit) {
+    const int wrow = threadIdx.x >> 4;
+    const int64_t row_raw = (int64_t)blockIdx.x * 4 + wrow;
+    const int64_t row = row_raw < rows ? row_raw : rows - 1;      // (rows beyond the last repeat it: the chains need all 64 lanes)
+    const int32_t *l3 = cnt + row * stride, *lh = hap + row * stride;
+    const int nn = n[row], maxn = rows_max(nn), pi = 1 + wrow;
+    const double te = tE[row], rr = r[row];
+    double tc = 0.0;
+    int tc_pi = -1;
+    (void)q_long_sum<1>(l3, nullptr, nn, maxn, te, nullptr, true, pi, tc, tc_pi);
+    const bool act2 = (wrow & 1) == 0;
+    const int n2 = act2 ? nn : 0;
+    (void)q_long_sum<1>(l3, nullptr, n2, rows_max(n2), te, nullptr, act2, act2 ? pi : 0, tc, tc_pi);
+    QSel a, b;
+    q_long_select<1>(l3, lh, nn, maxn, te, rr, true, H, a, nullptr, pi, tc, tc_pi);
+    q_long_select<1>(l3, lh, nn, maxn, te, rr, true, H, b, nullptr, pi, tc, -1);
+    if (row_raw < rows && (threadIdx.x & 15) == 0) {
+        k_hit[row] = a.k_hit; pre_hit[row] = a.pre_hit; w_hit[row] = a.w_hit; cnt_hit[row] = a.cnt_hit;
+        k_hit[rows + row] = b.k_hit; pre_hit[rows + row] = b.pre_hit; w_hit[rows + row] = b.w_hit; cnt_hit[rows + row] = b.cnt_hit;
+    }
+}
+extern "C" int vgx_test_quad_tile_choice(const int32_t *counts, const int32_t *haps, const int32_t *n, const double *tE, const double *r,
+                                         int64_t rows, int64_t maxlen, int H, int32_t *k_hit, double *pre_hit, double *w_hit, int64_t *cnt_hit) {
+    if (!counts || !haps || !n || !tE || !r || !k_hit || !pre_hit || !w_hit || !cnt_hit || rows < 0 || maxlen < 1 || maxlen > (1 << 20)) return 1;
+    if (rows == 0) return 0;
+    for (int64_t i = 0; i < rows; ++i)
+        if (n[i] < 0 || n[i] > maxlen) return 1;
+    const size_t nr = (size_t)rows;
+    const int64_t stride = (maxlen + 63) / 64 * 64 + 64;          // whole tiles, and the tile of padding behind every list
+    std::vector<int32_t> hc(nr * (size_t)stride, 0), hh(nr * (size_t)stride, 0);
+    for (size_t i = 0; i < nr; ++i)
+        for (int64_t k = 0; k < n[i]; ++k) {
+            hc[i * (size_t)stride + (size_t)k] = counts[i * (size_t)maxlen + (size_t)k];
+            hh[i * (size_t)stride + (size_t)k] = haps[i * (size_t)maxlen + (size_t)k];
+        }
+    const size_t lb = nr * (size_t)stride * 4;
+    char *d = nullptr;
+    if (hipMalloc((void **)&d, 2 * lb + nr * (8 + 8 + 8 + 16 + 16 + 16 + 8)) != hipSuccess) return 2;
+    int32_t *dc = (int32_t *)d, *dh = (int32_t *)(d + lb);
+    double *dte = (double *)(d + 2 * lb), *dr = dte + nr, *dpre = dr + nr, *dw = dpre + 2 * nr;
+    int64_t *dcnt = (int64_t *)(dw + 2 * nr);
+    int32_t *dn = (int32_t *)(dcnt + 2 * nr), *dk = dn + nr + (nr & 1);
+    int rc = 0;
+    if (hipMemcpy(dc, hc.data(), lb, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dh, hh.data(), lb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dte, tE, nr * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dr, r, nr * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dn, n, nr * 4, hipMemcpyHostToDevice) != hipSuccess)
+        rc = 2;
+    if (!rc) {
+        hipLaunchKernelGGL(vgx_quad_tilechoice_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(64), 0, nullptr, dc, dh, dn, dte, dr, rows, stride, H,
+                           dk, dpre, dw, dcnt);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+            hipMemcpy(k_hit, dk, 2 * nr * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(pre_hit, dpre, 2 * nr * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(w_hit, dw, 2 * nr * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(cnt_hit, dcnt, 2 * nr * 8, hipMemcpyDeviceToHost) != hipSuccess)
             rc = 2;
     }
     (void)hipFree(d);
