@@ -162,6 +162,20 @@ int vgx_device_count(void);
 
 /* ---- model hand-over ------------------------------------------------------------------------ */
 int vgx_set_params(vgx_engine *e, const vgx_params *p);
+/* Scenario ensembles: n_sets parameter sets over the one start state of vgx_set_state, and for every replicate the set it runs under.
+ * Replicate r of the next vgx_simulate_direct call is, bit for bit, the run of an engine that was given sets[set_of[r]] through
+ * vgx_set_params, the same state and seed r: one launch of the one-replicate-per-wavefront kernel runs all of them, every wavefront
+ * reading its own set's tables (classes of identical rate rows, actualSizes, the recomputed migration diagonal, suscepCumul,
+ * maxEffectiveBirth are built per set).  n_sets == 1 is vgx_set_params(e, &sets[0]); a later vgx_set_params returns the engine to one
+ * set.  Like vgx_set_params the call invalidates the device state.  Dimensions, start state and recombination settings are the
+ * engine's, shared by all sets; so `sizes` must be bitwise equal in all sets (VGX_ERR_ARG otherwise).  VGX_ERR_CLASSES and the LDS
+ * limit of the kernel's tables are reported for the set that exceeds them, by its index.  vgx_get_state, the event and lockdown
+ * logs, vgx_get_genealogies, vgx_get_timelines and the trajectories read logs and state only and work unchanged.
+ * Limits while more than one set is installed (each refused with VGX_ERR_ARG and a message naming it): vgx_simulate_direct runs in
+ * mode 0 on kernel 0 or 1 only (the row, latency and lane kernels, FAST and the counter-based stream read one shared parameter
+ * copy); vgx_simulate_tau and vgx_stage_tau are refused.  Device memory: one copy of every parameter array per set. */
+int vgx_set_param_sets(vgx_engine *e, int64_t n_sets, const vgx_params *sets /* [n_sets] */,
+                       const int32_t *set_of /* [n_replicates], values in [0, n_sets) */);
 /* Recombination branch of Birth (pyx:575-596): `recombination_probability` (pyx:93, set_coinfection_parameters
  * pyx:1422-1426), `genome_length` (pyx:1409-1417) and sitesPosition[sites] (pyx:98-101, set_mutation_position
  * pyx:1516-1524).  Optional: without this call the probability is 0 and the branch is never taken.  With a non-zero
@@ -169,7 +183,8 @@ int vgx_set_params(vgx_engine *e, const vgx_params *p);
  * four-replicates-per-wavefront kernel (its *_rec instantiations) or the one-replicate-per-wavefront kernel (any shape). */
 int vgx_set_recombination(vgx_engine *e, double recombination_probability, int64_t genome_length,
                           const int64_t *sitesPosition /* [sites], may be NULL when the probability is 0 */);
-/* The same state is given to every replicate; replicates differ by their seed only. */
+/* The same state is given to every replicate; replicates differ by their seed only (and, after vgx_set_param_sets, by their
+ * parameter set). */
 int vgx_set_state(vgx_engine *e, const vgx_state *s);
 int vgx_get_state(vgx_engine *e, int64_t replicate, vgx_state *out);
 /* user_seed of each replicate: the RNG of attempt k is PCG64(SeedSequence(seed, spawn_key=(k,))),
@@ -487,6 +502,8 @@ typedef struct vgx_direct_shape {
     int64_t have_counts32;           /* the device state keeps the 4-byte copy of the counts */
     int64_t tot_sus_is_sus;          /* one group, and totalSusceptible == susceptible in every population */
     int64_t no_lone, solo_general;   /* diagnostics: VGX_NO_LONE, VGX_SOLO_GENERAL are set */
+    int64_t param_sets;              /* parameter sets installed (vgx_set_param_sets); 0 or 1: one shared copy.  More: kernel 1 for
+                                        opts.kernel 0 or 1 in mode 0, everything else refused; C and CB are the largest over the sets */
 } vgx_direct_shape;
 /* What the rest of the call needs from the choice.  The fields of a kernel that was not chosen are 0. */
 typedef struct vgx_direct_plan {

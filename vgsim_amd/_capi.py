@@ -132,7 +132,7 @@ class VgxDirectShape(C.Structure):
     _fields_ = [(n, C.c_int64) for n in (
         "P", "H", "S", "sites", "R", "C", "CB", "cap", "n_seg", "n_solo_seg", "solo_npass0", "solo_npass1", "solo_ncls",
         "solo_maxnnz", "start_lone_rows", "start_max_nocc", "max_size", "hosts_below_2p53", "ld_possible", "recomb",
-        "fresh_state", "suscep_cumul0_zero", "have_counts32", "tot_sus_is_sus", "no_lone", "solo_general")]
+        "fresh_state", "suscep_cumul0_zero", "have_counts32", "tot_sus_is_sus", "no_lone", "solo_general", "param_sets")]
 
 
 class VgxDirectPlan(C.Structure):
@@ -156,6 +156,7 @@ SIGNATURES = {
     "vgx_last_error": (C.c_char_p, [_H]),
     "vgx_device_count": (C.c_int, []),
     "vgx_set_params": (C.c_int, [_H, C.POINTER(VgxParams)]),
+    "vgx_set_param_sets": (C.c_int, [_H, C.c_int64, C.POINTER(VgxParams), C.POINTER(C.c_int32)]),
     "vgx_set_recombination": (C.c_int, [_H, C.c_double, C.c_int64, _I]),
     "vgx_get_recombinations": (C.c_int, [_H, C.c_int64, C.c_int64, _I, _I, _I, _I, _I, _I]),
     "vgx_set_state": (C.c_int, [_H, C.POINTER(VgxState)]),
@@ -273,15 +274,41 @@ class HipEngine:
             raise VgxError(rc, self.lib.vgx_last_error(self.handle).decode())
 
     # ---------------------------------------------------------------- hand-over
-    def set_params(self, m):
-        p = VgxParams()
-        conv = []   # the arrays the pointers refer to (contiguous, of the declared dtype): alive until the call returns
+    @staticmethod
+    def _fill_params(p, m):
+        """The pointers of a ``VgxParams`` from host model ``m``; returns the arrays they refer to (contiguous, of the declared
+        dtype), which must stay alive until the library call returns."""
+        conv = []
         for name, ctype in VgxParams._fields_:
             a = np.ascontiguousarray(getattr(m, name), dtype=np.int64 if ctype is _I else np.float64)
             conv.append(a)
             setattr(p, name, _p(a))
-        self._keep = conv
+        return conv
+
+    def set_params(self, m):
+        p = VgxParams()
+        self._keep = self._fill_params(p, m)
         self._check(self.lib.vgx_set_params(self.handle, C.byref(p)))
+        self._set_recombination(m)
+
+    def set_param_sets(self, models, set_of):
+        """Scenario ensembles (``vgx_set_param_sets``): replicate r runs under the parameters of ``models[set_of[r]]``.
+        Recombination settings are those of ``models[0]`` (shared by all sets)."""
+        sets = (VgxParams * len(models))()
+        keep, filled = [], {}
+        for g, m in enumerate(models):
+            if id(m) in filled:        # the same model object given again: the same arrays
+                sets[g] = sets[filled[id(m)]]
+                continue
+            filled[id(m)] = g
+            keep.append(self._fill_params(sets[g], m))
+        of = np.ascontiguousarray(set_of, dtype=np.int32)
+        assert of.shape == (self.R,)
+        self._keep = keep
+        self._check(self.lib.vgx_set_param_sets(self.handle, len(models), sets, of.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._set_recombination(models[0])
+
+    def _set_recombination(self, m):
         pos = np.ascontiguousarray(getattr(m, "sitesPosition", np.zeros(0)), dtype=np.int64)
         self._check(self.lib.vgx_set_recombination(self.handle, float(getattr(m, "recombination", 0.0)),
                                                    int(getattr(m, "genome_length", 0)), _p(pos) if len(pos) else None))

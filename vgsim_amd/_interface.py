@@ -138,7 +138,7 @@ class Simulator(PlotMixin):
         else:
             print("Unknown method. Choose between 'direct' and 'tau'.")
 
-    def ensemble(self, n_replicates, seeds=None, device=0):
+    def ensemble(self, n_replicates, seeds=None, device=0, scenarios=None, scenario_of=None):
         """Many independent seeded trajectories of THIS model on one GPU (``vgsim_amd.ensemble.Ensemble``): what the engine
         is built for.  One ``simulate()`` call on a small model is a single sequential event loop and runs at the speed of
         one wavefront (about 1e5 events/s, slower than the reference's CPU loop); replicates run concurrently, four per
@@ -149,15 +149,19 @@ class Simulator(PlotMixin):
             res = ens.simulate(100000, record_events=True)        # direct Gillespie for every replicate
             chain = ens.replicate_events(17)                      # (6, n) chain of one replicate, as export_chain_events
             state = ens.replicate_state(17)                       # compartments, counters, epidemic time
+
+        ``scenarios`` (a list of configured ``Simulator`` s) and ``scenario_of`` (one index per replicate, default
+        ``arange(n_replicates) % len(scenarios)``) make it a scenario ensemble: replicate r runs under the parameters of
+        ``scenarios[scenario_of[r]]`` from this simulator's state, all in the same launch (``Ensemble`` has the limits).
         """
         from .ensemble import Ensemble
-        return Ensemble(self, n_replicates, seeds=seeds, device=device)
+        return Ensemble(self, n_replicates, seeds=seeds, device=device, scenarios=scenarios, scenario_of=scenario_of)
 
     def simulate_ensemble(self, n_replicates, iterations=1000, sample_size=None, epidemic_time=-1, method='direct', attempts=200,
-                          seeds=None, **kw):
+                          seeds=None, scenarios=None, scenario_of=None, **kw):
         """``simulate`` for ``n_replicates`` seeded copies of this model in one launch; returns ``(ensemble, result)``
         (``result.events`` = events.ptr of every replicate; chains and states through the ensemble's ``replicate_*``)."""
-        ens = self.ensemble(n_replicates, seeds=seeds)
+        ens = self.ensemble(n_replicates, seeds=seeds, scenarios=scenarios, scenario_of=scenario_of)
         if method == 'direct':
             res = ens.simulate(iterations, sample_size=sample_size, epidemic_time=epidemic_time, attempts=attempts,
                                record_events=kw.pop('record_events', True), **kw)

@@ -83,28 +83,38 @@ extern "C" int vgx_set_seeds(vgx_engine *e, const int64_t *seeds) {
     return VGX_OK;
 }
 
-extern "C" int vgx_set_params(vgx_engine *e, const vgx_params *p) {
-    if (!e || !p) return VGX_ERR_ARG;
-    HIPCHECK(e, hipSetDevice(e->device));
-    const int64_t H = e->d.hapNum, P = e->d.popNum, S = e->d.susNum, sites = e->d.sites;
+// The tables VgxDevParams points to that are derived from one vgx_params: the classes of identical per-haplotype rate rows and the
+// parameter-only parts of UpdateAllRates.  vgx_set_params installs one of them; vgx_set_param_sets builds one per set.
+struct ParamTables {
+    std::vector<int32_t> cls, c_bidx, c_stype;
+    std::vector<double> c_d, c_s, c_tm, cb_b, cb_sig, suscepCumul, mig, actualSizes;
+    double maxEffectiveBirth = 0.0;
+};
+
+// `who` opens the message of a refusal ("vgx_set_params", "vgx_set_param_sets: set 3")
+static int build_param_tables(const vgx_dims &d, const vgx_params *p, const std::string &who, ParamTables &t, std::string &err) {
+    const int64_t H = d.hapNum, P = d.popNum, S = d.susNum, sites = d.sites;
     if (!p->bRate || !p->dRate || !p->sRate || !p->susceptibility || !p->suscType || !p->suscepTransition ||
         !p->sizes || !p->contactDensityBeforeLockdown || !p->contactDensityAfterLockdown || !p->startLD ||
-        !p->endLD || !p->samplingMultiplier || !p->migrationRates || (sites > 0 && (!p->mRate || !p->hapMutType)))
-        return fail(e, VGX_ERR_ARG, "vgx_set_params: null parameter array");
+        !p->endLD || !p->samplingMultiplier || !p->migrationRates || (sites > 0 && (!p->mRate || !p->hapMutType))) {
+        err = who + ": null parameter array";
+        return VGX_ERR_ARG;
+    }
     for (int64_t h = 0; h < H; h++)
-        if (p->suscType[h] < 0 || p->suscType[h] >= S) return fail(e, VGX_ERR_ARG, "vgx_set_params: suscType out of range");
+        if (p->suscType[h] < 0 || p->suscType[h] >= S) { err = who + ": suscType out of range"; return VGX_ERR_ARG; }
 
     // ---- classes of identical per-haplotype rate rows ----
     std::vector<double> tm((size_t)H);
     for (int64_t h = 0; h < H; h++) {  // tmRate, pyx:306-308
-        double t = 0;
-        for (int64_t s = 0; s < sites; s++) t += p->mRate[h * sites + s];
-        tm[(size_t)h] = t;
+        double tt = 0;
+        for (int64_t s = 0; s < sites; s++) tt += p->mRate[h * sites + s];
+        tm[(size_t)h] = tt;
     }
     std::unordered_map<std::string, int> fullmap, birthmap;
-    std::vector<double> c_d, c_s, c_tm, cb_b, cb_sig;
-    std::vector<int32_t> c_bidx, c_stype;
-    e->cls.assign((size_t)H, 0);
+    std::vector<double> &c_d = t.c_d, &c_s = t.c_s, &c_tm = t.c_tm, &cb_b = t.cb_b, &cb_sig = t.cb_sig;
+    std::vector<int32_t> &c_bidx = t.c_bidx, &c_stype = t.c_stype;
+    c_d.clear(); c_s.clear(); c_tm.clear(); cb_b.clear(); cb_sig.clear(); c_bidx.clear(); c_stype.clear();
+    t.cls.assign((size_t)H, 0);
     std::string key;
     for (int64_t h = 0; h < H; h++) {
         key.assign((const char *)&p->bRate[h], 8);
@@ -133,15 +143,61 @@ extern "C" int vgx_set_params(vgx_engine *e, const vgx_params *p) {
             c_tm.push_back(tm[(size_t)h]);
             c_bidx.push_back(cb);
             c_stype.push_back((int32_t)p->suscType[h]);
-            if (c_d.size() > VGX_MAX_CLASSES)
-                return fail(e, VGX_ERR_CLASSES,
-                            "vgx_set_params: more than " + std::to_string(VGX_MAX_CLASSES) +
-                                " distinct per-haplotype rate rows (bRate, susceptibility, dRate, sRate, sum of mRate, suscType)");
+            if (c_d.size() > VGX_MAX_CLASSES) {
+                err = who + ": more than " + std::to_string(VGX_MAX_CLASSES) +
+                      " distinct per-haplotype rate rows (bRate, susceptibility, dRate, sRate, sum of mRate, suscType)";
+                return VGX_ERR_CLASSES;
+            }
         } else {
             c = fi->second;
         }
-        e->cls[(size_t)h] = c;
+        t.cls[(size_t)h] = c;
     }
+
+    // ---- parameter-only parts of UpdateAllRates, in the reference's order ----
+    t.suscepCumul.assign((size_t)S, 0.0);
+    for (int64_t s1 = 0; s1 < S; s1++) {  // pyx:284-287
+        double v = 0;
+        for (int64_t s2 = 0; s2 < S; s2++) v += p->suscepTransition[s1 * S + s2];
+        t.suscepCumul[(size_t)s1] = v;
+    }
+    t.mig.assign(p->migrationRates, p->migrationRates + P * P);
+    t.actualSizes.assign((size_t)P, 0.0);
+    for (int64_t p1 = 0; p1 < P; p1++) {  // pyx:289-297
+        t.mig[(size_t)(p1 * P + p1)] = 1.0;
+        double a = 0.0;
+        for (int64_t p2 = 0; p2 < P; p2++) {
+            if (p1 == p2) continue;
+            t.mig[(size_t)(p1 * P + p1)] -= t.mig[(size_t)(p1 * P + p2)];
+            a += t.mig[(size_t)(p2 * P + p1)] * (double)p->sizes[p2];
+        }
+        // NB: the reference reads migrationRates[pn2, pn1] for pn2 != pn1 only, so the not-yet-rewritten
+        // diagonals of later rows never enter (pyx:296)
+        a += t.mig[(size_t)(p1 * P + p1)] * (double)p->sizes[p1];
+        t.actualSizes[(size_t)p1] = a;
+    }
+    t.maxEffectiveBirth = 0.0;  // pyx:340-344
+    for (int64_t h = 0; h < H; h++)
+        for (int64_t s = 0; s < S; s++) {
+            double v = p->bRate[h] * p->susceptibility[h * S + s];
+            if (v > t.maxEffectiveBirth) t.maxEffectiveBirth = v;
+        }
+    return VGX_OK;
+}
+
+extern "C" int vgx_set_params(vgx_engine *e, const vgx_params *p) {
+    if (!e || !p) return VGX_ERR_ARG;
+    HIPCHECK(e, hipSetDevice(e->device));
+    const int64_t H = e->d.hapNum, P = e->d.popNum, S = e->d.susNum, sites = e->d.sites;
+    ParamTables t;
+    {
+        std::string msg;
+        const int rc = build_param_tables(e->d, p, "vgx_set_params", t, msg);
+        if (rc) return fail(e, rc, msg);
+    }
+    const std::vector<double> &c_d = t.c_d, &c_s = t.c_s, &c_tm = t.c_tm, &cb_b = t.cb_b, &cb_sig = t.cb_sig;
+    const std::vector<int32_t> &c_bidx = t.c_bidx, &c_stype = t.c_stype;
+    e->cls = t.cls;
     e->C = (int)c_d.size();
     e->CB = (int)cb_b.size();
     {   // BirthRate (pyx:382-392) per birth class as a program of chain segments: the groups with a non-zero susceptibility in
@@ -244,15 +300,9 @@ extern "C" int vgx_set_params(vgx_engine *e, const vgx_params *p) {
     for (size_t c = 0; c < c_d.size(); c++)
         e->h_class_pos[c] = (c_d[c] > 0.0 || c_s[c] > 0.0 || c_tm[c] > 0.0 || cb_b[(size_t)c_bidx[c]] > 0.0) ? 1 : 0;
 
-    // ---- parameter-only parts of UpdateAllRates, in the reference's order ----
-    e->suscepCumul.assign((size_t)S, 0.0);
-    for (int64_t s1 = 0; s1 < S; s1++) {  // pyx:284-287
-        double v = 0;
-        for (int64_t s2 = 0; s2 < S; s2++) v += p->suscepTransition[s1 * S + s2];
-        e->suscepCumul[(size_t)s1] = v;
-    }
-    e->mig.assign(p->migrationRates, p->migrationRates + P * P);
-    e->actualSizes.assign((size_t)P, 0.0);
+    e->suscepCumul = t.suscepCumul;
+    e->mig = t.mig;
+    e->actualSizes = t.actualSizes;
     e->sizes.assign(p->sizes, p->sizes + P);
     e->h_startLD.assign(p->startLD, p->startLD + P);
     e->h_endLD.assign(p->endLD, p->endLD + P);
@@ -277,25 +327,7 @@ extern "C" int vgx_set_params(vgx_engine *e, const vgx_params *p) {
             e->h_mut_total += e->h_mutp[s2][i];
         }
     }
-    for (int64_t p1 = 0; p1 < P; p1++) {  // pyx:289-297
-        e->mig[(size_t)(p1 * P + p1)] = 1.0;
-        double a = 0.0;
-        for (int64_t p2 = 0; p2 < P; p2++) {
-            if (p1 == p2) continue;
-            e->mig[(size_t)(p1 * P + p1)] -= e->mig[(size_t)(p1 * P + p2)];
-            a += e->mig[(size_t)(p2 * P + p1)] * (double)p->sizes[p2];
-        }
-        // NB: the reference reads migrationRates[pn2, pn1] for pn2 != pn1 only, so the not-yet-rewritten
-        // diagonals of later rows never enter (pyx:296)
-        a += e->mig[(size_t)(p1 * P + p1)] * (double)p->sizes[p1];
-        e->actualSizes[(size_t)p1] = a;
-    }
-    double maxEffectiveBirth = 0.0;  // pyx:340-344
-    for (int64_t h = 0; h < H; h++)
-        for (int64_t s = 0; s < S; s++) {
-            double v = p->bRate[h] * p->susceptibility[h * S + s];
-            if (v > maxEffectiveBirth) maxEffectiveBirth = v;
-        }
+    const double maxEffectiveBirth = t.maxEffectiveBirth;
 
     int rc = 0;
     rc |= upload(e, e->p_cls, e->cls.data(), (size_t)H);
@@ -376,8 +408,112 @@ extern "C" int vgx_set_params(vgx_engine *e, const vgx_params *p) {
     d.recombination = e->recombination; d.genome_length = e->genome_length;
     d.sitesPosition = (const int64_t *)e->p_sitesPos.p;
     e->have_params = true;
+    e->n_sets = 1;
     e->tau_staged = false;
     e->dev_state_valid = false;  // class ids in the occupancy lists refer to the old parameter rows
+    return VGX_OK;
+}
+
+// The blocks of the installed parameter sets with the engine's recombination settings (shared by all sets), to the device
+static int upload_param_sets(vgx_engine *e) {
+    for (VgxDevParams &d : e->h_psets) {
+        d.recombination = e->recombination; d.genome_length = e->genome_length;
+        d.sitesPosition = (const int64_t *)e->p_sitesPos.p;
+    }
+    int rc = ensure(e, e->ps_blocks, e->h_psets.size() * sizeof(VgxDevParams));
+    if (rc) return rc;
+    HIPCHECK(e, hipMemcpy(e->ps_blocks.p, e->h_psets.data(), e->h_psets.size() * sizeof(VgxDevParams), hipMemcpyHostToDevice));
+    return VGX_OK;
+}
+
+extern "C" int vgx_set_param_sets(vgx_engine *e, int64_t n_sets, const vgx_params *sets, const int32_t *set_of) {
+    if (!e) return VGX_ERR_ARG;
+    if (!sets || !set_of || n_sets < 1) return fail(e, VGX_ERR_ARG, "vgx_set_param_sets: needs at least one set and the map from replicate to set");
+    const int64_t H = e->d.hapNum, P = e->d.popNum, S = e->d.susNum, sites = e->d.sites, R = e->R;
+    for (int64_t r = 0; r < R; r++)
+        if (set_of[r] < 0 || set_of[r] >= n_sets)
+            return fail(e, VGX_ERR_ARG, "vgx_set_param_sets: set_of[" + std::to_string(r) + "] = " + std::to_string(set_of[r]) +
+                                            " is outside [0, " + std::to_string(n_sets) + ")");
+    for (int64_t g = 0; g < n_sets; g++) {
+        if (!sets[g].sizes) return fail(e, VGX_ERR_ARG, "vgx_set_param_sets: set " + std::to_string(g) + ": null parameter array");
+        if (memcmp(sets[g].sizes, sets[0].sizes, (size_t)P * 8) != 0)
+            return fail(e, VGX_ERR_ARG, "vgx_set_param_sets: set " + std::to_string(g) + ": sizes differ from set 0's (every set runs "
+                                        "from the one start state of vgx_set_state)");
+    }
+    if (n_sets == 1) return vgx_set_params(e, &sets[0]);
+    if (S > 64) return fail(e, VGX_ERR_ARG, "vgx_set_param_sets: at most 64 susceptibility groups are supported");
+
+    // every set's tables on the host first: a refused set leaves the engine as it was
+    std::vector<ParamTables> tabs((size_t)n_sets);
+    int maxC = 0, maxCB = 0;
+    for (int64_t g = 0; g < n_sets; g++) {
+        const std::string who = "vgx_set_param_sets: set " + std::to_string(g);
+        std::string msg;
+        const int rc = build_param_tables(e->d, &sets[g], who, tabs[(size_t)g], msg);
+        if (rc) return fail(e, rc, msg);
+        const int C = (int)tabs[(size_t)g].c_d.size(), CB = (int)tabs[(size_t)g].cb_b.size();
+        const size_t lds = vgxi_direct_lds_bytes((int)P, (int)S, C, CB);
+        if (lds > 160 * 1024)
+            return fail(e, VGX_ERR_ARG, who + ": the population/class tables need " + std::to_string(lds) +
+                                            " bytes of LDS per wavefront (limit 163840): too many populations x rate classes");
+        maxC = std::max(maxC, C); maxCB = std::max(maxCB, CB);
+    }
+    // what the engine holds per model (host copies, the shared sizes, the other kernels' tables) is set 0's
+    const int rc0 = vgx_set_params(e, &sets[0]);
+    if (rc0) return rc0;
+
+    // all sets' arrays in one device allocation, 16-byte aligned; the blocks point into it
+    std::vector<char> blob;
+    auto put = [&blob](const void *src, size_t bytes) {
+        const size_t off = (blob.size() + 15) & ~(size_t)15;
+        blob.resize(off + bytes);
+        if (bytes) memcpy(blob.data() + off, src, bytes);
+        return off;
+    };
+    e->h_psets.assign((size_t)n_sets, VgxDevParams{});
+    e->sets_startLD.resize((size_t)(n_sets * P));
+    for (int64_t g = 0; g < n_sets; g++) {
+        const vgx_params &p = sets[g];
+        const ParamTables &t = tabs[(size_t)g];
+        VgxDevParams &d = e->h_psets[(size_t)g];
+        d.H = (int32_t)H; d.P = (int32_t)P; d.S = (int32_t)S; d.sites = (int32_t)sites;
+        d.C = (int32_t)t.c_d.size(); d.CB = (int32_t)t.cb_b.size();
+        d.maxEffectiveBirth = t.maxEffectiveBirth;
+        // (offsets for now: the allocation's address is added below)
+#define VGX_PUT(field, src, count) d.field = (decltype(d.field))put((src), (size_t)(count) * sizeof(*d.field))
+        VGX_PUT(cls, t.cls.data(), H); VGX_PUT(suscType, p.suscType, H);
+        VGX_PUT(mRate, p.mRate, H * sites); VGX_PUT(hapMutType, p.hapMutType, H * sites * 3);
+        VGX_PUT(bRate, p.bRate, H); VGX_PUT(susc, p.susceptibility, H * S);
+        VGX_PUT(c_d, t.c_d.data(), d.C); VGX_PUT(c_s, t.c_s.data(), d.C); VGX_PUT(c_tm, t.c_tm.data(), d.C);
+        VGX_PUT(c_bidx, t.c_bidx.data(), d.C); VGX_PUT(c_stype, t.c_stype.data(), d.C);
+        VGX_PUT(cb_b, t.cb_b.data(), d.CB); VGX_PUT(cb_sigma, t.cb_sig.data(), (int64_t)d.CB * S);
+        VGX_PUT(sizes, p.sizes, P);
+        VGX_PUT(cdBefore, p.contactDensityBeforeLockdown, P); VGX_PUT(cdAfter, p.contactDensityAfterLockdown, P);
+        VGX_PUT(startLD, p.startLD, P); VGX_PUT(endLD, p.endLD, P); VGX_PUT(sampMult, p.samplingMultiplier, P);
+        VGX_PUT(actualSizes, t.actualSizes.data(), P); VGX_PUT(mig, t.mig.data(), P * P);
+        VGX_PUT(suscepTransition, p.suscepTransition, S * S); VGX_PUT(suscepCumul, t.suscepCumul.data(), S);
+#undef VGX_PUT
+        std::copy(p.startLD, p.startLD + P, e->sets_startLD.begin() + g * P);
+    }
+    int rc = ensure(e, e->ps_blob, blob.size());
+    if (rc) return rc;
+    HIPCHECK(e, hipMemcpy(e->ps_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    const char *base = (const char *)e->ps_blob.p;
+    for (VgxDevParams &d : e->h_psets) {
+#define VGX_AT(field) d.field = (decltype(d.field))(base + (size_t)d.field)
+        VGX_AT(cls); VGX_AT(suscType); VGX_AT(mRate); VGX_AT(hapMutType); VGX_AT(bRate); VGX_AT(susc);
+        VGX_AT(c_d); VGX_AT(c_s); VGX_AT(c_tm); VGX_AT(c_bidx); VGX_AT(c_stype); VGX_AT(cb_b); VGX_AT(cb_sigma);
+        VGX_AT(sizes); VGX_AT(cdBefore); VGX_AT(cdAfter); VGX_AT(startLD); VGX_AT(endLD); VGX_AT(sampMult);
+        VGX_AT(actualSizes); VGX_AT(mig); VGX_AT(suscepTransition); VGX_AT(suscepCumul);
+#undef VGX_AT
+    }
+    rc = upload_param_sets(e);
+    if (rc) return rc;
+    rc = ensure(e, e->ps_setof, (size_t)R * 4);
+    if (rc) return rc;
+    HIPCHECK(e, hipMemcpy(e->ps_setof.p, set_of, (size_t)R * 4, hipMemcpyHostToDevice));
+    e->sets_C = maxC; e->sets_CB = maxCB;
+    e->n_sets = n_sets;
     return VGX_OK;
 }
 
@@ -400,6 +536,7 @@ extern "C" int vgx_set_recombination(vgx_engine *e, double recombination_probabi
     }
     e->dp.recombination = e->recombination; e->dp.genome_length = e->genome_length;
     e->dp.sitesPosition = (const int64_t *)e->p_sitesPos.p;
+    if (e->n_sets > 1) return upload_param_sets(e);
     return VGX_OK;
 }
 

@@ -1,6 +1,7 @@
 // vgx_dev.h — structures shared by the host side of libvgx (vgx_api.hip, vgx_direct_run.hip, vgx_tau_run.hip) and the gfx950 kernels.
 //
-// HBM layout.  Parameters are one read-only copy shared by all replicates.  Each
+// HBM layout.  Parameters are one read-only copy shared by all replicates — or, in a scenario ensemble
+// (vgx_set_param_sets), G such copies in one device array of VgxDevParams blocks and a map from replicate to block.  Each
 // replicate (= one seeded trajectory) owns:
 //   * a population block: per-population rate caches and counters, [field][P], loaded into LDS by the
 //     replicate's wavefront for the whole run;
@@ -32,6 +33,8 @@ enum { PD_POPRATE = 0, PD_INFECT, PD_IMMUNE, PD_MIG, PD_MAXEBM, PD_CD, PD_COUNT 
 // fields of the per-replicate i64 population block
 enum { PI_TOTSUS = 0, PI_TOTINF, PI_LOCK, PI_COUNT };
 
+// A new field also goes into the field-by-field copy of the scenario kernels (vgx_direct.hip, direct_body: a static_assert on the
+// size stands next to the list).
 struct VgxDevParams {
     int32_t H, P, S, sites, C, CB;
     const int32_t *cls;         // [H] full rate class of a haplotype
@@ -143,6 +146,14 @@ struct VgxDirectArgs {
     int32_t fast;            // 0: reference summation order (bit-exact); 1: order-free sums (vgx_run_opts.mode)
     int32_t rng_philox;      // FAST mode only: 1 = the counter-based Philox stream of vgx_rng.h instead of PCG64 (vgx_run_opts.mode = 2)
     int32_t pad_;
+};
+
+// The scenario entry points of vgx_direct.hip: replicate r runs under psets[set_of[r]] instead of a.p.  A wrapper, so that
+// VgxDirectArgs — the kernarg block of every other direct kernel — keeps its layout.
+struct VgxDirectSetsArgs {
+    VgxDirectArgs a;
+    const VgxDevParams *psets;   // [n_sets] device
+    const int32_t *set_of;       // [n_replicates] device, values in [0, n_sets)
 };
 
 // Dense per-replicate state of the lane-per-replicate kernel (vgx_lanes.hip): element i of replicate r at [i * R + r].

@@ -1127,7 +1127,8 @@ static __device__ __forceinline__ int generate_event(Ctx &c, double u, Tile &t, 
 }
 
 // Restart (pyx:714-738): compartments back to the initial snapshot; the caller re-checks lockdowns and
-// rebuilds all rates.
+// rebuilds all rates.  SETS: the list classes come from the replicate's own parameter set (the shared snapshot holds set 0's).
+template <int SETS>
 static __device__ __forceinline__ void restart_state(Ctx &c, const VgxDevRep &r) {
     const int P = c.P, S = c.S, lane = c.lane;
     c.ev_ptr = 0;
@@ -1150,8 +1151,9 @@ static __device__ __forceinline__ void restart_state(Ctx &c, const VgxDevRep &r)
             int64_t ct = 0;
             if (k < n) {
                 ct = r.i_cnt[(int64_t)pn * r.i_cap + k];
-                LH(c, pn)[k] = r.i_hap[(int64_t)pn * r.i_cap + k];
-                LC(c, pn)[k] = r.i_cls[(int64_t)pn * r.i_cap + k];
+                const int32_t hap = r.i_hap[(int64_t)pn * r.i_cap + k];
+                LH(c, pn)[k] = hap;
+                LC(c, pn)[k] = SETS ? c.p->cls[hap] : r.i_cls[(int64_t)pn * r.i_cap + k];
                 LN(c, pn)[k] = ct;
             }
             int64_t tsum = bcast_i64(iscan(ct, lane), LANES - 1);
@@ -1170,12 +1172,37 @@ static __device__ __forceinline__ void restart_state(Ctx &c, const VgxDevRep &r)
 // Kernel body, specialised on the LDS stride of the per-population arrays (PT: 64 when popNum <= 64, so every
 // LDS address is a compile-time constant; 0 = runtime stride), on the number of susceptibility groups (ST: 1 or 0 =
 // runtime) and on a single rate class (ONE): the common shapes lose their address arithmetic and inner loops.
-template <int PT, int ST, int ONE, int FAST>
-static __device__ __forceinline__ void direct_body(const VgxDirectArgs &a) {
+// SETS (scenario ensembles): the replicate's parameters are block set_of[replicate] of psets instead of a.p — one address per
+// workgroup, so the block is read by scalar loads; its class tables are carved with its own C and CB out of an allocation sized
+// for the largest set.
+template <int PT, int ST, int ONE, int FAST, int SETS = 0>
+static __device__ __forceinline__ void direct_body(const VgxDirectArgs &a, const VgxDevParams *psets = nullptr,
+                                                   const int32_t *set_of = nullptr) {
     const int rep = blockIdx.x;
     if (rep >= a.n_replicates) return;
     const int lane = threadIdx.x;
-    const VgxDevParams &p = a.p;
+    // The replicate's block, copied field by field through the constant address space (nothing writes the blocks while the kernel
+    // runs): its fields are then scalar values like the kernel arguments the other entry points read a.p from, and its arrays are
+    // known to be global memory.  Read in place (p = psets[set_of[rep]], plain global memory) every field is loaded again after each
+    // store the compiler cannot tell apart, and the arrays behind the reloaded pointers are reached by flat loads, which wait on
+    // the LDS counter as well: that form had 215 VGPRs against the plain kernel's 148 and took 1.29 times its time.  This form has
+    // 154 (runtime stride) and 150 (p64) VGPRs against 148 and 144 of the plain kernels, no scratch, no flat loads.
+    // The list below names EVERY field of VgxDevParams: one left out stays uninitialised here alone (the other entry points read
+    // a.p whole), so a new field goes into the list and into the size below together.
+    static_assert(sizeof(VgxDevParams) == 6 * 4 + 23 * 8 + 3 * 8 + 8, "VgxDevParams changed: copy the new field in the list below");
+    VgxDevParams own;
+    if (SETS) {
+        typedef const VgxDevParams __attribute__((address_space(4))) *ConstBlock;
+        const ConstBlock blk = (ConstBlock)(psets + set_of[rep]);
+#define VGX_F(f) own.f = blk->f
+        VGX_F(H); VGX_F(P); VGX_F(S); VGX_F(sites); VGX_F(C); VGX_F(CB);
+        VGX_F(cls); VGX_F(suscType); VGX_F(mRate); VGX_F(hapMutType); VGX_F(bRate); VGX_F(susc); VGX_F(c_d); VGX_F(c_s); VGX_F(c_tm);
+        VGX_F(c_bidx); VGX_F(c_stype); VGX_F(cb_b); VGX_F(cb_sigma); VGX_F(sizes); VGX_F(cdBefore); VGX_F(cdAfter); VGX_F(startLD);
+        VGX_F(endLD); VGX_F(sampMult); VGX_F(actualSizes); VGX_F(mig); VGX_F(suscepTransition); VGX_F(suscepCumul);
+        VGX_F(maxEffectiveBirth); VGX_F(recombination); VGX_F(genome_length); VGX_F(sitesPosition);
+#undef VGX_F
+    }
+    const VgxDevParams &p = SETS ? own : a.p;
     const VgxDevRep &r = a.r;
     const int P = p.P, S = ST ? ST : p.S, C = ONE ? 1 : p.C, CB = ONE ? 1 : p.CB;
     const int PL = PT ? PT : P;   // LDS stride of the [P] arrays
@@ -1184,7 +1211,7 @@ static __device__ __forceinline__ void direct_body(const VgxDirectArgs &a) {
     Ctx c;
     c.P = P; c.S = S; c.H = p.H; c.C = C; c.CB = CB; c.sites = p.sites; c.lane = lane;
     c.fast = FAST;
-    c.p = &a.p;
+    c.p = &p;
     // LDS carve: keep in step with vgxi_direct_lds_bytes().  Arrays whose size depends only on (PL, S) first.
     double *ld = (double *)smem;
     c.popRate = ld; ld += PL;   c.infect = ld; ld += PL;   c.immune = ld; ld += PL;   c.migRate = ld; ld += PL;
@@ -1390,7 +1417,7 @@ static __device__ __forceinline__ void direct_body(const VgxDirectArgs &a) {
                 fa_n += n;
                 WSYNC();
             }
-            restart_state(c, r);
+            restart_state<SETS>(c, r);
             att_ev0 = 0;
             att_loc0 = c.loc_n;
             restarts += 1;
@@ -1447,6 +1474,13 @@ extern "C" __global__ void __launch_bounds__(LANES) vgx_direct_kernel_p64s1c1(Vg
 // FAST mode (vgx_run_opts.mode = 1): order-free sums, same random stream and event semantics
 extern "C" __global__ void __launch_bounds__(LANES) vgx_direct_fast_kernel(VgxDirectArgs a) { direct_body<0, 0, 0, 1>(a); }
 extern "C" __global__ void __launch_bounds__(LANES) vgx_direct_fast_kernel_p64s1(VgxDirectArgs a) { direct_body<64, 1, 1, 1>(a); }
+// scenario ensembles (exact mode): every replicate under its own parameter set; runtime shape, and popNum <= 64
+extern "C" __global__ void __launch_bounds__(LANES) vgx_direct_sets_kernel(VgxDirectSetsArgs s) {
+    direct_body<0, 0, 0, 0, 1>(s.a, s.psets, s.set_of);
+}
+extern "C" __global__ void __launch_bounds__(LANES) vgx_direct_sets_kernel_p64(VgxDirectSetsArgs s) {
+    direct_body<64, 0, 0, 0, 1>(s.a, s.psets, s.set_of);
+}
 
 // Gives every replicate the same start state (the host model's state at the beginning of the call):
 // occupancy lists, susceptible counts, contact densities, population totals and lockdown flags.
@@ -1486,6 +1520,21 @@ extern "C" __global__ void __launch_bounds__(LANES) vgx_init_reps_kernel(
     for (int i = lane; i < P * S; i += LANES) r.sus[rep * P * S + i] = s_sus[i];
 }
 
+// Scenario ensembles: a haplotype's class number differs between parameter sets, so after vgx_init_reps_kernel (which wrote
+// set 0's classes) every replicate's list classes are taken from its own set, block set_of[replicate] of psets.
+extern "C" __global__ void __launch_bounds__(LANES) vgx_init_reps_sets_kernel(VgxDevRep r, int P, int64_t R, const VgxDevParams *psets,
+                                                                              const int32_t *set_of) {
+    const int64_t rep = blockIdx.x;
+    if (rep >= R) return;
+    const int32_t *cls = psets[set_of[rep]].cls;
+    for (int pn = 0; pn < P; ++pn) {
+        const int n = r.nocc[rep * P + pn];
+        const int32_t *lh = r.lhap + (rep * P + pn) * r.cap;
+        int32_t *lc = r.lcls + (rep * P + pn) * r.cap;
+        for (int k = threadIdx.x; k < n; k += LANES) lc[k] = cls[lh[k]];
+    }
+}
+
 // ---- host-side launchers (this translation unit owns its kernels; no relocatable device code needed) ----
 extern "C" __attribute__((visibility("hidden"))) size_t vgxi_direct_lds_bytes(int P, int S, int C, int CB) {
     size_t PL = P <= 64 ? 64 : (size_t)P;
@@ -1510,11 +1559,31 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t vgxi_launch_direct(c
     return hipGetLastError();
 }
 
+// the scenario form: replicate r runs under psets[set_of[r]] (device arrays); lds is sized for the largest set; exact mode only
+extern "C" __attribute__((visibility("hidden"))) hipError_t vgxi_launch_direct_sets(const VgxDirectArgs *a, const VgxDevParams *psets,
+                                                                                   const int32_t *set_of, size_t lds, hipStream_t stream) {
+    if (a->fast || !psets || !set_of) return hipErrorInvalidValue;
+    void (*k)(VgxDirectSetsArgs) = a->p.P <= 64 ? vgx_direct_sets_kernel_p64 : vgx_direct_sets_kernel;
+    hipError_t err = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (err != hipSuccess) return err;
+    VgxDirectSetsArgs s;
+    s.a = *a; s.psets = psets; s.set_of = set_of;
+    hipLaunchKernelGGL(k, dim3((unsigned)a->n_replicates), dim3(LANES), lds, stream, s);
+    return hipGetLastError();
+}
+
 extern "C" __attribute__((visibility("hidden"))) hipError_t vgxi_launch_init_reps(
     const VgxDevRep *r, int P, int S, int64_t R, const int32_t *s_nocc, const int32_t *s_hap, const int32_t *s_cls,
     const int64_t *s_cnt, int64_t s_cap, const int64_t *s_sus, const double *s_cd, const int64_t *s_tot,
     hipStream_t stream) {
     hipLaunchKernelGGL(vgx_init_reps_kernel, dim3((unsigned)R), dim3(LANES), 0, stream, *r, P, S, R, s_nocc, s_hap,
                        s_cls, s_cnt, s_cap, s_sus, s_cd, s_tot);
+    return hipGetLastError();
+}
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t vgxi_launch_init_reps_sets(const VgxDevRep *r, int P, int64_t R,
+                                                                                      const VgxDevParams *psets, const int32_t *set_of,
+                                                                                      hipStream_t stream) {
+    hipLaunchKernelGGL(vgx_init_reps_sets_kernel, dim3((unsigned)R), dim3(LANES), 0, stream, *r, P, R, psets, set_of);
     return hipGetLastError();
 }

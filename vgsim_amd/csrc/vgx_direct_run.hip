@@ -72,6 +72,18 @@ int vgx_choose_direct(const vgx_direct_shape *s, const vgx_run_opts *o, vgx_dire
     *plan = vgx_direct_plan{};
     auto refuse = [&err](const char *msg) { err = msg; return (int)VGX_ERR_ARG; };
 
+    // Several parameter sets (vgx_set_param_sets): the wavefront kernel's scenario form, exact mode; every other kernel and mode reads
+    // one shared parameter copy.
+    if (s->param_sets > 1) {
+        if (o->mode != 0)
+            return refuse("vgx_simulate_direct: several parameter sets are installed (vgx_set_param_sets): they run in exact mode (mode 0) only");
+        if (k != 0 && k != 1)
+            return refuse("vgx_simulate_direct: several parameter sets are installed (vgx_set_param_sets): they run on the "
+                          "one-replicate-per-wavefront kernel only (kernel 0 or 1)");
+        plan->kernel = VGX_K_WAVE;
+        return VGX_OK;
+    }
+
     // A FAST request that the exact kernels serve counts as exact in every scope below.  Where the call then lands on no exact kernel,
     // plan->mode (set once, after the choice) is the request's own mode again.
     const Remap remap = remap_of(s, o);
@@ -234,7 +246,7 @@ static void build_lists(const vgx_engine *e, const std::vector<int64_t> &dense, 
 }
 
 static size_t lds_bytes_for(const vgx_engine *e) {
-    return vgxi_direct_lds_bytes((int)e->d.popNum, (int)e->d.susNum, e->C, e->CB);
+    return vgxi_direct_lds_bytes((int)e->d.popNum, (int)e->d.susNum, e->max_C(), e->max_CB());
 }
 
 static int init_device_state(vgx_engine *e, int64_t traj_points) {
@@ -278,14 +290,14 @@ static int init_device_state(vgx_engine *e, int64_t traj_points) {
     rc |= ensure(e, e->r_popI, (size_t)(R * PI_COUNT * P) * 8);
     rc |= ensure(e, e->r_sus, (size_t)(R * P * S) * 8);
     rc |= ensure(e, e->r_immSrc, (size_t)(R * P * S) * 8);
-    rc |= ensure(e, e->r_birthC, (size_t)(R * P * e->CB) * 8);
-    rc |= ensure(e, e->r_xC, (size_t)(R * P * e->CB * S) * 8);
+    rc |= ensure(e, e->r_birthC, (size_t)(R * P * e->max_CB()) * 8);
+    rc |= ensure(e, e->r_xC, (size_t)(R * P * e->max_CB() * S) * 8);
     rc |= ensure(e, e->r_effMig, (size_t)(R * P * P) * 8);
     rc |= ensure(e, e->r_nocc, (size_t)(R * P) * 4);
     rc |= ensure(e, e->r_lhap, (size_t)(R * P * cap + 64) * 4);
     rc |= ensure(e, e->r_lcls, (size_t)(R * P * cap) * 4);
     rc |= ensure(e, e->r_lcnt, (size_t)(R * P * cap + 64) * 8);   // + one tile: vgx_quad.hip reads whole 64-entry tiles
-    const bool want32 = one_class(P, S, e->C, e->CB);   // shapes the four-replicates-per-wavefront kernel takes
+    const bool want32 = one_class(P, S, e->max_C(), e->max_CB());   // shapes the four-replicates-per-wavefront kernel takes
     if (want32) rc |= ensure(e, e->r_lcnt32, (size_t)(R * P * cap + 64) * 4 + (size_t)(R * P * cap) + 128);   // + the one-byte copy of vgx_quad_long_kernel
     const int64_t capT = cap / 64 + 1;
     rc |= ensure(e, e->r_ltsum, (size_t)(R * P * capT) * 16 + 64);   // tile sums, then the exact row kernel's cached running sums
@@ -348,6 +360,8 @@ static int init_device_state(vgx_engine *e, int64_t traj_points) {
                                       (const int32_t *)e->s_cls.p, (const int64_t *)e->s_cnt.p, s_cap,
                                       (const int64_t *)e->s_sus.p, (const double *)e->s_cd.p,
                                       (const int64_t *)e->s_tot.p, e->stream));
+    if (e->n_sets > 1)   // the list classes of every replicate from its own set (s_cls holds set 0's)
+        HIPCHECK(e, vgxi_launch_init_reps_sets(&d, (int)P, R, (const VgxDevParams *)e->ps_blocks.p, (const int32_t *)e->ps_setof.p, e->stream));
     HIPCHECK(e, hipStreamSynchronize(e->stream));  // host vectors above go out of scope
     e->dev_state_valid = true;
     e->counts32_valid = want32;   // (vgx_init_reps_kernel fills both)
@@ -459,6 +473,9 @@ struct __attribute__((visibility("hidden"))) DirectRun {
         for (int64_t pn = 0; pn < P; pn++)
             if (e->h_startLD[(size_t)pn] * (double)e->sizes[(size_t)pn] < (double)e->sizes[(size_t)pn] || h.lockdownON[(size_t)pn] != 0)
                 ld_possible = true;
+        for (int64_t g = 0; g < e->n_sets && e->n_sets > 1; g++)   // ... under any of the parameter sets
+            for (int64_t pn = 0; pn < P; pn++)
+                if (e->sets_startLD[(size_t)(g * P + pn)] * (double)e->sizes[(size_t)pn] < (double)e->sizes[(size_t)pn]) ld_possible = true;
         e->loc_cap = ld_possible ? VGX_LOC_CAP : 1;
         e->fa_cap = (ld_possible && may_restart && o.record_events) ? VGX_FA_CAP : 0;
         int rc = 0;
@@ -512,7 +529,8 @@ struct __attribute__((visibility("hidden"))) DirectRun {
     void fill_shape() {
         vgx_direct_shape &s = shape;
         s.P = P; s.H = e->d.hapNum; s.S = e->d.susNum; s.sites = e->d.sites; s.R = R;
-        s.C = e->C; s.CB = e->CB; s.cap = e->cap;
+        s.C = e->max_C(); s.CB = e->max_CB(); s.cap = e->cap;
+        s.param_sets = e->n_sets;
         s.n_seg = (int64_t)e->h_seg_par.size(); s.n_solo_seg = (int64_t)e->h_so_sn.size();
         s.solo_npass0 = e->h_so_npass0; s.solo_npass1 = e->h_so_npass1;
         s.solo_ncls = e->h_so_ncls; s.solo_maxnnz = e->h_so_maxnnz;
@@ -655,7 +673,12 @@ struct __attribute__((visibility("hidden"))) DirectRun {
             HIPCHECK(e, vgxi_launch_quad_prep(&a.p, cd0, qeff, qmebm, qflag, e->stream));
             HIPCHECK(e, vgxi_launch_quadg(&a, &qga, e->stream));
             break;
-        default: HIPCHECK(e, vgxi_launch_direct(&a, lds, e->stream)); break;
+        default:
+            if (e->n_sets > 1)
+                HIPCHECK(e, vgxi_launch_direct_sets(&a, (const VgxDevParams *)e->ps_blocks.p, (const int32_t *)e->ps_setof.p, lds, e->stream));
+            else
+                HIPCHECK(e, vgxi_launch_direct(&a, lds, e->stream));
+            break;
         }
         e->counts32_valid = plan.kernel == VGX_K_QUAD || plan.kernel == VGX_K_QUADF;
         if (on_counts32()) e->counts64_valid = false;

@@ -28,6 +28,7 @@
 
 // launchers defined next to their kernels (vgx_direct.hip)
 extern "C" hipError_t vgxi_launch_direct(const VgxDirectArgs *a, size_t lds, hipStream_t stream);
+extern "C" hipError_t vgxi_launch_direct_sets(const VgxDirectArgs *a, const VgxDevParams *psets, const int32_t *set_of, size_t lds, hipStream_t stream);
 extern "C" int vgxi_tau_inc_shards(int64_t H, int64_t P);
 extern "C" int64_t vgxi_tau_queue_shards(int64_t H, int64_t P);
 extern "C" int64_t vgxi_tau_queue_shard_max(int64_t H);
@@ -55,6 +56,8 @@ extern "C" hipError_t vgxi_launch_init_reps(const VgxDevRep *r, int P, int S, in
                                             const int32_t *s_hap, const int32_t *s_cls, const int64_t *s_cnt,
                                             int64_t s_cap, const int64_t *s_sus, const double *s_cd,
                                             const int64_t *s_tot, hipStream_t stream);
+extern "C" hipError_t vgxi_launch_init_reps_sets(const VgxDevRep *r, int P, int64_t R, const VgxDevParams *psets, const int32_t *set_of,
+                                                 hipStream_t stream);
 
 #define TAU_DECL(name) extern "C" hipError_t vgxi_##name(const VgxTauArgs *a, hipStream_t s);
 TAU_DECL(tau_eff) TAU_DECL(tau_scatter) TAU_DECL(tau_prep) TAU_DECL(tau_drift) TAU_DECL(tau_choose) TAU_DECL(tau_draw)
@@ -111,6 +114,15 @@ struct vgx_engine {
     DevBuf p_cls, p_suscType, p_mRate, p_hapMutType, p_bRate, p_susc, p_cd, p_cs, p_ctm, p_cbidx, p_cstype, p_cbb, p_cbsig,
         p_sizes, p_cdBefore, p_cdAfter, p_startLD, p_endLD, p_sampMult, p_actualSizes, p_mig, p_suscTrans,
         p_suscCumul, p_sitesPos;
+    // scenario ensembles (vgx_set_param_sets): n_sets parameter sets, replicate r runs under set set_of[r].  1: none installed
+    // (vgx_set_params).  Everything above is set 0's then; the wavefront kernel reads block set_of[r] of ps_blocks instead.
+    int64_t n_sets = 1;
+    int sets_C = 0, sets_CB = 0;         // largest C and CB over the sets
+    std::vector<double> sets_startLD;    // [n_sets][P]
+    std::vector<VgxDevParams> h_psets;   // [n_sets] the blocks as uploaded: pointers into ps_blob
+    DevBuf ps_blob, ps_blocks, ps_setof;
+    int max_C() const { return n_sets > 1 ? sets_C : C; }
+    int max_CB() const { return n_sets > 1 ? sets_CB : CB; }
     double recombination = 0.0;          // pyx:93, 1422-1426
     int64_t genome_length = 1000000, rec_cap = 0;
     DevBuf r_rec;

@@ -73,6 +73,7 @@ static int64_t count_occupied(const vgx_engine *e) {
 extern "C" int vgx_stage_tau(vgx_engine *e) {
     if (!e) return VGX_ERR_ARG;
     if (!e->have_params || !e->have_state) return fail(e, VGX_ERR_ARG, "vgx_stage_tau: set params and state first");
+    if (e->n_sets > 1) return fail(e, VGX_ERR_ARG, "vgx_stage_tau: several parameter sets are installed (vgx_set_param_sets): tau-leaping runs one set only");
     HIPCHECK(e, hipSetDevice(e->device));
     const int64_t H = e->d.hapNum, P = e->d.popNum, S = e->d.susNum, R = e->R;
     for (int64_t pn = 0; pn < P; pn++)
@@ -1084,6 +1085,7 @@ extern "C" int vgx_simulate_tau(vgx_engine *e, int64_t iterations, int64_t sampl
     if (!e) return VGX_ERR_ARG;
     e->traj_points = 0;    // (until this call has written its own: vgx_get_trajectories never returns the bins of an earlier call)
     if (!e->have_params || !e->have_state) return fail(e, VGX_ERR_ARG, "vgx_simulate_tau: set params and state first");
+    if (e->n_sets > 1) return fail(e, VGX_ERR_ARG, "vgx_simulate_tau: several parameter sets are installed (vgx_set_param_sets): tau-leaping runs one set only");
     HIPCHECK(e, hipSetDevice(e->device));
     TauRun run{e, e->hs, e->d.hapNum, e->d.popNum, e->d.susNum, e->R, iterations, sample_size, attempts, time, !(time == -1.0f), e->hs.ev_ptr, e->hs.ev_size};
     run.o.record_events = 1;

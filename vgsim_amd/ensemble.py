@@ -28,14 +28,57 @@ class EnsembleResult:
         return int(self.events.sum())
 
 
+def _check_scenarios(base, scenarios, scenario_of, R):
+    """The checks of a scenario ensemble, before any engine exists: (models, scenario_of as an int32 array).  Everything a scenario
+    does not own — dimensions, population sizes (the start state is shared), recombination settings — must equal the base's."""
+    models = [getattr(s, "simulation", s) for s in scenarios]
+    if not models:
+        raise ValueError("scenarios must hold at least one model")
+    G = len(models)
+    for g, m in enumerate([base] + models):
+        who = "the base simulator" if g == 0 else "scenario %d" % (g - 1)
+        if m._memory_optimization:
+            raise ValueError("%s: scenario ensembles do not take memory_optimization=True" % who)
+        if g == 0:
+            continue
+        if (m.sites, m.popNum, m.susNum) != (base.sites, base.popNum, base.susNum):
+            raise ValueError("%s: its dimensions (sites, populations, susceptibility groups) = %r differ from the base simulator's %r"
+                             % (who, (m.sites, m.popNum, m.susNum), (base.sites, base.popNum, base.susNum)))
+        if not np.array_equal(m.sizes, base.sizes):
+            raise ValueError("%s: its population sizes differ from the base simulator's (every scenario runs from the one start state)" % who)
+        if m.recombination != base.recombination or m.genome_length != base.genome_length or \
+                not np.array_equal(m.sitesPosition, base.sitesPosition):
+            raise ValueError("%s: its recombination probability, genome length or site positions differ from the base simulator's "
+                             "(recombination settings are shared by all scenarios)" % who)
+        m._check_supported()
+    of = np.arange(R, dtype=np.int64) % G if scenario_of is None else np.asarray(scenario_of)
+    if of.shape != (R,):
+        raise ValueError("scenario_of must hold one scenario index per replicate: got shape %r for %d replicates" % (of.shape, R))
+    if not np.issubdtype(of.dtype, np.integer) or (R and (of.min() < 0 or of.max() >= G)):
+        raise ValueError("scenario_of must hold integers in [0, %d)" % G)
+    return models, np.ascontiguousarray(of, dtype=np.int32)
+
+
 class Ensemble:
-    def __init__(self, simulator, n_replicates, seeds=None, device=0):
+    def __init__(self, simulator, n_replicates, seeds=None, device=0, scenarios=None, scenario_of=None):
         """``simulator``: a configured ``vgsim_amd.Simulator`` (or its ``.simulation`` model) giving parameters
-        and the common start state; ``seeds``: one user seed per replicate (default seed, seed+1, ...)."""
+        and the common start state; ``seeds``: one user seed per replicate (default seed, seed+1, ...).
+
+        ``scenarios``: a sequence of configured ``Simulator`` s (or models), the COMPLETE list of parameter sets of a scenario
+        ensemble; ``simulator`` then gives the start state, the dimensions and the recombination settings only.  Replicate r runs
+        under ``scenarios[scenario_of[r]]`` (default ``arange(R) % len(scenarios)``) and is, bit for bit, the run of a single
+        ``Simulator`` with that scenario's parameters, this start state and seed ``seeds[r]``; one launch runs all of them.
+        Limits: the exact direct path on the one-replicate-per-wavefront kernel (``mode='exact'``, ``kernel`` 'auto' or 'wave');
+        no ``simulate_tau``; population sizes and recombination settings equal in all scenarios."""
         self.model = getattr(simulator, "simulation", simulator)
         m = self.model
-        m._check_supported()
         self.R = int(n_replicates)
+        self.scenarios, self.scenario_of = None, None
+        if scenarios is not None:
+            self.scenarios, self.scenario_of = _check_scenarios(m, scenarios, scenario_of, self.R)
+        elif scenario_of is not None:
+            raise ValueError("scenario_of needs scenarios")
+        m._check_supported()
         self.engine = _capi.HipEngine(m.sites, m.hapNum, m.popNum, m.susNum, n_replicates=self.R, device=device)
         self.seeds = np.arange(m.user_seed, m.user_seed + self.R, dtype=np.int64) if seeds is None \
             else np.ascontiguousarray(seeds, dtype=np.int64)
@@ -54,6 +97,11 @@ class Ensemble:
         (order-free sums).  Returns an :class:`EnsembleResult`."""
         if mode not in ('exact', 'fast', 'fast_philox'):
             raise ValueError("mode must be 'exact', 'fast' or 'fast_philox'")
+        if self.scenarios is not None:
+            if mode != 'exact':
+                raise ValueError("a scenario ensemble runs in mode='exact' only")
+            if kernel not in ('auto', 'wave'):
+                raise ValueError("a scenario ensemble runs on the one-replicate-per-wavefront kernel only: kernel must be 'auto' or 'wave'")
         m, eng = self.model, self.engine
         if seeds is not None:
             self.seeds = np.ascontiguousarray(seeds, dtype=np.int64)
@@ -64,7 +112,10 @@ class Ensemble:
         # Events.CreateEvents bookkeeping on a scratch copy of the counters (the host model keeps its own log)
         ptr, size = m.events.ptr, m.events.size
         size = size + iterations if ptr == 0 else max(size, ptr + iterations)
-        eng.set_params(m)
+        if self.scenarios is not None:
+            eng.set_param_sets(self.scenarios, self.scenario_of)
+        else:
+            eng.set_params(m)
         saved = (m.events.ptr, m.events.size)
         m.events.size = size
         try:
@@ -97,6 +148,8 @@ class Ensemble:
         ``events_drawn`` the sum of the drawn channel multiplicities.  ``traj_points`` / ``traj_window``: summary
         trajectories as ``simulate`` bins them (a grid point gets the totals before the step that takes the time past it),
         with or without the event log; read with ``trajectories()`` / ``gather_trajectories()``."""
+        if self.scenarios is not None:
+            raise ValueError("a scenario ensemble has no simulate_tau: tau-leaping runs one parameter set only")
         m, eng = self.model, self.engine
         if seeds is not None:
             self.seeds = np.ascontiguousarray(seeds, dtype=np.int64)
@@ -141,9 +194,10 @@ class Ensemble:
         return res
 
     def replicate_state(self, replicate):
-        """A host model object holding the state (compartments, counters, times) of one replicate."""
+        """A host model object holding the state (compartments, counters, times) of one replicate; in a scenario ensemble a
+        copy of the replicate's own scenario's model."""
         import copy
-        m = copy.copy(self.model)
+        m = copy.copy(self.model if self.scenarios is None else self.scenarios[int(self.scenario_of[replicate])])
         for name in ("susceptible", "infectious", "initial_susceptible", "initial_infectious", "totalSusceptible",
                      "totalInfectious", "lockdownON", "contactDensity"):
             setattr(m, name, getattr(self.model, name).copy())
