@@ -31,6 +31,8 @@
  *   VGX_TIMELINES_LDS_BYTES=n      vgx_get_timelines, vgx_get_tau_timelines: LDS budget of a replay workgroup (default 65536, at most 163840; the
  *                                  queries are split over launches)
  *   VGX_TIMELINES_CHUNK_BYTES=n    vgx_get_timelines, vgx_get_tau_timelines: device bytes of staging and outputs per chunk of replicates
+ *   VGX_COLSUMMARY_CHUNK_BYTES=n   vgx_get_trajectory_summary, vgx_test_column_summary: device bytes of the transposed scratch per chunk of
+ *                                  columns (default 2^28; one tile of 64 columns at the least)
  */
 #ifndef VGX_H
 #define VGX_H
@@ -479,6 +481,40 @@ typedef struct vgx_tau_timelines_chain {
     const int64_t *mev_num, *mev_types, *mev_haplotypes, *mev_populations, *mev_newHaplotypes, *mev_newPopulations;
 } vgx_tau_timelines_chain;
 int vgx_test_tau_timelines(vgx_tau_timelines_chain *io, char *errbuf, int64_t errcap);
+
+/* ---- summaries across replicates ------------------------------------------------------------ */
+/* What a user reads off an ensemble's trajectories: for every group of replicates (a scenario, or all of them) and every column
+ * n = (point, population, compartment) of the [R][N] block vgx_get_trajectories gives (N = traj_points * popNum * 2), from the m
+ * values the group's members hold there: count, min, max, the exact sum, the exact sum of squares (below 2^76: two 64-bit words,
+ * low then high) and the order statistics at K ranks per group: element ranks[g][k] in [0, m_g) of the values sorted ascending,
+ * ties included.  The block stays on the device and is only read: a transpose kernel narrows a chunk of columns to 32-bit keys
+ * with every group's members contiguous, then every (column, group) segment is sorted by a wavefront (groups of up to 64) or by
+ * a workgroup in LDS (larger ones).  All of it is integer arithmetic: no result depends on launch geometry or summation order.
+ * group_of[r] in [-1, G): the group of replicate r, -1 leaves it out.  An empty group is no error: count 0, every output 0 (its
+ * ranks are not read).  Refusals (VGX_ERR_ARG): the last call recorded no trajectories; a population size of 2^31 or more; a
+ * label or rank out of range; a group of more than VGX_COLSUMMARY_MAX_GROUP members (the message names the group, its size and
+ * the limit: such a group is not split across passes).  When the call returns an error the output arrays, passes and ms are
+ * undefined (count may already be written).  Device memory, freed before the call returns: the outputs below in
+ * their device form (G N (32 + 4 K) bytes) and the transposed scratch, 4 bytes per (member, column of a chunk), at most
+ * VGX_COLSUMMARY_CHUNK_BYTES (default 2^28) or 64 columns, whichever is more. */
+#define VGX_COLSUMMARY_MAX_GROUP 16384       /* u32 keys a workgroup sorts in LDS: 64 KiB of the 160 KiB it may declare */
+typedef struct vgx_traj_summary_io {
+    int64_t G;                               /* groups */
+    const int64_t *group_of;                 /* [R] */
+    int64_t K;                               /* ranks per group (0: none) */
+    const int64_t *ranks;                    /* [G][K] */
+    int64_t *count;                          /* [G] out: members */
+    int64_t *sum;                            /* [G][N] out */
+    uint64_t *sumsq;                         /* [G][N][2] out: low, high word */
+    int64_t *min, *max;                      /* [G][N] out */
+    int64_t *stat;                           /* [G][K][N] out (may be NULL when K == 0) */
+    int64_t passes;                          /* out: chunks of columns */
+    double ms[3];                            /* out: kernels (device time), uploads, read-out and widening of the results, whole call */
+} vgx_traj_summary_io;
+int vgx_get_trajectory_summary(vgx_engine *e, vgx_traj_summary_io *io);
+/* Test hook: the same kernels on a host matrix x[R][N] (uploaded; no engine).  Every entry must be a whole number in [0, 2^31):
+ * checked on the host, VGX_ERR_ARG otherwise.  The message of a refusal is written to errbuf. */
+int vgx_test_column_summary(const double *x, int64_t R, int64_t N, vgx_traj_summary_io *io, char *errbuf, int64_t errcap);
 
 /* ---- kernel choice of the direct path ------------------------------------------------------- */
 /* What the choice of a direct call's kernel reads: the model's dimensions, the state the call starts from and two diagnostic

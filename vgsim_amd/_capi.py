@@ -125,6 +125,13 @@ class VgxTauTimelinesChain(C.Structure):
                 ("mev_populations", _I), ("mev_newHaplotypes", _I), ("mev_newPopulations", _I)]
 
 
+class VgxTrajSummaryIO(C.Structure):
+    _fields_ = [("G", C.c_int64), ("group_of", _I), ("K", C.c_int64), ("ranks", _I), ("count", _I), ("sum", _I),
+                ("sumsq", C.POINTER(C.c_uint64)), ("min", _I), ("max", _I), ("stat", _I), ("passes", C.c_int64), ("ms", C.c_double * 3)]
+
+
+COLSUMMARY_MAX_GROUP = 16384   # members of one group the device pass sorts (vgx.h: VGX_COLSUMMARY_MAX_GROUP)
+
 TIMELINE_SEMANTICS = {'reference': 0, 'compartment': 1}
 
 
@@ -175,6 +182,8 @@ SIGNATURES = {
     "vgx_get_tau_states_all": (C.c_int, [_H, _I, _I, _I, _F]),
     "vgx_get_trajectories": (C.c_int, [_H, C.c_void_p, C.c_int]),
     "vgx_get_trajectories_int": (C.c_int, [_H, C.c_void_p]),
+    "vgx_get_trajectory_summary": (C.c_int, [_H, C.POINTER(VgxTrajSummaryIO)]),
+    "vgx_test_column_summary": (C.c_int, [_F, C.c_int64, C.c_int64, C.POINTER(VgxTrajSummaryIO), C.c_char_p, C.c_int64]),
     "vgx_clock_mismatches": (C.c_int64, [_H]),
     "vgx_last_kernel_ms": (C.c_double, [_H]),
     "vgx_last_kernel_launches": (C.c_int64, [_H]),
@@ -740,6 +749,35 @@ def replay_tau_timelines(m, infectious=(), susceptible=(), step_num=100, semanti
     if load_library().vgx_test_tau_timelines(C.byref(tio), err, 512) != 0:
         raise ValueError(err.value.decode() or "vgx_test_tau_timelines failed")
     return finish(tio.chain)
+
+
+def column_summary(x, group_of, G, ranks):
+    """The kernels of ``vgx_get_trajectory_summary`` on a host matrix ``x`` [R, N] of whole numbers in [0, 2^31) through
+    ``vgx_test_column_summary``: ``group_of`` [R] in [-1, G), ``ranks`` [G, K].  Returns a dict: ``count`` [G], ``sum``, ``min``,
+    ``max`` [G, N] int64, ``sumsq`` [G, N, 2] uint64 (low, high word), ``stat`` [G, K, N] int64, ``passes``, ``ms``.  A refusal
+    raises ``VgxError`` with the library's message."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    R, N = x.shape
+    group_of = np.ascontiguousarray(group_of, dtype=np.int64)
+    ranks = np.ascontiguousarray(ranks, dtype=np.int64).reshape(G, -1)
+    assert group_of.shape == (R,)
+    K = ranks.shape[1]
+    out = {k: np.zeros((G, N), dtype=np.int64) for k in ("sum", "min", "max")}
+    out["count"] = np.zeros(G, dtype=np.int64)
+    out["stat"] = np.zeros((G, max(K, 1), N), dtype=np.int64)
+    sumsq = np.zeros((G, N, 2), dtype=np.uint64)
+    io = VgxTrajSummaryIO()
+    io.G, io.group_of, io.K, io.ranks = G, _p(group_of), K, _p(ranks)
+    for k, a in out.items():
+        setattr(io, k, _p(a))
+    io.sumsq = sumsq.ctypes.data_as(C.POINTER(C.c_uint64))
+    err = C.create_string_buffer(512)
+    rc = load_library().vgx_test_column_summary(_p(x), R, N, C.byref(io), err, 512)
+    if rc != VGX_OK:
+        raise VgxError(rc, err.value.decode())
+    out["stat"] = out["stat"][:, :K]
+    out["sumsq"], out["passes"], out["ms"] = sumsq, int(io.passes), tuple(io.ms)
+    return out
 
 
 def direct_plan(shape, mode=0, kernel=0):

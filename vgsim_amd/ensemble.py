@@ -59,6 +59,111 @@ def _check_scenarios(base, scenarios, scenario_of, R):
     return models, np.ascontiguousarray(of, dtype=np.int32)
 
 
+SUMMARY_METHODS = ('linear', 'lower', 'higher')
+
+
+def _summary_position(q, m):
+    """Where quantile ``q`` lies among ``m`` sorted values, as a fractional index q (m - 1) in [0, m - 1].  Evaluated in numpy's
+    order for its default method (``m q + (1 - q) - 1``), so that the fractional part is numpy's to the last bit."""
+    q = np.asarray(q, dtype=np.float64)
+    return np.clip(m * q + (1.0 + q * -1.0) - 1.0, 0.0, float(m - 1))
+
+
+def _summary_ranks(q, m, method):
+    """The ranks (0-based indices into a group's ``m`` values sorted ascending) the device is asked for, per quantile ``q``:
+    'lower': floor(q (m - 1)); 'higher': its ceiling; 'linear': both neighbours of the fractional index, the Q lower ones, then
+    the Q upper ones (``min(lower + 1, m - 1)``).  int64; all zeros for an empty group."""
+    q = np.asarray(q, dtype=np.float64).ravel()
+    if method not in SUMMARY_METHODS:
+        raise ValueError("method must be 'linear', 'lower' or 'higher'")
+    if m <= 0:
+        return np.zeros(len(q) * (2 if method == 'linear' else 1), dtype=np.int64)
+    if method == 'linear':
+        lo = np.floor(_summary_position(q, m)).astype(np.int64)
+        return np.concatenate([lo, np.minimum(lo + 1, m - 1)])
+    pos = (m - 1) * q
+    return (np.floor(pos) if method == 'lower' else np.ceil(pos)).astype(np.int64)
+
+
+def _summary_lerp(lower, upper, q, m):
+    """The 'linear' quantile from the values at the two ranks ``_summary_ranks(q, m, 'linear')`` asks for (``q`` broadcasts
+    against them): with t the fractional part of the index q (m - 1), ``lower + (upper - lower) t``, taken from the upper end
+    (``upper - (upper - lower)(1 - t)``) when t >= 0.5 — numpy's rule."""
+    pos = _summary_position(q, m)
+    t = pos - np.floor(pos)
+    lower, upper = np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64)
+    d = upper - lower
+    return np.where(t >= 0.5, upper - d * (1.0 - t), lower + d * t)
+
+
+def _summary_groups(by, replicates, R, scenario_of, n_scenarios):
+    """(group_of [R] int64 with -1 for replicates left out, G) of a ``trajectory_summary`` call; ValueError for bad arguments."""
+    if isinstance(by, str):
+        if by != 'auto':
+            raise ValueError("by must be 'auto' or an integer array of one group label per replicate")
+        group_of = np.zeros(R, dtype=np.int64) if scenario_of is None else np.asarray(scenario_of, dtype=np.int64).copy()
+        G = 1 if scenario_of is None else int(n_scenarios)
+    else:
+        lab = np.asarray(by)
+        if lab.shape != (R,) or not np.issubdtype(lab.dtype, np.integer):
+            raise ValueError("by must hold one integer group label per replicate: got shape %r, dtype %s for %d replicates"
+                             % (lab.shape, lab.dtype, R))
+        if R and lab.min() < 0:
+            raise ValueError("group labels must not be negative")
+        if R and lab.max() >= R:   # (R replicates fill at most R groups: a stray large label would only size the outputs)
+            raise ValueError("group labels must be below the number of replicates (%d): got %d" % (R, lab.max()))
+        group_of = lab.astype(np.int64)
+        G = int(group_of.max()) + 1 if R else 1
+    if replicates is not None:
+        reps = np.asarray(replicates)
+        if reps.dtype == bool and reps.shape == (R,):
+            reps = np.nonzero(reps)[0]
+        reps = reps.astype(np.int64).ravel()
+        if len(reps) and (reps.min() < 0 or reps.max() >= R):
+            raise ValueError("replicate index out of range")
+        keep = np.zeros(R, dtype=bool)
+        keep[reps] = True
+        group_of[~keep] = -1
+    return np.ascontiguousarray(group_of), G
+
+
+class TrajectorySummary:
+    """What ``Ensemble.trajectory_summary`` returns: per group of replicates, across its members, for every time point,
+    population and compartment (0 = infectious, 1 = susceptible).
+
+    ``groups`` [G] the group labels (scenario indices for ``by='auto'`` on a scenario ensemble); ``count`` [G] members;
+    ``sum`` [G, T, P, 2] int64 and ``sumsq`` [G, T, P, 2] Python integers (object array, put together on first use from
+    ``sumsq_words`` [G, T, P, 2, 2] uint64: low, high), both exact; ``mean`` [G, T, P, 2]
+    = sum / count; ``min``, ``max`` [G, T, P, 2] int64; ``q`` the quantiles asked for and ``quantiles`` [G, Q, T, P, 2]
+    float64 (``method``); ``var(ddof=0)``.  An empty group has count 0, zero sum, min and max, and NaN mean, variance
+    and quantiles.  ``kernel_ms``, ``copy_ms``, ``wall_ms``: device time of the kernels, uploads and read-out, the whole library call;
+    ``passes``: chunks of columns."""
+
+    _sumsq = None
+
+    @property
+    def sumsq(self):
+        if self._sumsq is None:
+            w = self.sumsq_words
+            self._sumsq = w[..., 0].astype(object) + w[..., 1].astype(object) * (1 << 64)
+        return self._sumsq
+
+    @sumsq.setter
+    def sumsq(self, value):
+        self._sumsq = value
+
+    def var(self, ddof=0):
+        """Variance across the group's members from the exact integers, ``(n sumsq - sum^2) / (n (n - ddof))`` with the numerator formed
+        in integer arithmetic and one rounding in the division: population variance by default; NaN where n <= ddof."""
+        out = np.full(self.sum.shape, np.nan)
+        for g, n in enumerate(self.count):
+            n = int(n)
+            if n > ddof:
+                s = self.sum[g].astype(object)
+                out[g] = ((n * self.sumsq[g] - s * s) / (n * (n - ddof))).astype(np.float64)
+        return out
+
+
 class Ensemble:
     def __init__(self, simulator, n_replicates, seeds=None, device=0, scenarios=None, scenario_of=None):
         """``simulator``: a configured ``vgsim_amd.Simulator`` (or its ``.simulation`` model) giving parameters
@@ -575,6 +680,60 @@ class Ensemble:
         assert tuple(out.shape) == self.traj_shape and out.is_contiguous() and str(out.dtype) == "torch.float64"
         eng._check(eng.lib.vgx_get_trajectories(eng.handle, C.c_void_p(out.data_ptr()), 1 if out.is_cuda else 0))
         return out
+
+    def trajectory_summary(self, quantiles=(0.025, 0.5, 0.975), by='auto', replicates=None, method='linear'):
+        """Bands of the last call's trajectories across replicates, formed on the device (``vgx_get_trajectory_summary``; the
+        ``[R, T, P, 2]`` block is not copied to the host): count, mean, variance, min, max and quantiles per group, time point,
+        population and compartment.  Returns a :class:`TrajectorySummary`.
+
+        ``by``: 'auto' = one group per scenario of a scenario ensemble, else one group of all replicates; or an integer array
+        ``[R]`` of group labels in [0, R) (groups 0 .. max label; a label nobody carries is an empty group).  ``replicates``: indices
+        (or a boolean mask) of the replicates that take part; the others are left out of every group.  ``method``: 'lower' /
+        'higher' give the member value at rank floor / ceil of q (m - 1) among the group's m values (exact; numpy's methods of
+        the same names); 'linear' (numpy's default) asks the device for both neighbours and interpolates on the host: with
+        i = q (m - 1), t = i - floor(i): ``v[floor(i)] + (v[floor(i) + 1] - v[floor(i)]) t``.  A group of more than 16 384
+        members is refused by the library."""
+        if self.traj_shape is None:
+            raise ValueError("trajectory_summary() needs trajectories: the last simulate call recorded none (traj_points=0)")
+        if method not in SUMMARY_METHODS:
+            raise ValueError("method must be 'linear', 'lower' or 'higher'")
+        q = np.asarray(quantiles, dtype=np.float64).ravel()
+        if not np.all((q >= 0.0) & (q <= 1.0)):   # (NaN fails too)
+            raise ValueError("quantiles must lie in [0, 1]")
+        R, T, P, _ = self.traj_shape
+        group_of, G = _summary_groups(by, replicates, R, self.scenario_of, len(self.scenarios) if self.scenarios is not None else 1)
+        count = np.bincount(group_of[group_of >= 0], minlength=G)
+        ranks = np.ascontiguousarray(np.stack([_summary_ranks(q, int(m), method) for m in count]))
+        K, N = ranks.shape[1], T * P * 2
+        io = _capi.VgxTrajSummaryIO()
+        out = {k: np.zeros((G, N), dtype=np.int64) for k in ("sum", "min", "max")}
+        out["count"] = np.zeros(G, dtype=np.int64)
+        out["stat"] = np.zeros((G, max(K, 1), N), dtype=np.int64)
+        sumsq = np.zeros((G, N, 2), dtype=np.uint64)
+        io.G, io.group_of, io.K, io.ranks = G, _capi._p(group_of), K, _capi._p(ranks)
+        for k, a in out.items():
+            setattr(io, k, _capi._p(a))
+        io.sumsq = sumsq.ctypes.data_as(C.POINTER(C.c_uint64))
+        eng = self.engine
+        eng._check(eng.lib.vgx_get_trajectory_summary(eng.handle, C.byref(io)))
+        s = TrajectorySummary()
+        shape = (G, T, P, 2)
+        s.groups, s.count, s.q, s.method = np.arange(G), out["count"], q, method
+        s.sum, s.min, s.max = out["sum"].reshape(shape), out["min"].reshape(shape), out["max"].reshape(shape)
+        s.sumsq_words = sumsq.reshape(shape + (2,))
+        n = s.count.astype(np.float64).reshape(G, 1, 1, 1)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            s.mean = s.sum / n
+        Q = len(q)
+        stat = out["stat"][:, :K].reshape(G, K, T, P, 2)
+        if method == 'linear':
+            s.quantiles = np.stack([_summary_lerp(stat[g, :Q], stat[g, Q:], q.reshape(Q, 1, 1, 1), int(m)) if m else
+                                    np.full((Q, T, P, 2), np.nan) for g, m in enumerate(s.count)])
+        else:
+            s.quantiles = stat.astype(np.float64)
+            s.quantiles[s.count == 0] = np.nan
+        s.passes, s.kernel_ms, s.copy_ms, s.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
+        return s
 
     def gather_trajectories(self, dst=0, out=None, async_op=False, wire_dtype=None, device=None):
         """One collective for the whole ensemble: every rank's ``[R, T, P, 2]`` block to rank ``dst``
