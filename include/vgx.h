@@ -33,6 +33,7 @@
  *   VGX_TIMELINES_CHUNK_BYTES=n    vgx_get_timelines, vgx_get_tau_timelines: device bytes of staging and outputs per chunk of replicates
  *   VGX_COLSUMMARY_CHUNK_BYTES=n   vgx_get_trajectory_summary, vgx_test_column_summary: device bytes of the transposed scratch per chunk of
  *                                  columns (default 2^28; one tile of 64 columns at the least)
+ *   VGX_INCIDENCE_TILE_EVENTS=n    vgx_get_incidence: consecutive events a counting workgroup takes (default 4096; no result depends on it)
  */
 #ifndef VGX_H
 #define VGX_H
@@ -515,6 +516,52 @@ int vgx_get_trajectory_summary(vgx_engine *e, vgx_traj_summary_io *io);
 /* Test hook: the same kernels on a host matrix x[R][N] (uploaded; no engine).  Every entry must be a whole number in [0, 2^31):
  * checked on the host, VGX_ERR_ARG otherwise.  The message of a refusal is written to errbuf. */
 int vgx_test_column_summary(const double *x, int64_t R, int64_t N, vgx_traj_summary_io *io, char *errbuf, int64_t errcap);
+
+/* ---- incidence: event counts per time bin --------------------------------------------------- */
+/* What is compared with surveillance data: how many events of every kind happened per time bin and population, on ONE grid
+ * for all replicates.  The caller gives the bin edges edges[0 .. T] (strictly increasing, finite, T >= 1); bin b holds the
+ * events with edges[b] <= t < edges[b + 1] as the literal loop over the chain sees them: with the event times vgx_get_events
+ * gives, cut[k] = first event index i with edges[k] <= t_i (n_ev if none; the loop's position never goes back, whatever the
+ * times do), event i is in bin b when cut[b] <= i < cut[b + 1], and outside[r] = (cut[0], n_ev - cut[T]) counts the events
+ * before and after the window.  A log record (type, haplotype, population, newHaplotype, newPopulation) counts in channel
+ *   0 BIRTH, 1 DEATH, 2 SAMPLING, 3 MUTATION, 4 SUSCCHANGE            keyed by population
+ *   5 MIGRATION as an arrival (the new infection)                      keyed by newPopulation
+ *   6 MIGRATION as a departure (its source)                            keyed by population
+ * so a MIGRATION counts twice and new infections in p are channels 0 + 5.  A key outside [0, popNum) or a type outside 0..5
+ * counts nowhere.  hap_mask (bit h of word h / 32 = haplotype h, ceil(hapNum / 32) words) restricts the count to records whose
+ * judged haplotype is in the mask: `haplotype` for BIRTH, DEATH, SAMPLING and MIGRATION, `newHaplotype` (the variant that arises)
+ * for MUTATION; SUSCCHANGE carries none and is not counted under a mask.
+ * The device reads every selected replicate's log in place: a workgroup takes one replicate and a tile of consecutive events
+ * (VGX_INCIDENCE_TILE_EVENTS, default 4096), finds its first bin by a search in the replicate's cuts, counts into a histogram
+ * of popNum * 7 int32 in LDS and adds the nonzero cells to the block counts[n][T][popNum][7] in device memory at every bin
+ * change and at the tile's end.  All of it is integer work: no result depends on the tile size or the launch geometry.  The
+ * host clock runs as in vgx_get_timelines (12 bytes per event staged in pinned memory, in chunks of replicates:
+ * VGX_TIMELINES_CHUNK_BYTES); the log itself is never copied.  `summary`, when given, is the column summary of
+ * vgx_get_trajectory_summary over the block as a matrix [n][T * popNum * 7] where it lies (group_of has n entries, one per
+ * SELECTED replicate in the order of `replicates`); `counts` may then be NULL and the block is not copied to the host.
+ * Preconditions as vgx_get_timelines: the last call was direct and recorded events; every selected chain starts at log index 0.
+ * Refusals (VGX_ERR_ARG, worded alike behind "vgx_get_incidence: "): those; replicates out of range or given twice; edges
+ * that are not finite or do not increase; popNum * 28 bytes of counters above the 65536 bytes of LDS a counting workgroup may
+ * use; a block above half of the free device memory (the message gives the bytes: select fewer replicates); a chain of 2^30
+ * events or more.  vgx_clock_mismatches counts every selected replicate once. */
+#define VGX_INC_CHANNELS 7
+typedef struct vgx_incidence_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    int64_t T; const double *edges;              /* [T + 1] strictly increasing */
+    const uint32_t *hap_mask;                    /* NULL or ceil(hapNum / 32) words */
+    int32_t *counts;                             /* NULL or host [n][T][P][7] */
+    int64_t *outside;                            /* [n][2] events before / after the window */
+    vgx_traj_summary_io *summary;                /* NULL or the summary of the [n][T*P*7] block; group_of has n entries */
+    int64_t passes; double ms[3];                /* out: launches of the counting kernel; kernels, host clock, whole call */
+} vgx_incidence_io;
+int vgx_get_incidence(vgx_engine *e, vgx_incidence_io *io);
+/* Test hook: the rule and the tile walk of vgx_get_incidence compiled for the host, on one chain given as arrays (no device, no
+ * engine), tile after tile with `tile` events each (0: the default).  counts [T][P][7] and outside [2] are overwritten.  The
+ * same limits: P * 28 bytes above the LDS budget, a chain of 2^30 events and bad edges are refused with the message in errbuf. */
+int vgx_test_incidence(const double *times, const int64_t *types, const int64_t *haplotypes, const int64_t *populations,
+                       const int64_t *newHaplotypes, const int64_t *newPopulations, int64_t n_ev, int64_t P, int64_t hapNum,
+                       const double *edges, int64_t T, const uint32_t *hap_mask, int64_t tile, int32_t *counts, int64_t *outside,
+                       char *errbuf, int64_t errcap);
 
 /* ---- kernel choice of the direct path ------------------------------------------------------- */
 /* What the choice of a direct call's kernel reads: the model's dimensions, the state the call starts from and two diagnostic

@@ -130,6 +130,14 @@ class VgxTrajSummaryIO(C.Structure):
                 ("sumsq", C.POINTER(C.c_uint64)), ("min", _I), ("max", _I), ("stat", _I), ("passes", C.c_int64), ("ms", C.c_double * 3)]
 
 
+class VgxIncidenceIO(C.Structure):
+    _fields_ = [("n", C.c_int64), ("replicates", _I), ("T", C.c_int64), ("edges", _F), ("hap_mask", C.POINTER(C.c_uint32)),
+                ("counts", C.POINTER(C.c_int32)), ("outside", _I), ("summary", C.POINTER(VgxTrajSummaryIO)),
+                ("passes", C.c_int64), ("ms", C.c_double * 3)]
+
+
+INCIDENCE_CHANNELS = ('birth', 'death', 'sampling', 'mutation', 'immunity', 'arrival', 'departure')   # vgx.h: channels 0 .. 6
+
 COLSUMMARY_MAX_GROUP = 16384   # members of one group the device pass sorts (vgx.h: VGX_COLSUMMARY_MAX_GROUP)
 
 TIMELINE_SEMANTICS = {'reference': 0, 'compartment': 1}
@@ -203,6 +211,9 @@ SIGNATURES = {
     "vgx_test_timelines": (C.c_int, [C.POINTER(VgxTimelinesChain), C.c_char_p, C.c_int64]),
     "vgx_get_tau_timelines": (C.c_int, [_H, C.POINTER(VgxTimelinesIO), C.POINTER(VgxTimelinesPrefix)]),
     "vgx_test_tau_timelines": (C.c_int, [C.POINTER(VgxTauTimelinesChain), C.c_char_p, C.c_int64]),
+    "vgx_get_incidence": (C.c_int, [_H, C.POINTER(VgxIncidenceIO)]),
+    "vgx_test_incidence": (C.c_int, [_F, _I, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, _F, C.c_int64, C.POINTER(C.c_uint32), C.c_int64,
+                                     C.POINTER(C.c_int32), _I, C.c_char_p, C.c_int64]),
     "vgx_test_direct_plan": (C.c_int, [C.POINTER(VgxDirectShape), C.POINTER(VgxRunOpts), C.POINTER(VgxDirectPlan), C.c_char_p, C.c_int64]),
     "vgx_rng_position": (None, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64 * 4)]),
     "vgx_propensity_scan": (C.c_int, [C.POINTER(VgxRowScan)]),
@@ -749,6 +760,46 @@ def replay_tau_timelines(m, infectious=(), susceptible=(), step_num=100, semanti
     if load_library().vgx_test_tau_timelines(C.byref(tio), err, 512) != 0:
         raise ValueError(err.value.decode() or "vgx_test_tau_timelines failed")
     return finish(tio.chain)
+
+
+def haplotype_mask(haplotypes, hapNum):
+    """The bitmask ``vgx_get_incidence`` takes for a haplotype filter: bit h of word h // 32 for every index in ``haplotypes``
+    (uint32, ceil(hapNum / 32) words); ValueError for an index outside [0, hapNum)."""
+    idx = np.asarray(haplotypes).ravel()
+    if len(idx) and not np.issubdtype(idx.dtype, np.integer):
+        raise ValueError("haplotypes must be integer indices")
+    idx = idx.astype(np.int64)
+    if len(idx) and (idx.min() < 0 or idx.max() >= hapNum):
+        raise ValueError("haplotype index out of range")
+    mask = np.zeros((int(hapNum) + 31) // 32, dtype=np.uint32)
+    np.bitwise_or.at(mask, idx >> 5, (np.uint32(1) << (idx & 31).astype(np.uint32)).astype(np.uint32))
+    return mask
+
+
+def replay_incidence(times, types, haplotypes, populations, newHaplotypes, newPopulations, popNum, hapNum, edges, hap_mask=None, tile=0):
+    """The event counts of ``Ensemble.incidence`` for one chain given as arrays through ``vgx_test_incidence``: the device's rule
+    and tile walk (vgx_incidence.h) compiled for the host, tile after tile of ``tile`` events (0: the default); no GPU.
+    ``hap_mask``: None or the words of ``haplotype_mask``.  Returns (counts [T, P, 7] int32, outside [2] int64); a refusal raises
+    ``ValueError`` with the library's message."""
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.int64) for c in (types, haplotypes, populations, newHaplotypes, newPopulations)]
+    n = len(times)
+    if any(len(c) != n for c in cols):
+        raise ValueError("event columns of different lengths")
+    edges = np.ascontiguousarray(edges, dtype=np.float64)
+    T = len(edges) - 1
+    counts = np.zeros((max(T, 1), max(int(popNum), 1), len(INCIDENCE_CHANNELS)), dtype=np.int32)
+    outside = np.zeros(2, dtype=np.int64)
+    mask = None if hap_mask is None else np.ascontiguousarray(hap_mask, dtype=np.uint32)
+    if mask is not None and len(mask) != (int(hapNum) + 31) // 32:
+        raise ValueError("hap_mask must hold ceil(hapNum / 32) words")
+    err = C.create_string_buffer(512)
+    rc = load_library().vgx_test_incidence(_p(times), *[_p(c) for c in cols], n, int(popNum), int(hapNum), _p(edges), T,
+                                           None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint32)), int(tile),
+                                           counts.ctypes.data_as(C.POINTER(C.c_int32)), _p(outside), err, 512)
+    if rc != VGX_OK:
+        raise ValueError(err.value.decode() or "vgx_test_incidence failed")
+    return counts, outside
 
 
 def column_summary(x, group_of, G, ranks):

@@ -1594,3 +1594,186 @@ extern "C" int vgx_get_timelines(vgx_engine *e, vgx_timelines_io *io) {
     io->ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
     return VGX_OK;
 }
+
+// ---- event counts per time bin of many replicates on the device (vgx_incidence.hip, vgx_incidence.h) ----------
+// The split of vgx_get_timelines: the host runs every replicate's clock from the packed (iteration, rate) logs in pinned memory,
+// chunk of replicates by chunk, and turns the times into T + 1 event indices per replicate; the device counts over the log in
+// place into one block for all selected replicates, which the column summary then reads where it lies.
+extern "C" int vgx_get_incidence(vgx_engine *e, vgx_incidence_io *io) {
+    if (!e || !io || io->n < 0 || (io->n > 0 && (!io->replicates || !io->outside))) return VGX_ERR_ARG;
+    const auto t_call = std::chrono::steady_clock::now();
+    auto wall = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(); };
+    io->passes = 0;
+    io->ms[0] = io->ms[1] = io->ms[2] = 0.0;
+    if (e->last_was_tau) return fail(e, VGX_ERR_ARG, "vgx_get_incidence: the last call was vgx_simulate_tau (counts direct chains only)");
+    if (!e->sc_host_valid || !e->dev_state_valid) return fail(e, VGX_ERR_ARG, "vgx_get_incidence: needs a direct vgx_simulate_direct call with the event log first");
+    if (!e->call_recorded) return fail(e, VGX_ERR_ARG, "vgx_get_incidence: the last call did not record events");
+    const int64_t n = io->n, P = e->d.popNum, H = e->d.hapNum, T = io->T, cells = P * VGX_INC_CHANNELS;
+    if (T < 1 || T >= VGX_INC_MAX_BINS || !io->edges) return fail(e, VGX_ERR_ARG, "vgx_get_incidence: T = " + std::to_string(T) + " bins: at least 1, below 2^24, with edges");
+    for (int64_t k = 0; k <= T; k++) {
+        if (!std::isfinite(io->edges[k])) return fail(e, VGX_ERR_ARG, "vgx_get_incidence: edges[" + std::to_string(k) + "] is not finite");
+        if (k > 0 && !(io->edges[k - 1] < io->edges[k]))
+            return fail(e, VGX_ERR_ARG, "vgx_get_incidence: edges must increase strictly (edges[" + std::to_string(k) + "])");
+    }
+    if (vgx_inc_lds_bytes(P) > VGX_INC_LDS_MAX)
+        return fail(e, VGX_ERR_ARG, "vgx_get_incidence: " + std::to_string(P) + " populations need " + std::to_string(vgx_inc_lds_bytes(P)) +
+                                        " bytes of counters, above the " + std::to_string((int64_t)VGX_INC_LDS_MAX) + " bytes of LDS a counting workgroup may use");
+    std::vector<int32_t> n_ev((size_t)n);
+    {
+        std::vector<char> seen((size_t)e->R, 0);
+        for (int64_t i = 0; i < n; i++) {
+            const int64_t r = io->replicates[i];
+            if (r < 0 || r >= e->R) return fail(e, VGX_ERR_ARG, "vgx_get_incidence: replicate index out of range");
+            if (seen[(size_t)r]) return fail(e, VGX_ERR_ARG, "vgx_get_incidence: replicates must be distinct");
+            seen[(size_t)r] = 1;
+            const VgxRepScalars &s = e->sc_host[(size_t)r];
+            const int64_t first = s.restarts > 0 ? 0 : ((size_t)r < e->call_ev0.size() ? e->call_ev0[(size_t)r] : e->ev_ptr0);
+            if (first != 0 || e->ev_base != 0)
+                return fail(e, VGX_ERR_ARG, "vgx_get_incidence: replicate " + std::to_string(r) + ": its chain does not start in the last call's device log (the model held " +
+                                                std::to_string(e->ev_base != 0 ? e->ev_base : first) + " events when the ensemble started)");
+            if (s.ev_ptr >= VGX_INC_MAX_EVENTS)
+                return fail(e, VGX_ERR_ARG, "vgx_get_incidence: replicate " + std::to_string(r) + " holds a chain of " + std::to_string(s.ev_ptr) + " events (2^30 or more)");
+            if (s.ev_ptr < 0 || s.ev_ptr > e->evcap)
+                return fail(e, VGX_ERR_ARG, "vgx_get_incidence: event range of replicate " + std::to_string(r) + " outside the device log");
+            n_ev[(size_t)i] = (int32_t)s.ev_ptr;
+        }
+    }
+    if (n == 0) {
+        io->ms[2] = wall();
+        return VGX_OK;
+    }
+    int64_t tile = VGX_INC_TILE_DEFAULT;
+    if (const char *tb = getenv("VGX_INCIDENCE_TILE_EVENTS")) tile = std::min<int64_t>(std::max<int64_t>(atoll(tb), 1), VGX_INC_MAX_EVENTS);
+    HIPCHECK(e, hipSetDevice(e->device));
+    size_t free_b = 0, total_b = 0;
+    HIPCHECK(e, hipMemGetInfo(&free_b, &total_b));
+    auto up8 = [](int64_t b) { return (b + 255) / 256 * 256; };
+    auto dev_free = [](char *p) { (void)hipFree(p); };
+    // what stays for the whole call: [rep | n_ev | cut | mask | counts]
+    const int64_t mask_words = (H + 31) / 32;
+    const int64_t block_bytes = n * T * cells * 4;
+    const int64_t o_rep = 0, o_nev = o_rep + up8(n * 8), o_cut = o_nev + up8(n * 4), o_mask = o_cut + up8(n * (T + 1) * 4),
+                  o_cnt = o_mask + up8(mask_words * 4), keep_total = o_cnt + up8(block_bytes);
+    if (keep_total > (int64_t)(free_b / 2))
+        return fail(e, VGX_ERR_ARG, "vgx_get_incidence: the block of " + std::to_string(n) + " x " + std::to_string(T) + " x " + std::to_string(P) + " x 7 counts and its cuts take " +
+                                        std::to_string(keep_total) + " bytes, above half of the " + std::to_string((int64_t)free_b) +
+                                        " bytes of free device memory: select fewer replicates per call");
+    char *kws = nullptr;
+    hipError_t er = hipMalloc((void **)&kws, (size_t)keep_total);
+    if (er != hipSuccess) return fail(e, VGX_ERR_HIP, "vgx_get_incidence: hipMalloc of " + std::to_string(keep_total) + " bytes: " + hipGetErrorString(er));
+    std::unique_ptr<char, void (*)(char *)> khold(kws, dev_free);
+    std::vector<int64_t> reps_all(io->replicates, io->replicates + n);
+    HIPCHECK(e, hipMemcpyAsync(kws + o_rep, reps_all.data(), (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_nev, n_ev.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    if (io->hap_mask) HIPCHECK(e, hipMemcpyAsync(kws + o_mask, io->hap_mask, (size_t)mask_words * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemsetAsync(kws + o_cnt, 0, (size_t)block_bytes, e->stream));   // zeroed once
+
+    // chunks of replicates: the packed logs of a chunk fit `share` bytes of device memory (and 12 bytes per event of pinned host memory)
+    int64_t share = std::min<int64_t>((int64_t)(free_b / 2) - keep_total + 4096, (int64_t)1 << 30);
+    if (const char *cb = getenv("VGX_TIMELINES_CHUNK_BYTES")) share = std::min<int64_t>(share, std::max<int64_t>(atoll(cb), 1));
+    std::vector<int64_t> mism((size_t)n, 0);
+    std::vector<int32_t> cuts((size_t)(n * (T + 1)));
+    int64_t i0 = 0;
+    while (i0 < n) {
+        int64_t i1 = i0, sum = 0, E = 0, max_n = 0;
+        while (i1 < n && i1 - i0 < ((int64_t)1 << 20)) {
+            const int64_t b = (int64_t)n_ev[(size_t)i1] * 12 + 64;
+            if (i1 > i0 && sum + b > share) break;
+            sum += b;
+            E += n_ev[(size_t)i1];
+            max_n = std::max<int64_t>(max_n, n_ev[(size_t)i1]);
+            i1++;
+        }
+        const int64_t m = i1 - i0;
+        std::vector<int64_t> off((size_t)m);
+        for (int64_t j = 0, o = 0; j < m; j++) { off[(size_t)j] = o; o += n_ev[(size_t)(i0 + j)]; }
+        const int64_t o_off = 0, o_iter = o_off + up8(m * 8), o_rate = o_iter + up8(E * 4), total = o_rate + up8(E * 8);
+        char *ws = nullptr;
+        er = hipMalloc((void **)&ws, (size_t)total);
+        if (er != hipSuccess) return fail(e, VGX_ERR_HIP, "vgx_get_incidence: hipMalloc of " + std::to_string(total) + " bytes: " + hipGetErrorString(er));
+        std::unique_ptr<char, void (*)(char *)> hold(ws, dev_free);
+        const int64_t pin_rate = up8(E * 4), pin_need = pin_rate + up8(E * 8);
+        if ((int64_t)e->pin_tl_bytes < pin_need) {
+            if (e->pin_tl) (void)hipHostFree(e->pin_tl);
+            e->pin_tl = nullptr; e->pin_tl_bytes = 0;
+            HIPCHECK(e, hipHostMalloc(&e->pin_tl, (size_t)pin_need, hipHostMallocDefault));
+            e->pin_tl_bytes = (size_t)pin_need;
+        }
+        const int32_t *h_iter = (const int32_t *)e->pin_tl;
+        const double *h_rate = (const double *)((char *)e->pin_tl + pin_rate);
+        HIPCHECK(e, hipMemcpyAsync(ws + o_off, off.data(), (size_t)m * 8, hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
+        HIPCHECK(e, vgxi_tl_pack((const int32_t *)e->r_evcols.p, (const double *)e->r_evrate.p, e->evcap, (const int64_t *)(kws + o_rep) + i0,
+                                 (const int32_t *)(kws + o_nev) + i0, (const int64_t *)(ws + o_off), m, max_n, (int32_t *)(ws + o_iter),
+                                 (double *)(ws + o_rate), e->stream));
+        HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
+        if (E > 0) {
+            HIPCHECK(e, hipMemcpyAsync(e->pin_tl, ws + o_iter, (size_t)E * 4, hipMemcpyDeviceToHost, e->stream));
+            HIPCHECK(e, hipMemcpyAsync((char *)e->pin_tl + pin_rate, ws + o_rate, (size_t)E * 8, hipMemcpyDeviceToHost, e->stream));
+        }
+        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)
+            return fail(e, VGX_ERR_HIP, std::string("vgx_get_incidence: pack kernel failed: ") + hipGetErrorString(er));
+        float kms = 0.f;
+        HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
+        io->ms[0] += kms;
+        // host: every replicate's clock -> its T + 1 cuts (one replicate per thread at a time)
+        const auto t_clock = std::chrono::steady_clock::now();
+        std::vector<std::string> errs((size_t)m);
+        std::vector<int> rcs((size_t)m, 0);
+        for_parts(m, [&](int64_t j0, int64_t j1, unsigned) {
+            if (hipSetDevice(e->device) != hipSuccess) { for (int64_t j = j0; j < j1; j++) { rcs[(size_t)j] = VGX_ERR_HIP; errs[(size_t)j] = "hipSetDevice"; } return; }
+            vgx_engine::HostClock hc;
+            for (int64_t j = j0; j < j1; j++) {
+                const int64_t gi = i0 + j, r = reps_all[(size_t)gi], ne = n_ev[(size_t)gi];
+                const ClockStaged st{h_rate + off[(size_t)j], h_iter + off[(size_t)j]};
+                int rc = clock_build(e, r, hc, errs[(size_t)j], &st);
+                if (rc) { rcs[(size_t)j] = rc; continue; }
+                if ((int64_t)hc.times.size() != ne) {
+                    rcs[(size_t)j] = VGX_ERR_ARG;
+                    errs[(size_t)j] = "vgx_get_incidence: the host clock of replicate " + std::to_string(r) + " does not cover its chain";
+                    continue;
+                }
+                mism[(size_t)gi] = hc.limit_mismatch ? 1 : 0;
+                int32_t *cut = cuts.data() + gi * (T + 1);
+                VgxIncCutter ct{io->edges, T, cut};
+                for (int64_t k = 0; k < ne; k++) ct.event(k, hc.times[(size_t)k]);
+                ct.finish(ne);
+                io->outside[2 * gi] = cut[0];
+                io->outside[2 * gi + 1] = ne - cut[(size_t)T];
+            }
+        }, std::max<int64_t>(E / std::max<int64_t>(m, 1), 1) * 64);
+        for (int64_t j = 0; j < m; j++)
+            if (rcs[(size_t)j]) return fail(e, rcs[(size_t)j], errs[(size_t)j]);
+        io->ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_clock).count();
+        // device: the count of the chunk's replicates into their rows of the block
+        HIPCHECK(e, hipMemcpyAsync(kws + o_cut + i0 * (T + 1) * 4, cuts.data() + i0 * (T + 1), (size_t)(m * (T + 1)) * 4, hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
+        VgxIncLaunch a{};
+        a.m = m;
+        a.log = (const int32_t *)e->r_evcols.p; a.evcap = e->evcap;
+        a.rep = (const int64_t *)(kws + o_rep) + i0; a.n_ev = (const int32_t *)(kws + o_nev) + i0;
+        a.cut = (const int32_t *)(kws + o_cut) + i0 * (T + 1);
+        a.T = (int32_t)T; a.P = (int32_t)P; a.hapNum = (int32_t)H;
+        a.mask = io->hap_mask ? (const uint32_t *)(kws + o_mask) : nullptr;
+        a.tile = (int32_t)tile; a.max_n = max_n;
+        a.counts = (int32_t *)(kws + o_cnt) + i0 * T * cells;
+        HIPCHECK(e, vgxi_inc_count(&a, e->stream));
+        if (max_n > 0) io->passes += 1;
+        HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
+        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)
+            return fail(e, VGX_ERR_HIP, std::string("vgx_get_incidence: counting kernel failed: ") + hipGetErrorString(er));
+        HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
+        io->ms[0] += kms;
+        i0 = i1;
+    }
+    // every replicate's clock was built once, as when the replicates are fetched one by one
+    for (int64_t i = 0; i < n; i++) e->clock_mismatches += mism[(size_t)i];
+    if (io->summary) {
+        char msg[512] = "";
+        const int rc = vgxi_column_summary_i32("vgx_get_incidence: summary", (const int32_t *)(kws + o_cnt), n, T * cells, io->summary, e->stream, msg, sizeof msg);
+        if (rc) return fail(e, rc, msg);
+    }
+    if (io->counts) HIPCHECK(e, hipMemcpy(io->counts, kws + o_cnt, (size_t)block_bytes, hipMemcpyDeviceToHost));
+    io->ms[2] = wall();
+    return VGX_OK;
+}

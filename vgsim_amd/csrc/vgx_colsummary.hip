@@ -1,8 +1,9 @@
-// vgx_colsummary.hip — summaries down the columns of a row-major f64 matrix x[R][N] of whole numbers in [0, 2^31), per group of rows:
+// vgx_colsummary.hip — summaries down the columns of a row-major matrix x[R][N] (f64, or int32 for the event counts of
+// vgx_get_incidence) of whole numbers in [0, 2^31), per group of rows:
 // count, min, max, exact integer sum and sum of squares, and the order statistics at ranks the caller gives.
 // vgx_get_trajectory_summary runs it on the trajectories of the last call where the kernels left them (r_traj is only read),
 // vgx_test_column_summary on a matrix it uploads.  Three kernels, all integer work, so no result depends on launch geometry:
-//   colsum_transpose  x[perm[slot]][c0 + j] (f64, a column strided by 8 N bytes) -> y[j][slot] (u32), a 64 x 64 tile through LDS,
+//   colsum_transpose  x[perm[slot]][c0 + j] (f64 or int32, a column strided by N elements) -> y[j][slot] (u32), a 64 x 64 tile through LDS,
 //                     coalesced on both sides; `perm` lists the member rows group by group, so a (column, group) segment of y is
 //                     contiguous;
 //   colsum_wave       a segment of at most 64 keys per wavefront, four segments per workgroup: one key per lane, a bitonic network
@@ -73,7 +74,8 @@ __device__ __forceinline__ Acc wave_sum(Acc a) {
     return a;
 }
 
-__global__ __launch_bounds__(256) void colsum_transpose(const double *__restrict__ x, int64_t N, const int64_t *__restrict__ perm, int64_t M,
+template <typename X>
+__global__ __launch_bounds__(256) void colsum_transpose(const X *__restrict__ x, int64_t N, const int64_t *__restrict__ perm, int64_t M,
                                                         int64_t c0, int ncols, uint32_t *__restrict__ y) {
     __shared__ uint32_t tile[TILE][TILE + 1];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -202,7 +204,8 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
 
 // The summary of the matrix x[R][N] into the host arrays of `io`: x is a device matrix, or (x_on_host) a host matrix that is uploaded
 // once the arguments have passed.  `what` prefixes every message.
-int column_summary(const char *what, const double *x, bool x_on_host, int64_t R, int64_t N, vgx_traj_summary_io *io, hipStream_t stream,
+template <typename X>
+int column_summary(const char *what, const X *x, bool x_on_host, int64_t R, int64_t N, vgx_traj_summary_io *io, hipStream_t stream,
                    std::string &err) {
     const auto wall0 = std::chrono::steady_clock::now();
     const int64_t G = io->G, K = io->K;
@@ -270,11 +273,11 @@ int column_summary(const char *what, const double *x, bool x_on_host, int64_t R,
     int32_t *d_small = nullptr, *d_big = nullptr, *d_ranks = nullptr;
     uint32_t *d_y = nullptr;
     ColsumOut out{};
-    const double *d_x = x;
+    const X *d_x = x;
     if (x_on_host) {
-        double *up = nullptr;
+        X *up = nullptr;
         CS_HIP(dm.get(&up, (size_t)(R * N)));
-        if (R) CS_HIP(hipMemcpyAsync(up, x, (size_t)(R * N) * 8, hipMemcpyHostToDevice, stream));
+        if (R) CS_HIP(hipMemcpyAsync(up, x, (size_t)(R * N) * sizeof(X), hipMemcpyHostToDevice, stream));
         d_x = up;
     }
     CS_HIP(dm.get(&d_perm, perm.size()));
@@ -317,7 +320,7 @@ int column_summary(const char *what, const double *x, bool x_on_host, int64_t R,
     io->passes = 0;
     for (int64_t c0 = 0; c0 < N && M > 0 && rc == hipSuccess; c0 += chunk, io->passes++) {
         const int ncols = (int)std::min<int64_t>(chunk, N - c0);
-        hipLaunchKernelGGL(colsum_transpose, dim3((unsigned)((M + TILE - 1) / TILE), (unsigned)((ncols + TILE - 1) / TILE)), dim3(256), 0, stream,
+        hipLaunchKernelGGL(colsum_transpose<X>, dim3((unsigned)((M + TILE - 1) / TILE), (unsigned)((ncols + TILE - 1) / TILE)), dim3(256), 0, stream,
                            d_x, N, d_perm, M, c0, ncols, d_y);
         if (!small.empty()) {
             const int64_t nseg = (int64_t)small.size() * ncols;
@@ -359,6 +362,16 @@ int column_summary(const char *what, const double *x, bool x_on_host, int64_t R,
 }  // namespace
 
 #pragma GCC visibility pop
+
+// the same kernels on a device int32 matrix (vgx_get_incidence: the block of event counts where the counting kernel left it)
+extern "C" __attribute__((visibility("hidden"))) int vgxi_column_summary_i32(const char *what, const int32_t *x, int64_t R, int64_t N,
+                                                                             vgx_traj_summary_io *io, hipStream_t stream, char *errbuf,
+                                                                             int64_t errcap) {
+    std::string err;
+    const int rc = io ? column_summary<int32_t>(what, x, false, R, N, io, stream, err) : VGX_ERR_ARG;
+    if (rc && errbuf && errcap > 0) snprintf(errbuf, (size_t)errcap, "%s", err.c_str());
+    return rc;
+}
 
 extern "C" int vgx_get_trajectory_summary(vgx_engine *e, vgx_traj_summary_io *io) {
     if (!e || !io) return VGX_ERR_ARG;

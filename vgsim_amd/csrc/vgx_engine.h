@@ -23,6 +23,7 @@
 #include "vgx_gwalk.h"
 #include "vgx_tline.h"
 #include "vgx_timelines.h"
+#include "vgx_incidence.h"
 
 #pragma GCC visibility push(hidden)   // nothing here is part of the exported C ABI
 
@@ -51,6 +52,10 @@ extern "C" hipError_t vgxi_gw_walk(const VgxGwLaunch *a, int wave, hipStream_t s
 extern "C" hipError_t vgxi_tl_pack(const int32_t *log, const double *evrate, int64_t evcap, const int64_t *rep, const int32_t *n_ev,
                                    const int64_t *off, int64_t m, int64_t max_n, int32_t *iter_out, double *rate_out, hipStream_t s);
 extern "C" hipError_t vgxi_tl_replay(const VgxTlLaunch *a, hipStream_t s);
+extern "C" hipError_t vgxi_inc_count(const VgxIncLaunch *a, hipStream_t s);
+// the column summary of vgx_colsummary.hip on a device int32 matrix x[R][N] of values in [0, 2^31) (a refusal's message goes to errbuf)
+extern "C" int vgxi_column_summary_i32(const char *what, const int32_t *x, int64_t R, int64_t N, vgx_traj_summary_io *io, hipStream_t stream,
+                                       char *errbuf, int64_t errcap);
 extern "C" hipError_t vgxi_launch_counts32(const int64_t *c64, int32_t *c32, int64_t n, hipStream_t stream);
 extern "C" hipError_t vgxi_launch_init_reps(const VgxDevRep *r, int P, int S, int64_t R, const int32_t *s_nocc,
                                             const int32_t *s_hap, const int32_t *s_cls, const int64_t *s_cnt,

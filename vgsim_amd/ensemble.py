@@ -164,6 +164,97 @@ class TrajectorySummary:
         return out
 
 
+def _summary_request(group_of, G, q, method, cols):
+    """A ``VgxTrajSummaryIO`` with its outputs allocated for the column summary of a matrix whose columns have the shape ``cols``
+    (rows labelled by ``group_of`` in [-1, G)): (io, finish), where ``finish()`` builds the :class:`TrajectorySummary` once the
+    library has filled the outputs."""
+    count = np.bincount(group_of[group_of >= 0], minlength=G)
+    ranks = np.ascontiguousarray(np.stack([_summary_ranks(q, int(m), method) for m in count]))
+    K, N = ranks.shape[1], int(np.prod(cols))
+    io = _capi.VgxTrajSummaryIO()
+    out = {k: np.zeros((G, N), dtype=np.int64) for k in ("sum", "min", "max")}
+    out["count"] = np.zeros(G, dtype=np.int64)
+    out["stat"] = np.zeros((G, max(K, 1), N), dtype=np.int64)
+    sumsq = np.zeros((G, N, 2), dtype=np.uint64)
+    io.G, io.group_of, io.K, io.ranks = G, _capi._p(group_of), K, _capi._p(ranks)
+    for k, a in out.items():
+        setattr(io, k, _capi._p(a))
+    io.sumsq = sumsq.ctypes.data_as(C.POINTER(C.c_uint64))
+    cols = tuple(int(c) for c in cols)
+
+    def finish(_alive=(group_of, ranks)):   # (the input arrays live as long as this closure)
+        s = TrajectorySummary()
+        shape = (G,) + cols
+        s.groups, s.count, s.q, s.method = np.arange(G), out["count"], q, method
+        s.sum, s.min, s.max = out["sum"].reshape(shape), out["min"].reshape(shape), out["max"].reshape(shape)
+        s.sumsq_words = sumsq.reshape(shape + (2,))
+        n = s.count.astype(np.float64).reshape((G,) + (1,) * len(cols))
+        with np.errstate(invalid='ignore', divide='ignore'):
+            s.mean = s.sum / n
+        Q = len(q)
+        stat = out["stat"][:, :K].reshape((G, K) + cols)
+        if method == 'linear':
+            s.quantiles = np.stack([_summary_lerp(stat[g, :Q], stat[g, Q:], q.reshape((Q,) + (1,) * len(cols)), int(m)) if m else
+                                    np.full((Q,) + cols, np.nan) for g, m in enumerate(s.count)])
+        else:
+            s.quantiles = stat.astype(np.float64)
+            s.quantiles[s.count == 0] = np.nan
+        s.passes, s.kernel_ms, s.copy_ms, s.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
+        return s
+    return io, finish
+
+
+def _summary_quantiles(quantiles, method):
+    """The checks on ``quantiles`` and ``method`` every summary shares: the quantiles as a flat float64 array."""
+    if method not in SUMMARY_METHODS:
+        raise ValueError("method must be 'linear', 'lower' or 'higher'")
+    q = np.asarray(quantiles, dtype=np.float64).ravel()
+    if not np.all((q >= 0.0) & (q <= 1.0)):   # (NaN fails too)
+        raise ValueError("quantiles must lie in [0, 1]")
+    return q
+
+
+class Incidence:
+    """What ``Ensemble.incidence`` returns: event counts per selected replicate, time bin, population and channel.
+
+    ``counts`` [n, T, P, 7] int32 (None when the call had ``counts=False``), channel k as ``CHANNELS`` names it: births, deaths
+    (recoveries), samplings (recorded cases), mutations, immunity changes, migrations counted where they arrive (a new infection
+    there) and where they depart from; ``edges`` [T + 1] the bin edges (bin b holds edges[b] <= t < edges[b + 1]); ``outside``
+    [n, 2] the events of every replicate before ``edges[0]`` and from ``edges[T]`` on; ``replicates`` [n]; ``summary`` a
+    :class:`TrajectorySummary` over the [T, P, 7] columns, or None; ``passes``, ``kernel_ms``, ``clock_ms``, ``wall_ms``."""
+
+    CHANNELS = _capi.INCIDENCE_CHANNELS
+
+    def new_infections(self):
+        """Births plus arriving migrations, [n, T, P]."""
+        return self.counts[..., 0] + self.counts[..., 5]
+
+
+def _incidence_edges(edges, bins, window):
+    """The bin edges of an ``incidence`` call as a float64 array; ValueError for bad arguments."""
+    if (edges is None) == (bins is None):
+        raise ValueError("give either edges or bins (with window), not both and not neither")
+    if edges is None:
+        bins = int(bins)
+        if bins < 1:
+            raise ValueError("bins must be at least 1")
+        if window is None or len(window) != 2:
+            raise ValueError("bins needs window=(t0, t1)")
+        t0, t1 = float(window[0]), float(window[1])
+        with np.errstate(invalid='ignore', over='ignore'):   # (a window that is not finite is refused below)
+            e = t0 + (np.arange(bins + 1, dtype=np.float64) * (t1 - t0)) / bins
+        e[bins] = t1
+    else:
+        e = np.array(edges, dtype=np.float64).ravel()
+        if len(e) < 2:
+            raise ValueError("edges must hold at least two values")
+    if not np.all(np.isfinite(e)):
+        raise ValueError("edges must be finite")
+    if not np.all(e[1:] > e[:-1]):
+        raise ValueError("edges must increase strictly")
+    return np.ascontiguousarray(e)
+
+
 class Ensemble:
     def __init__(self, simulator, n_replicates, seeds=None, device=0, scenarios=None, scenario_of=None):
         """``simulator``: a configured ``vgsim_amd.Simulator`` (or its ``.simulation`` model) giving parameters
@@ -667,6 +758,68 @@ class Ensemble:
         b.passes, b.kernel_ms, b.clock_ms, b.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
         return b
 
+    def incidence(self, edges=None, bins=None, window=None, replicates=None, haplotypes=None, summary=None, counts=True):
+        """Event counts per time bin, population and channel of every selected replicate of the last direct
+        ``simulate(record_events=True)`` call, on ONE grid for all replicates and on the device (``vgx_get_incidence``): one
+        streaming pass over every replicate's log where the kernel left it.  Returns an :class:`Incidence`.
+
+        The grid: ``edges`` [T + 1] strictly increasing, or ``bins`` and ``window=(t0, t1)``, which form
+        ``edges[k] = t0 + (k (t1 - t0)) / bins`` with ``edges[bins] = t1``.  Bin b holds the events with
+        ``edges[b] <= t < edges[b + 1]``.  ``replicates``: indices (default all, in order).  ``haplotypes``: indices of the
+        haplotypes to count (default all): a birth, death, sampling or migration counts if its haplotype is among them, a
+        mutation if the variant that arises is; immunity changes carry no haplotype and are not counted under a filter.
+        ``summary``: a dict of ``quantiles``, ``by`` and ``method`` as ``trajectory_summary`` takes them: the counts are
+        summarised across the selected replicates in the same call, where they lie (``by='auto'``: one group per scenario of a
+        scenario ensemble); with ``counts=False`` the block itself is not copied to the host.  Direct chains only."""
+        e = _incidence_edges(edges, bins, window)
+        if self._last_call is None:
+            raise ValueError("incidence() needs a direct simulate(record_events=True) call first")
+        if self._last_call[0] != 'direct':
+            raise ValueError("incidence() counts direct chains only: the last call was simulate_tau")
+        if not self._last_call[1]:
+            raise ValueError("incidence() needs the event log: the last call had record_events=False")
+        m = self.model
+        reps = np.arange(self.R, dtype=np.int64) if replicates is None else np.ascontiguousarray(replicates, dtype=np.int64).ravel()
+        n = len(reps)
+        if n and (reps.min() < 0 or reps.max() >= self.R):
+            raise ValueError("replicate index out of range")
+        if len(np.unique(reps)) != n:
+            raise ValueError("replicates must be distinct")
+        mask = None if haplotypes is None else _capi.haplotype_mask(haplotypes, m.hapNum)
+        T, P, K = len(e) - 1, m.popNum, len(Incidence.CHANNELS)
+        sio = finish = None
+        if summary is not None:
+            unknown = set(summary) - {"quantiles", "by", "method"}
+            if unknown:
+                raise ValueError("summary takes quantiles, by and method: got %s" % ", ".join(sorted(unknown)))
+            method = summary.get("method", 'linear')
+            q = _summary_quantiles(summary.get("quantiles", (0.025, 0.5, 0.975)), method)
+            group_of, G = _summary_groups(summary.get("by", 'auto'), None, self.R, self.scenario_of,
+                                          len(self.scenarios) if self.scenarios is not None else 1)
+            sio, finish = _summary_request(np.ascontiguousarray(group_of[reps]), G, q, method, (T, P, K))
+        elif not counts:
+            raise ValueError("counts=False needs summary=: the call would return nothing")
+        eng = self.engine
+        for r in reps:
+            c = eng.counters(int(r))
+            if c.ev_first_new != 0:
+                raise ValueError("replicate %d: its chain does not start in the last call's device log (the model held %d events "
+                                 "when the ensemble started)" % (r, c.ev_first_new))
+        io = _capi.VgxIncidenceIO()
+        block = np.zeros((n, T, P, K), dtype=np.int32) if counts else None
+        outside = np.zeros((max(n, 1), 2), dtype=np.int64)
+        io.n, io.replicates, io.T, io.edges = n, _capi._p(reps), T, _capi._p(e)
+        io.hap_mask = None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint32))
+        io.counts = block.ctypes.data_as(C.POINTER(C.c_int32)) if counts and n else None
+        io.outside = _capi._p(outside)
+        io.summary = C.pointer(sio) if sio is not None and n else None
+        eng._check(eng.lib.vgx_get_incidence(eng.handle, C.byref(io)))
+        inc = Incidence()
+        inc.counts, inc.edges, inc.outside, inc.replicates = block, e, outside[:n], reps
+        inc.summary = finish() if finish is not None else None
+        inc.passes, inc.kernel_ms, inc.clock_ms, inc.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
+        return inc
+
     def trajectories(self, out=None):
         """Summary trajectories of the last call, ``[R, T, P, 2]`` float64 (infectious, susceptible per population).
         ``out`` may be a CUDA torch tensor (filled on the device, no host round trip) or None (numpy)."""
@@ -695,45 +848,13 @@ class Ensemble:
         members is refused by the library."""
         if self.traj_shape is None:
             raise ValueError("trajectory_summary() needs trajectories: the last simulate call recorded none (traj_points=0)")
-        if method not in SUMMARY_METHODS:
-            raise ValueError("method must be 'linear', 'lower' or 'higher'")
-        q = np.asarray(quantiles, dtype=np.float64).ravel()
-        if not np.all((q >= 0.0) & (q <= 1.0)):   # (NaN fails too)
-            raise ValueError("quantiles must lie in [0, 1]")
+        q = _summary_quantiles(quantiles, method)
         R, T, P, _ = self.traj_shape
         group_of, G = _summary_groups(by, replicates, R, self.scenario_of, len(self.scenarios) if self.scenarios is not None else 1)
-        count = np.bincount(group_of[group_of >= 0], minlength=G)
-        ranks = np.ascontiguousarray(np.stack([_summary_ranks(q, int(m), method) for m in count]))
-        K, N = ranks.shape[1], T * P * 2
-        io = _capi.VgxTrajSummaryIO()
-        out = {k: np.zeros((G, N), dtype=np.int64) for k in ("sum", "min", "max")}
-        out["count"] = np.zeros(G, dtype=np.int64)
-        out["stat"] = np.zeros((G, max(K, 1), N), dtype=np.int64)
-        sumsq = np.zeros((G, N, 2), dtype=np.uint64)
-        io.G, io.group_of, io.K, io.ranks = G, _capi._p(group_of), K, _capi._p(ranks)
-        for k, a in out.items():
-            setattr(io, k, _capi._p(a))
-        io.sumsq = sumsq.ctypes.data_as(C.POINTER(C.c_uint64))
+        io, finish = _summary_request(group_of, G, q, method, (T, P, 2))
         eng = self.engine
         eng._check(eng.lib.vgx_get_trajectory_summary(eng.handle, C.byref(io)))
-        s = TrajectorySummary()
-        shape = (G, T, P, 2)
-        s.groups, s.count, s.q, s.method = np.arange(G), out["count"], q, method
-        s.sum, s.min, s.max = out["sum"].reshape(shape), out["min"].reshape(shape), out["max"].reshape(shape)
-        s.sumsq_words = sumsq.reshape(shape + (2,))
-        n = s.count.astype(np.float64).reshape(G, 1, 1, 1)
-        with np.errstate(invalid='ignore', divide='ignore'):
-            s.mean = s.sum / n
-        Q = len(q)
-        stat = out["stat"][:, :K].reshape(G, K, T, P, 2)
-        if method == 'linear':
-            s.quantiles = np.stack([_summary_lerp(stat[g, :Q], stat[g, Q:], q.reshape(Q, 1, 1, 1), int(m)) if m else
-                                    np.full((Q, T, P, 2), np.nan) for g, m in enumerate(s.count)])
-        else:
-            s.quantiles = stat.astype(np.float64)
-            s.quantiles[s.count == 0] = np.nan
-        s.passes, s.kernel_ms, s.copy_ms, s.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
-        return s
+        return finish()
 
     def gather_trajectories(self, dst=0, out=None, async_op=False, wire_dtype=None, device=None):
         """One collective for the whole ensemble: every rank's ``[R, T, P, 2]`` block to rank ``dst``
