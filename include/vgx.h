@@ -171,7 +171,10 @@ int vgx_set_params(vgx_engine *e, const vgx_params *p);
  * reading its own set's tables (classes of identical rate rows, actualSizes, the recomputed migration diagonal, suscepCumul,
  * maxEffectiveBirth are built per set).  n_sets == 1 is vgx_set_params(e, &sets[0]); a later vgx_set_params returns the engine to one
  * set.  Like vgx_set_params the call invalidates the device state.  Dimensions, start state and recombination settings are the
- * engine's, shared by all sets; so `sizes` must be bitwise equal in all sets (VGX_ERR_ARG otherwise).  VGX_ERR_CLASSES and the LDS
+ * engine's, shared by all sets; so `sizes` must be bitwise equal in all sets (VGX_ERR_ARG otherwise).  One value of the state is a
+ * set's own: a replicate starts with contactDensityAfterLockdown of its set in the populations whose lockdownON is set in the start
+ * state and contactDensityBeforeLockdown in the others (what a model with that set's parameters holds there); vgx_state's
+ * contactDensity is the start value while one set is installed.  VGX_ERR_CLASSES and the LDS
  * limit of the kernel's tables are reported for the set that exceeds them, by its index.  vgx_get_state, the event and lockdown
  * logs, vgx_get_genealogies, vgx_get_timelines and the trajectories read logs and state only and work unchanged.
  * Limits while more than one set is installed (each refused with VGX_ERR_ARG and a message naming it): vgx_simulate_direct runs in

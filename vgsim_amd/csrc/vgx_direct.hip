@@ -1521,18 +1521,24 @@ extern "C" __global__ void __launch_bounds__(LANES) vgx_init_reps_kernel(
 }
 
 // Scenario ensembles: a haplotype's class number differs between parameter sets, so after vgx_init_reps_kernel (which wrote
-// set 0's classes) every replicate's list classes are taken from its own set, block set_of[replicate] of psets.
+// set 0's classes) every replicate's list classes are taken from its own set, block set_of[replicate] of psets.  So is its contact
+// density: the start state holds one value per population, the one of the model it came from, and a set may have another (the
+// reference's set_contact_density and set_npi change it): a population starts with its own set's value for the lockdown state it
+// is in, as a single model with that set's parameters holds it (pyx:698-710).
 extern "C" __global__ void __launch_bounds__(LANES) vgx_init_reps_sets_kernel(VgxDevRep r, int P, int64_t R, const VgxDevParams *psets,
                                                                               const int32_t *set_of) {
     const int64_t rep = blockIdx.x;
     if (rep >= R) return;
-    const int32_t *cls = psets[set_of[rep]].cls;
+    const VgxDevParams *ps = psets + set_of[rep];
+    const int32_t *cls = ps->cls;
     for (int pn = 0; pn < P; ++pn) {
         const int n = r.nocc[rep * P + pn];
         const int32_t *lh = r.lhap + (rep * P + pn) * r.cap;
         int32_t *lc = r.lcls + (rep * P + pn) * r.cap;
         for (int k = threadIdx.x; k < n; k += LANES) lc[k] = cls[lh[k]];
     }
+    for (int pn = threadIdx.x; pn < P; pn += LANES)
+        r.popD[(rep * PD_COUNT + PD_CD) * P + pn] = r.popI[(rep * PI_COUNT + PI_LOCK) * P + pn] != 0 ? ps->cdAfter[pn] : ps->cdBefore[pn];
 }
 
 // ---- host-side launchers (this translation unit owns its kernels; no relocatable device code needed) ----

@@ -265,7 +265,9 @@ class Ensemble:
         under ``scenarios[scenario_of[r]]`` (default ``arange(R) % len(scenarios)``) and is, bit for bit, the run of a single
         ``Simulator`` with that scenario's parameters, this start state and seed ``seeds[r]``; one launch runs all of them.
         Limits: the exact direct path on the one-replicate-per-wavefront kernel (``mode='exact'``, ``kernel`` 'auto' or 'wave');
-        no ``simulate_tau``; population sizes and recombination settings equal in all scenarios."""
+        no ``simulate_tau``; population sizes and recombination settings equal in all scenarios.  The contact densities a
+        replicate starts with are its own scenario's (``set_contact_density``, ``set_npi``) for the lockdown state of the start
+        state; a scenario whose model holds another value is refused by ``simulate``."""
         self.model = getattr(simulator, "simulation", simulator)
         m = self.model
         self.R = int(n_replicates)
@@ -309,6 +311,14 @@ class Ensemble:
         ptr, size = m.events.ptr, m.events.size
         size = size + iterations if ptr == 0 else max(size, ptr + iterations)
         if self.scenarios is not None:
+            # every replicate starts with its own scenario's contact densities for the lockdown state of the start state (the engine
+            # takes them from the set's parameters): a scenario whose model holds anything else would not be what runs
+            for g, s in enumerate(self.scenarios):
+                cd = np.where(np.asarray(m.lockdownON) != 0, s.contactDensityAfterLockdown, s.contactDensityBeforeLockdown)
+                bad = np.nonzero(np.asarray(s.contactDensity, dtype=np.float64) != cd)[0]
+                if len(bad):
+                    raise ValueError("scenario %d: the contact density of population %d is %r, its own settings give %r for the lockdown "
+                                     "state of the start state" % (g, bad[0], float(s.contactDensity[bad[0]]), float(cd[bad[0]])))
             eng.set_param_sets(self.scenarios, self.scenario_of)
         else:
             eng.set_params(m)
