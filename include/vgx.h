@@ -33,7 +33,7 @@
  *   VGX_TIMELINES_CHUNK_BYTES=n    vgx_get_timelines, vgx_get_tau_timelines: device bytes of staging and outputs per chunk of replicates
  *   VGX_COLSUMMARY_CHUNK_BYTES=n   vgx_get_trajectory_summary, vgx_test_column_summary: device bytes of the transposed scratch per chunk of
  *                                  columns (default 2^28; one tile of 64 columns at the least)
- *   VGX_INCIDENCE_TILE_EVENTS=n    vgx_get_incidence: consecutive events a counting workgroup takes (default 4096; no result depends on it)
+ *   VGX_INCIDENCE_TILE_EVENTS=n    vgx_get_incidence / vgx_get_tau_incidence: consecutive events (rows) a counting workgroup takes (default 4096; no result depends on it)
  */
 #ifndef VGX_H
 #define VGX_H
@@ -565,6 +565,61 @@ int vgx_test_incidence(const double *times, const int64_t *types, const int64_t 
                        const int64_t *newHaplotypes, const int64_t *newPopulations, int64_t n_ev, int64_t P, int64_t hapNum,
                        const double *edges, int64_t T, const uint32_t *hap_mask, int64_t tile, int32_t *counts, int64_t *outside,
                        char *errbuf, int64_t errcap);
+
+/* The same counts for many replicates of the last vgx_simulate_tau call (with the event log), on the device.
+ * A tau replicate's chain is a list of weighted rows (num, type, haplotype, population, newHaplotype, newPopulation), six int64:
+ * the events the model held when the call started (`prefix`, as vgx_get_tau_timelines takes it; its lockdown columns are not
+ * read), flattened (a direct event = a row with num 1, a MULTITYPE event of an earlier tau call = its multievent rows), then the
+ * replicate's own rows where the tau kernels left them (nothing of them is copied or compacted).  A replicate that restarted
+ * (vgx_counters.restarts > 0) has no prefix.  An EVENT is a direct event or a step, and a step's time is the time of its MULTITYPE
+ * record: this is where the reference's own replays place a step's events.  The cuts are row indices:
+ * cut[k] = first row of the first event i with edges[k] <= t_i (the row count if none), by the same literal loop over events (an
+ * event without rows still advances it; its cut is the first row after it); row j is in bin b when cut[b] <= j < cut[b + 1], so
+ * all rows of a step share a bin.  A row counts `num` times in the cells of vgx_get_incidence (same channels, keys, double count
+ * of MIGRATION and haplotype filter; num <= 0 counts nothing; a field that is not a 32-bit index matches nothing).
+ * outside[r] = (sum of num over the rows before cut[0], over the rows from cut[T] on), over num > 0, unfiltered.
+ * Counts are int64: a bin sums num over many steps.  The LDS histogram is popNum * 56 bytes (popNum <= 1170).
+ * No host clock runs (step times are host doubles).  With one grid the prefix is the same part of every chain that carries it: it
+ * is flattened, uploaded and counted ONCE per call into a block of its own; the block of every replicate that did not restart
+ * starts from it, and the replicate's own rows are added (a workgroup per replicate and tile of VGX_INCIDENCE_TILE_EVENTS rows).
+ * Replicates go in chunks under VGX_TIMELINES_CHUNK_BYTES.  `summary` as in vgx_get_incidence: a device pass narrows the block to
+ * int32 for it; if a count is 2^31 or more the summary is refused (VGX_ERR_ARG, the largest count in the message) after `counts`,
+ * if asked for, has been written.  ms[1] is the host's cut search.
+ * Refusals (VGX_ERR_ARG, worded alike behind "vgx_get_tau_incidence: "): the last call was not vgx_simulate_tau; it recorded no
+ * rows; a replicate that did not restart continues a log of another length than prefix->ev_ptr; prefix plus own rows reach 2^31;
+ * a null prefix column; bad edges; T outside [1, 2^24); replicates out of range or given twice; the block (8 bytes per cell, 4
+ * more with a summary) above half of the free device memory; the LDS limit. */
+typedef struct vgx_tau_incidence_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    int64_t T; const double *edges;              /* [T + 1] strictly increasing, finite */
+    const uint32_t *hap_mask;                    /* NULL or ceil(hapNum / 32) words */
+    int64_t *counts;                             /* NULL or host [n][T][P][7] */
+    int64_t *outside;                            /* [n][2] */
+    vgx_traj_summary_io *summary;                /* NULL or the summary of the [n][T*P*7] block; group_of has n entries */
+    int64_t passes; double ms[3];                /* out: counting launches; kernels, host cut search, whole call */
+} vgx_tau_incidence_io;
+int vgx_get_tau_incidence(vgx_engine *e, vgx_tau_incidence_io *io, const vgx_timelines_prefix *prefix);
+/* Test hook: the flattening, cuts, cells and tile walk of vgx_get_tau_incidence compiled for the host, on one chain given as
+ * event columns and multievent columns (no device, no engine), tile after tile of `tile` rows (0: the default).  The last
+ * n_own_events events play the replicate's own steps (-1: the chain's trailing MULTITYPE events), everything before them the
+ * prefix; the prefix is counted once as a chain of its own and added, as on the device.  Prefix rows pass the checks of the
+ * flattening (a negative num or a field outside 32 bits is refused); own rows are taken as they are, as the device reads them.
+ * counts [T][P][7] and outside [2] are overwritten.  Refused with the message in errbuf: bad edges, P * 56 bytes above the LDS
+ * budget, a MULTITYPE row range outside the multievent log. */
+typedef struct vgx_tau_incidence_chain {
+    int64_t popNum, hapNum;
+    int64_t ev_ptr;
+    const double *ev_times;
+    const int64_t *ev_types, *ev_haplotypes, *ev_populations, *ev_newHaplotypes, *ev_newPopulations;
+    int64_t mev_rows;
+    const int64_t *mev_num, *mev_types, *mev_haplotypes, *mev_populations, *mev_newHaplotypes, *mev_newPopulations;
+    int64_t T; const double *edges;              /* [T + 1] */
+    const uint32_t *hap_mask;
+    int64_t tile, n_own_events;
+    int64_t *counts;                             /* out [T][P][7] */
+    int64_t *outside;                            /* out [2] */
+} vgx_tau_incidence_chain;
+int vgx_test_tau_incidence(vgx_tau_incidence_chain *io, char *errbuf, int64_t errcap);
 
 /* ---- kernel choice of the direct path ------------------------------------------------------- */
 /* What the choice of a direct call's kernel reads: the model's dimensions, the state the call starts from and two diagnostic

@@ -136,6 +136,22 @@ class VgxIncidenceIO(C.Structure):
                 ("passes", C.c_int64), ("ms", C.c_double * 3)]
 
 
+class VgxTauIncidenceIO(C.Structure):
+    _fields_ = [("n", C.c_int64), ("replicates", _I), ("T", C.c_int64), ("edges", _F), ("hap_mask", C.POINTER(C.c_uint32)),
+                ("counts", _I), ("outside", _I), ("summary", C.POINTER(VgxTrajSummaryIO)),
+                ("passes", C.c_int64), ("ms", C.c_double * 3)]
+
+
+class VgxTauIncidenceChain(C.Structure):
+    _fields_ = [("popNum", C.c_int64), ("hapNum", C.c_int64), ("ev_ptr", C.c_int64),
+                ("ev_times", _F), ("ev_types", _I), ("ev_haplotypes", _I), ("ev_populations", _I),
+                ("ev_newHaplotypes", _I), ("ev_newPopulations", _I),
+                ("mev_rows", C.c_int64), ("mev_num", _I), ("mev_types", _I), ("mev_haplotypes", _I), ("mev_populations", _I),
+                ("mev_newHaplotypes", _I), ("mev_newPopulations", _I),
+                ("T", C.c_int64), ("edges", _F), ("hap_mask", C.POINTER(C.c_uint32)), ("tile", C.c_int64), ("n_own_events", C.c_int64),
+                ("counts", _I), ("outside", _I)]
+
+
 INCIDENCE_CHANNELS = ('birth', 'death', 'sampling', 'mutation', 'immunity', 'arrival', 'departure')   # vgx.h: channels 0 .. 6
 
 COLSUMMARY_MAX_GROUP = 16384   # members of one group the device pass sorts (vgx.h: VGX_COLSUMMARY_MAX_GROUP)
@@ -214,6 +230,8 @@ SIGNATURES = {
     "vgx_get_incidence": (C.c_int, [_H, C.POINTER(VgxIncidenceIO)]),
     "vgx_test_incidence": (C.c_int, [_F, _I, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, _F, C.c_int64, C.POINTER(C.c_uint32), C.c_int64,
                                      C.POINTER(C.c_int32), _I, C.c_char_p, C.c_int64]),
+    "vgx_get_tau_incidence": (C.c_int, [_H, C.POINTER(VgxTauIncidenceIO), C.POINTER(VgxTimelinesPrefix)]),
+    "vgx_test_tau_incidence": (C.c_int, [C.POINTER(VgxTauIncidenceChain), C.c_char_p, C.c_int64]),
     "vgx_test_direct_plan": (C.c_int, [C.POINTER(VgxDirectShape), C.POINTER(VgxRunOpts), C.POINTER(VgxDirectPlan), C.c_char_p, C.c_int64]),
     "vgx_rng_position": (None, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64 * 4)]),
     "vgx_propensity_scan": (C.c_int, [C.POINTER(VgxRowScan)]),
@@ -799,6 +817,46 @@ def replay_incidence(times, types, haplotypes, populations, newHaplotypes, newPo
                                            counts.ctypes.data_as(C.POINTER(C.c_int32)), _p(outside), err, 512)
     if rc != VGX_OK:
         raise ValueError(err.value.decode() or "vgx_test_incidence failed")
+    return counts, outside
+
+
+def replay_tau_incidence(events, mev, popNum, hapNum, edges, hap_mask=None, tile=0, n_own_events=-1):
+    """The event counts of ``Ensemble.tau_incidence`` for one chain through ``vgx_test_tau_incidence``: the device's flattening,
+    cuts, cells and tile walk (vgx_tau_incidence.h) compiled for the host, tile after tile of ``tile`` rows (0: the default); no GPU.
+    ``events``: the six event columns (times, types, haplotypes, populations, newHaplotypes, newPopulations); ``mev``: a dict of the
+    multievent columns num, types, haplotypes, populations, newHaplotypes, newPopulations that the MULTITYPE events index, or None.
+    The last ``n_own_events`` events play the replicate's own steps (-1: the trailing MULTITYPE events), everything before them the
+    prefix, which is counted once and added as on the device.  ``hap_mask``: None or the words of ``haplotype_mask``.  Returns
+    (counts [T, P, 7] int64, outside [2] int64); a refusal raises ``ValueError`` with the library's message."""
+    times = np.ascontiguousarray(events[0], dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.int64) for c in events[1:6]]
+    n = len(times)
+    if len(cols) != 5 or any(len(c) != n for c in cols):
+        raise ValueError("event columns of different lengths")
+    mcols = [np.ascontiguousarray(mev[c] if mev is not None else [], dtype=np.int64) for c in MEV_COLUMNS]
+    if len({len(c) for c in mcols}) != 1:
+        raise ValueError("multievent columns of different lengths")
+    edges = np.ascontiguousarray(edges, dtype=np.float64)
+    T = len(edges) - 1
+    counts = np.zeros((max(T, 1), max(int(popNum), 1), len(INCIDENCE_CHANNELS)), dtype=np.int64)
+    outside = np.zeros(2, dtype=np.int64)
+    mask = None if hap_mask is None else np.ascontiguousarray(hap_mask, dtype=np.uint32)
+    if mask is not None and len(mask) != (int(hapNum) + 31) // 32:
+        raise ValueError("hap_mask must hold ceil(hapNum / 32) words")
+    io = VgxTauIncidenceChain()
+    io.popNum, io.hapNum, io.ev_ptr, io.ev_times = int(popNum), int(hapNum), n, _p(times)
+    for name, col in zip(("types", "haplotypes", "populations", "newHaplotypes", "newPopulations"), cols):
+        setattr(io, "ev_" + name, _p(col))
+    io.mev_rows = len(mcols[0])
+    for name, col in zip(MEV_COLUMNS, mcols):
+        setattr(io, "mev_" + name, _p(col))
+    io.T, io.edges = T, _p(edges)
+    io.hap_mask = None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint32))
+    io.tile, io.n_own_events = int(tile), int(n_own_events)
+    io.counts, io.outside = _p(counts), _p(outside)
+    err = C.create_string_buffer(512)
+    if load_library().vgx_test_tau_incidence(C.byref(io), err, 512) != VGX_OK:
+        raise ValueError(err.value.decode() or "vgx_test_tau_incidence failed")
     return counts, outside
 
 

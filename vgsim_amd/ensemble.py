@@ -217,7 +217,7 @@ def _summary_quantiles(quantiles, method):
 class Incidence:
     """What ``Ensemble.incidence`` returns: event counts per selected replicate, time bin, population and channel.
 
-    ``counts`` [n, T, P, 7] int32 (None when the call had ``counts=False``), channel k as ``CHANNELS`` names it: births, deaths
+    ``counts`` [n, T, P, 7] int32 (int64 from ``tau_incidence``; None when the call had ``counts=False``), channel k as ``CHANNELS`` names it: births, deaths
     (recoveries), samplings (recorded cases), mutations, immunity changes, migrations counted where they arrive (a new infection
     there) and where they depart from; ``edges`` [T + 1] the bin edges (bin b holds edges[b] <= t < edges[b + 1]); ``outside``
     [n, 2] the events of every replicate before ``edges[0]`` and from ``edges[T]`` on; ``replicates`` [n]; ``summary`` a
@@ -699,6 +699,13 @@ class Ensemble:
             raise ValueError("tau_timelines() needs the multievent rows: the last call had record_events=False")
         step_num, qi, ii, qs, si, reps = self._timeline_arguments(infectious, susceptible, step_num, replicates, semantics)
         eng = self.engine
+        pre = self._tau_prefix_struct()
+        return self._timeline_batch(lambda io: eng.lib.vgx_get_tau_timelines(eng.handle, C.byref(io), C.byref(pre)),
+                                    step_num, qi, ii, qs, si, reps, semantics)
+
+    def _tau_prefix_struct(self):
+        """The ``vgx_timelines_prefix`` of the last ``simulate_tau(record_events=True)`` call: the model's events, multievent rows and
+        lockdown records as they were when it started (the arrays live in ``self._tau_prefix``)."""
         pre = _capi.VgxTimelinesPrefix()
         ev, mv, loc = self._tau_prefix
         pre.ev_ptr, pre.ev_times = len(ev[0]), _capi._p(ev[0])
@@ -708,8 +715,7 @@ class Ensemble:
         for name, col in zip(_capi.MEV_COLUMNS, mv):
             setattr(pre, "mev_" + name, _capi._p(col))
         pre.loc_n, pre.loc_state, pre.loc_pop, pre.loc_time = len(loc[0]), _capi._p(loc[0]), _capi._p(loc[1]), _capi._p(loc[2])
-        return self._timeline_batch(lambda io: eng.lib.vgx_get_tau_timelines(eng.handle, C.byref(io), C.byref(pre)),
-                                    step_num, qi, ii, qs, si, reps, semantics)
+        return pre
 
     def _timeline_arguments(self, infectious, susceptible, step_num, replicates, semantics):
         """The checks ``timelines()`` and ``tau_timelines()`` share: (step_num, unique infectious queries and the index of every given
@@ -768,6 +774,47 @@ class Ensemble:
         b.passes, b.kernel_ms, b.clock_ms, b.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
         return b
 
+    def _incidence_request(self, io, e, replicates, haplotypes, summary, counts, dtype, scenario_of, n_scenarios):
+        """What ``incidence()`` and ``tau_incidence()`` share: the checks on ``replicates``, ``haplotypes``, ``summary`` and ``counts``
+        (ValueError before the library is called) and the fields both io structures have.  Returns ``finish(check)``, which the caller
+        invokes after its own checks: ``check()`` makes the library call; the result is the :class:`Incidence`."""
+        m = self.model
+        reps = np.arange(self.R, dtype=np.int64) if replicates is None else np.ascontiguousarray(replicates, dtype=np.int64).ravel()
+        n = len(reps)
+        if n and (reps.min() < 0 or reps.max() >= self.R):
+            raise ValueError("replicate index out of range")
+        if len(np.unique(reps)) != n:
+            raise ValueError("replicates must be distinct")
+        mask = None if haplotypes is None else _capi.haplotype_mask(haplotypes, m.hapNum)
+        T, P, K = len(e) - 1, m.popNum, len(Incidence.CHANNELS)
+        sio = done = None
+        if summary is not None:
+            unknown = set(summary) - {"quantiles", "by", "method"}
+            if unknown:
+                raise ValueError("summary takes quantiles, by and method: got %s" % ", ".join(sorted(unknown)))
+            method = summary.get("method", 'linear')
+            q = _summary_quantiles(summary.get("quantiles", (0.025, 0.5, 0.975)), method)
+            group_of, G = _summary_groups(summary.get("by", 'auto'), None, self.R, scenario_of, n_scenarios)
+            sio, done = _summary_request(np.ascontiguousarray(group_of[reps]), G, q, method, (T, P, K))
+        elif not counts:
+            raise ValueError("counts=False needs summary=: the call would return nothing")
+        block = np.zeros((n, T, P, K), dtype=dtype) if counts else None
+        outside = np.zeros((max(n, 1), 2), dtype=np.int64)
+        io.n, io.replicates, io.T, io.edges = n, _capi._p(reps), T, _capi._p(e)
+        io.hap_mask = None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint32))
+        io.counts = block.ctypes.data_as(type(io.counts)) if counts and n else None
+        io.outside = _capi._p(outside)
+        io.summary = C.pointer(sio) if sio is not None and n else None
+
+        def finish(check, _alive=(reps, mask, e)):
+            check()
+            inc = Incidence()
+            inc.counts, inc.edges, inc.outside, inc.replicates = block, e, outside[:n], reps
+            inc.summary = done() if done is not None else None
+            inc.passes, inc.kernel_ms, inc.clock_ms, inc.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
+            return inc
+        return finish
+
     def incidence(self, edges=None, bins=None, window=None, replicates=None, haplotypes=None, summary=None, counts=True):
         """Event counts per time bin, population and channel of every selected replicate of the last direct
         ``simulate(record_events=True)`` call, on ONE grid for all replicates and on the device (``vgx_get_incidence``): one
@@ -788,47 +835,39 @@ class Ensemble:
             raise ValueError("incidence() counts direct chains only: the last call was simulate_tau")
         if not self._last_call[1]:
             raise ValueError("incidence() needs the event log: the last call had record_events=False")
-        m = self.model
-        reps = np.arange(self.R, dtype=np.int64) if replicates is None else np.ascontiguousarray(replicates, dtype=np.int64).ravel()
-        n = len(reps)
-        if n and (reps.min() < 0 or reps.max() >= self.R):
-            raise ValueError("replicate index out of range")
-        if len(np.unique(reps)) != n:
-            raise ValueError("replicates must be distinct")
-        mask = None if haplotypes is None else _capi.haplotype_mask(haplotypes, m.hapNum)
-        T, P, K = len(e) - 1, m.popNum, len(Incidence.CHANNELS)
-        sio = finish = None
-        if summary is not None:
-            unknown = set(summary) - {"quantiles", "by", "method"}
-            if unknown:
-                raise ValueError("summary takes quantiles, by and method: got %s" % ", ".join(sorted(unknown)))
-            method = summary.get("method", 'linear')
-            q = _summary_quantiles(summary.get("quantiles", (0.025, 0.5, 0.975)), method)
-            group_of, G = _summary_groups(summary.get("by", 'auto'), None, self.R, self.scenario_of,
-                                          len(self.scenarios) if self.scenarios is not None else 1)
-            sio, finish = _summary_request(np.ascontiguousarray(group_of[reps]), G, q, method, (T, P, K))
-        elif not counts:
-            raise ValueError("counts=False needs summary=: the call would return nothing")
+        io = _capi.VgxIncidenceIO()
+        finish = self._incidence_request(io, e, replicates, haplotypes, summary, counts, np.int32, self.scenario_of,
+                                         len(self.scenarios) if self.scenarios is not None else 1)
         eng = self.engine
-        for r in reps:
-            c = eng.counters(int(r))
+        for r in range(io.n):
+            c = eng.counters(int(io.replicates[r]))
             if c.ev_first_new != 0:
                 raise ValueError("replicate %d: its chain does not start in the last call's device log (the model held %d events "
-                                 "when the ensemble started)" % (r, c.ev_first_new))
-        io = _capi.VgxIncidenceIO()
-        block = np.zeros((n, T, P, K), dtype=np.int32) if counts else None
-        outside = np.zeros((max(n, 1), 2), dtype=np.int64)
-        io.n, io.replicates, io.T, io.edges = n, _capi._p(reps), T, _capi._p(e)
-        io.hap_mask = None if mask is None else mask.ctypes.data_as(C.POINTER(C.c_uint32))
-        io.counts = block.ctypes.data_as(C.POINTER(C.c_int32)) if counts and n else None
-        io.outside = _capi._p(outside)
-        io.summary = C.pointer(sio) if sio is not None and n else None
-        eng._check(eng.lib.vgx_get_incidence(eng.handle, C.byref(io)))
-        inc = Incidence()
-        inc.counts, inc.edges, inc.outside, inc.replicates = block, e, outside[:n], reps
-        inc.summary = finish() if finish is not None else None
-        inc.passes, inc.kernel_ms, inc.clock_ms, inc.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
-        return inc
+                                 "when the ensemble started)" % (io.replicates[r], c.ev_first_new))
+        return finish(lambda: eng._check(eng.lib.vgx_get_incidence(eng.handle, C.byref(io))))
+
+    def tau_incidence(self, edges=None, bins=None, window=None, replicates=None, haplotypes=None, summary=None, counts=True):
+        """``incidence()`` for the replicates of the last ``simulate_tau(record_events=True)`` call (``vgx_get_tau_incidence``): the
+        same grid arguments, channels, haplotype filter, ``summary`` and :class:`Incidence`, with ``counts`` [n, T, P, 7] int64 (a
+        bin sums the multiplicities of many steps) and ``outside`` the summed multiplicities before and after the window.
+
+        A replicate's chain is the model's chain before the tau call (``model.events`` / ``model.multievents`` as they were
+        then; a replicate that restarted has none), then its own steps, every multievent row counting ``num`` times.  All events
+        of a step carry the time of the step's MULTITYPE record, which is where the reference's own replays place them, so a
+        step falls into one bin whole.  The shared part is counted once per call on the device, not once per replicate; no
+        host clock runs.  ``summary``: refused by the library when a count reaches 2^31 (``counts`` stays available: call
+        again without ``summary``).  ``by='auto'`` is one group (scenario ensembles have no ``simulate_tau``)."""
+        e = _incidence_edges(edges, bins, window)
+        if self._last_call is None:
+            raise ValueError("tau_incidence() needs a simulate_tau(record_events=True) call first")
+        if self._last_call[0] != 'tau':
+            raise ValueError("tau_incidence() counts tau chains only: the last call was a direct simulate()")
+        if not self._last_call[1]:
+            raise ValueError("tau_incidence() needs the multievent rows: the last call had record_events=False")
+        io = _capi.VgxTauIncidenceIO()
+        finish = self._incidence_request(io, e, replicates, haplotypes, summary, counts, np.int64, None, 1)
+        eng, pre = self.engine, self._tau_prefix_struct()
+        return finish(lambda: eng._check(eng.lib.vgx_get_tau_incidence(eng.handle, C.byref(io), C.byref(pre))))
 
     def trajectories(self, out=None):
         """Summary trajectories of the last call, ``[R, T, P, 2]`` float64 (infectious, susceptible per population).
