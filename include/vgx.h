@@ -34,6 +34,7 @@
  *   VGX_COLSUMMARY_CHUNK_BYTES=n   vgx_get_trajectory_summary, vgx_test_column_summary: device bytes of the transposed scratch per chunk of
  *                                  columns (default 2^28; one tile of 64 columns at the least)
  *   VGX_INCIDENCE_TILE_EVENTS=n    vgx_get_incidence / vgx_get_tau_incidence: consecutive events (rows) a counting workgroup takes (default 4096; no result depends on it)
+ *   VGX_PREVALENCE_TILE_EVENTS=n   vgx_get_prevalence: consecutive events a counting workgroup takes (default 4096; no result depends on it)
  */
 #ifndef VGX_H
 #define VGX_H
@@ -565,6 +566,63 @@ int vgx_test_incidence(const double *times, const int64_t *types, const int64_t 
                        const int64_t *newHaplotypes, const int64_t *newPopulations, int64_t n_ev, int64_t P, int64_t hapNum,
                        const double *edges, int64_t T, const uint32_t *hap_mask, int64_t tile, int32_t *counts, int64_t *outside,
                        char *errbuf, int64_t errcap);
+
+/* ---- prevalence: infectious hosts per variant class on a common grid --------------------------- */
+/* How many hosts carry which variant, when: the stock where vgx_get_incidence gives the flows, on ONE grid for all replicates
+ * (DESIGN.md §18).  The caller gives the grid times grid[0 .. T-1] (strictly increasing, finite, 1 <= T < 2^24) and a map
+ * variant_of[hapNum] with values in [-1, V): the class of every haplotype, -1 = not tracked.  With the event times vgx_get_events
+ * gives, cut[j] = first event index i with grid[j] < t_i (n_ev if none; the loop's position never goes back, whatever the times
+ * do).  The comparison is strict, as the trajectories' is: a grid point gets the state before the event that takes the time past
+ * it, and an event at exactly grid[j] is applied before point j.  Interval j = 0 .. T holds the events cut[j-1] <= i < cut[j]
+ * (cut[-1] = 0, cut[T] = n_ev; interval T is the tail after the last grid point), and outside[r] = (cut[0], n_ev - cut[T-1]).
+ * A log record (type, haplotype, population, newHaplotype, newPopulation) changes, with c = variant_of[haplotype],
+ *   BIRTH              +1 at (population, c)
+ *   DEATH, SAMPLING    -1 at (population, c)
+ *   MUTATION           -1 at (population, c), +1 at (population, variant_of[newHaplotype]); equal classes change nothing
+ *   MIGRATION          +1 at (newPopulation, c)
+ *   SUSCCHANGE         nothing
+ * each side only if its class is tracked (the 'compartment' semantics of vgx_get_timelines folded through variant_of).  A type
+ * outside 0..5, a population key outside [0, popNum) or a haplotype outside [0, hapNum) counts nowhere.
+ *   values[r][j] = start_r + the sum of the changes of the intervals 0 .. j,   final[r] = the same over all T + 1 intervals
+ * where start_r is the state the call started from (the host state after its first-call preparation, the index case included)
+ * folded through variant_of, or the initial state for a replicate that restarted (vgx_counters.restarts > 0).  With every
+ * haplotype tracked final[r] is the replicate's final infectious state (vgx_get_state) folded through variant_of.
+ * The device reads every selected replicate's log in place: a workgroup takes one replicate and a tile of consecutive events
+ * (VGX_PREVALENCE_TILE_EVENTS, default 4096), finds its first interval by a search in the replicate's cuts, accumulates the
+ * signed changes in popNum * V int32 cells in LDS and adds the nonzero cells to a block of net changes in device memory at every
+ * interval change and at the tile's end; a scan kernel then turns every (replicate, population, class) column into running sums where
+ * it lies.  All of it is integer work: no result depends on the tile size, the launch geometry or the chunking.  The host clock
+ * runs as in vgx_get_incidence (VGX_TIMELINES_CHUNK_BYTES); the log itself is never copied.  `summary`, when given, is the
+ * column summary of vgx_get_trajectory_summary over `values` as a matrix [n][T * popNum * V] where it lies (`final` is not part
+ * of it; group_of has n entries, one per SELECTED replicate in the order of `replicates`); it needs whole numbers in
+ * [0, 2^31), which a device min/max pass checks: if it fails the summary is refused with the offending value in the message,
+ * after values and final, if asked for, have been written (a negative value can come only from a log with records outside
+ * the model).  `values` may be NULL: the block is then not copied to the host.
+ * Preconditions as vgx_get_incidence: the last call was direct and recorded events; every selected chain starts at log index 0.
+ * Refusals (VGX_ERR_ARG, worded alike behind "vgx_get_prevalence: "): those; replicates out of range or given twice; a grid
+ * that is not finite or does not increase; T outside [1, 2^24); V < 1 or a variant_of value outside [-1, V); a population size
+ * of 2^31 or more; popNum * V * 4 bytes of cells above the 65536 bytes of LDS a counting workgroup may use; a block
+ * (4 n (T + 1) popNum V bytes) above half of the free device memory (the message gives the bytes: select fewer replicates); a
+ * chain of 2^30 events or more.  vgx_clock_mismatches counts every selected replicate once. */
+typedef struct vgx_prevalence_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    int64_t T; const double *grid;               /* [T] strictly increasing, finite */
+    int64_t V; const int32_t *variant_of;        /* [hapNum], values in [-1, V) */
+    int32_t *values;                             /* NULL or host [n][T][P][V] */
+    int32_t *final;                              /* NULL or host [n][P][V] */
+    int64_t *outside;                            /* [n][2]: events before cut[0] / from cut[T-1] on */
+    vgx_traj_summary_io *summary;                /* NULL or the summary of [n][T*P*V]; group_of has n entries */
+    int64_t passes; double ms[3];                /* out: launches of the counting kernel; kernels, host clock, whole call */
+} vgx_prevalence_io;
+int vgx_get_prevalence(vgx_engine *e, vgx_prevalence_io *io);
+/* Test hook: the rule, the tile walk and the scan of vgx_get_prevalence compiled for the host, on one chain given as arrays (no
+ * device, no engine), tile after tile with `tile` events each (0: the default).  start [P][V]: whole numbers in [0, 2^31).
+ * values [T][P][V], final [P][V] and outside [2] are overwritten.  The same limits: the LDS budget, a chain of 2^30 events, a bad
+ * grid, V or variant_of are refused with the message in errbuf. */
+int vgx_test_prevalence(const double *times, const int64_t *types, const int64_t *haplotypes, const int64_t *populations,
+                        const int64_t *newHaplotypes, const int64_t *newPopulations, int64_t n_ev, int64_t P, int64_t hapNum,
+                        const double *grid, int64_t T, const int32_t *variant_of, int64_t V, const int64_t *start, int64_t tile,
+                        int32_t *values, int32_t *final, int64_t *outside, char *errbuf, int64_t errcap);
 
 /* The same counts for many replicates of the last vgx_simulate_tau call (with the event log), on the device.
  * A tau replicate's chain is a list of weighted rows (num, type, haplotype, population, newHaplotype, newPopulation), six int64:

@@ -136,6 +136,12 @@ class VgxIncidenceIO(C.Structure):
                 ("passes", C.c_int64), ("ms", C.c_double * 3)]
 
 
+class VgxPrevalenceIO(C.Structure):
+    _fields_ = [("n", C.c_int64), ("replicates", _I), ("T", C.c_int64), ("grid", _F), ("V", C.c_int64), ("variant_of", C.POINTER(C.c_int32)),
+                ("values", C.POINTER(C.c_int32)), ("final", C.POINTER(C.c_int32)), ("outside", _I), ("summary", C.POINTER(VgxTrajSummaryIO)),
+                ("passes", C.c_int64), ("ms", C.c_double * 3)]
+
+
 class VgxTauIncidenceIO(C.Structure):
     _fields_ = [("n", C.c_int64), ("replicates", _I), ("T", C.c_int64), ("edges", _F), ("hap_mask", C.POINTER(C.c_uint32)),
                 ("counts", _I), ("outside", _I), ("summary", C.POINTER(VgxTrajSummaryIO)),
@@ -230,6 +236,9 @@ SIGNATURES = {
     "vgx_get_incidence": (C.c_int, [_H, C.POINTER(VgxIncidenceIO)]),
     "vgx_test_incidence": (C.c_int, [_F, _I, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, _F, C.c_int64, C.POINTER(C.c_uint32), C.c_int64,
                                      C.POINTER(C.c_int32), _I, C.c_char_p, C.c_int64]),
+    "vgx_get_prevalence": (C.c_int, [_H, C.POINTER(VgxPrevalenceIO)]),
+    "vgx_test_prevalence": (C.c_int, [_F, _I, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, _F, C.c_int64, C.POINTER(C.c_int32), C.c_int64, _I,
+                                      C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, C.c_char_p, C.c_int64]),
     "vgx_get_tau_incidence": (C.c_int, [_H, C.POINTER(VgxTauIncidenceIO), C.POINTER(VgxTimelinesPrefix)]),
     "vgx_test_tau_incidence": (C.c_int, [C.POINTER(VgxTauIncidenceChain), C.c_char_p, C.c_int64]),
     "vgx_test_direct_plan": (C.c_int, [C.POINTER(VgxDirectShape), C.POINTER(VgxRunOpts), C.POINTER(VgxDirectPlan), C.c_char_p, C.c_int64]),
@@ -818,6 +827,68 @@ def replay_incidence(times, types, haplotypes, populations, newHaplotypes, newPo
     if rc != VGX_OK:
         raise ValueError(err.value.decode() or "vgx_test_incidence failed")
     return counts, outside
+
+
+def variant_map(variants, hapNum):
+    """The map ``vgx_get_prevalence`` takes, (variant_of [hapNum] int32 with values in [-1, V), V), from what ``Ensemble.prevalence``
+    accepts as ``variants``: None (every haplotype its own class, V = hapNum); an integer array [hapNum] with values -1 (not
+    tracked) or a class (V = the largest class + 1, at least 1); or a sequence of sequences of haplotype indices (class k = the k-th
+    sequence, unlisted haplotypes not tracked).  ValueError for anything else."""
+    H = int(hapNum)
+    if variants is None:
+        return np.arange(H, dtype=np.int32), H
+    if len(variants) and all(np.ndim(v) == 1 for v in variants):   # classes as lists of haplotypes
+        vo = np.full(H, -1, dtype=np.int32)
+        for k, members in enumerate(variants):
+            idx = np.asarray(members).ravel()
+            if len(idx) and not np.issubdtype(idx.dtype, np.integer):
+                raise ValueError("variants must hold integer haplotype indices")
+            idx = idx.astype(np.int64)
+            if len(idx) and (idx.min() < 0 or idx.max() >= H):
+                raise ValueError("haplotype index out of range")
+            if len(np.unique(idx)) != len(idx) or (vo[idx] >= 0).any():
+                raise ValueError("a haplotype is listed twice in variants")
+            vo[idx] = k
+        return vo, len(variants)
+    a = np.asarray(variants)
+    if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("variants must be an integer array [hapNum] or a sequence of sequences of haplotype indices")
+    if len(a) != H:
+        raise ValueError("variants must hold one class per haplotype (%d), got %d" % (H, len(a)))
+    V = max(int(a.max()) + 1, 1)
+    if a.min() < -1 or V > np.iinfo(np.int32).max:
+        raise ValueError("variant_of[%d] = %d is outside [-1, %d)" % (int(a.argmin()), int(a.min()), V))
+    return np.ascontiguousarray(a, dtype=np.int32), V
+
+
+def replay_prevalence(times, types, haplotypes, populations, newHaplotypes, newPopulations, popNum, hapNum, grid, variant_of, V, start, tile=0):
+    """The values of ``Ensemble.prevalence`` for one chain given as arrays through ``vgx_test_prevalence``: the device's rule, tile
+    walk and scan (vgx_prevalence.h) compiled for the host, tile after tile of ``tile`` events (0: the default); no GPU.
+    ``variant_of`` [hapNum] with values in [-1, V); ``start`` [P, V] the chain's start folded through it.  Returns (values
+    [T, P, V] int32, final [P, V] int32, outside [2] int64); a refusal raises ``ValueError`` with the library's message."""
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.int64) for c in (types, haplotypes, populations, newHaplotypes, newPopulations)]
+    n = len(times)
+    if any(len(c) != n for c in cols):
+        raise ValueError("event columns of different lengths")
+    grid = np.ascontiguousarray(grid, dtype=np.float64)
+    T, P, V = len(grid), int(popNum), int(V)
+    vo = np.ascontiguousarray(variant_of, dtype=np.int32)
+    if len(vo) != int(hapNum):
+        raise ValueError("variant_of must hold hapNum values")
+    start = np.ascontiguousarray(start, dtype=np.int64)
+    if start.shape != (P, V):
+        raise ValueError("start must have the shape [P, V]")
+    values = np.zeros((max(T, 1), max(P, 1), max(V, 1)), dtype=np.int32)
+    final = np.zeros((max(P, 1), max(V, 1)), dtype=np.int32)
+    outside = np.zeros(2, dtype=np.int64)
+    err = C.create_string_buffer(512)
+    i32 = C.POINTER(C.c_int32)
+    rc = load_library().vgx_test_prevalence(_p(times), *[_p(c) for c in cols], n, P, int(hapNum), _p(grid), T, vo.ctypes.data_as(i32), V,
+                                            _p(start), int(tile), values.ctypes.data_as(i32), final.ctypes.data_as(i32), _p(outside), err, 512)
+    if rc != VGX_OK:
+        raise ValueError(err.value.decode() or "vgx_test_prevalence failed")
+    return values, final, outside
 
 
 def replay_tau_incidence(events, mev, popNum, hapNum, edges, hap_mask=None, tile=0, n_own_events=-1):

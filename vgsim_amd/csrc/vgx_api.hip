@@ -1595,6 +1595,95 @@ extern "C" int vgx_get_timelines(vgx_engine *e, vgx_timelines_io *io) {
     return VGX_OK;
 }
 
+// ---- the host clock of many replicates, chunk by chunk: what vgx_get_incidence and vgx_get_prevalence share ---------------------
+// reps / n_ev: the selected replicates and the events of their chains, d_rep / d_nev the same on the device.  A chunk is as many
+// consecutive replicates as `share` bytes of device memory (at most 2^30, or VGX_TIMELINES_CHUNK_BYTES) hold at 12 bytes per event,
+// staged through pinned host memory; the log itself is not copied.  on_chain(i, times) gets the event times of selected
+// replicate i (from several threads, one replicate each at a time), then on_chunk(i0, i1, max_n) runs the device pass over the
+// replicates [i0, i1) and returns its code.  ms[0] gains the pack kernel's time, ms[1] the host clock's.  Every replicate's clock
+// is built once, as when the replicates are fetched one by one: vgx_clock_mismatches counts each once.
+template <class Chain, class Chunk>
+static int clock_chunks(vgx_engine *e, const char *what, const std::vector<int64_t> &reps, const std::vector<int32_t> &n_ev, const int64_t *d_rep,
+                        const int32_t *d_nev, int64_t share, double *ms, Chain on_chain, Chunk on_chunk) {
+    const std::string pre = std::string(what) + ": ";
+    const int64_t n = (int64_t)reps.size();
+    auto up8 = [](int64_t b) { return (b + 255) / 256 * 256; };
+    auto dev_free = [](char *p) { (void)hipFree(p); };
+    share = std::min<int64_t>(share, (int64_t)1 << 30);
+    if (const char *cb = getenv("VGX_TIMELINES_CHUNK_BYTES")) share = std::min<int64_t>(share, std::max<int64_t>(atoll(cb), 1));
+    std::vector<int64_t> mism((size_t)n, 0);
+    int64_t i0 = 0;
+    while (i0 < n) {
+        int64_t i1 = i0, sum = 0, E = 0, max_n = 0;
+        while (i1 < n && i1 - i0 < ((int64_t)1 << 20)) {
+            const int64_t b = (int64_t)n_ev[(size_t)i1] * 12 + 64;
+            if (i1 > i0 && sum + b > share) break;
+            sum += b;
+            E += n_ev[(size_t)i1];
+            max_n = std::max<int64_t>(max_n, n_ev[(size_t)i1]);
+            i1++;
+        }
+        const int64_t m = i1 - i0;
+        std::vector<int64_t> off((size_t)m);
+        for (int64_t j = 0, o = 0; j < m; j++) { off[(size_t)j] = o; o += n_ev[(size_t)(i0 + j)]; }
+        const int64_t o_off = 0, o_iter = o_off + up8(m * 8), o_rate = o_iter + up8(E * 4), total = o_rate + up8(E * 8);
+        char *ws = nullptr;
+        hipError_t er = hipMalloc((void **)&ws, (size_t)total);
+        if (er != hipSuccess) return fail(e, VGX_ERR_HIP, pre + "hipMalloc of " + std::to_string(total) + " bytes: " + hipGetErrorString(er));
+        std::unique_ptr<char, void (*)(char *)> hold(ws, dev_free);
+        const int64_t pin_rate = up8(E * 4), pin_need = pin_rate + up8(E * 8);
+        if ((int64_t)e->pin_tl_bytes < pin_need) {
+            if (e->pin_tl) (void)hipHostFree(e->pin_tl);
+            e->pin_tl = nullptr; e->pin_tl_bytes = 0;
+            HIPCHECK(e, hipHostMalloc(&e->pin_tl, (size_t)pin_need, hipHostMallocDefault));
+            e->pin_tl_bytes = (size_t)pin_need;
+        }
+        const int32_t *h_iter = (const int32_t *)e->pin_tl;
+        const double *h_rate = (const double *)((char *)e->pin_tl + pin_rate);
+        HIPCHECK(e, hipMemcpyAsync(ws + o_off, off.data(), (size_t)m * 8, hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
+        HIPCHECK(e, vgxi_tl_pack((const int32_t *)e->r_evcols.p, (const double *)e->r_evrate.p, e->evcap, d_rep + i0, d_nev + i0,
+                                 (const int64_t *)(ws + o_off), m, max_n, (int32_t *)(ws + o_iter), (double *)(ws + o_rate), e->stream));
+        HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
+        if (E > 0) {
+            HIPCHECK(e, hipMemcpyAsync(e->pin_tl, ws + o_iter, (size_t)E * 4, hipMemcpyDeviceToHost, e->stream));
+            HIPCHECK(e, hipMemcpyAsync((char *)e->pin_tl + pin_rate, ws + o_rate, (size_t)E * 8, hipMemcpyDeviceToHost, e->stream));
+        }
+        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(e, VGX_ERR_HIP, pre + "pack kernel failed: " + hipGetErrorString(er));
+        float kms = 0.f;
+        HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
+        ms[0] += kms;
+        const auto t_clock = std::chrono::steady_clock::now();
+        std::vector<std::string> errs((size_t)m);
+        std::vector<int> rcs((size_t)m, 0);
+        for_parts(m, [&](int64_t j0, int64_t j1, unsigned) {
+            if (hipSetDevice(e->device) != hipSuccess) { for (int64_t j = j0; j < j1; j++) { rcs[(size_t)j] = VGX_ERR_HIP; errs[(size_t)j] = "hipSetDevice"; } return; }
+            vgx_engine::HostClock hc;
+            for (int64_t j = j0; j < j1; j++) {
+                const int64_t gi = i0 + j, r = reps[(size_t)gi], ne = n_ev[(size_t)gi];
+                const ClockStaged st{h_rate + off[(size_t)j], h_iter + off[(size_t)j]};
+                int rc = clock_build(e, r, hc, errs[(size_t)j], &st);
+                if (rc) { rcs[(size_t)j] = rc; continue; }
+                if ((int64_t)hc.times.size() != ne) {
+                    rcs[(size_t)j] = VGX_ERR_ARG;
+                    errs[(size_t)j] = pre + "the host clock of replicate " + std::to_string(r) + " does not cover its chain";
+                    continue;
+                }
+                mism[(size_t)gi] = hc.limit_mismatch ? 1 : 0;
+                on_chain(gi, hc.times);
+            }
+        }, std::max<int64_t>(E / std::max<int64_t>(m, 1), 1) * 64);
+        for (int64_t j = 0; j < m; j++)
+            if (rcs[(size_t)j]) return fail(e, rcs[(size_t)j], errs[(size_t)j]);
+        ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_clock).count();
+        const int rc = on_chunk(i0, i1, max_n);
+        if (rc) return rc;
+        i0 = i1;
+    }
+    for (int64_t i = 0; i < n; i++) e->clock_mismatches += mism[(size_t)i];
+    return VGX_OK;
+}
+
 // ---- event counts per time bin of many replicates on the device (vgx_incidence.hip, vgx_incidence.h) ----------
 // The split of vgx_get_timelines: the host runs every replicate's clock from the packed (iteration, rate) logs in pinned memory,
 // chunk of replicates by chunk, and turns the times into T + 1 event indices per replicate; the device counts over the log in
@@ -1668,112 +1757,205 @@ extern "C" int vgx_get_incidence(vgx_engine *e, vgx_incidence_io *io) {
     if (io->hap_mask) HIPCHECK(e, hipMemcpyAsync(kws + o_mask, io->hap_mask, (size_t)mask_words * 4, hipMemcpyHostToDevice, e->stream));
     HIPCHECK(e, hipMemsetAsync(kws + o_cnt, 0, (size_t)block_bytes, e->stream));   // zeroed once
 
-    // chunks of replicates: the packed logs of a chunk fit `share` bytes of device memory (and 12 bytes per event of pinned host memory)
-    int64_t share = std::min<int64_t>((int64_t)(free_b / 2) - keep_total + 4096, (int64_t)1 << 30);
-    if (const char *cb = getenv("VGX_TIMELINES_CHUNK_BYTES")) share = std::min<int64_t>(share, std::max<int64_t>(atoll(cb), 1));
-    std::vector<int64_t> mism((size_t)n, 0);
+    const int64_t share = (int64_t)(free_b / 2) - keep_total + 4096;
     std::vector<int32_t> cuts((size_t)(n * (T + 1)));
-    int64_t i0 = 0;
-    while (i0 < n) {
-        int64_t i1 = i0, sum = 0, E = 0, max_n = 0;
-        while (i1 < n && i1 - i0 < ((int64_t)1 << 20)) {
-            const int64_t b = (int64_t)n_ev[(size_t)i1] * 12 + 64;
-            if (i1 > i0 && sum + b > share) break;
-            sum += b;
-            E += n_ev[(size_t)i1];
-            max_n = std::max<int64_t>(max_n, n_ev[(size_t)i1]);
-            i1++;
-        }
-        const int64_t m = i1 - i0;
-        std::vector<int64_t> off((size_t)m);
-        for (int64_t j = 0, o = 0; j < m; j++) { off[(size_t)j] = o; o += n_ev[(size_t)(i0 + j)]; }
-        const int64_t o_off = 0, o_iter = o_off + up8(m * 8), o_rate = o_iter + up8(E * 4), total = o_rate + up8(E * 8);
-        char *ws = nullptr;
-        er = hipMalloc((void **)&ws, (size_t)total);
-        if (er != hipSuccess) return fail(e, VGX_ERR_HIP, "vgx_get_incidence: hipMalloc of " + std::to_string(total) + " bytes: " + hipGetErrorString(er));
-        std::unique_ptr<char, void (*)(char *)> hold(ws, dev_free);
-        const int64_t pin_rate = up8(E * 4), pin_need = pin_rate + up8(E * 8);
-        if ((int64_t)e->pin_tl_bytes < pin_need) {
-            if (e->pin_tl) (void)hipHostFree(e->pin_tl);
-            e->pin_tl = nullptr; e->pin_tl_bytes = 0;
-            HIPCHECK(e, hipHostMalloc(&e->pin_tl, (size_t)pin_need, hipHostMallocDefault));
-            e->pin_tl_bytes = (size_t)pin_need;
-        }
-        const int32_t *h_iter = (const int32_t *)e->pin_tl;
-        const double *h_rate = (const double *)((char *)e->pin_tl + pin_rate);
-        HIPCHECK(e, hipMemcpyAsync(ws + o_off, off.data(), (size_t)m * 8, hipMemcpyHostToDevice, e->stream));
-        HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
-        HIPCHECK(e, vgxi_tl_pack((const int32_t *)e->r_evcols.p, (const double *)e->r_evrate.p, e->evcap, (const int64_t *)(kws + o_rep) + i0,
-                                 (const int32_t *)(kws + o_nev) + i0, (const int64_t *)(ws + o_off), m, max_n, (int32_t *)(ws + o_iter),
-                                 (double *)(ws + o_rate), e->stream));
-        HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
-        if (E > 0) {
-            HIPCHECK(e, hipMemcpyAsync(e->pin_tl, ws + o_iter, (size_t)E * 4, hipMemcpyDeviceToHost, e->stream));
-            HIPCHECK(e, hipMemcpyAsync((char *)e->pin_tl + pin_rate, ws + o_rate, (size_t)E * 8, hipMemcpyDeviceToHost, e->stream));
-        }
-        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)
-            return fail(e, VGX_ERR_HIP, std::string("vgx_get_incidence: pack kernel failed: ") + hipGetErrorString(er));
-        float kms = 0.f;
-        HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
-        io->ms[0] += kms;
-        // host: every replicate's clock -> its T + 1 cuts (one replicate per thread at a time)
-        const auto t_clock = std::chrono::steady_clock::now();
-        std::vector<std::string> errs((size_t)m);
-        std::vector<int> rcs((size_t)m, 0);
-        for_parts(m, [&](int64_t j0, int64_t j1, unsigned) {
-            if (hipSetDevice(e->device) != hipSuccess) { for (int64_t j = j0; j < j1; j++) { rcs[(size_t)j] = VGX_ERR_HIP; errs[(size_t)j] = "hipSetDevice"; } return; }
-            vgx_engine::HostClock hc;
-            for (int64_t j = j0; j < j1; j++) {
-                const int64_t gi = i0 + j, r = reps_all[(size_t)gi], ne = n_ev[(size_t)gi];
-                const ClockStaged st{h_rate + off[(size_t)j], h_iter + off[(size_t)j]};
-                int rc = clock_build(e, r, hc, errs[(size_t)j], &st);
-                if (rc) { rcs[(size_t)j] = rc; continue; }
-                if ((int64_t)hc.times.size() != ne) {
-                    rcs[(size_t)j] = VGX_ERR_ARG;
-                    errs[(size_t)j] = "vgx_get_incidence: the host clock of replicate " + std::to_string(r) + " does not cover its chain";
-                    continue;
-                }
-                mism[(size_t)gi] = hc.limit_mismatch ? 1 : 0;
-                int32_t *cut = cuts.data() + gi * (T + 1);
-                VgxIncCutter ct{io->edges, T, cut};
-                for (int64_t k = 0; k < ne; k++) ct.event(k, hc.times[(size_t)k]);
-                ct.finish(ne);
-                io->outside[2 * gi] = cut[0];
-                io->outside[2 * gi + 1] = ne - cut[(size_t)T];
-            }
-        }, std::max<int64_t>(E / std::max<int64_t>(m, 1), 1) * 64);
-        for (int64_t j = 0; j < m; j++)
-            if (rcs[(size_t)j]) return fail(e, rcs[(size_t)j], errs[(size_t)j]);
-        io->ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_clock).count();
+    const int rc_chunks = clock_chunks(e, "vgx_get_incidence", reps_all, n_ev, (const int64_t *)(kws + o_rep), (const int32_t *)(kws + o_nev), share, io->ms,
+        // host: a replicate's event times -> its T + 1 cuts
+        [&](int64_t gi, const std::vector<double> &times) {
+            int32_t *cut = cuts.data() + gi * (T + 1);
+            VgxIncCutter ct{io->edges, T, cut};
+            for (size_t k = 0; k < times.size(); k++) ct.event((int64_t)k, times[k]);
+            ct.finish((int64_t)times.size());
+            io->outside[2 * gi] = cut[0];
+            io->outside[2 * gi + 1] = (int64_t)times.size() - cut[(size_t)T];
+        },
         // device: the count of the chunk's replicates into their rows of the block
-        HIPCHECK(e, hipMemcpyAsync(kws + o_cut + i0 * (T + 1) * 4, cuts.data() + i0 * (T + 1), (size_t)(m * (T + 1)) * 4, hipMemcpyHostToDevice, e->stream));
-        HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
-        VgxIncLaunch a{};
-        a.m = m;
-        a.log = (const int32_t *)e->r_evcols.p; a.evcap = e->evcap;
-        a.rep = (const int64_t *)(kws + o_rep) + i0; a.n_ev = (const int32_t *)(kws + o_nev) + i0;
-        a.cut = (const int32_t *)(kws + o_cut) + i0 * (T + 1);
-        a.T = (int32_t)T; a.P = (int32_t)P; a.hapNum = (int32_t)H;
-        a.mask = io->hap_mask ? (const uint32_t *)(kws + o_mask) : nullptr;
-        a.tile = (int32_t)tile; a.max_n = max_n;
-        a.counts = (int32_t *)(kws + o_cnt) + i0 * T * cells;
-        HIPCHECK(e, vgxi_inc_count(&a, e->stream));
-        if (max_n > 0) io->passes += 1;
-        HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
-        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)
-            return fail(e, VGX_ERR_HIP, std::string("vgx_get_incidence: counting kernel failed: ") + hipGetErrorString(er));
-        HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
-        io->ms[0] += kms;
-        i0 = i1;
-    }
-    // every replicate's clock was built once, as when the replicates are fetched one by one
-    for (int64_t i = 0; i < n; i++) e->clock_mismatches += mism[(size_t)i];
+        [&](int64_t i0, int64_t i1, int64_t max_n) -> int {
+            const int64_t m = i1 - i0;
+            HIPCHECK(e, hipMemcpyAsync(kws + o_cut + i0 * (T + 1) * 4, cuts.data() + i0 * (T + 1), (size_t)(m * (T + 1)) * 4, hipMemcpyHostToDevice, e->stream));
+            HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
+            VgxIncLaunch a{};
+            a.m = m;
+            a.log = (const int32_t *)e->r_evcols.p; a.evcap = e->evcap;
+            a.rep = (const int64_t *)(kws + o_rep) + i0; a.n_ev = (const int32_t *)(kws + o_nev) + i0;
+            a.cut = (const int32_t *)(kws + o_cut) + i0 * (T + 1);
+            a.T = (int32_t)T; a.P = (int32_t)P; a.hapNum = (int32_t)H;
+            a.mask = io->hap_mask ? (const uint32_t *)(kws + o_mask) : nullptr;
+            a.tile = (int32_t)tile; a.max_n = max_n;
+            a.counts = (int32_t *)(kws + o_cnt) + i0 * T * cells;
+            HIPCHECK(e, vgxi_inc_count(&a, e->stream));
+            if (max_n > 0) io->passes += 1;
+            HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
+            if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)
+                return fail(e, VGX_ERR_HIP, std::string("vgx_get_incidence: counting kernel failed: ") + hipGetErrorString(er));
+            float kms = 0.f;
+            HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
+            io->ms[0] += kms;
+            return VGX_OK;
+        });
+    if (rc_chunks) return rc_chunks;
     if (io->summary) {
         char msg[512] = "";
         const int rc = vgxi_column_summary_i32("vgx_get_incidence: summary", (const int32_t *)(kws + o_cnt), n, T * cells, io->summary, e->stream, msg, sizeof msg);
         if (rc) return fail(e, rc, msg);
     }
     if (io->counts) HIPCHECK(e, hipMemcpy(io->counts, kws + o_cnt, (size_t)block_bytes, hipMemcpyDeviceToHost));
+    io->ms[2] = wall();
+    return VGX_OK;
+}
+
+// ---- infectious hosts per variant class of many replicates at the times of one grid (vgx_prevalence.hip, vgx_prevalence.h)
+// The split of vgx_get_incidence: the host clock turns every replicate's times into T + 2 bounds, the device forms the net change
+// of every (interval, population, class) over the log in place and sums the intervals up per column; the column summary reads the
+// values where they lie.
+extern "C" int vgx_get_prevalence(vgx_engine *e, vgx_prevalence_io *io) {
+    if (!e || !io || io->n < 0 || (io->n > 0 && (!io->replicates || !io->outside))) return VGX_ERR_ARG;
+    const auto t_call = std::chrono::steady_clock::now();
+    auto wall = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(); };
+    io->passes = 0;
+    io->ms[0] = io->ms[1] = io->ms[2] = 0.0;
+    if (e->last_was_tau) return fail(e, VGX_ERR_ARG, "vgx_get_prevalence: the last call was vgx_simulate_tau (counts direct chains only)");
+    if (!e->sc_host_valid || !e->dev_state_valid) return fail(e, VGX_ERR_ARG, "vgx_get_prevalence: needs a direct vgx_simulate_direct call with the event log first");
+    if (!e->call_recorded) return fail(e, VGX_ERR_ARG, "vgx_get_prevalence: the last call did not record events");
+    const int64_t n = io->n, P = e->d.popNum, H = e->d.hapNum, T = io->T, V = io->V;
+    if (T < 1 || T >= VGX_PREV_MAX_POINTS || !io->grid) return fail(e, VGX_ERR_ARG, "vgx_get_prevalence: T = " + std::to_string(T) + " grid points: at least 1, below 2^24, with grid");
+    for (int64_t k = 0; k < T; k++) {
+        if (!std::isfinite(io->grid[k])) return fail(e, VGX_ERR_ARG, "vgx_get_prevalence: grid[" + std::to_string(k) + "] is not finite");
+        if (k > 0 && !(io->grid[k - 1] < io->grid[k]))
+            return fail(e, VGX_ERR_ARG, "vgx_get_prevalence: grid must increase strictly (grid[" + std::to_string(k) + "])");
+    }
+    if (V < 1 || V > INT32_MAX || !io->variant_of) return fail(e, VGX_ERR_ARG, "vgx_get_prevalence: V = " + std::to_string(V) + " classes: at least 1, with variant_of");
+    for (int64_t h = 0; h < H; h++)
+        if (io->variant_of[h] < -1 || io->variant_of[h] >= V)
+            return fail(e, VGX_ERR_ARG, "vgx_get_prevalence: variant_of[" + std::to_string(h) + "] = " + std::to_string(io->variant_of[h]) + " is outside [-1, " + std::to_string(V) + ")");
+    for (int64_t pn = 0; pn < P; pn++)
+        if (e->sizes[(size_t)pn] >= ((int64_t)1 << 31)) return fail(e, VGX_ERR_ARG, "vgx_get_prevalence: population sizes of 2^31 or more");
+    if (vgx_prev_lds_bytes(P, V) > VGX_PREV_LDS_MAX)
+        return fail(e, VGX_ERR_ARG, "vgx_get_prevalence: " + std::to_string(P) + " populations x " + std::to_string(V) + " classes need " + std::to_string(vgx_prev_lds_bytes(P, V)) +
+                                        " bytes of cells, above the " + std::to_string((int64_t)VGX_PREV_LDS_MAX) + " bytes of LDS a counting workgroup may use");
+    const int64_t cells = P * V;
+    std::vector<int32_t> n_ev((size_t)n);
+    {
+        std::vector<char> seen((size_t)e->R, 0);
+        for (int64_t i = 0; i < n; i++) {
+            const int64_t r = io->replicates[i];
+            if (r < 0 || r >= e->R) return fail(e, VGX_ERR_ARG, "vgx_get_prevalence: replicate index out of range");
+            if (seen[(size_t)r]) return fail(e, VGX_ERR_ARG, "vgx_get_prevalence: replicates must be distinct");
+            seen[(size_t)r] = 1;
+            const VgxRepScalars &s = e->sc_host[(size_t)r];
+            const int64_t first = s.restarts > 0 ? 0 : ((size_t)r < e->call_ev0.size() ? e->call_ev0[(size_t)r] : e->ev_ptr0);
+            if (first != 0 || e->ev_base != 0)
+                return fail(e, VGX_ERR_ARG, "vgx_get_prevalence: replicate " + std::to_string(r) + ": its chain does not start in the last call's device log (the model held " +
+                                                std::to_string(e->ev_base != 0 ? e->ev_base : first) + " events when the ensemble started)");
+            if (s.ev_ptr >= VGX_PREV_MAX_EVENTS)
+                return fail(e, VGX_ERR_ARG, "vgx_get_prevalence: replicate " + std::to_string(r) + " holds a chain of " + std::to_string(s.ev_ptr) + " events (2^30 or more)");
+            if (s.ev_ptr < 0 || s.ev_ptr > e->evcap)
+                return fail(e, VGX_ERR_ARG, "vgx_get_prevalence: event range of replicate " + std::to_string(r) + " outside the device log");
+            n_ev[(size_t)i] = (int32_t)s.ev_ptr;
+        }
+    }
+    if (n == 0) {
+        io->ms[2] = wall();
+        return VGX_OK;
+    }
+    // the start of a chain folded through variant_of: the state the call started from, or the initial state after a restart
+    std::vector<int32_t> start((size_t)(n * cells));
+    {
+        std::vector<int64_t> fold[2] = {std::vector<int64_t>((size_t)cells, 0), std::vector<int64_t>((size_t)cells, 0)};
+        const std::vector<int64_t> *src[2] = {&e->hs.infectious, &e->hs.initial_infectious};
+        for (int k = 0; k < 2; k++)
+            for (int64_t pn = 0; pn < P; pn++)
+                for (int64_t h = 0; h < H; h++)
+                    if (io->variant_of[h] >= 0) fold[k][(size_t)(pn * V + io->variant_of[h])] += (*src[k])[(size_t)(pn * H + h)];
+        for (int k = 0; k < 2; k++)
+            for (int64_t c = 0; c < cells; c++)
+                if (fold[k][(size_t)c] < 0 || fold[k][(size_t)c] > INT32_MAX) return fail(e, VGX_ERR_ARG, "vgx_get_prevalence: a start value outside [0, 2^31)");
+        for (int64_t i = 0; i < n; i++) {
+            const std::vector<int64_t> &f = fold[e->sc_host[(size_t)io->replicates[i]].restarts > 0 ? 1 : 0];
+            for (int64_t c = 0; c < cells; c++) start[(size_t)(i * cells + c)] = (int32_t)f[(size_t)c];
+        }
+    }
+    int64_t tile = VGX_PREV_TILE_DEFAULT;
+    if (const char *tb = getenv("VGX_PREVALENCE_TILE_EVENTS")) tile = std::min<int64_t>(std::max<int64_t>(atoll(tb), 1), VGX_PREV_MAX_EVENTS);
+    HIPCHECK(e, hipSetDevice(e->device));
+    size_t free_b = 0, total_b = 0;
+    HIPCHECK(e, hipMemGetInfo(&free_b, &total_b));
+    auto up8 = [](int64_t b) { return (b + 255) / 256 * 256; };
+    auto dev_free = [](char *p) { (void)hipFree(p); };
+    // what stays for the whole call: [rep | n_ev | bound | variant_of | start | val | fin | min, max]
+    const int64_t val_bytes = n * T * cells * 4, fin_bytes = n * cells * 4;
+    const int64_t o_rep = 0, o_nev = o_rep + up8(n * 8), o_bnd = o_nev + up8(n * 4), o_map = o_bnd + up8(n * (T + 2) * 4), o_start = o_map + up8(H * 4),
+                  o_val = o_start + up8(fin_bytes), o_fin = o_val + up8(val_bytes), o_mm = o_fin + up8(fin_bytes), keep_total = o_mm + 256;
+    if (keep_total > (int64_t)(free_b / 2))
+        return fail(e, VGX_ERR_ARG, "vgx_get_prevalence: the block of " + std::to_string(n) + " x " + std::to_string(T + 1) + " x " + std::to_string(P) + " x " + std::to_string(V) +
+                                        " values (" + std::to_string(val_bytes + fin_bytes) + " bytes), its cuts and start take " + std::to_string(keep_total) +
+                                        " bytes, above half of the " + std::to_string((int64_t)free_b) + " bytes of free device memory: select fewer replicates per call");
+    char *kws = nullptr;
+    hipError_t er = hipMalloc((void **)&kws, (size_t)keep_total);
+    if (er != hipSuccess) return fail(e, VGX_ERR_HIP, "vgx_get_prevalence: hipMalloc of " + std::to_string(keep_total) + " bytes: " + hipGetErrorString(er));
+    std::unique_ptr<char, void (*)(char *)> khold(kws, dev_free);
+    std::vector<int64_t> reps_all(io->replicates, io->replicates + n);
+    HIPCHECK(e, hipMemcpyAsync(kws + o_rep, reps_all.data(), (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_nev, n_ev.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_map, io->variant_of, (size_t)H * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_start, start.data(), (size_t)fin_bytes, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemsetAsync(kws + o_val, 0, (size_t)(o_mm - o_val), e->stream));   // val and fin, zeroed once
+
+    const int64_t share = (int64_t)(free_b / 2) - keep_total + 4096;
+    std::vector<int32_t> bounds((size_t)(n * (T + 2)));
+    const int rc_chunks = clock_chunks(e, "vgx_get_prevalence", reps_all, n_ev, (const int64_t *)(kws + o_rep), (const int32_t *)(kws + o_nev), share, io->ms,
+        // host: a replicate's event times -> its T + 2 bounds
+        [&](int64_t gi, const std::vector<double> &times) {
+            int32_t *bound = bounds.data() + gi * (T + 2);
+            VgxPrevCutter ct{io->grid, T, bound};
+            for (size_t k = 0; k < times.size(); k++) ct.event((int64_t)k, times[k]);
+            ct.finish((int64_t)times.size());
+            io->outside[2 * gi] = bound[1];
+            io->outside[2 * gi + 1] = (int64_t)times.size() - bound[(size_t)T];
+        },
+        // device: the net changes of the chunk's replicates into their rows of the block, then the running sums of those rows
+        [&](int64_t i0, int64_t i1, int64_t max_n) -> int {
+            const int64_t m = i1 - i0;
+            HIPCHECK(e, hipMemcpyAsync(kws + o_bnd + i0 * (T + 2) * 4, bounds.data() + i0 * (T + 2), (size_t)(m * (T + 2)) * 4, hipMemcpyHostToDevice, e->stream));
+            HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
+            VgxPrevLaunch a{};
+            a.m = m;
+            a.log = (const int32_t *)e->r_evcols.p; a.evcap = e->evcap;
+            a.rep = (const int64_t *)(kws + o_rep) + i0; a.n_ev = (const int32_t *)(kws + o_nev) + i0;
+            a.bound = (const int32_t *)(kws + o_bnd) + i0 * (T + 2);
+            a.T = (int32_t)T; a.P = (int32_t)P; a.hapNum = (int32_t)H; a.V = (int32_t)V;
+            a.variant_of = (const int32_t *)(kws + o_map);
+            a.tile = (int32_t)tile; a.max_n = max_n;
+            a.val = (int32_t *)(kws + o_val) + i0 * T * cells;
+            a.fin = (int32_t *)(kws + o_fin) + i0 * cells;
+            a.start = (const int32_t *)(kws + o_start) + i0 * cells;
+            HIPCHECK(e, vgxi_prev_count(&a, e->stream));
+            if (max_n > 0) io->passes += 1;
+            HIPCHECK(e, vgxi_prev_scan(&a, e->stream));
+            HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
+            if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)
+                return fail(e, VGX_ERR_HIP, std::string("vgx_get_prevalence: counting or scan kernel failed: ") + hipGetErrorString(er));
+            float kms = 0.f;
+            HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
+            io->ms[0] += kms;
+            return VGX_OK;
+        });
+    if (rc_chunks) return rc_chunks;
+    if (io->values) HIPCHECK(e, hipMemcpy(io->values, kws + o_val, (size_t)val_bytes, hipMemcpyDeviceToHost));
+    if (io->final) HIPCHECK(e, hipMemcpy(io->final, kws + o_fin, (size_t)fin_bytes, hipMemcpyDeviceToHost));
+    if (io->summary) {
+        // the column summary sorts 32-bit keys of whole numbers in [0, 2^31)
+        int32_t mm[2] = {0, 0};
+        HIPCHECK(e, vgxi_prev_minmax((const int32_t *)(kws + o_val), n * T * cells, (int32_t *)(kws + o_mm), e->stream));
+        HIPCHECK(e, hipMemcpyAsync(mm, kws + o_mm, sizeof mm, hipMemcpyDeviceToHost, e->stream));
+        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)
+            return fail(e, VGX_ERR_HIP, std::string("vgx_get_prevalence: min/max kernel failed: ") + hipGetErrorString(er));
+        if (mm[0] < 0)
+            return fail(e, VGX_ERR_ARG, "vgx_get_prevalence: summary: a value of " + std::to_string(mm[0]) + " is not a whole number in [0, 2^31) (the log holds records outside the model)");
+        char msg[512] = "";
+        const int rc = vgxi_column_summary_i32("vgx_get_prevalence: summary", (const int32_t *)(kws + o_val), n, T * cells, io->summary, e->stream, msg, sizeof msg);
+        if (rc) return fail(e, rc, msg);
+    }
     io->ms[2] = wall();
     return VGX_OK;
 }

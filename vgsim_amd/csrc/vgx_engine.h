@@ -24,6 +24,7 @@
 #include "vgx_tline.h"
 #include "vgx_timelines.h"
 #include "vgx_incidence.h"
+#include "vgx_prevalence.h"
 
 #pragma GCC visibility push(hidden)   // nothing here is part of the exported C ABI
 
@@ -53,6 +54,9 @@ extern "C" hipError_t vgxi_tl_pack(const int32_t *log, const double *evrate, int
                                    const int64_t *off, int64_t m, int64_t max_n, int32_t *iter_out, double *rate_out, hipStream_t s);
 extern "C" hipError_t vgxi_tl_replay(const VgxTlLaunch *a, hipStream_t s);
 extern "C" hipError_t vgxi_inc_count(const VgxIncLaunch *a, hipStream_t s);
+extern "C" hipError_t vgxi_prev_count(const VgxPrevLaunch *a, hipStream_t s);
+extern "C" hipError_t vgxi_prev_scan(const VgxPrevLaunch *a, hipStream_t s);
+extern "C" hipError_t vgxi_prev_minmax(const int32_t *x, int64_t n, int32_t *out, hipStream_t s);   // out[0] = min, out[1] = max of x[0 .. n)
 // the column summary of vgx_colsummary.hip on a device int32 matrix x[R][N] of values in [0, 2^31) (a refusal's message goes to errbuf)
 extern "C" int vgxi_column_summary_i32(const char *what, const int32_t *x, int64_t R, int64_t N, vgx_traj_summary_io *io, hipStream_t stream,
                                        char *errbuf, int64_t errcap);

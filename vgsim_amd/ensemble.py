@@ -255,6 +255,51 @@ def _incidence_edges(edges, bins, window):
     return np.ascontiguousarray(e)
 
 
+class Prevalence:
+    """What ``Ensemble.prevalence`` returns: infectious hosts per selected replicate, grid time, population and variant class.
+
+    ``values`` [n, T, P, V] int32 (None when the call had ``values=False``): the hosts of class c in population p at ``times[j]``,
+    events at exactly that time applied; ``final`` [n, P, V] int32 the same after the whole chain; ``times`` [T]; ``variant_of``
+    [H] the class of every haplotype (-1: not tracked); ``outside`` [n, 2] the events of every replicate up to ``times[0]`` and
+    after ``times[T - 1]``; ``replicates`` [n]; ``summary`` a :class:`TrajectorySummary` over the [T, P, V] columns, or None;
+    ``passes``, ``kernel_ms``, ``clock_ms``, ``wall_ms``."""
+
+    def share(self):
+        """Every class's share of the tracked infected hosts of its population, [n, T, P, V] float64: ``values`` over their sum
+        across classes, 0 where no tracked host is infected."""
+        total = self.values.sum(axis=-1, keepdims=True, dtype=np.int64)
+        out = np.zeros(self.values.shape, dtype=np.float64)
+        np.divide(self.values, total, out=out, where=total != 0)
+        return out
+
+
+def _prevalence_grid(times, points, window):
+    """The grid of a ``prevalence`` call as a float64 array; ValueError for bad arguments."""
+    if (times is None) == (points is None):
+        raise ValueError("give either times or points (with window), not both and not neither")
+    if times is None:
+        points = int(points)
+        if points < 1:
+            raise ValueError("points must be at least 1")
+        if window is None or len(window) != 2:
+            raise ValueError("points needs window=(t0, t1)")
+        t0, t1 = float(window[0]), float(window[1])
+        with np.errstate(invalid='ignore', over='ignore'):   # (a window that is not finite is refused below)
+            # the trajectories' grid (t0 + j dt with dt formed once), so that both read the same instants
+            g = t0 + np.arange(points, dtype=np.float64) * ((t1 - t0) / (points - 1)) if points > 1 else np.array([t0])
+    else:
+        g = np.array(times, dtype=np.float64).ravel()
+        if len(g) < 1:
+            raise ValueError("times must hold at least one value")
+    if len(g) >= 1 << 24:
+        raise ValueError("T = %d must be at least 1 and below 2^24" % len(g))
+    if not np.all(np.isfinite(g)):
+        raise ValueError("grid must be finite")
+    if not np.all(g[1:] > g[:-1]):
+        raise ValueError("grid must increase strictly")
+    return np.ascontiguousarray(g)
+
+
 class Ensemble:
     def __init__(self, simulator, n_replicates, seeds=None, device=0, scenarios=None, scenario_of=None):
         """``simulator``: a configured ``vgsim_amd.Simulator`` (or its ``.simulation`` model) giving parameters
@@ -733,13 +778,7 @@ class Ensemble:
                 raise ValueError("population index out of range")
             if len(q) and (q[:, 1].min() < 0 or q[:, 1].max() >= width):
                 raise ValueError("%s index out of range" % what)
-        reps = np.arange(self.R, dtype=np.int64) if replicates is None else np.ascontiguousarray(replicates, dtype=np.int64).ravel()
-        n = len(reps)
-        if n and (reps.min() < 0 or reps.max() >= self.R):
-            raise ValueError("replicate index out of range")
-        if len(np.unique(reps)) != n:
-            raise ValueError("replicates must be distinct")
-        return step_num, qi, ii, qs, si, reps
+        return step_num, qi, ii, qs, si, self._selected_replicates(replicates)
 
     def _timeline_batch(self, call, step_num, qi, ii, qs, si, reps, semantics):
         """The two-call protocol of ``vgx_get_timelines`` / ``vgx_get_tau_timelines`` (``call(io)`` returns the library's code)."""
@@ -774,29 +813,40 @@ class Ensemble:
         b.passes, b.kernel_ms, b.clock_ms, b.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
         return b
 
+    def _selected_replicates(self, replicates):
+        """``replicates`` as an int64 array of distinct indices (default all, in order); ValueError otherwise."""
+        reps = np.arange(self.R, dtype=np.int64) if replicates is None else np.ascontiguousarray(replicates, dtype=np.int64).ravel()
+        if len(reps) and (reps.min() < 0 or reps.max() >= self.R):
+            raise ValueError("replicate index out of range")
+        if len(np.unique(reps)) != len(reps):
+            raise ValueError("replicates must be distinct")
+        return reps
+
+    def _block_summary(self, summary, reps, cols, scenario_of, n_scenarios):
+        """The ``summary=`` dict of ``incidence()``, ``tau_incidence()`` and ``prevalence()`` checked and turned into the
+        (io, finish) of ``_summary_request`` over the selected replicates' block with columns of the shape ``cols``;
+        (None, None) without one."""
+        if summary is None:
+            return None, None
+        unknown = set(summary) - {"quantiles", "by", "method"}
+        if unknown:
+            raise ValueError("summary takes quantiles, by and method: got %s" % ", ".join(sorted(unknown)))
+        method = summary.get("method", 'linear')
+        q = _summary_quantiles(summary.get("quantiles", (0.025, 0.5, 0.975)), method)
+        group_of, G = _summary_groups(summary.get("by", 'auto'), None, self.R, scenario_of, n_scenarios)
+        return _summary_request(np.ascontiguousarray(group_of[reps]), G, q, method, cols)
+
     def _incidence_request(self, io, e, replicates, haplotypes, summary, counts, dtype, scenario_of, n_scenarios):
         """What ``incidence()`` and ``tau_incidence()`` share: the checks on ``replicates``, ``haplotypes``, ``summary`` and ``counts``
         (ValueError before the library is called) and the fields both io structures have.  Returns ``finish(check)``, which the caller
         invokes after its own checks: ``check()`` makes the library call; the result is the :class:`Incidence`."""
         m = self.model
-        reps = np.arange(self.R, dtype=np.int64) if replicates is None else np.ascontiguousarray(replicates, dtype=np.int64).ravel()
+        reps = self._selected_replicates(replicates)
         n = len(reps)
-        if n and (reps.min() < 0 or reps.max() >= self.R):
-            raise ValueError("replicate index out of range")
-        if len(np.unique(reps)) != n:
-            raise ValueError("replicates must be distinct")
         mask = None if haplotypes is None else _capi.haplotype_mask(haplotypes, m.hapNum)
         T, P, K = len(e) - 1, m.popNum, len(Incidence.CHANNELS)
-        sio = done = None
-        if summary is not None:
-            unknown = set(summary) - {"quantiles", "by", "method"}
-            if unknown:
-                raise ValueError("summary takes quantiles, by and method: got %s" % ", ".join(sorted(unknown)))
-            method = summary.get("method", 'linear')
-            q = _summary_quantiles(summary.get("quantiles", (0.025, 0.5, 0.975)), method)
-            group_of, G = _summary_groups(summary.get("by", 'auto'), None, self.R, scenario_of, n_scenarios)
-            sio, done = _summary_request(np.ascontiguousarray(group_of[reps]), G, q, method, (T, P, K))
-        elif not counts:
+        sio, done = self._block_summary(summary, reps, (T, P, K), scenario_of, n_scenarios)
+        if summary is None and not counts:
             raise ValueError("counts=False needs summary=: the call would return nothing")
         block = np.zeros((n, T, P, K), dtype=dtype) if counts else None
         outside = np.zeros((max(n, 1), 2), dtype=np.int64)
@@ -868,6 +918,61 @@ class Ensemble:
         finish = self._incidence_request(io, e, replicates, haplotypes, summary, counts, np.int64, None, 1)
         eng, pre = self.engine, self._tau_prefix_struct()
         return finish(lambda: eng._check(eng.lib.vgx_get_tau_incidence(eng.handle, C.byref(io), C.byref(pre))))
+
+    def prevalence(self, times=None, points=None, window=None, variants=None, replicates=None, summary=None, values=True):
+        """Infectious hosts per grid time, population and variant class of every selected replicate of the last direct
+        ``simulate(record_events=True)`` call, on ONE grid for all replicates and on the device (``vgx_get_prevalence``): a
+        tile-parallel pass over every replicate's log where the kernel left it forms the net change per interval, a scan sums
+        the intervals up.  Returns a :class:`Prevalence`.
+
+        The grid: ``times`` [T] strictly increasing, or ``points`` and ``window=(t0, t1)``, which form
+        ``t0 + j ((t1 - t0) / (points - 1))``, the grid of ``simulate(traj_points=, traj_window=)`` (``points=1``: ``[t0]``).  A
+        grid time gets the state with every event up to and including that time applied, as the trajectories do.
+        ``variants``: None (every haplotype its own class), an integer array [H] of classes with -1 for haplotypes that are not
+        tracked, or a sequence of sequences of haplotype indices (class k = the k-th sequence, the rest not tracked).
+        ``replicates``: indices (default all, in order).  ``summary``: a dict of ``quantiles``, ``by`` and ``method`` as
+        ``trajectory_summary`` takes them: the values are summarised across the selected replicates in the same call, where
+        they lie (``by='auto'``: one group per scenario of a scenario ensemble); with ``values=False`` the block itself is not
+        copied to the host.  Direct chains only."""
+        g = _prevalence_grid(times, points, window)
+        if self._last_call is None:
+            raise ValueError("prevalence() needs a direct simulate(record_events=True) call first")
+        if self._last_call[0] != 'direct':
+            raise ValueError("prevalence() counts direct chains only: the last call was simulate_tau")
+        if not self._last_call[1]:
+            raise ValueError("prevalence() needs the event log: the last call had record_events=False")
+        m, eng = self.model, self.engine
+        reps = self._selected_replicates(replicates)
+        n = len(reps)
+        vo, V = _capi.variant_map(variants, m.hapNum)
+        T, P = len(g), m.popNum
+        if 4 * P * V > 65536:
+            raise ValueError("%d populations x %d classes need %d bytes of cells, above the 65536 bytes of LDS a counting workgroup may use"
+                             % (P, V, 4 * P * V))
+        sio, done = self._block_summary(summary, reps, (T, P, V), self.scenario_of, len(self.scenarios) if self.scenarios is not None else 1)
+        if summary is None and not values:
+            raise ValueError("values=False needs summary=: the call would return nothing")
+        for r in reps:
+            c = eng.counters(int(r))
+            if c.ev_first_new != 0:
+                raise ValueError("replicate %d: its chain does not start in the last call's device log (the model held %d events "
+                                 "when the ensemble started)" % (r, c.ev_first_new))
+        block = np.zeros((n, T, P, V), dtype=np.int32) if values else None
+        final = np.zeros((n, P, V), dtype=np.int32)
+        outside = np.zeros((max(n, 1), 2), dtype=np.int64)
+        i32 = C.POINTER(C.c_int32)
+        io = _capi.VgxPrevalenceIO()
+        io.n, io.replicates, io.T, io.grid, io.V, io.variant_of = n, _capi._p(reps), T, _capi._p(g), V, vo.ctypes.data_as(i32)
+        io.values = block.ctypes.data_as(i32) if values and n else None
+        io.final = final.ctypes.data_as(i32) if n else None
+        io.outside = _capi._p(outside)
+        io.summary = C.pointer(sio) if sio is not None and n else None
+        eng._check(eng.lib.vgx_get_prevalence(eng.handle, C.byref(io)))
+        pv = Prevalence()
+        pv.values, pv.final, pv.times, pv.variant_of, pv.outside, pv.replicates = block, final, g, vo, outside[:n], reps
+        pv.summary = done() if done is not None else None
+        pv.passes, pv.kernel_ms, pv.clock_ms, pv.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
+        return pv
 
     def trajectories(self, out=None):
         """Summary trajectories of the last call, ``[R, T, P, 2]`` float64 (infectious, susceptible per population).
