@@ -34,7 +34,7 @@
  *   VGX_COLSUMMARY_CHUNK_BYTES=n   vgx_get_trajectory_summary, vgx_test_column_summary: device bytes of the transposed scratch per chunk of
  *                                  columns (default 2^28; one tile of 64 columns at the least)
  *   VGX_INCIDENCE_TILE_EVENTS=n    vgx_get_incidence / vgx_get_tau_incidence: consecutive events (rows) a counting workgroup takes (default 4096; no result depends on it)
- *   VGX_PREVALENCE_TILE_EVENTS=n   vgx_get_prevalence: consecutive events a counting workgroup takes (default 4096; no result depends on it)
+ *   VGX_PREVALENCE_TILE_EVENTS=n   vgx_get_prevalence / vgx_get_tau_prevalence: consecutive events (rows) a counting workgroup takes (default 4096; no result depends on it)
  */
 #ifndef VGX_H
 #define VGX_H
@@ -678,6 +678,76 @@ typedef struct vgx_tau_incidence_chain {
     int64_t *outside;                            /* out [2] */
 } vgx_tau_incidence_chain;
 int vgx_test_tau_incidence(vgx_tau_incidence_chain *io, char *errbuf, int64_t errcap);
+
+/* vgx_get_prevalence for many replicates of the last vgx_simulate_tau call (with the event log), on the device.
+ * The chain is that of vgx_get_tau_incidence: weighted rows (num, type, haplotype, population, newHaplotype, newPopulation), six
+ * int64: `prefix` flattened, then the replicate's own rows where the tau kernels left them; a replicate that restarted has no
+ * prefix.  An EVENT is a direct event or a step, with the time of its log record.  The bounds are row indices:
+ * cut[j] = first row of the first event i with grid[j] < t_i (the row count if none), by the literal loop over events (an event
+ * without rows still advances it; its cut is the first row after it).  The comparison is strict, as vgx_get_prevalence's and the
+ * tau trajectories' is: all rows of a step share an interval, and a grid point at exactly a step's time has the step applied.
+ * A row changes the cells of vgx_get_prevalence's table with sign * num: VGX_TL_ROW_DIRECT is masked off the type, a field that
+ * is not a 32-bit index matches nothing, a row with num <= 0 changes nothing.
+ *   values[r][j] = start_r + the sum of the changes of the intervals 0 .. j,   final[r] = the same over all T + 1 intervals
+ * outside[r] = (sum of num over the rows before cut[0], over the rows from cut[T-1] on), over num > 0.
+ * start_r is the state the chain starts from, folded through variant_of: the model's initial state (what vgx_get_state gives as
+ * initial_infectious) when the replicate restarted (vgx_counters.restarts > 0) or the prefix is not empty, since the chain then
+ * starts at the beginning of the model's history; otherwise the state the call started from (the host state after its first-call
+ * preparation, the index case included), which is the source vgx_get_prevalence uses for its rows that did not restart.  With
+ * every haplotype tracked final[r] is the replicate's final infectious state (vgx_get_tau_states_all).
+ * Cells and values are int64: an interval sums num over many steps.  A counting workgroup takes one chain and a tile of
+ * VGX_PREVALENCE_TILE_EVENTS rows (default 4096), finds its first interval by a search in the chain's bounds, accumulates the
+ * signed num in popNum * V int64 cells in LDS and adds the nonzero cells to a block of net changes in device memory at every
+ * interval change and at the tile's end; rows outside [cut[0], cut[T-1]) still count, in interval 0 or the tail.  With one grid
+ * the prefix is the same part of every chain that carries it: it is flattened, uploaded and counted ONCE per call into a net block
+ * of its own; the net block of every replicate that did not restart starts from it (value intervals, tail and `outside`), the
+ * replicate's own rows are added, and a scan kernel turns every (replicate, population, class) column into running sums (wrapping
+ * as unsigned 64-bit integers).  All of it is integer work: no result depends on the tile size, the launch geometry or the
+ * chunking.  No host clock runs (step times are host doubles); replicates go in chunks under VGX_TIMELINES_CHUNK_BYTES.
+ * `summary` as in vgx_get_prevalence, over `values` as a matrix [n][T * popNum * V]: one device pass narrows the block to int32
+ * and finds its minimum and maximum; a value below 0 or of 2^31 or more refuses the summary (VGX_ERR_ARG, the offending value in
+ * the message) after values and final, if asked for, have been written.  ms[1] is the host's cut search.
+ * Refusals (VGX_ERR_ARG, worded alike behind "vgx_get_tau_prevalence: "): the last call was not vgx_simulate_tau; it recorded no
+ * rows; a replicate that did not restart continues a log of another length than prefix->ev_ptr; prefix plus own rows reach 2^31;
+ * a null prefix column; replicates out of range or given twice; a grid that is not finite or does not increase; T outside
+ * [1, 2^24); V < 1 or a variant_of value outside [-1, V); popNum * V * 8 bytes of cells above the 65536 bytes of LDS a counting
+ * workgroup may use; a block (8 n (T + 1) popNum V bytes, 4 more per cell with a summary) above half of the free device memory
+ * (the message gives the bytes: select fewer replicates). */
+typedef struct vgx_tau_prevalence_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    int64_t T; const double *grid;               /* [T] strictly increasing, finite */
+    int64_t V; const int32_t *variant_of;        /* [hapNum], values in [-1, V) */
+    int64_t *values;                             /* NULL or host [n][T][P][V] */
+    int64_t *final;                              /* NULL or host [n][P][V] */
+    int64_t *outside;                            /* [n][2] */
+    vgx_traj_summary_io *summary;                /* NULL or the summary of [n][T*P*V]; group_of has n entries */
+    int64_t passes; double ms[3];                /* out: counting launches; kernels, host cut search, whole call */
+} vgx_tau_prevalence_io;
+int vgx_get_tau_prevalence(vgx_engine *e, vgx_tau_prevalence_io *io, const vgx_timelines_prefix *prefix);
+/* Test hook: the flattening, bounds, tile walk, prefix-plus-own sum and scan of vgx_get_tau_prevalence compiled for the host, on
+ * one chain given as event columns and multievent columns (no device, no engine), tile after tile of `tile` rows (0: the default).
+ * The last n_own_events events play the replicate's own steps (-1: the chain's trailing MULTITYPE events), everything before them
+ * the prefix; the prefix is counted once as a chain of its own and the own rows' net changes are added, as on the device.  Prefix
+ * rows pass the checks of the flattening (a negative num or a field outside 32 bits is refused); own rows are taken as they are,
+ * as the device reads them.  start [P][V]: the state the chain starts from, folded.  values [T][P][V], final [P][V] and outside
+ * [2] are overwritten.  Refused with the message in errbuf: a bad grid, V or variant_of, P * V * 8 bytes above the LDS budget, a
+ * MULTITYPE row range outside the multievent log. */
+typedef struct vgx_tau_prevalence_chain {
+    int64_t popNum, hapNum;
+    int64_t ev_ptr;
+    const double *ev_times;
+    const int64_t *ev_types, *ev_haplotypes, *ev_populations, *ev_newHaplotypes, *ev_newPopulations;
+    int64_t mev_rows;
+    const int64_t *mev_num, *mev_types, *mev_haplotypes, *mev_populations, *mev_newHaplotypes, *mev_newPopulations;
+    int64_t T; const double *grid;               /* [T] */
+    int64_t V; const int32_t *variant_of;        /* [hapNum] */
+    const int64_t *start;                        /* [P][V] */
+    int64_t tile, n_own_events;
+    int64_t *values;                             /* out [T][P][V] */
+    int64_t *final;                              /* out [P][V] */
+    int64_t *outside;                            /* out [2] */
+} vgx_tau_prevalence_chain;
+int vgx_test_tau_prevalence(vgx_tau_prevalence_chain *io, char *errbuf, int64_t errcap);
 
 /* ---- kernel choice of the direct path ------------------------------------------------------- */
 /* What the choice of a direct call's kernel reads: the model's dimensions, the state the call starts from and two diagnostic

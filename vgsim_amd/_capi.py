@@ -158,6 +158,22 @@ class VgxTauIncidenceChain(C.Structure):
                 ("counts", _I), ("outside", _I)]
 
 
+class VgxTauPrevalenceIO(C.Structure):
+    _fields_ = [("n", C.c_int64), ("replicates", _I), ("T", C.c_int64), ("grid", _F), ("V", C.c_int64), ("variant_of", C.POINTER(C.c_int32)),
+                ("values", _I), ("final", _I), ("outside", _I), ("summary", C.POINTER(VgxTrajSummaryIO)),
+                ("passes", C.c_int64), ("ms", C.c_double * 3)]
+
+
+class VgxTauPrevalenceChain(C.Structure):
+    _fields_ = [("popNum", C.c_int64), ("hapNum", C.c_int64), ("ev_ptr", C.c_int64),
+                ("ev_times", _F), ("ev_types", _I), ("ev_haplotypes", _I), ("ev_populations", _I),
+                ("ev_newHaplotypes", _I), ("ev_newPopulations", _I),
+                ("mev_rows", C.c_int64), ("mev_num", _I), ("mev_types", _I), ("mev_haplotypes", _I), ("mev_populations", _I),
+                ("mev_newHaplotypes", _I), ("mev_newPopulations", _I),
+                ("T", C.c_int64), ("grid", _F), ("V", C.c_int64), ("variant_of", C.POINTER(C.c_int32)), ("start", _I),
+                ("tile", C.c_int64), ("n_own_events", C.c_int64), ("values", _I), ("final", _I), ("outside", _I)]
+
+
 INCIDENCE_CHANNELS = ('birth', 'death', 'sampling', 'mutation', 'immunity', 'arrival', 'departure')   # vgx.h: channels 0 .. 6
 
 COLSUMMARY_MAX_GROUP = 16384   # members of one group the device pass sorts (vgx.h: VGX_COLSUMMARY_MAX_GROUP)
@@ -241,6 +257,8 @@ SIGNATURES = {
                                       C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, C.c_char_p, C.c_int64]),
     "vgx_get_tau_incidence": (C.c_int, [_H, C.POINTER(VgxTauIncidenceIO), C.POINTER(VgxTimelinesPrefix)]),
     "vgx_test_tau_incidence": (C.c_int, [C.POINTER(VgxTauIncidenceChain), C.c_char_p, C.c_int64]),
+    "vgx_get_tau_prevalence": (C.c_int, [_H, C.POINTER(VgxTauPrevalenceIO), C.POINTER(VgxTimelinesPrefix)]),
+    "vgx_test_tau_prevalence": (C.c_int, [C.POINTER(VgxTauPrevalenceChain), C.c_char_p, C.c_int64]),
     "vgx_test_direct_plan": (C.c_int, [C.POINTER(VgxDirectShape), C.POINTER(VgxRunOpts), C.POINTER(VgxDirectPlan), C.c_char_p, C.c_int64]),
     "vgx_rng_position": (None, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64 * 4)]),
     "vgx_propensity_scan": (C.c_int, [C.POINTER(VgxRowScan)]),
@@ -929,6 +947,49 @@ def replay_tau_incidence(events, mev, popNum, hapNum, edges, hap_mask=None, tile
     if load_library().vgx_test_tau_incidence(C.byref(io), err, 512) != VGX_OK:
         raise ValueError(err.value.decode() or "vgx_test_tau_incidence failed")
     return counts, outside
+
+
+def replay_tau_prevalence(events, mev, popNum, hapNum, grid, variant_of, V, start, tile=0, n_own_events=-1):
+    """The values of ``Ensemble.tau_prevalence`` for one chain through ``vgx_test_tau_prevalence``: the device's flattening, bounds,
+    signed cells, tile walk, prefix-plus-own sum and scan (vgx_tau_prevalence.h) compiled for the host, tile after tile of ``tile``
+    rows (0: the default); no GPU.  ``events`` and ``mev`` as ``replay_tau_incidence`` takes them; the last ``n_own_events`` events
+    play the replicate's own steps (-1: the trailing MULTITYPE events), everything before them the prefix, which is counted once
+    as on the device.  ``variant_of`` [hapNum] with values in [-1, V); ``start`` [P, V] the chain's start folded through it.
+    Returns (values [T, P, V] int64, final [P, V] int64, outside [2] int64); a refusal raises ``ValueError`` with the library's
+    message."""
+    times = np.ascontiguousarray(events[0], dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.int64) for c in events[1:6]]
+    n = len(times)
+    if len(cols) != 5 or any(len(c) != n for c in cols):
+        raise ValueError("event columns of different lengths")
+    mcols = [np.ascontiguousarray(mev[c] if mev is not None else [], dtype=np.int64) for c in MEV_COLUMNS]
+    if len({len(c) for c in mcols}) != 1:
+        raise ValueError("multievent columns of different lengths")
+    grid = np.ascontiguousarray(grid, dtype=np.float64)
+    T, P, V = len(grid), int(popNum), int(V)
+    vo = np.ascontiguousarray(variant_of, dtype=np.int32)
+    if len(vo) != int(hapNum):
+        raise ValueError("variant_of must hold hapNum values")
+    start = np.ascontiguousarray(start, dtype=np.int64)
+    if start.shape != (P, V):
+        raise ValueError("start must have the shape [P, V]")
+    values = np.zeros((max(T, 1), max(P, 1), max(V, 1)), dtype=np.int64)
+    final = np.zeros((max(P, 1), max(V, 1)), dtype=np.int64)
+    outside = np.zeros(2, dtype=np.int64)
+    io = VgxTauPrevalenceChain()
+    io.popNum, io.hapNum, io.ev_ptr, io.ev_times = P, int(hapNum), n, _p(times)
+    for name, col in zip(("types", "haplotypes", "populations", "newHaplotypes", "newPopulations"), cols):
+        setattr(io, "ev_" + name, _p(col))
+    io.mev_rows = len(mcols[0])
+    for name, col in zip(MEV_COLUMNS, mcols):
+        setattr(io, "mev_" + name, _p(col))
+    io.T, io.grid, io.V, io.variant_of, io.start = T, _p(grid), V, vo.ctypes.data_as(C.POINTER(C.c_int32)), _p(start)
+    io.tile, io.n_own_events = int(tile), int(n_own_events)
+    io.values, io.final, io.outside = _p(values), _p(final), _p(outside)
+    err = C.create_string_buffer(512)
+    if load_library().vgx_test_tau_prevalence(C.byref(io), err, 512) != VGX_OK:
+        raise ValueError(err.value.decode() or "vgx_test_tau_prevalence failed")
+    return values, final, outside
 
 
 def column_summary(x, group_of, G, ranks):

@@ -258,7 +258,7 @@ def _incidence_edges(edges, bins, window):
 class Prevalence:
     """What ``Ensemble.prevalence`` returns: infectious hosts per selected replicate, grid time, population and variant class.
 
-    ``values`` [n, T, P, V] int32 (None when the call had ``values=False``): the hosts of class c in population p at ``times[j]``,
+    ``values`` [n, T, P, V] int32 (int64 from ``tau_prevalence``, as ``final``; None when the call had ``values=False``): the hosts of class c in population p at ``times[j]``,
     events at exactly that time applied; ``final`` [n, P, V] int32 the same after the whole chain; ``times`` [T]; ``variant_of``
     [H] the class of every haplotype (-1: not tracked); ``outside`` [n, 2] the events of every replicate up to ``times[0]`` and
     after ``times[T - 1]``; ``replicates`` [n]; ``summary`` a :class:`TrajectorySummary` over the [T, P, V] columns, or None;
@@ -823,7 +823,7 @@ class Ensemble:
         return reps
 
     def _block_summary(self, summary, reps, cols, scenario_of, n_scenarios):
-        """The ``summary=`` dict of ``incidence()``, ``tau_incidence()`` and ``prevalence()`` checked and turned into the
+        """The ``summary=`` dict of ``incidence()``, ``tau_incidence()``, ``prevalence()`` and ``tau_prevalence()`` checked and turned into the
         (io, finish) of ``_summary_request`` over the selected replicates' block with columns of the shape ``cols``;
         (None, None) without one."""
         if summary is None:
@@ -941,17 +941,9 @@ class Ensemble:
             raise ValueError("prevalence() counts direct chains only: the last call was simulate_tau")
         if not self._last_call[1]:
             raise ValueError("prevalence() needs the event log: the last call had record_events=False")
-        m, eng = self.model, self.engine
-        reps = self._selected_replicates(replicates)
-        n = len(reps)
-        vo, V = _capi.variant_map(variants, m.hapNum)
-        T, P = len(g), m.popNum
-        if 4 * P * V > 65536:
-            raise ValueError("%d populations x %d classes need %d bytes of cells, above the 65536 bytes of LDS a counting workgroup may use"
-                             % (P, V, 4 * P * V))
-        sio, done = self._block_summary(summary, reps, (T, P, V), self.scenario_of, len(self.scenarios) if self.scenarios is not None else 1)
-        if summary is None and not values:
-            raise ValueError("values=False needs summary=: the call would return nothing")
+        eng = self.engine
+        reps, n, vo, V, T, P, sio, done = self._prevalence_request(g, variants, replicates, summary, values, 4, self.scenario_of,
+                                                                   len(self.scenarios) if self.scenarios is not None else 1)
         for r in reps:
             c = eng.counters(int(r))
             if c.ev_first_new != 0:
@@ -968,6 +960,62 @@ class Ensemble:
         io.outside = _capi._p(outside)
         io.summary = C.pointer(sio) if sio is not None and n else None
         eng._check(eng.lib.vgx_get_prevalence(eng.handle, C.byref(io)))
+        pv = Prevalence()
+        pv.values, pv.final, pv.times, pv.variant_of, pv.outside, pv.replicates = block, final, g, vo, outside[:n], reps
+        pv.summary = done() if done is not None else None
+        pv.passes, pv.kernel_ms, pv.clock_ms, pv.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
+        return pv
+
+    def _prevalence_request(self, g, variants, replicates, summary, values, cell_bytes, scenario_of, n_scenarios):
+        """What ``prevalence()`` and ``tau_prevalence()`` share: the checks on ``replicates``, ``variants``, the LDS limit (cells of
+        ``cell_bytes`` bytes), ``summary`` and ``values`` (ValueError before the library is called).  Returns (replicates, n,
+        variant_of, V, T, P, the summary's io, its finish)."""
+        m = self.model
+        reps = self._selected_replicates(replicates)
+        vo, V = _capi.variant_map(variants, m.hapNum)
+        T, P = len(g), m.popNum
+        if cell_bytes * P * V > 65536:
+            raise ValueError("%d populations x %d classes need %d bytes of cells, above the 65536 bytes of LDS a counting workgroup may use"
+                             % (P, V, cell_bytes * P * V))
+        sio, done = self._block_summary(summary, reps, (T, P, V), scenario_of, n_scenarios)
+        if summary is None and not values:
+            raise ValueError("values=False needs summary=: the call would return nothing")
+        return reps, len(reps), vo, V, T, P, sio, done
+
+    def tau_prevalence(self, times=None, points=None, window=None, variants=None, replicates=None, summary=None, values=True):
+        """``prevalence()`` for the replicates of the last ``simulate_tau(record_events=True)`` call (``vgx_get_tau_prevalence``):
+        the same grid arguments, ``variants``, ``summary`` and :class:`Prevalence`, with ``values`` [n, T, P, V] and ``final``
+        [n, P, V] int64 (an interval sums the multiplicities of many steps) and ``outside`` the summed multiplicities up to
+        ``times[0]`` and after ``times[T - 1]``.
+
+        A replicate's chain is the model's chain before the tau call (a replicate that restarted has none), then its own steps,
+        every multievent row changing its cells by ``num``.  All events of a step carry the time of the step's MULTITYPE record, so
+        a grid time at exactly a step's time has the whole step applied, as ``simulate_tau(traj_points=, traj_window=)`` has.  The
+        values start from the model's initial state when the chain starts at the beginning of the model's history (the model held
+        events before the call, or the replicate restarted), else from the state the call started from.  The shared part is
+        counted once per call on the device, not once per replicate; no host clock runs.  ``summary``: refused by the library
+        when a value is negative or reaches 2^31 (``values`` stays available: call again without ``summary``).  ``by='auto'`` is
+        one group (scenario ensembles have no ``simulate_tau``)."""
+        g = _prevalence_grid(times, points, window)
+        if self._last_call is None:
+            raise ValueError("tau_prevalence() needs a simulate_tau(record_events=True) call first")
+        if self._last_call[0] != 'tau':
+            raise ValueError("tau_prevalence() counts tau chains only: the last call was a direct simulate()")
+        if not self._last_call[1]:
+            raise ValueError("tau_prevalence() needs the multievent rows: the last call had record_events=False")
+        reps, n, vo, V, T, P, sio, done = self._prevalence_request(g, variants, replicates, summary, values, 8, None, 1)
+        block = np.zeros((n, T, P, V), dtype=np.int64) if values else None
+        final = np.zeros((n, P, V), dtype=np.int64)
+        outside = np.zeros((max(n, 1), 2), dtype=np.int64)
+        io = _capi.VgxTauPrevalenceIO()
+        io.n, io.replicates, io.T, io.grid, io.V = n, _capi._p(reps), T, _capi._p(g), V
+        io.variant_of = vo.ctypes.data_as(C.POINTER(C.c_int32))
+        io.values = _capi._p(block) if values and n else None
+        io.final = _capi._p(final) if n else None
+        io.outside = _capi._p(outside)
+        io.summary = C.pointer(sio) if sio is not None and n else None
+        eng, pre = self.engine, self._tau_prefix_struct()
+        eng._check(eng.lib.vgx_get_tau_prevalence(eng.handle, C.byref(io), C.byref(pre)))
         pv = Prevalence()
         pv.values, pv.final, pv.times, pv.variant_of, pv.outside, pv.replicates = block, final, g, vo, outside[:n], reps
         pv.summary = done() if done is not None else None
