@@ -34,7 +34,7 @@
  *   VGX_COLSUMMARY_CHUNK_BYTES=n   vgx_get_trajectory_summary, vgx_test_column_summary: device bytes of the transposed scratch per chunk of
  *                                  columns (default 2^28; one tile of 64 columns at the least)
  *   VGX_INCIDENCE_TILE_EVENTS=n    vgx_get_incidence / vgx_get_tau_incidence: consecutive events (rows) a counting workgroup takes (default 4096; no result depends on it)
- *   VGX_PREVALENCE_TILE_EVENTS=n   vgx_get_prevalence / vgx_get_tau_prevalence: consecutive events (rows) a counting workgroup takes (default 4096; no result depends on it)
+ *   VGX_PREVALENCE_TILE_EVENTS=n   vgx_get_prevalence / vgx_get_tau_prevalence and vgx_get_susceptibles / vgx_get_tau_susceptibles: consecutive events (rows) a counting workgroup takes (default 4096; no result depends on it)
  */
 #ifndef VGX_H
 #define VGX_H
@@ -748,6 +748,91 @@ typedef struct vgx_tau_prevalence_chain {
     int64_t *outside;                            /* out [2] */
 } vgx_tau_prevalence_chain;
 int vgx_test_tau_prevalence(vgx_tau_prevalence_chain *io, char *errbuf, int64_t errcap);
+
+/* ---- susceptibles: hosts per immunity group on a common grid ------------------------------------ */
+/* How many hosts are immune to what, when: the other half of the state vgx_get_prevalence counts, on the same kind of grid
+ * (DESIGN.md §20).  The caller gives grid[0 .. T-1] as for vgx_get_prevalence and a map class_of[susNum] with values in [-1, G):
+ * the class of every susceptibility group, -1 = not tracked.  Cuts, intervals, the strict comparison and `outside` are
+ * vgx_get_prevalence's, literally.  A log record (type, haplotype, population, newHaplotype, newPopulation) changes
+ *   BIRTH              -1 at (population, class_of[newHaplotype])
+ *   DEATH, SAMPLING    +1 at (population, class_of[newHaplotype])
+ *   SUSCCHANGE         +1 at (population, class_of[newHaplotype]), -1 at (population, class_of[haplotype]); equal classes change nothing
+ *   MIGRATION          -1 at (newPopulation, class_of[newHaplotype])
+ *   MUTATION           nothing
+ * each side only if its class is tracked (the susceptible side of the 'compartment' semantics of vgx_get_timelines folded through
+ * class_of: the log keeps the group of the host that leaves or joins the susceptibles in newHaplotype).  A type outside 0..5, a
+ * population key outside [0, popNum) or a group outside [0, susNum) counts nowhere; a record changes at most two cells.
+ *   values[r][j] = start_r + the sum of the changes of the intervals 0 .. j,   final[r] = the same over all T + 1 intervals
+ * where start_r is the susceptible state the call started from folded through class_of, or the initial susceptible state for a
+ * replicate that restarted (vgx_counters.restarts > 0).  With every group tracked final[r] is the replicate's final susceptible
+ * state (vgx_get_state) folded through class_of, and with every haplotype tracked in a vgx_get_prevalence call on the same grid
+ * the two blocks add up to the population sizes at every grid point.
+ * The device pass is vgx_get_prevalence's with a counting kernel of its own for this rule (popNum * G int32 cells in LDS,
+ * class_of staged behind them when it fits, VGX_PREVALENCE_TILE_EVENTS events per tile) and the same scan, min/max pass and
+ * column summary; the host clock runs as there (VGX_TIMELINES_CHUNK_BYTES).  No result depends on the tile size, the launch
+ * geometry or the chunking.  `summary` and a NULL `values` as in vgx_get_prevalence.
+ * Preconditions and refusals are vgx_get_prevalence's, worded alike behind "vgx_get_susceptibles: " with G and class_of in place
+ * of V and variant_of: popNum * G * 4 bytes of cells above the 65536 bytes of LDS a counting workgroup may use, T outside
+ * [1, 2^24), a chain of 2^30 events or more, a block above half of the free device memory.  vgx_clock_mismatches counts every
+ * selected replicate once. */
+typedef struct vgx_susceptibles_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    int64_t T; const double *grid;               /* [T] strictly increasing, finite */
+    int64_t G; const int32_t *class_of;          /* [susNum], values in [-1, G) */
+    int32_t *values;                             /* NULL or host [n][T][P][G] */
+    int32_t *final;                              /* NULL or host [n][P][G] */
+    int64_t *outside;                            /* [n][2]: events before cut[0] / from cut[T-1] on */
+    vgx_traj_summary_io *summary;                /* NULL or the summary of [n][T*P*G]; group_of has n entries */
+    int64_t passes; double ms[3];                /* out: launches of the counting kernel; kernels, host clock, whole call */
+} vgx_susceptibles_io;
+int vgx_get_susceptibles(vgx_engine *e, vgx_susceptibles_io *io);
+/* Test hook: the rule, the tile walk and the scan of vgx_get_susceptibles compiled for the host, on one chain given as arrays (no
+ * device, no engine), tile after tile with `tile` events each (0: the default).  start [P][G]: whole numbers in [0, 2^31).
+ * values [T][P][G], final [P][G] and outside [2] are overwritten.  The same limits: the LDS budget, a chain of 2^30 events, a bad
+ * grid, G or class_of are refused with the message in errbuf. */
+int vgx_test_susceptibles(const double *times, const int64_t *types, const int64_t *haplotypes, const int64_t *populations,
+                          const int64_t *newHaplotypes, const int64_t *newPopulations, int64_t n_ev, int64_t P, int64_t susNum,
+                          const double *grid, int64_t T, const int32_t *class_of, int64_t G, const int64_t *start, int64_t tile,
+                          int32_t *values, int32_t *final, int64_t *outside, char *errbuf, int64_t errcap);
+
+/* vgx_get_susceptibles for many replicates of the last vgx_simulate_tau call (with the event log), on the device: vgx_get_tau_prevalence
+ * over the table above.  Rows, bounds, `outside`, the prefix counted once, int64 cells and values, the chunking
+ * and the summary are vgx_get_tau_prevalence's: a row changes the cells of the table with sign * num, VGX_TL_ROW_DIRECT is masked
+ * off the type, a field that is not a 32-bit index matches nothing, a row with num <= 0 changes nothing.  A MIGRATION row's group
+ * is its newHaplotype field, as for a direct record.  start_r is the model's initial susceptible state (initial_susceptible of
+ * vgx_get_state) when the replicate restarted or the prefix is not empty, otherwise the susceptible state the call started from,
+ * folded through class_of.  With every group tracked final[r] is the replicate's final susceptible state
+ * (vgx_get_tau_states_all).  Refusals as vgx_get_tau_prevalence's behind "vgx_get_tau_susceptibles: ", with popNum * G * 8 bytes
+ * of cells against the LDS budget. */
+typedef struct vgx_tau_susceptibles_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    int64_t T; const double *grid;               /* [T] strictly increasing, finite */
+    int64_t G; const int32_t *class_of;          /* [susNum], values in [-1, G) */
+    int64_t *values;                             /* NULL or host [n][T][P][G] */
+    int64_t *final;                              /* NULL or host [n][P][G] */
+    int64_t *outside;                            /* [n][2] */
+    vgx_traj_summary_io *summary;                /* NULL or the summary of [n][T*P*G]; group_of has n entries */
+    int64_t passes; double ms[3];                /* out: counting launches; kernels, host cut search, whole call */
+} vgx_tau_susceptibles_io;
+int vgx_get_tau_susceptibles(vgx_engine *e, vgx_tau_susceptibles_io *io, const vgx_timelines_prefix *prefix);
+/* Test hook: vgx_test_tau_prevalence over the table above (the flattening, bounds, tile walk, prefix-plus-own sum and scan of
+ * vgx_get_tau_susceptibles compiled for the host).  start [P][G], values [T][P][G], final [P][G], outside [2]. */
+typedef struct vgx_tau_susceptibles_chain {
+    int64_t popNum, susNum;
+    int64_t ev_ptr;
+    const double *ev_times;
+    const int64_t *ev_types, *ev_haplotypes, *ev_populations, *ev_newHaplotypes, *ev_newPopulations;
+    int64_t mev_rows;
+    const int64_t *mev_num, *mev_types, *mev_haplotypes, *mev_populations, *mev_newHaplotypes, *mev_newPopulations;
+    int64_t T; const double *grid;               /* [T] */
+    int64_t G; const int32_t *class_of;          /* [susNum] */
+    const int64_t *start;                        /* [P][G] */
+    int64_t tile, n_own_events;
+    int64_t *values;                             /* out [T][P][G] */
+    int64_t *final;                              /* out [P][G] */
+    int64_t *outside;                            /* out [2] */
+} vgx_tau_susceptibles_chain;
+int vgx_test_tau_susceptibles(vgx_tau_susceptibles_chain *io, char *errbuf, int64_t errcap);
 
 /* ---- kernel choice of the direct path ------------------------------------------------------- */
 /* What the choice of a direct call's kernel reads: the model's dimensions, the state the call starts from and two diagnostic

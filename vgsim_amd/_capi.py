@@ -174,6 +174,28 @@ class VgxTauPrevalenceChain(C.Structure):
                 ("tile", C.c_int64), ("n_own_events", C.c_int64), ("values", _I), ("final", _I), ("outside", _I)]
 
 
+class VgxSusceptiblesIO(C.Structure):
+    _fields_ = [("n", C.c_int64), ("replicates", _I), ("T", C.c_int64), ("grid", _F), ("G", C.c_int64), ("class_of", C.POINTER(C.c_int32)),
+                ("values", C.POINTER(C.c_int32)), ("final", C.POINTER(C.c_int32)), ("outside", _I), ("summary", C.POINTER(VgxTrajSummaryIO)),
+                ("passes", C.c_int64), ("ms", C.c_double * 3)]
+
+
+class VgxTauSusceptiblesIO(C.Structure):
+    _fields_ = [("n", C.c_int64), ("replicates", _I), ("T", C.c_int64), ("grid", _F), ("G", C.c_int64), ("class_of", C.POINTER(C.c_int32)),
+                ("values", _I), ("final", _I), ("outside", _I), ("summary", C.POINTER(VgxTrajSummaryIO)),
+                ("passes", C.c_int64), ("ms", C.c_double * 3)]
+
+
+class VgxTauSusceptiblesChain(C.Structure):
+    _fields_ = [("popNum", C.c_int64), ("susNum", C.c_int64), ("ev_ptr", C.c_int64),
+                ("ev_times", _F), ("ev_types", _I), ("ev_haplotypes", _I), ("ev_populations", _I),
+                ("ev_newHaplotypes", _I), ("ev_newPopulations", _I),
+                ("mev_rows", C.c_int64), ("mev_num", _I), ("mev_types", _I), ("mev_haplotypes", _I), ("mev_populations", _I),
+                ("mev_newHaplotypes", _I), ("mev_newPopulations", _I),
+                ("T", C.c_int64), ("grid", _F), ("G", C.c_int64), ("class_of", C.POINTER(C.c_int32)), ("start", _I),
+                ("tile", C.c_int64), ("n_own_events", C.c_int64), ("values", _I), ("final", _I), ("outside", _I)]
+
+
 INCIDENCE_CHANNELS = ('birth', 'death', 'sampling', 'mutation', 'immunity', 'arrival', 'departure')   # vgx.h: channels 0 .. 6
 
 COLSUMMARY_MAX_GROUP = 16384   # members of one group the device pass sorts (vgx.h: VGX_COLSUMMARY_MAX_GROUP)
@@ -259,6 +281,11 @@ SIGNATURES = {
     "vgx_test_tau_incidence": (C.c_int, [C.POINTER(VgxTauIncidenceChain), C.c_char_p, C.c_int64]),
     "vgx_get_tau_prevalence": (C.c_int, [_H, C.POINTER(VgxTauPrevalenceIO), C.POINTER(VgxTimelinesPrefix)]),
     "vgx_test_tau_prevalence": (C.c_int, [C.POINTER(VgxTauPrevalenceChain), C.c_char_p, C.c_int64]),
+    "vgx_get_susceptibles": (C.c_int, [_H, C.POINTER(VgxSusceptiblesIO)]),
+    "vgx_test_susceptibles": (C.c_int, [_F, _I, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, _F, C.c_int64, C.POINTER(C.c_int32), C.c_int64, _I,
+                                        C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, C.c_char_p, C.c_int64]),
+    "vgx_get_tau_susceptibles": (C.c_int, [_H, C.POINTER(VgxTauSusceptiblesIO), C.POINTER(VgxTimelinesPrefix)]),
+    "vgx_test_tau_susceptibles": (C.c_int, [C.POINTER(VgxTauSusceptiblesChain), C.c_char_p, C.c_int64]),
     "vgx_test_direct_plan": (C.c_int, [C.POINTER(VgxDirectShape), C.POINTER(VgxRunOpts), C.POINTER(VgxDirectPlan), C.c_char_p, C.c_int64]),
     "vgx_rng_position": (None, [C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_uint64 * 4)]),
     "vgx_propensity_scan": (C.c_int, [C.POINTER(VgxRowScan)]),
@@ -989,6 +1016,109 @@ def replay_tau_prevalence(events, mev, popNum, hapNum, grid, variant_of, V, star
     err = C.create_string_buffer(512)
     if load_library().vgx_test_tau_prevalence(C.byref(io), err, 512) != VGX_OK:
         raise ValueError(err.value.decode() or "vgx_test_tau_prevalence failed")
+    return values, final, outside
+
+
+def group_map(groups, susNum):
+    """The map ``vgx_get_susceptibles`` takes, (class_of [susNum] int32 with values in [-1, G), G), from what
+    ``Ensemble.susceptibles`` accepts as ``groups``: what ``variant_map`` does, over the susceptibility groups.  None (every group
+    its own class, G = susNum); an integer array [susNum] with values -1 (not tracked) or a class (G = the largest class + 1, at
+    least 1); or a sequence of sequences of group indices (class k = the k-th sequence, unlisted groups not tracked).  ValueError
+    for anything else."""
+    S = int(susNum)
+    if groups is None:
+        return np.arange(S, dtype=np.int32), S
+    if len(groups) and all(np.ndim(v) == 1 for v in groups):   # classes as lists of groups
+        co = np.full(S, -1, dtype=np.int32)
+        for k, members in enumerate(groups):
+            idx = np.asarray(members).ravel()
+            if len(idx) and not np.issubdtype(idx.dtype, np.integer):
+                raise ValueError("groups must hold integer susceptibility group indices")
+            idx = idx.astype(np.int64)
+            if len(idx) and (idx.min() < 0 or idx.max() >= S):
+                raise ValueError("susceptibility group index out of range")
+            if len(np.unique(idx)) != len(idx) or (co[idx] >= 0).any():
+                raise ValueError("a susceptibility group is listed twice in groups")
+            co[idx] = k
+        return co, len(groups)
+    a = np.asarray(groups)
+    if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("groups must be an integer array [susNum] or a sequence of sequences of group indices")
+    if len(a) != S:
+        raise ValueError("groups must hold one class per susceptibility group (%d), got %d" % (S, len(a)))
+    G = max(int(a.max()) + 1, 1)
+    if a.min() < -1 or G > np.iinfo(np.int32).max:
+        raise ValueError("class_of[%d] = %d is outside [-1, %d)" % (int(a.argmin()), int(a.min()), G))
+    return np.ascontiguousarray(a, dtype=np.int32), G
+
+
+def replay_susceptibles(times, types, haplotypes, populations, newHaplotypes, newPopulations, popNum, susNum, grid, class_of, G, start, tile=0):
+    """The values of ``Ensemble.susceptibles`` for one chain given as arrays through ``vgx_test_susceptibles``: the device's rule
+    (vgx_susceptible.h), tile walk and scan compiled for the host, tile after tile of ``tile`` events (0: the default); no GPU.
+    ``class_of`` [susNum] with values in [-1, G); ``start`` [P, G] the chain's susceptible start folded through it.  Returns
+    (values [T, P, G] int32, final [P, G] int32, outside [2] int64); a refusal raises ``ValueError`` with the library's message."""
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.int64) for c in (types, haplotypes, populations, newHaplotypes, newPopulations)]
+    n = len(times)
+    if any(len(c) != n for c in cols):
+        raise ValueError("event columns of different lengths")
+    grid = np.ascontiguousarray(grid, dtype=np.float64)
+    T, P, G = len(grid), int(popNum), int(G)
+    co = np.ascontiguousarray(class_of, dtype=np.int32)
+    if len(co) != int(susNum):
+        raise ValueError("class_of must hold susNum values")
+    start = np.ascontiguousarray(start, dtype=np.int64)
+    if start.shape != (P, G):
+        raise ValueError("start must have the shape [P, G]")
+    values = np.zeros((max(T, 1), max(P, 1), max(G, 1)), dtype=np.int32)
+    final = np.zeros((max(P, 1), max(G, 1)), dtype=np.int32)
+    outside = np.zeros(2, dtype=np.int64)
+    err = C.create_string_buffer(512)
+    i32 = C.POINTER(C.c_int32)
+    rc = load_library().vgx_test_susceptibles(_p(times), *[_p(c) for c in cols], n, P, int(susNum), _p(grid), T, co.ctypes.data_as(i32), G,
+                                              _p(start), int(tile), values.ctypes.data_as(i32), final.ctypes.data_as(i32), _p(outside), err, 512)
+    if rc != VGX_OK:
+        raise ValueError(err.value.decode() or "vgx_test_susceptibles failed")
+    return values, final, outside
+
+
+def replay_tau_susceptibles(events, mev, popNum, susNum, grid, class_of, G, start, tile=0, n_own_events=-1):
+    """The values of ``Ensemble.tau_susceptibles`` for one chain through ``vgx_test_tau_susceptibles``: ``replay_tau_prevalence``
+    over the susceptible rule (vgx_tau_susceptible.h); no GPU.  ``events``, ``mev`` and ``n_own_events`` as there; ``class_of``
+    [susNum] with values in [-1, G); ``start`` [P, G].  Returns (values [T, P, G] int64, final [P, G] int64, outside [2] int64); a
+    refusal raises ``ValueError`` with the library's message."""
+    times = np.ascontiguousarray(events[0], dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.int64) for c in events[1:6]]
+    n = len(times)
+    if len(cols) != 5 or any(len(c) != n for c in cols):
+        raise ValueError("event columns of different lengths")
+    mcols = [np.ascontiguousarray(mev[c] if mev is not None else [], dtype=np.int64) for c in MEV_COLUMNS]
+    if len({len(c) for c in mcols}) != 1:
+        raise ValueError("multievent columns of different lengths")
+    grid = np.ascontiguousarray(grid, dtype=np.float64)
+    T, P, G = len(grid), int(popNum), int(G)
+    co = np.ascontiguousarray(class_of, dtype=np.int32)
+    if len(co) != int(susNum):
+        raise ValueError("class_of must hold susNum values")
+    start = np.ascontiguousarray(start, dtype=np.int64)
+    if start.shape != (P, G):
+        raise ValueError("start must have the shape [P, G]")
+    values = np.zeros((max(T, 1), max(P, 1), max(G, 1)), dtype=np.int64)
+    final = np.zeros((max(P, 1), max(G, 1)), dtype=np.int64)
+    outside = np.zeros(2, dtype=np.int64)
+    io = VgxTauSusceptiblesChain()
+    io.popNum, io.susNum, io.ev_ptr, io.ev_times = P, int(susNum), n, _p(times)
+    for name, col in zip(("types", "haplotypes", "populations", "newHaplotypes", "newPopulations"), cols):
+        setattr(io, "ev_" + name, _p(col))
+    io.mev_rows = len(mcols[0])
+    for name, col in zip(MEV_COLUMNS, mcols):
+        setattr(io, "mev_" + name, _p(col))
+    io.T, io.grid, io.G, io.class_of, io.start = T, _p(grid), G, co.ctypes.data_as(C.POINTER(C.c_int32)), _p(start)
+    io.tile, io.n_own_events = int(tile), int(n_own_events)
+    io.values, io.final, io.outside = _p(values), _p(final), _p(outside)
+    err = C.create_string_buffer(512)
+    if load_library().vgx_test_tau_susceptibles(C.byref(io), err, 512) != VGX_OK:
+        raise ValueError(err.value.decode() or "vgx_test_tau_susceptibles failed")
     return values, final, outside
 
 

@@ -1959,3 +1959,155 @@ extern "C" int vgx_get_prevalence(vgx_engine *e, vgx_prevalence_io *io) {
     io->ms[2] = wall();
     return VGX_OK;
 }
+
+// ---- susceptible hosts per class of immunity groups of many replicates at the times of one grid (vgx_susceptible.hip,
+// vgx_susceptible.h).  vgx_get_prevalence over the other half of the state: the same host clock, bounds, net block,
+// scan, min/max pass and summary, with the counting kernel of the susceptible rule and the susceptible start state.
+extern "C" int vgx_get_susceptibles(vgx_engine *e, vgx_susceptibles_io *io) {
+    if (!e || !io || io->n < 0 || (io->n > 0 && (!io->replicates || !io->outside))) return VGX_ERR_ARG;
+    const auto t_call = std::chrono::steady_clock::now();
+    auto wall = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(); };
+    const std::string me = "vgx_get_susceptibles: ";
+    io->passes = 0;
+    io->ms[0] = io->ms[1] = io->ms[2] = 0.0;
+    if (e->last_was_tau) return fail(e, VGX_ERR_ARG, me + "the last call was vgx_simulate_tau (counts direct chains only)");
+    if (!e->sc_host_valid || !e->dev_state_valid) return fail(e, VGX_ERR_ARG, me + "needs a direct vgx_simulate_direct call with the event log first");
+    if (!e->call_recorded) return fail(e, VGX_ERR_ARG, me + "the last call did not record events");
+    const int64_t n = io->n, P = e->d.popNum, S = e->d.susNum, T = io->T, G = io->G;
+    if (T < 1 || T >= VGX_PREV_MAX_POINTS || !io->grid) return fail(e, VGX_ERR_ARG, me + "T = " + std::to_string(T) + " grid points: at least 1, below 2^24, with grid");
+    for (int64_t k = 0; k < T; k++) {
+        if (!std::isfinite(io->grid[k])) return fail(e, VGX_ERR_ARG, me + "grid[" + std::to_string(k) + "] is not finite");
+        if (k > 0 && !(io->grid[k - 1] < io->grid[k])) return fail(e, VGX_ERR_ARG, me + "grid must increase strictly (grid[" + std::to_string(k) + "])");
+    }
+    if (G < 1 || G > INT32_MAX || !io->class_of) return fail(e, VGX_ERR_ARG, me + "G = " + std::to_string(G) + " classes: at least 1, with class_of");
+    for (int64_t g = 0; g < S; g++)
+        if (io->class_of[g] < -1 || io->class_of[g] >= G)
+            return fail(e, VGX_ERR_ARG, me + "class_of[" + std::to_string(g) + "] = " + std::to_string(io->class_of[g]) + " is outside [-1, " + std::to_string(G) + ")");
+    for (int64_t pn = 0; pn < P; pn++)
+        if (e->sizes[(size_t)pn] >= ((int64_t)1 << 31)) return fail(e, VGX_ERR_ARG, me + "population sizes of 2^31 or more");
+    if (vgx_prev_lds_bytes(P, G) > VGX_PREV_LDS_MAX)
+        return fail(e, VGX_ERR_ARG, me + std::to_string(P) + " populations x " + std::to_string(G) + " classes need " + std::to_string(vgx_prev_lds_bytes(P, G)) +
+                                        " bytes of cells, above the " + std::to_string((int64_t)VGX_PREV_LDS_MAX) + " bytes of LDS a counting workgroup may use");
+    const int64_t cells = P * G;
+    std::vector<int32_t> n_ev((size_t)n);
+    {
+        std::vector<char> seen((size_t)e->R, 0);
+        for (int64_t i = 0; i < n; i++) {
+            const int64_t r = io->replicates[i];
+            if (r < 0 || r >= e->R) return fail(e, VGX_ERR_ARG, me + "replicate index out of range");
+            if (seen[(size_t)r]) return fail(e, VGX_ERR_ARG, me + "replicates must be distinct");
+            seen[(size_t)r] = 1;
+            const VgxRepScalars &s = e->sc_host[(size_t)r];
+            const int64_t first = s.restarts > 0 ? 0 : ((size_t)r < e->call_ev0.size() ? e->call_ev0[(size_t)r] : e->ev_ptr0);
+            if (first != 0 || e->ev_base != 0)
+                return fail(e, VGX_ERR_ARG, me + "replicate " + std::to_string(r) + ": its chain does not start in the last call's device log (the model held " +
+                                                std::to_string(e->ev_base != 0 ? e->ev_base : first) + " events when the ensemble started)");
+            if (s.ev_ptr >= VGX_PREV_MAX_EVENTS)
+                return fail(e, VGX_ERR_ARG, me + "replicate " + std::to_string(r) + " holds a chain of " + std::to_string(s.ev_ptr) + " events (2^30 or more)");
+            if (s.ev_ptr < 0 || s.ev_ptr > e->evcap) return fail(e, VGX_ERR_ARG, me + "event range of replicate " + std::to_string(r) + " outside the device log");
+            n_ev[(size_t)i] = (int32_t)s.ev_ptr;
+        }
+    }
+    if (n == 0) {
+        io->ms[2] = wall();
+        return VGX_OK;
+    }
+    // the start of a chain folded through class_of: the state the call started from, or the initial state after a restart
+    std::vector<int32_t> start((size_t)(n * cells));
+    {
+        std::vector<int64_t> fold[2] = {std::vector<int64_t>((size_t)cells, 0), std::vector<int64_t>((size_t)cells, 0)};
+        const std::vector<int64_t> *src[2] = {&e->hs.susceptible, &e->hs.initial_susceptible};
+        for (int k = 0; k < 2; k++)
+            for (int64_t pn = 0; pn < P; pn++)
+                for (int64_t g = 0; g < S; g++)
+                    if (io->class_of[g] >= 0) fold[k][(size_t)(pn * G + io->class_of[g])] += (*src[k])[(size_t)(pn * S + g)];
+        for (int k = 0; k < 2; k++)
+            for (int64_t c = 0; c < cells; c++)
+                if (fold[k][(size_t)c] < 0 || fold[k][(size_t)c] > INT32_MAX) return fail(e, VGX_ERR_ARG, me + "a start value outside [0, 2^31)");
+        for (int64_t i = 0; i < n; i++) {
+            const std::vector<int64_t> &f = fold[e->sc_host[(size_t)io->replicates[i]].restarts > 0 ? 1 : 0];
+            for (int64_t c = 0; c < cells; c++) start[(size_t)(i * cells + c)] = (int32_t)f[(size_t)c];
+        }
+    }
+    int64_t tile = VGX_PREV_TILE_DEFAULT;
+    if (const char *tb = getenv("VGX_PREVALENCE_TILE_EVENTS")) tile = std::min<int64_t>(std::max<int64_t>(atoll(tb), 1), VGX_PREV_MAX_EVENTS);
+    HIPCHECK(e, hipSetDevice(e->device));
+    size_t free_b = 0, total_b = 0;
+    HIPCHECK(e, hipMemGetInfo(&free_b, &total_b));
+    auto up8 = [](int64_t b) { return (b + 255) / 256 * 256; };
+    auto dev_free = [](char *p) { (void)hipFree(p); };
+    // what stays for the whole call: [rep | n_ev | bound | class_of | start | val | fin | min, max]
+    const int64_t val_bytes = n * T * cells * 4, fin_bytes = n * cells * 4;
+    const int64_t o_rep = 0, o_nev = o_rep + up8(n * 8), o_bnd = o_nev + up8(n * 4), o_map = o_bnd + up8(n * (T + 2) * 4), o_start = o_map + up8(S * 4),
+                  o_val = o_start + up8(fin_bytes), o_fin = o_val + up8(val_bytes), o_mm = o_fin + up8(fin_bytes), keep_total = o_mm + 256;
+    if (keep_total > (int64_t)(free_b / 2))
+        return fail(e, VGX_ERR_ARG, me + "the block of " + std::to_string(n) + " x " + std::to_string(T + 1) + " x " + std::to_string(P) + " x " + std::to_string(G) +
+                                        " values (" + std::to_string(val_bytes + fin_bytes) + " bytes), its cuts and start take " + std::to_string(keep_total) +
+                                        " bytes, above half of the " + std::to_string((int64_t)free_b) + " bytes of free device memory: select fewer replicates per call");
+    char *kws = nullptr;
+    hipError_t er = hipMalloc((void **)&kws, (size_t)keep_total);
+    if (er != hipSuccess) return fail(e, VGX_ERR_HIP, me + "hipMalloc of " + std::to_string(keep_total) + " bytes: " + hipGetErrorString(er));
+    std::unique_ptr<char, void (*)(char *)> khold(kws, dev_free);
+    std::vector<int64_t> reps_all(io->replicates, io->replicates + n);
+    HIPCHECK(e, hipMemcpyAsync(kws + o_rep, reps_all.data(), (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_nev, n_ev.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_map, io->class_of, (size_t)S * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_start, start.data(), (size_t)fin_bytes, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemsetAsync(kws + o_val, 0, (size_t)(o_mm - o_val), e->stream));   // val and fin, zeroed once
+
+    const int64_t share = (int64_t)(free_b / 2) - keep_total + 4096;
+    std::vector<int32_t> bounds((size_t)(n * (T + 2)));
+    const int rc_chunks = clock_chunks(e, "vgx_get_susceptibles", reps_all, n_ev, (const int64_t *)(kws + o_rep), (const int32_t *)(kws + o_nev), share, io->ms,
+        // host: a replicate's event times -> its T + 2 bounds
+        [&](int64_t gi, const std::vector<double> &times) {
+            int32_t *bound = bounds.data() + gi * (T + 2);
+            VgxPrevCutter ct{io->grid, T, bound};
+            for (size_t k = 0; k < times.size(); k++) ct.event((int64_t)k, times[k]);
+            ct.finish((int64_t)times.size());
+            io->outside[2 * gi] = bound[1];
+            io->outside[2 * gi + 1] = (int64_t)times.size() - bound[(size_t)T];
+        },
+        // device: the net changes of the chunk's replicates into their rows of the block, then the running sums of those rows
+        [&](int64_t i0, int64_t i1, int64_t max_n) -> int {
+            const int64_t m = i1 - i0;
+            HIPCHECK(e, hipMemcpyAsync(kws + o_bnd + i0 * (T + 2) * 4, bounds.data() + i0 * (T + 2), (size_t)(m * (T + 2)) * 4, hipMemcpyHostToDevice, e->stream));
+            HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
+            VgxPrevLaunch a{};
+            a.m = m;
+            a.log = (const int32_t *)e->r_evcols.p; a.evcap = e->evcap;
+            a.rep = (const int64_t *)(kws + o_rep) + i0; a.n_ev = (const int32_t *)(kws + o_nev) + i0;
+            a.bound = (const int32_t *)(kws + o_bnd) + i0 * (T + 2);
+            a.T = (int32_t)T; a.P = (int32_t)P; a.hapNum = (int32_t)S; a.V = (int32_t)G;   // the launch of §18 with susNum, G and class_of
+            a.variant_of = (const int32_t *)(kws + o_map);
+            a.tile = (int32_t)tile; a.max_n = max_n;
+            a.val = (int32_t *)(kws + o_val) + i0 * T * cells;
+            a.fin = (int32_t *)(kws + o_fin) + i0 * cells;
+            a.start = (const int32_t *)(kws + o_start) + i0 * cells;
+            HIPCHECK(e, vgxi_sus_count(&a, e->stream));
+            if (max_n > 0) io->passes += 1;
+            HIPCHECK(e, vgxi_prev_scan(&a, e->stream));
+            HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
+            if ((er = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(e, VGX_ERR_HIP, me + "counting or scan kernel failed: " + hipGetErrorString(er));
+            float kms = 0.f;
+            HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
+            io->ms[0] += kms;
+            return VGX_OK;
+        });
+    if (rc_chunks) return rc_chunks;
+    if (io->values) HIPCHECK(e, hipMemcpy(io->values, kws + o_val, (size_t)val_bytes, hipMemcpyDeviceToHost));
+    if (io->final) HIPCHECK(e, hipMemcpy(io->final, kws + o_fin, (size_t)fin_bytes, hipMemcpyDeviceToHost));
+    if (io->summary) {
+        // the column summary sorts 32-bit keys of whole numbers in [0, 2^31)
+        int32_t mm[2] = {0, 0};
+        HIPCHECK(e, vgxi_prev_minmax((const int32_t *)(kws + o_val), n * T * cells, (int32_t *)(kws + o_mm), e->stream));
+        HIPCHECK(e, hipMemcpyAsync(mm, kws + o_mm, sizeof mm, hipMemcpyDeviceToHost, e->stream));
+        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(e, VGX_ERR_HIP, me + "min/max kernel failed: " + hipGetErrorString(er));
+        if (mm[0] < 0)
+            return fail(e, VGX_ERR_ARG, me + "summary: a value of " + std::to_string(mm[0]) + " is not a whole number in [0, 2^31) (the log holds records outside the model)");
+        char msg[512] = "";
+        const int rc = vgxi_column_summary_i32("vgx_get_susceptibles: summary", (const int32_t *)(kws + o_val), n, T * cells, io->summary, e->stream, msg, sizeof msg);
+        if (rc) return fail(e, rc, msg);
+    }
+    io->ms[2] = wall();
+    return VGX_OK;
+}

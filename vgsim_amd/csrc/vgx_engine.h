@@ -57,6 +57,14 @@ extern "C" hipError_t vgxi_inc_count(const VgxIncLaunch *a, hipStream_t s);
 extern "C" hipError_t vgxi_prev_count(const VgxPrevLaunch *a, hipStream_t s);
 extern "C" hipError_t vgxi_prev_scan(const VgxPrevLaunch *a, hipStream_t s);
 extern "C" hipError_t vgxi_prev_minmax(const int32_t *x, int64_t n, int32_t *out, hipStream_t s);   // out[0] = min, out[1] = max of x[0 .. n)
+extern "C" hipError_t vgxi_sus_count(const VgxPrevLaunch *a, hipStream_t s);   // vgx_susceptible.hip: hapNum := susNum, V := G, variant_of := class_of
+// the launchers of vgx_tau_prevalence.hip that vgx_tau_susceptible.hip shares (net blocks from the prefix's, the 64-bit running
+// sums, the narrowing min/max pass)
+struct VgxTauPrevLaunch;
+extern "C" hipError_t vgxi_tau_prev_init(int64_t m, int64_t tc, int64_t cells, const int32_t *with, const int64_t *pre_val, const int64_t *pre_fin,
+                                         const int64_t *pre_out, int64_t *val, int64_t *fin, int64_t *outside, hipStream_t s);
+extern "C" hipError_t vgxi_tau_prev_scan(const VgxTauPrevLaunch *a, hipStream_t s);
+extern "C" hipError_t vgxi_tau_prev_minmax(int64_t total, const int64_t *src, int32_t *dst, uint64_t *mm, hipStream_t s);
 // the column summary of vgx_colsummary.hip on a device int32 matrix x[R][N] of values in [0, 2^31) (a refusal's message goes to errbuf)
 extern "C" int vgxi_column_summary_i32(const char *what, const int32_t *x, int64_t R, int64_t N, vgx_traj_summary_io *io, hipStream_t stream,
                                        char *errbuf, int64_t errcap);

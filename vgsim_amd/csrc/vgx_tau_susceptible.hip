@@ -1,28 +1,22 @@
-// vgx_tau_prevalence.hip — infectious hosts per population and variant class of every selected replicate of a TAU ensemble at the
-// times of one grid, on the device (vgx_get_tau_prevalence), the host side of that call, and the same rule, tile walk and scan
-// compiled for the host (vgx_test_tau_prevalence).  The rule is vgx_tau_prevalence.h; DESIGN.md §19.
+// vgx_tau_susceptible.hip — susceptible hosts per population and class of immunity groups of every selected replicate of a TAU
+// ensemble at the times of one grid, on the device (vgx_get_tau_susceptibles), the host side of that call, and the same rule,
+// tile walk and scan compiled for the host (vgx_test_tau_susceptibles).  The rule is vgx_tau_susceptible.h; DESIGN.md §20.
 //
-// COUNTING kernel.  As in vgx_prevalence.hip the stock is formed as the NET change of every (interval, population, class),
-// tile-parallel, and summed up per column afterwards.  A workgroup of 256 threads takes one chain (a selected replicate's own rows
-// in its block of t_mev, or the flattened prefix) and a TILE of consecutive rows; consecutive lanes read consecutive rows (three
-// 16-byte loads per lane).  The tile's first interval comes from a search in the chain's bounds, read where they lie; interval by
-// interval the signed num goes into P * V int64 cells in LDS with 64-bit LDS atomics, and at every interval change and at the
-// tile's end the nonzero cells go to the net block in device memory with 64-bit atomics and are cleared.  variant_of is staged in
-// LDS behind the cells when it fits.  Rows outside [cut[0], cut[T-1]) count like any other (interval 0 or the tail); every thread
-// also sums their positive num, and at the end a wave sum and one global atomic per wavefront feed the chain's two `outside`
-// counters.  All arithmetic is integer: the block does not depend on the tile size or the launch geometry.
-// The prefix is counted ONCE per call as a chain of its own; an INIT kernel starts the net block (value intervals, tail, outside)
-// of every selected replicate that did not restart from the prefix's, the replicates' own rows are added on top, and the SCAN
-// kernel (one thread per (chain, population, class) column, consecutive threads consecutive classes) turns the net block into
-// running sums from the `start` block.  The tile size is VGX_PREVALENCE_TILE_EVENTS (rows here; default 4096, the value DESIGN.md
-// §16 reasons out; not the result of a sweep).
+// This is vgx_tau_prevalence.hip over another table.  COUNTING kernel: a workgroup of 256 threads takes one chain (a selected
+// replicate's own rows in its block of t_mev, or the flattened prefix) and a TILE of consecutive rows (three 16-byte loads per
+// lane); the tile's first interval comes from a search in the chain's bounds; interval by interval the signed num goes into
+// P * G int64 cells in LDS with 64-bit LDS atomics, and at every interval change and at the tile's end the nonzero cells go to
+// the net block in device memory with 64-bit atomics and are cleared.  class_of is staged in LDS behind the cells when it fits.
+// Every thread also sums the positive num of the rows outside [cut[0], cut[T-1]); a wave sum and one global atomic per wavefront
+// feed the chain's two `outside` counters.  The prefix is counted ONCE per call; the init, scan and min/max launches are §19's
+// (vgxi_tau_prev_init / _scan / _minmax), on VgxTauPrevLaunch with hapNum := susNum, V := G, variant_of := class_of.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdio.h>
 #include <string>
 #include <vector>
 #include "vgx_engine.h"
-#include "vgx_tau_prevalence.h"
+#include "vgx_tau_susceptible.h"
 #include "vgx_tau_rows.h"   // EventCols, RowCols, FlatChain, flatten
 
 namespace {
@@ -37,22 +31,22 @@ __device__ __forceinline__ void add64(long long *p, long long v) {
     atomicAdd((unsigned long long *)p, (unsigned long long)v);   // two's complement: the sum is the signed one
 }
 
-__global__ void __launch_bounds__(256) vgxtp_count_kernel(VgxTauPrevLaunch a, int stage) {
-    extern __shared__ __attribute__((aligned(16))) long long hist[];   // [P][V] cells, then (stage) variant_of [hapNum]
+__global__ void __launch_bounds__(256) vgxts_count_kernel(VgxTauPrevLaunch a, int stage) {
+    extern __shared__ __attribute__((aligned(16))) long long hist[];   // [P][G] cells, then (stage) class_of [susNum]
     const int tid = (int)threadIdx.x, lane = tid & 63;
     const int64_t row = blockIdx.x;
-    const int32_t n = a.n_rows[row], T = a.T, P = a.P, V = a.V, cells = P * V;
+    const int32_t n = a.n_rows[row], T = a.T, P = a.P, G = a.V, cells = P * G;
     if ((int64_t)blockIdx.y * a.tile >= n) return;         // (the whole workgroup: the chain ends before its first tile)
     const int32_t *bound = a.bound + row * (int64_t)(T + 2);   // (uniform addresses: every thread reads the same bounds)
     // 16-byte aligned: 48-byte rows from 256-byte aligned bases
     const longlong2 *rows = (const longlong2 *)(a.rows + (a.rep ? a.rep[row] * a.stride * 6 : 0));
     long long *val = (long long *)a.val, *fin = (long long *)a.fin, *outside = (long long *)a.outside + 2 * row;
-    const int32_t *vo = a.variant_of;
+    const int32_t *co = a.variant_of;
     for (int i = tid; i < cells; i += 256) hist[i] = 0;
     if (stage) {
         int32_t *map = (int32_t *)(hist + cells);
-        for (int i = tid; i < a.hapNum; i += 256) map[i] = vo[i];
-        vo = map;
+        for (int i = tid; i < a.hapNum; i += 256) map[i] = co[i];
+        co = map;
     }
     __syncthreads();
     const int32_t first = bound[1], last = bound[T];       // rows before `first` / from `last` on are outside the grid
@@ -71,7 +65,7 @@ __global__ void __launch_bounds__(256) vgxtp_count_kernel(VgxTauPrevLaunch a, in
                 }
                 int32_t cell[2], sign[2];
                 int k;
-                const long long w = vgx_tau_prev_row(r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, P, a.hapNum, V, vo, cell, sign, k);
+                const long long w = vgx_tau_sus_row(r0.x, r0.y, r1.x, r1.y, r2.x, r2.y, P, a.hapNum, G, co, cell, sign, k);
                 if (k > 0) add64(&hist[cell[0]], sign[0] < 0 ? -w : w);
                 if (k > 1) add64(&hist[cell[1]], sign[1] < 0 ? -w : w);
             }
@@ -93,58 +87,6 @@ __global__ void __launch_bounds__(256) vgxtp_count_kernel(VgxTauPrevLaunch a, in
     }
 }
 
-// the net blocks (tc value cells and `cells` tail cells per chain) and `outside` counters of m chains start from the prefix's
-// (with[i] != 0) or from zero
-__global__ void __launch_bounds__(256) vgxtp_init_kernel(int64_t m, int64_t tc, int64_t cells, const int32_t *with, const long long *pre_val,
-                                                         const long long *pre_fin, const long long *pre_out, long long *val, long long *fin,
-                                                         long long *outside) {
-    const int64_t stride = (int64_t)gridDim.x * 256, i0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    for (int64_t i = i0; i < m * tc; i += stride) {
-        const int64_t c = i / tc;
-        val[i] = with[c] ? pre_val[i - c * tc] : 0;
-    }
-    for (int64_t i = i0; i < m * cells; i += stride) {
-        const int64_t c = i / cells;
-        fin[i] = with[c] ? pre_fin[i - c * cells] : 0;
-    }
-    for (int64_t i = i0; i < 2 * m; i += stride) outside[i] = with[i >> 1] ? pre_out[i & 1] : 0;
-}
-
-// one thread per (chain, population, class) column, consecutive threads consecutive classes: every step of the running sum reads
-// and writes whole lines
-__global__ void __launch_bounds__(256) vgxtp_scan_kernel(VgxTauPrevLaunch a) {
-    const int64_t cells = (int64_t)a.P * a.V, idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= a.m * cells) return;
-    const int64_t row = idx / cells, cell = idx % cells;
-    vgx_tau_prev_scan_column(a.val + row * a.T * cells + cell, a.fin + idx, a.start[idx], a.T, cells);
-}
-
-// int64 block -> int32 for the column summary (clamped: a block with a value that does not fit is refused), and the block's
-// smallest and largest value: mm[0] = min, mm[1] = max, both with the sign bit flipped so that unsigned order is signed order
-// (the caller sets ~0 and 0)
-__global__ void __launch_bounds__(256) vgxtp_minmax_kernel(int64_t total, const long long *src, int32_t *dst, unsigned long long *mm) {
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    long long lo = LLONG_MAX, hi = LLONG_MIN;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-        const long long v = src[i];
-        dst[i] = (int32_t)(v < INT32_MIN ? INT32_MIN : v > INT32_MAX ? INT32_MAX : v);
-        lo = v < lo ? v : lo;
-        hi = v > hi ? v : hi;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const long long ol = __shfl_xor(lo, d), oh = __shfl_xor(hi, d);
-        lo = ol < lo ? ol : lo;
-        hi = oh > hi ? oh : hi;
-    }
-    if ((threadIdx.x & 63) == 0 && lo <= hi) {
-        atomicMin(&mm[0], (unsigned long long)lo ^ 0x8000000000000000ull);
-        atomicMax(&mm[1], (unsigned long long)hi ^ 0x8000000000000000ull);
-    }
-}
-
-unsigned flat_grid(int64_t total) { return (unsigned)std::min<int64_t>(std::max<int64_t>((total + 255) / 256, 1), 1 << 16); }
-
 hipError_t launch_count(const VgxTauPrevLaunch *a, hipStream_t s) {
     if (a->m <= 0 || a->max_n <= 0) return hipSuccess;
     if (vgx_tau_prev_lds_bytes(a->P, a->V) > VGX_PREV_LDS_MAX || a->tile < 1) return hipErrorInvalidValue;
@@ -152,32 +94,25 @@ hipError_t launch_count(const VgxTauPrevLaunch *a, hipStream_t s) {
     const int64_t lds = vgx_tau_prev_lds_bytes(a->P, a->V) + (stage ? 4 * (int64_t)a->hapNum : 0);
     const int64_t all_tiles = (a->max_n + a->tile - 1) / a->tile;
     const unsigned tiles = (unsigned)(all_tiles < 65535 ? all_tiles : 65535);   // (a workgroup takes several tiles beyond that)
-    hipError_t err = hipFuncSetAttribute((const void *)vgxtp_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t err = hipFuncSetAttribute((const void *)vgxts_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(vgxtp_count_kernel, dim3((unsigned)a->m, tiles), dim3(256), (size_t)lds, s, *a, stage ? 1 : 0);
-    return hipGetLastError();
-}
-
-hipError_t launch_scan(const VgxTauPrevLaunch *a, hipStream_t s) {
-    const int64_t cols = a->m * a->P * a->V;
-    if (cols <= 0) return hipSuccess;
-    hipLaunchKernelGGL(vgxtp_scan_kernel, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, s, *a);
+    hipLaunchKernelGGL(vgxts_count_kernel, dim3((unsigned)a->m, tiles), dim3(256), (size_t)lds, s, *a, stage ? 1 : 0);
     return hipGetLastError();
 }
 
 // what both the call and the hook check about the grid, the map and the dimensions; "" or why not
-std::string check_request(const double *grid, int64_t T, int64_t V, const int32_t *variant_of, int64_t P, int64_t H) {
+std::string check_request(const double *grid, int64_t T, int64_t G, const int32_t *class_of, int64_t P, int64_t S) {
     if (T < 1 || T >= VGX_PREV_MAX_POINTS || !grid) return "T = " + std::to_string(T) + " grid points: at least 1, below 2^24, with grid";
     for (int64_t k = 0; k < T; k++) {
         if (!std::isfinite(grid[k])) return "grid[" + std::to_string(k) + "] is not finite";
         if (k > 0 && !(grid[k - 1] < grid[k])) return "grid must increase strictly (grid[" + std::to_string(k) + "])";
     }
-    if (V < 1 || V > INT32_MAX || !variant_of) return "V = " + std::to_string(V) + " classes: at least 1, with variant_of";
-    for (int64_t h = 0; h < H; h++)
-        if (variant_of[h] < -1 || variant_of[h] >= V)
-            return "variant_of[" + std::to_string(h) + "] = " + std::to_string(variant_of[h]) + " is outside [-1, " + std::to_string(V) + ")";
-    if (vgx_tau_prev_lds_bytes(P, V) > VGX_PREV_LDS_MAX)
-        return std::to_string(P) + " populations x " + std::to_string(V) + " classes need " + std::to_string(vgx_tau_prev_lds_bytes(P, V)) +
+    if (G < 1 || G > INT32_MAX || !class_of) return "G = " + std::to_string(G) + " classes: at least 1, with class_of";
+    for (int64_t g = 0; g < S; g++)
+        if (class_of[g] < -1 || class_of[g] >= G)
+            return "class_of[" + std::to_string(g) + "] = " + std::to_string(class_of[g]) + " is outside [-1, " + std::to_string(G) + ")";
+    if (vgx_tau_prev_lds_bytes(P, G) > VGX_PREV_LDS_MAX)
+        return std::to_string(P) + " populations x " + std::to_string(G) + " classes need " + std::to_string(vgx_tau_prev_lds_bytes(P, G)) +
                " bytes of cells, above the " + std::to_string((int64_t)VGX_PREV_LDS_MAX) + " bytes of LDS a counting workgroup may use";
     return "";
 }
@@ -202,48 +137,33 @@ void own_bounds(const double *grid, int64_t T, int64_t point0, int64_t n_own, Ow
     ct.finish(n_rows);
 }
 
-// a state [P][H] folded through variant_of: [P][V]
-std::vector<int64_t> fold_state(const std::vector<int64_t> &src, int64_t P, int64_t H, int64_t V, const int32_t *variant_of) {
-    std::vector<int64_t> out((size_t)(P * V), 0);
+// a state [P][S] folded through class_of: [P][G]
+std::vector<int64_t> fold_state(const std::vector<int64_t> &src, int64_t P, int64_t S, int64_t G, const int32_t *class_of) {
+    std::vector<int64_t> out((size_t)(P * G), 0);
     for (int64_t pn = 0; pn < P; pn++)
-        for (int64_t h = 0; h < H; h++)
-            if (variant_of[h] >= 0) out[(size_t)(pn * V + variant_of[h])] += src[(size_t)(pn * H + h)];
+        for (int64_t g = 0; g < S; g++)
+            if (class_of[g] >= 0) out[(size_t)(pn * G + class_of[g])] += src[(size_t)(pn * S + g)];
     return out;
 }
 
 }  // namespace
 
-// the init, scan and min/max launches as vgx_tau_susceptible.hip shares them (declared in vgx_engine.h)
-extern "C" hipError_t vgxi_tau_prev_init(int64_t m, int64_t tc, int64_t cells, const int32_t *with, const int64_t *pre_val, const int64_t *pre_fin,
-                                         const int64_t *pre_out, int64_t *val, int64_t *fin, int64_t *outside, hipStream_t s) {
-    hipLaunchKernelGGL(vgxtp_init_kernel, dim3(flat_grid(m * tc)), dim3(256), 0, s, m, tc, cells, with, (const long long *)pre_val,
-                       (const long long *)pre_fin, (const long long *)pre_out, (long long *)val, (long long *)fin, (long long *)outside);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t vgxi_tau_prev_scan(const VgxTauPrevLaunch *a, hipStream_t s) { return launch_scan(a, s); }
-
-extern "C" hipError_t vgxi_tau_prev_minmax(int64_t total, const int64_t *src, int32_t *dst, uint64_t *mm, hipStream_t s) {
-    hipLaunchKernelGGL(vgxtp_minmax_kernel, dim3(flat_grid(total)), dim3(256), 0, s, total, (const long long *)src, dst, (unsigned long long *)mm);
-    return hipGetLastError();
-}
-
-extern "C" int vgx_get_tau_prevalence(vgx_engine *e, vgx_tau_prevalence_io *io, const vgx_timelines_prefix *prefix) {
+extern "C" int vgx_get_tau_susceptibles(vgx_engine *e, vgx_tau_susceptibles_io *io, const vgx_timelines_prefix *prefix) {
     if (!e || !io || io->n < 0 || (io->n > 0 && (!io->replicates || !io->outside))) return VGX_ERR_ARG;
     const auto t_call = std::chrono::steady_clock::now();
     auto since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-    const std::string me = "vgx_get_tau_prevalence: ";
+    const std::string me = "vgx_get_tau_susceptibles: ";
     io->passes = 0;
     io->ms[0] = io->ms[1] = io->ms[2] = 0.0;
     if (!e->sc_host_valid || !e->last_was_tau || (int64_t)e->tau_log.size() < e->R)
         return fail(e, VGX_ERR_ARG, me + "the last call was not vgx_simulate_tau (counts tau chains only)");
     if (e->tau_mev_cap <= 0) return fail(e, VGX_ERR_ARG, me + "the last call recorded no multievent rows (record_events = 0)");
-    const int64_t n = io->n, P = e->d.popNum, H = e->d.hapNum, T = io->T, V = io->V, mev_cap = e->tau_mev_cap;
+    const int64_t n = io->n, P = e->d.popNum, S = e->d.susNum, T = io->T, G = io->G, mev_cap = e->tau_mev_cap;
     {
-        const std::string why = check_request(io->grid, T, V, io->variant_of, P, H);
+        const std::string why = check_request(io->grid, T, G, io->class_of, P, S);
         if (!why.empty()) return fail(e, VGX_ERR_ARG, me + why);
     }
-    const int64_t cells = P * V, tc = T * cells;
+    const int64_t cells = P * G, tc = T * cells;
     // the prefix: what the model held when the call started
     const int64_t pre_ev = prefix ? prefix->ev_ptr : 0;
     if (pre_ev < 0 || (pre_ev > 0 && (!prefix->ev_times || !prefix->ev_types || !prefix->ev_haplotypes || !prefix->ev_populations ||
@@ -294,11 +214,11 @@ extern "C" int vgx_get_tau_prevalence(vgx_engine *e, vgx_tau_prevalence_io *io, 
         io->ms[2] = since(t_call);
         return VGX_OK;
     }
-    // the state every chain starts from, folded through variant_of: the initial state for a chain that starts at the beginning of
+    // the state every chain starts from, folded through class_of: the initial state for a chain that starts at the beginning of
     // the model's history (a restarted replicate, or one that carries a prefix), else the state the call started from
     std::vector<int64_t> start((size_t)(n * cells));
     {
-        const std::vector<int64_t> fold[2] = {fold_state(e->hs.infectious, P, H, V, io->variant_of), fold_state(e->hs.initial_infectious, P, H, V, io->variant_of)};
+        const std::vector<int64_t> fold[2] = {fold_state(e->hs.susceptible, P, S, G, io->class_of), fold_state(e->hs.initial_susceptible, P, S, G, io->class_of)};
         for (int64_t i = 0; i < n; i++) {
             const std::vector<int64_t> &f = fold[e->sc_host[(size_t)io->replicates[i]].restarts > 0 || pre_ev > 0 ? 1 : 0];
             std::copy(f.begin(), f.end(), start.begin() + i * cells);
@@ -312,14 +232,14 @@ extern "C" int vgx_get_tau_prevalence(vgx_engine *e, vgx_tau_prevalence_io *io, 
     auto up8 = [](int64_t b) { return (b + 255) / 256 * 256; };
     auto dev_free = [](char *p) { (void)hipFree(p); };
     // what stays for the whole call:
-    // [rep | n_own | with | variant_of | prefix: rows, bound, n_rows, val, fin, outside | start | val | fin | outside | narrow | min, max]
+    // [rep | n_own | with | class_of | prefix: rows, bound, n_rows, val, fin, outside | start | val | fin | outside | narrow | min, max]
     const int64_t val_bytes = n * tc * 8, fin_bytes = n * cells * 8, narrow_bytes = io->summary ? n * tc * 4 : 0;
-    const int64_t o_rep = 0, o_nown = o_rep + up8(n * 8), o_with = o_nown + up8(n * 4), o_map = o_with + up8(n * 4), o_prow = o_map + up8(H * 4),
+    const int64_t o_rep = 0, o_nown = o_rep + up8(n * 8), o_with = o_nown + up8(n * 4), o_map = o_with + up8(n * 4), o_prow = o_map + up8(S * 4),
                   o_pbnd = o_prow + up8(pre_rows * 48 + 8), o_pn = o_pbnd + up8((T + 2) * 4), o_pval = o_pn + up8(4), o_pfin = o_pval + up8(tc * 8),
                   o_pout = o_pfin + up8(cells * 8), o_start = o_pout + up8(16), o_val = o_start + up8(fin_bytes), o_fin = o_val + up8(val_bytes),
                   o_out = o_fin + up8(fin_bytes), o_nar = o_out + up8(n * 16), o_mm = o_nar + up8(narrow_bytes + 8), keep_total = o_mm + up8(16);
     if (keep_total > (int64_t)(free_b / 2))
-        return fail(e, VGX_ERR_ARG, me + "the block of " + std::to_string(n) + " x " + std::to_string(T + 1) + " x " + std::to_string(P) + " x " + std::to_string(V) +
+        return fail(e, VGX_ERR_ARG, me + "the block of " + std::to_string(n) + " x " + std::to_string(T + 1) + " x " + std::to_string(P) + " x " + std::to_string(G) +
                                         " values of 8 bytes (" + std::to_string(val_bytes + fin_bytes) + " bytes), the prefix rows, the start and " +
                                         (io->summary ? "the summary's 4-byte copy take " : "the bounds take ") + std::to_string(keep_total) + " bytes, above half of the " +
                                         std::to_string((int64_t)free_b) + " bytes of free device memory: select fewer replicates per call");
@@ -331,7 +251,7 @@ extern "C" int vgx_get_tau_prevalence(vgx_engine *e, vgx_tau_prevalence_io *io, 
     HIPCHECK(e, hipMemcpyAsync(kws + o_rep, reps_all.data(), (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
     HIPCHECK(e, hipMemcpyAsync(kws + o_nown, n_own.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
     HIPCHECK(e, hipMemcpyAsync(kws + o_with, with_prefix.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-    HIPCHECK(e, hipMemcpyAsync(kws + o_map, io->variant_of, (size_t)H * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_map, io->class_of, (size_t)S * 4, hipMemcpyHostToDevice, e->stream));
     HIPCHECK(e, hipMemcpyAsync(kws + o_start, start.data(), (size_t)fin_bytes, hipMemcpyHostToDevice, e->stream));
     HIPCHECK(e, hipMemsetAsync(kws + o_pval, 0, (size_t)(o_start - o_pval), e->stream));   // the prefix's net block and its outside counters
     const int32_t *d_map = (const int32_t *)(kws + o_map);
@@ -352,7 +272,7 @@ extern "C" int vgx_get_tau_prevalence(vgx_engine *e, vgx_tau_prevalence_io *io, 
         a.m = 1;
         a.rows = (const int64_t *)(kws + o_prow); a.stride = 0; a.rep = nullptr;
         a.n_rows = (const int32_t *)(kws + o_pn); a.bound = (const int32_t *)(kws + o_pbnd);
-        a.T = (int32_t)T; a.P = (int32_t)P; a.hapNum = (int32_t)H; a.V = (int32_t)V; a.variant_of = d_map;
+        a.T = (int32_t)T; a.P = (int32_t)P; a.hapNum = (int32_t)S; a.V = (int32_t)G; a.variant_of = d_map;
         a.tile = (int32_t)tile; a.max_n = pre_rows;
         a.val = (int64_t *)(kws + o_pval); a.fin = (int64_t *)(kws + o_pfin); a.outside = (int64_t *)(kws + o_pout);
         HIPCHECK(e, launch_count(&a, e->stream));
@@ -400,17 +320,15 @@ extern "C" int vgx_get_tau_prevalence(vgx_engine *e, vgx_tau_prevalence_io *io, 
         a.rows = (const int64_t *)e->t_mev.p; a.stride = mev_cap;
         a.rep = (const int64_t *)(kws + o_rep) + i0; a.n_rows = (const int32_t *)(kws + o_nown) + i0;
         a.bound = (const int32_t *)ws;
-        a.T = (int32_t)T; a.P = (int32_t)P; a.hapNum = (int32_t)H; a.V = (int32_t)V; a.variant_of = d_map;
+        a.T = (int32_t)T; a.P = (int32_t)P; a.hapNum = (int32_t)S; a.V = (int32_t)G; a.variant_of = d_map;
         a.tile = (int32_t)tile; a.max_n = max_n;
         a.val = (int64_t *)(kws + o_val) + i0 * tc; a.fin = (int64_t *)(kws + o_fin) + i0 * cells; a.outside = (int64_t *)(kws + o_out) + 2 * i0;
         a.start = (const int64_t *)(kws + o_start) + i0 * cells;
-        hipLaunchKernelGGL(vgxtp_init_kernel, dim3(flat_grid(m * tc)), dim3(256), 0, e->stream, m, tc, cells, (const int32_t *)(kws + o_with) + i0,
-                           (const long long *)(kws + o_pval), (const long long *)(kws + o_pfin), (const long long *)(kws + o_pout), (long long *)a.val,
-                           (long long *)a.fin, (long long *)a.outside);
-        HIPCHECK(e, hipGetLastError());
+        HIPCHECK(e, vgxi_tau_prev_init(m, tc, cells, (const int32_t *)(kws + o_with) + i0, (const int64_t *)(kws + o_pval), (const int64_t *)(kws + o_pfin),
+                                       (const int64_t *)(kws + o_pout), a.val, a.fin, a.outside, e->stream));
         HIPCHECK(e, launch_count(&a, e->stream));
         if (max_n > 0) io->passes += 1;
-        HIPCHECK(e, launch_scan(&a, e->stream));
+        HIPCHECK(e, vgxi_tau_prev_scan(&a, e->stream));
         HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
         if ((er = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(e, VGX_ERR_HIP, me + "counting or scan kernel failed: " + hipGetErrorString(er));
         float kms = 0.f;
@@ -426,9 +344,7 @@ extern "C" int vgx_get_tau_prevalence(vgx_engine *e, vgx_tau_prevalence_io *io, 
         uint64_t mm[2] = {0, 0};
         HIPCHECK(e, hipMemcpyAsync(kws + o_mm, init, sizeof init, hipMemcpyHostToDevice, e->stream));
         HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
-        hipLaunchKernelGGL(vgxtp_minmax_kernel, dim3(flat_grid(n * tc)), dim3(256), 0, e->stream, n * tc, (const long long *)(kws + o_val),
-                           (int32_t *)(kws + o_nar), (unsigned long long *)(kws + o_mm));
-        HIPCHECK(e, hipGetLastError());
+        HIPCHECK(e, vgxi_tau_prev_minmax(n * tc, (const int64_t *)(kws + o_val), (int32_t *)(kws + o_nar), (uint64_t *)(kws + o_mm), e->stream));
         HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
         HIPCHECK(e, hipMemcpyAsync(mm, kws + o_mm, sizeof mm, hipMemcpyDeviceToHost, e->stream));
         if ((er = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(e, VGX_ERR_HIP, me + "min/max kernel failed: " + hipGetErrorString(er));
@@ -440,7 +356,7 @@ extern "C" int vgx_get_tau_prevalence(vgx_engine *e, vgx_tau_prevalence_io *io, 
             return fail(e, VGX_ERR_ARG, me + "summary: a value of " + std::to_string(lo < 0 ? lo : hi) +
                                             " is not a whole number in [0, 2^31) (summarise the int64 values on the host)");
         char msg[512] = "";
-        const int rc = vgxi_column_summary_i32("vgx_get_tau_prevalence: summary", (const int32_t *)(kws + o_nar), n, tc, io->summary, e->stream, msg, sizeof msg);
+        const int rc = vgxi_column_summary_i32("vgx_get_tau_susceptibles: summary", (const int32_t *)(kws + o_nar), n, tc, io->summary, e->stream, msg, sizeof msg);
         if (rc) return fail(e, rc, msg);
     }
     io->ms[2] = since(t_call);
@@ -448,19 +364,17 @@ extern "C" int vgx_get_tau_prevalence(vgx_engine *e, vgx_tau_prevalence_io *io, 
 }
 
 // ---- the host instance: the same flattening, bounds, cells, tile walk, prefix-plus-own sum and scan on a chain given as arrays (no
-// device, no engine).  The last n_own_events events play the replicate's own steps (their rows are taken as they are, as the device
-// reads t_mev), everything before them the prefix, which is flattened and counted once as a chain of its own; the chain's net block
-// starts from the prefix's, as on the device.
-extern "C" int vgx_test_tau_prevalence(vgx_tau_prevalence_chain *io, char *errbuf, int64_t errcap) {
+// device, no engine), as vgx_test_tau_prevalence does it over this rule
+extern "C" int vgx_test_tau_susceptibles(vgx_tau_susceptibles_chain *io, char *errbuf, int64_t errcap) {
     auto fail_ = [&](const std::string &m) {
-        if (errbuf && errcap > 0) snprintf(errbuf, (size_t)errcap, "vgx_test_tau_prevalence: %s", m.c_str());
+        if (errbuf && errcap > 0) snprintf(errbuf, (size_t)errcap, "vgx_test_tau_susceptibles: %s", m.c_str());
         return VGX_ERR_ARG;
     };
     if (!io || !io->values || !io->final || !io->outside || !io->start) return fail_("null argument");
-    const int64_t n = io->ev_ptr, T = io->T, P = io->popNum, H = io->hapNum, V = io->V;
-    if (P < 1 || H < 1 || P > INT32_MAX || H > INT32_MAX) return fail_("bad dimensions");
+    const int64_t n = io->ev_ptr, T = io->T, P = io->popNum, S = io->susNum, G = io->G;
+    if (P < 1 || S < 1 || P > INT32_MAX || S > INT32_MAX) return fail_("bad dimensions");
     {
-        const std::string why = check_request(io->grid, T, V, io->variant_of, P, H);
+        const std::string why = check_request(io->grid, T, G, io->class_of, P, S);
         if (!why.empty()) return fail_(why);
     }
     if (n < 0 || n >= ((int64_t)1 << 31)) return fail_("chain too long");
@@ -472,7 +386,7 @@ extern "C" int vgx_test_tau_prevalence(vgx_tau_prevalence_chain *io, char *errbu
     int64_t tile = io->tile;
     if (tile < 0) return fail_("tile must not be negative");
     if (tile == 0) tile = VGX_PREV_TILE_DEFAULT;
-    const int64_t cells = P * V;
+    const int64_t cells = P * G;
     if (T * cells >= ((int64_t)1 << 40)) return fail_("block too large");
     int64_t n_own_ev = io->n_own_events;
     if (n_own_ev < -1 || n_own_ev > n) return fail_("n_own_events must be -1 or lie in [0, ev_ptr]");
@@ -516,16 +430,16 @@ extern "C" int vgx_test_tau_prevalence(vgx_tau_prevalence_chain *io, char *errbu
     std::vector<int64_t> pval((size_t)(T * cells), 0), pfin((size_t)cells, 0), hist((size_t)cells, 0);
     int64_t pout[2] = {0, 0};
     for (int64_t t0 = 0; t0 < pre_rows; t0 += tile)
-        vgx_tau_prev_tile_host(pre.rows.data(), pbound.data(), (int32_t)T, (int32_t)P, (int32_t)H, (int32_t)V, io->variant_of, (int32_t)t0,
-                               (int32_t)std::min<int64_t>(t0 + tile, pre_rows), hist.data(), pval.data(), pfin.data(), pout);
+        vgx_tau_sus_tile_host(pre.rows.data(), pbound.data(), (int32_t)T, (int32_t)P, (int32_t)S, (int32_t)G, io->class_of, (int32_t)t0,
+                              (int32_t)std::min<int64_t>(t0 + tile, pre_rows), hist.data(), pval.data(), pfin.data(), pout);
     // ... is what the chain's net block starts from; its own rows are added on top, and the columns are summed up
     for (int64_t i = 0; i < T * cells; i++) io->values[i] = pval[(size_t)i];
     for (int64_t i = 0; i < cells; i++) io->final[i] = pfin[(size_t)i];
     io->outside[0] = pout[0];
     io->outside[1] = pout[1];
     for (int64_t t0 = 0; t0 < own_rows; t0 += tile)
-        vgx_tau_prev_tile_host(own.data(), obound.data(), (int32_t)T, (int32_t)P, (int32_t)H, (int32_t)V, io->variant_of, (int32_t)t0,
-                               (int32_t)std::min<int64_t>(t0 + tile, own_rows), hist.data(), io->values, io->final, io->outside);
+        vgx_tau_sus_tile_host(own.data(), obound.data(), (int32_t)T, (int32_t)P, (int32_t)S, (int32_t)G, io->class_of, (int32_t)t0,
+                              (int32_t)std::min<int64_t>(t0 + tile, own_rows), hist.data(), io->values, io->final, io->outside);
     for (int64_t i = 0; i < cells; i++) vgx_tau_prev_scan_column(io->values + i, io->final + i, io->start[i], (int32_t)T, cells);
     return VGX_OK;
 }

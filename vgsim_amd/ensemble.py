@@ -273,6 +273,34 @@ class Prevalence:
         return out
 
 
+class Susceptibles:
+    """What ``Ensemble.susceptibles`` returns: susceptible hosts per selected replicate, grid time, population and class of
+    susceptibility groups.
+
+    ``values`` [n, T, P, G] int32 (int64 from ``tau_susceptibles``, as ``final``; None when the call had ``values=False``): the
+    susceptible hosts of class c in population p at ``times[j]``, events at exactly that time applied; ``final`` [n, P, G] the same
+    after the whole chain; ``times`` [T]; ``class_of`` [susNum] the class of every susceptibility group (-1: not tracked);
+    ``outside`` [n, 2] the events of every replicate up to ``times[0]`` and after ``times[T - 1]``; ``replicates`` [n];
+    ``summary`` a :class:`TrajectorySummary` over the [T, P, G] columns, or None; ``passes``, ``kernel_ms``, ``clock_ms``,
+    ``wall_ms``."""
+
+    @classmethod
+    def _of(cls, values, final, times, class_of, outside, replicates, done, io):
+        sv = cls()
+        sv.values, sv.final, sv.times, sv.class_of, sv.outside, sv.replicates = values, final, times, class_of, outside, replicates
+        sv.summary = done() if done is not None else None
+        sv.passes, sv.kernel_ms, sv.clock_ms, sv.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
+        return sv
+
+    def share(self):
+        """Every class's share of the tracked susceptible hosts of its population, [n, T, P, G] float64: ``values`` over their sum
+        across classes, 0 where no tracked host is susceptible."""
+        total = self.values.sum(axis=-1, keepdims=True, dtype=np.int64)
+        out = np.zeros(self.values.shape, dtype=np.float64)
+        np.divide(self.values, total, out=out, where=total != 0)
+        return out
+
+
 def _prevalence_grid(times, points, window):
     """The grid of a ``prevalence`` call as a float64 array; ValueError for bad arguments."""
     if (times is None) == (points is None):
@@ -970,10 +998,16 @@ class Ensemble:
         """What ``prevalence()`` and ``tau_prevalence()`` share: the checks on ``replicates``, ``variants``, the LDS limit (cells of
         ``cell_bytes`` bytes), ``summary`` and ``values`` (ValueError before the library is called).  Returns (replicates, n,
         variant_of, V, T, P, the summary's io, its finish)."""
-        m = self.model
+        return self._class_block_request(g, _capi.variant_map, variants, self.model.hapNum, replicates, summary, values, cell_bytes,
+                                         scenario_of, n_scenarios)
+
+    def _class_block_request(self, g, class_map, classes, members, replicates, summary, values, cell_bytes, scenario_of, n_scenarios):
+        """The request checks of the calls that return a [n, T, P, classes] block (``prevalence``, ``susceptibles`` and their tau
+        forms): ``class_map(classes, members)`` is ``_capi.variant_map`` over the haplotypes or ``_capi.group_map`` over the
+        susceptibility groups."""
         reps = self._selected_replicates(replicates)
-        vo, V = _capi.variant_map(variants, m.hapNum)
-        T, P = len(g), m.popNum
+        vo, V = class_map(classes, members)
+        T, P = len(g), self.model.popNum
         if cell_bytes * P * V > 65536:
             raise ValueError("%d populations x %d classes need %d bytes of cells, above the 65536 bytes of LDS a counting workgroup may use"
                              % (P, V, cell_bytes * P * V))
@@ -981,6 +1015,74 @@ class Ensemble:
         if summary is None and not values:
             raise ValueError("values=False needs summary=: the call would return nothing")
         return reps, len(reps), vo, V, T, P, sio, done
+
+    def susceptibles(self, times=None, points=None, window=None, groups=None, replicates=None, summary=None, values=True):
+        """Susceptible hosts per grid time, population and class of susceptibility (immunity) groups of every selected replicate
+        of the last direct ``simulate(record_events=True)`` call, on ONE grid for all replicates and on the device
+        (``vgx_get_susceptibles``): the other half of the state ``prevalence()`` counts, by the same pass over every replicate's
+        log where the kernel left it.  Returns a :class:`Susceptibles`.
+
+        The grid arguments, ``replicates``, ``summary`` and ``values`` are ``prevalence()``'s.  ``groups``: None (every
+        susceptibility group its own class), an integer array [susNum] of classes with -1 for groups that are not tracked, or a
+        sequence of sequences of group indices (class k = the k-th sequence, the rest not tracked).  With every group tracked
+        here and every haplotype tracked in ``prevalence()`` on the same grid, the two blocks add up to the population sizes at
+        every grid time.  Direct chains only."""
+        g = _prevalence_grid(times, points, window)
+        if self._last_call is None:
+            raise ValueError("susceptibles() needs a direct simulate(record_events=True) call first")
+        if self._last_call[0] != 'direct':
+            raise ValueError("susceptibles() counts direct chains only: the last call was simulate_tau")
+        if not self._last_call[1]:
+            raise ValueError("susceptibles() needs the event log: the last call had record_events=False")
+        eng = self.engine
+        reps, n, co, G, T, P, sio, done = self._class_block_request(g, _capi.group_map, groups, self.model.susNum, replicates, summary, values, 4,
+                                                                    self.scenario_of, len(self.scenarios) if self.scenarios is not None else 1)
+        for r in reps:
+            c = eng.counters(int(r))
+            if c.ev_first_new != 0:
+                raise ValueError("replicate %d: its chain does not start in the last call's device log (the model held %d events "
+                                 "when the ensemble started)" % (r, c.ev_first_new))
+        block = np.zeros((n, T, P, G), dtype=np.int32) if values else None
+        final = np.zeros((n, P, G), dtype=np.int32)
+        outside = np.zeros((max(n, 1), 2), dtype=np.int64)
+        i32 = C.POINTER(C.c_int32)
+        io = _capi.VgxSusceptiblesIO()
+        io.n, io.replicates, io.T, io.grid, io.G, io.class_of = n, _capi._p(reps), T, _capi._p(g), G, co.ctypes.data_as(i32)
+        io.values = block.ctypes.data_as(i32) if values and n else None
+        io.final = final.ctypes.data_as(i32) if n else None
+        io.outside = _capi._p(outside)
+        io.summary = C.pointer(sio) if sio is not None and n else None
+        eng._check(eng.lib.vgx_get_susceptibles(eng.handle, C.byref(io)))
+        return Susceptibles._of(block, final, g, co, outside[:n], reps, done, io)
+
+    def tau_susceptibles(self, times=None, points=None, window=None, groups=None, replicates=None, summary=None, values=True):
+        """``susceptibles()`` for the replicates of the last ``simulate_tau(record_events=True)`` call
+        (``vgx_get_tau_susceptibles``): the same arguments and :class:`Susceptibles`, with ``values`` [n, T, P, G] and ``final``
+        [n, P, G] int64 and ``outside`` the summed multiplicities, as ``tau_prevalence()`` has them.  The chain, the time of a
+        step, the start state (the model's initial susceptible state when the chain starts at the beginning of the model's
+        history, else the state the call started from) and the summary's refusals are ``tau_prevalence()``'s."""
+        g = _prevalence_grid(times, points, window)
+        if self._last_call is None:
+            raise ValueError("tau_susceptibles() needs a simulate_tau(record_events=True) call first")
+        if self._last_call[0] != 'tau':
+            raise ValueError("tau_susceptibles() counts tau chains only: the last call was a direct simulate()")
+        if not self._last_call[1]:
+            raise ValueError("tau_susceptibles() needs the multievent rows: the last call had record_events=False")
+        reps, n, co, G, T, P, sio, done = self._class_block_request(g, _capi.group_map, groups, self.model.susNum, replicates, summary, values, 8,
+                                                                    None, 1)
+        block = np.zeros((n, T, P, G), dtype=np.int64) if values else None
+        final = np.zeros((n, P, G), dtype=np.int64)
+        outside = np.zeros((max(n, 1), 2), dtype=np.int64)
+        io = _capi.VgxTauSusceptiblesIO()
+        io.n, io.replicates, io.T, io.grid, io.G = n, _capi._p(reps), T, _capi._p(g), G
+        io.class_of = co.ctypes.data_as(C.POINTER(C.c_int32))
+        io.values = _capi._p(block) if values and n else None
+        io.final = _capi._p(final) if n else None
+        io.outside = _capi._p(outside)
+        io.summary = C.pointer(sio) if sio is not None and n else None
+        eng, pre = self.engine, self._tau_prefix_struct()
+        eng._check(eng.lib.vgx_get_tau_susceptibles(eng.handle, C.byref(io), C.byref(pre)))
+        return Susceptibles._of(block, final, g, co, outside[:n], reps, done, io)
 
     def tau_prevalence(self, times=None, points=None, window=None, variants=None, replicates=None, summary=None, values=True):
         """``prevalence()`` for the replicates of the last ``simulate_tau(record_events=True)`` call (``vgx_get_tau_prevalence``):
