@@ -35,6 +35,8 @@
  *                                  columns (default 2^28; one tile of 64 columns at the least)
  *   VGX_INCIDENCE_TILE_EVENTS=n    vgx_get_incidence / vgx_get_tau_incidence: consecutive events (rows) a counting workgroup takes (default 4096; no result depends on it)
  *   VGX_PREVALENCE_TILE_EVENTS=n   vgx_get_prevalence / vgx_get_tau_prevalence and vgx_get_susceptibles / vgx_get_tau_susceptibles: consecutive events (rows) a counting workgroup takes (default 4096; no result depends on it)
+ *   VGX_MILESTONES_TILE_EVENTS=n   vgx_get_milestones: consecutive events a walking workgroup takes, and pass A's tile (default 4096; no result depends on it)
+ *   VGX_MILESTONES_WAVES=4         vgx_get_milestones, diagnostic: four wavefronts per (replicate, tile) taking rounds in turn behind a barrier instead of one (same results)
  */
 #ifndef VGX_H
 #define VGX_H
@@ -833,6 +835,81 @@ typedef struct vgx_tau_susceptibles_chain {
     int64_t *outside;                            /* out [2] */
 } vgx_tau_susceptibles_chain;
 int vgx_test_tau_susceptibles(vgx_tau_susceptibles_chain *io, char *errbuf, int64_t errcap);
+
+/* ---- milestones: peaks, first passages and extinctions ------------------------------------------ */
+/* What a grid cannot answer: how high a variant peaks and when, when it first reaches a number of hosts, whether and when it dies
+ * out, per population and over all populations, exactly and on the device.
+ * Cells.  Keys are 0 .. P-1 for the populations and P for all populations together; classes are 0 .. V-1 through
+ * variant_of[hapNum] (values in [-1, V), -1 = not tracked), as vgx_get_prevalence takes it: cells = (P + 1) * V.  A log record
+ * changes the population cells exactly as vgx_get_prevalence's table says, and every change to cell (p, c) is also made to
+ * (P, c): a migration adds one host to (newPopulation, c) and to (P, c), a mutation between two classes changes both classes in
+ * row P too.
+ * Values.  x[-1] is the start: the state the call started from, or the initial state for a replicate that restarted, folded
+ * through variant_of; row P of the start is the sum over the populations.  x[i] is the value after event i, for i in [0, n_ev).
+ * Every step is +1, 0 or -1 per cell.  Values are signed int32 and are compared as such.
+ * Results per (replicate, key, class), with event indices as int32:
+ *   final          = x[n_ev - 1]; for an empty chain it is x[-1]
+ *   peak           = the maximum of x[i] over i in [-1, n_ev); peak_event is the smallest i that attains it, -1 means the start
+ *   first_event[k] = for each of the K thresholds theta_k (int32, any sign, 0 <= K <= 16) the smallest i >= -1 with
+ *                    x[i] >= theta_k; VGX_MS_NEVER = INT32_MAX if there is none
+ *   last_positive  = the largest i in [-1, n_ev) with x[i] > 0; -2 if there is none
+ * Times are doubles, formed on the host from the replicate's clock: index i >= 0 becomes the time of event i, the same double
+ * vgx_get_events gives; index -1 becomes the time the chain starts from; VGX_MS_NEVER and -2 become NaN.  The chains this call
+ * accepts hold no event before the last call's log, and their clock starts where the call started: at the model's time when the
+ * ensemble's first call began (0.0 for a model that had not run) for a first attempt, at 0.0 for a replicate that restarted,
+ * which is what the host clock opens its run with; index -1 gets that value.  extinction_time is the time of event
+ * last_positive + 1, the record that emptied the cell for good, where last_positive >= -1 and final == 0, NaN elsewhere (a chain
+ * that stops at its iteration cap with hosts left is not extinct).
+ * The device passes.  Pass A forms the net change of every (tile, population, class) with vgx_get_prevalence's counting kernel
+ * over the tile edges as bounds, bound[j] = min(j * tile, n_ev), and its scan turns them into running sums: the values at every
+ * tile's first event, the base of that tile (m * tiles * popNum * V * 4 bytes per chunk, counted in the chunk's share of device
+ * memory).  Pass B, the ordered walk: one wavefront takes a (replicate, tile); its LDS holds one record per cell (the current
+ * value, the peak and its event, the last positive event, K first events: 4 (4 + K) bytes per cell); the population rows start
+ * from the tile's base, row P from their sum; it walks its events in log order, 64 consecutive events per round, one per lane.
+ * Within a round, for one cell, pos is the ballot of the lanes that add to it and neg of those that take from it, and the value
+ * after lane l's event is cur + popcount(pos & le(l)) - popcount(neg & le(l)).  A loop over the distinct cells of the round (a
+ * wave has no match instruction) forms the two ballots of every cell and hands the j-th cell to lane j; every lane then settles
+ * its cell from the masks alone: the first lane at or above theta_k, the last lane above zero and the maximum with its first
+ * lane, all cells of the round at once.  When its tile ends the workgroup merges its records into the replicate's block with integer atomics: the peak as a
+ * 64-bit atomicMax of the value biased to unsigned in the high word and 0xFFFFFFFF - (event + 1) in the low word, first events
+ * with atomicMin, the last positive event with atomicMax.  The host initialises the block from the start state first (peak =
+ * x[-1] at event -1, thresholds already met at -1, last_positive = -1 where the start is positive), so a chain of zero events
+ * gets its answer without a walk.  final of a population row is the last running sum, row P their sum.  No result depends on the
+ * tile size (VGX_MILESTONES_TILE_EVENTS, default 4096), the launch geometry, the chunking (VGX_TIMELINES_CHUNK_BYTES) or the
+ * order in which workgroups finish.  The log is never copied; the host clock runs as in vgx_get_prevalence.
+ * Any output pointer may be NULL (not written).  passes counts the launches of the walk; ms: kernels, host clock, whole call.
+ * Preconditions as vgx_get_prevalence.  Refusals (VGX_ERR_ARG, worded alike behind "vgx_get_milestones: "): those; replicates
+ * out of range or given twice; V < 1 or a variant_of value outside [-1, V); K outside [0, 16]; a population size of 2^31 or more;
+ * (popNum + 1) * V * 4 * (4 + K) bytes of records above the 65536 bytes of LDS a walking workgroup may use (the message names
+ * popNum, V, K and the bytes); a replicate whose tile bases alone do not fit in the call's share of device memory; a chain of
+ * 2^30 events or more.  vgx_clock_mismatches counts every selected replicate once. */
+#define VGX_MS_NEVER 2147483647
+typedef struct vgx_milestones_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    int64_t V; const int32_t *variant_of;        /* [hapNum], values in [-1, V) */
+    int64_t K; const int32_t *thresholds;        /* [K], 0 <= K <= 16 */
+    int32_t *final;                              /* NULL or host [n][P+1][V] */
+    int32_t *peak;                               /* NULL or host [n][P+1][V] */
+    int32_t *peak_event;                         /* NULL or host [n][P+1][V] */
+    int32_t *last_positive_event;                /* NULL or host [n][P+1][V] */
+    int32_t *first_event;                        /* NULL or host [n][K][P+1][V] */
+    double *peak_time;                           /* NULL or host [n][P+1][V] */
+    double *extinction_time;                     /* NULL or host [n][P+1][V] */
+    double *first_time;                          /* NULL or host [n][K][P+1][V] */
+    int64_t passes; double ms[3];                /* out: launches of the walk; kernels, host clock, whole call */
+} vgx_milestones_io;
+int vgx_get_milestones(vgx_engine *e, vgx_milestones_io *io);
+/* Test hook: the rule, pass A, the walk in rounds of 64 emulated lanes with the same mask arithmetic and the merge of
+ * vgx_get_milestones compiled for the host, on one chain given as arrays (no device, no engine), tile after tile with `tile`
+ * events each (0: the default).  start [P][V]: whole numbers in [0, 2^31), their sums too.  t_start: the time of index -1.  The
+ * outputs ([P+1][V], first_* [K][P+1][V]) are overwritten.  The same limits: the LDS budget, K, a chain of 2^30 events, a bad V or
+ * variant_of are refused with the message in errbuf. */
+int vgx_test_milestones(const double *times, const int64_t *types, const int64_t *haplotypes, const int64_t *populations,
+                        const int64_t *newHaplotypes, const int64_t *newPopulations, int64_t n_ev, int64_t P, int64_t hapNum,
+                        const int32_t *variant_of, int64_t V, const int64_t *start, const int32_t *thresholds, int64_t K, int64_t tile,
+                        double t_start, int32_t *final, int32_t *peak, int32_t *peak_event, int32_t *last_positive_event,
+                        int32_t *first_event, double *peak_time, double *extinction_time, double *first_time, char *errbuf,
+                        int64_t errcap);
 
 /* ---- kernel choice of the direct path ------------------------------------------------------- */
 /* What the choice of a direct call's kernel reads: the model's dimensions, the state the call starts from and two diagnostic

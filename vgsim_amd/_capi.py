@@ -142,6 +142,15 @@ class VgxPrevalenceIO(C.Structure):
                 ("passes", C.c_int64), ("ms", C.c_double * 3)]
 
 
+class VgxMilestonesIO(C.Structure):
+    _fields_ = [("n", C.c_int64), ("replicates", _I), ("V", C.c_int64), ("variant_of", C.POINTER(C.c_int32)),
+                ("K", C.c_int64), ("thresholds", C.POINTER(C.c_int32)),
+                ("final", C.POINTER(C.c_int32)), ("peak", C.POINTER(C.c_int32)), ("peak_event", C.POINTER(C.c_int32)),
+                ("last_positive_event", C.POINTER(C.c_int32)), ("first_event", C.POINTER(C.c_int32)),
+                ("peak_time", _F), ("extinction_time", _F), ("first_time", _F),
+                ("passes", C.c_int64), ("ms", C.c_double * 3)]
+
+
 class VgxTauIncidenceIO(C.Structure):
     _fields_ = [("n", C.c_int64), ("replicates", _I), ("T", C.c_int64), ("edges", _F), ("hap_mask", C.POINTER(C.c_uint32)),
                 ("counts", _I), ("outside", _I), ("summary", C.POINTER(VgxTrajSummaryIO)),
@@ -277,6 +286,10 @@ SIGNATURES = {
     "vgx_get_prevalence": (C.c_int, [_H, C.POINTER(VgxPrevalenceIO)]),
     "vgx_test_prevalence": (C.c_int, [_F, _I, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, _F, C.c_int64, C.POINTER(C.c_int32), C.c_int64, _I,
                                       C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, C.c_char_p, C.c_int64]),
+    "vgx_get_milestones": (C.c_int, [_H, C.POINTER(VgxMilestonesIO)]),
+    "vgx_test_milestones": (C.c_int, [_F, _I, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int64, _I,
+                                      C.POINTER(C.c_int32), C.c_int64, C.c_int64, C.c_double] + [C.POINTER(C.c_int32)] * 5 + [_F] * 3 +
+                            [C.c_char_p, C.c_int64]),
     "vgx_get_tau_incidence": (C.c_int, [_H, C.POINTER(VgxTauIncidenceIO), C.POINTER(VgxTimelinesPrefix)]),
     "vgx_test_tau_incidence": (C.c_int, [C.POINTER(VgxTauIncidenceChain), C.c_char_p, C.c_int64]),
     "vgx_get_tau_prevalence": (C.c_int, [_H, C.POINTER(VgxTauPrevalenceIO), C.POINTER(VgxTimelinesPrefix)]),
@@ -934,6 +947,73 @@ def replay_prevalence(times, types, haplotypes, populations, newHaplotypes, newP
     if rc != VGX_OK:
         raise ValueError(err.value.decode() or "vgx_test_prevalence failed")
     return values, final, outside
+
+
+MS_NEVER = 2 ** 31 - 1     # VGX_MS_NEVER: first_event of a threshold no value reaches
+MS_MAX_K = 16
+
+
+def milestone_thresholds(thresholds):
+    """``thresholds`` of ``Ensemble.milestones`` as an int32 array [K], K <= 16; ValueError for anything else."""
+    th = np.asarray(thresholds if thresholds is not None else ())
+    if th.ndim != 1:
+        raise ValueError("thresholds must be a sequence of integers")
+    if len(th) and not np.issubdtype(th.dtype, np.integer):
+        raise ValueError("thresholds must be integers")
+    if len(th) > MS_MAX_K:
+        raise ValueError("K = %d thresholds: at most %d" % (len(th), MS_MAX_K))
+    th = th.astype(object) if len(th) else th
+    if len(th) and (min(th) < -2 ** 31 or max(th) > 2 ** 31 - 1):
+        raise ValueError("thresholds must be integers in int32")
+    return np.ascontiguousarray(th, dtype=np.int32)
+
+
+def milestones_lds_check(P, V, K):
+    """The LDS limit of the walk, worded as the library words it; ValueError above it."""
+    need = (P + 1) * V * 4 * (4 + K)
+    if need > 65536:
+        raise ValueError("%d populations (and their total) x %d classes x %d thresholds need %d bytes of records, above the 65536 bytes of "
+                         "LDS a walking workgroup may use" % (P, V, K, need))
+
+
+def replay_milestones(times, types, haplotypes, populations, newHaplotypes, newPopulations, popNum, hapNum, variant_of, V, start, thresholds=(),
+                      tile=0, t_start=0.0):
+    """The results of ``Ensemble.milestones`` for one chain given as arrays through ``vgx_test_milestones``: the device's rule, tile
+    bases, rounds of 64 lanes and merge (vgx_milestones.h) compiled for the host, tile after tile of ``tile`` events (0: the
+    default); no GPU.  ``variant_of`` [hapNum] with values in [-1, V); ``start`` [P, V] the chain's start folded through it;
+    ``t_start`` the time of event index -1.  Returns a dict of final, peak, peak_event, last_positive_event [P + 1, V] int32,
+    first_event [K, P + 1, V] int32, peak_time, extinction_time [P + 1, V] and first_time [K, P + 1, V] float64; a refusal raises
+    ``ValueError`` with the library's message."""
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.int64) for c in (types, haplotypes, populations, newHaplotypes, newPopulations)]
+    n = len(times)
+    if any(len(c) != n for c in cols):
+        raise ValueError("event columns of different lengths")
+    P, V = int(popNum), int(V)
+    vo = np.ascontiguousarray(variant_of, dtype=np.int32)
+    if len(vo) != int(hapNum):
+        raise ValueError("variant_of must hold hapNum values")
+    start = np.ascontiguousarray(start, dtype=np.int64)
+    if start.shape != (P, V):
+        raise ValueError("start must have the shape [P, V]")
+    th = np.ascontiguousarray(thresholds, dtype=np.int32).ravel()
+    K = len(th)
+    shape, kshape = (P + 1, max(V, 1)), (max(K, 1), P + 1, max(V, 1))
+    out = {k: np.zeros(shape, dtype=np.int32) for k in ("final", "peak", "peak_event", "last_positive_event")}
+    out["first_event"] = np.zeros(kshape, dtype=np.int32)
+    out["peak_time"], out["extinction_time"] = np.zeros(shape), np.zeros(shape)
+    out["first_time"] = np.zeros(kshape)
+    err = C.create_string_buffer(512)
+    i32 = C.POINTER(C.c_int32)
+    rc = load_library().vgx_test_milestones(
+        _p(times), *[_p(c) for c in cols], n, P, int(hapNum), vo.ctypes.data_as(i32), V, _p(start), th.ctypes.data_as(i32), K, int(tile),
+        float(t_start), *[out[k].ctypes.data_as(i32) for k in ("final", "peak", "peak_event", "last_positive_event", "first_event")],
+        *[_p(out[k]) for k in ("peak_time", "extinction_time", "first_time")], err, 512)
+    if rc != VGX_OK:
+        raise ValueError(err.value.decode() or "vgx_test_milestones failed")
+    for k in ("first_event", "first_time"):
+        out[k] = out[k][:K]
+    return out
 
 
 def replay_tau_incidence(events, mev, popNum, hapNum, edges, hap_mask=None, tile=0, n_own_events=-1):

@@ -1601,10 +1601,11 @@ extern "C" int vgx_get_timelines(vgx_engine *e, vgx_timelines_io *io) {
 // staged through pinned host memory; the log itself is not copied.  on_chain(i, times) gets the event times of selected
 // replicate i (from several threads, one replicate each at a time), then on_chunk(i0, i1, max_n) runs the device pass over the
 // replicates [i0, i1) and returns its code.  ms[0] gains the pack kernel's time, ms[1] the host clock's.  Every replicate's clock
-// is built once, as when the replicates are fetched one by one: vgx_clock_mismatches counts each once.
+// is built once, as when the replicates are fetched one by one: vgx_clock_mismatches counts each once.  With `tile` > 0 a chunk's
+// replicates each also hold tile_bytes per tile of the chunk's longest chain (the bases of vgx_get_milestones), counted in `share`.
 template <class Chain, class Chunk>
 static int clock_chunks(vgx_engine *e, const char *what, const std::vector<int64_t> &reps, const std::vector<int32_t> &n_ev, const int64_t *d_rep,
-                        const int32_t *d_nev, int64_t share, double *ms, Chain on_chain, Chunk on_chunk) {
+                        const int32_t *d_nev, int64_t share, double *ms, Chain on_chain, Chunk on_chunk, int64_t tile = 0, int64_t tile_bytes = 0) {
     const std::string pre = std::string(what) + ": ";
     const int64_t n = (int64_t)reps.size();
     auto up8 = [](int64_t b) { return (b + 255) / 256 * 256; };
@@ -1617,7 +1618,9 @@ static int clock_chunks(vgx_engine *e, const char *what, const std::vector<int64
         int64_t i1 = i0, sum = 0, E = 0, max_n = 0;
         while (i1 < n && i1 - i0 < ((int64_t)1 << 20)) {
             const int64_t b = (int64_t)n_ev[(size_t)i1] * 12 + 64;
-            if (i1 > i0 && sum + b > share) break;
+            // (vgx_get_milestones: every replicate of the chunk also holds tile_bytes per tile of the chunk's longest chain)
+            const int64_t tiles = tile > 0 ? std::max<int64_t>((std::max<int64_t>(max_n, n_ev[(size_t)i1]) + tile - 1) / tile, 1) : 0;
+            if (i1 > i0 && sum + b + (i1 - i0 + 1) * tiles * tile_bytes > share) break;
             sum += b;
             E += n_ev[(size_t)i1];
             max_n = std::max<int64_t>(max_n, n_ev[(size_t)i1]);
@@ -1956,6 +1959,199 @@ extern "C" int vgx_get_prevalence(vgx_engine *e, vgx_prevalence_io *io) {
         const int rc = vgxi_column_summary_i32("vgx_get_prevalence: summary", (const int32_t *)(kws + o_val), n, T * cells, io->summary, e->stream, msg, sizeof msg);
         if (rc) return fail(e, rc, msg);
     }
+    io->ms[2] = wall();
+    return VGX_OK;
+}
+
+// ---- peaks, first passages and last positive events of many replicates (vgx_milestones.hip, vgx_milestones.h) -----
+// vgx_get_prevalence's host side with the tile edges in place of a grid: per chunk, pass A (its counting and scan kernels) gives
+// every tile its base, the ordered walk merges every tile's records into the block the host initialised from the start state, and
+// the host turns the event indices into times with the clock it has just run.
+extern "C" int vgx_get_milestones(vgx_engine *e, vgx_milestones_io *io) {
+    if (!e || !io || io->n < 0 || (io->n > 0 && !io->replicates)) return VGX_ERR_ARG;
+    const auto t_call = std::chrono::steady_clock::now();
+    auto wall = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(); };
+    io->passes = 0;
+    io->ms[0] = io->ms[1] = io->ms[2] = 0.0;
+    if (e->last_was_tau) return fail(e, VGX_ERR_ARG, "vgx_get_milestones: the last call was vgx_simulate_tau (walks direct chains only)");
+    if (!e->sc_host_valid || !e->dev_state_valid) return fail(e, VGX_ERR_ARG, "vgx_get_milestones: needs a direct vgx_simulate_direct call with the event log first");
+    if (!e->call_recorded) return fail(e, VGX_ERR_ARG, "vgx_get_milestones: the last call did not record events");
+    const int64_t n = io->n, P = e->d.popNum, H = e->d.hapNum, V = io->V, K = io->K;
+    if (V < 1 || V > INT32_MAX || !io->variant_of) return fail(e, VGX_ERR_ARG, "vgx_get_milestones: V = " + std::to_string(V) + " classes: at least 1, with variant_of");
+    for (int64_t h = 0; h < H; h++)
+        if (io->variant_of[h] < -1 || io->variant_of[h] >= V)
+            return fail(e, VGX_ERR_ARG, "vgx_get_milestones: variant_of[" + std::to_string(h) + "] = " + std::to_string(io->variant_of[h]) + " is outside [-1, " + std::to_string(V) + ")");
+    if (K < 0 || K > VGX_MS_MAX_K || (K > 0 && !io->thresholds))
+        return fail(e, VGX_ERR_ARG, "vgx_get_milestones: K = " + std::to_string(K) + " thresholds: at most 16, with thresholds");
+    for (int64_t pn = 0; pn < P; pn++)
+        if (e->sizes[(size_t)pn] >= ((int64_t)1 << 31)) return fail(e, VGX_ERR_ARG, "vgx_get_milestones: population sizes of 2^31 or more");
+    if (vgx_ms_lds_bytes(P, V, K) > VGX_MS_LDS_MAX)
+        return fail(e, VGX_ERR_ARG, "vgx_get_milestones: " + std::to_string(P) + " populations (and their total) x " + std::to_string(V) + " classes x " + std::to_string(K) +
+                                        " thresholds need " + std::to_string(vgx_ms_lds_bytes(P, V, K)) + " bytes of records, above the " + std::to_string((int64_t)VGX_MS_LDS_MAX) +
+                                        " bytes of LDS a walking workgroup may use");
+    const int64_t pv = P * V, cells = pv + V;
+    std::vector<int32_t> n_ev((size_t)n);
+    {
+        std::vector<char> seen((size_t)e->R, 0);
+        for (int64_t i = 0; i < n; i++) {
+            const int64_t r = io->replicates[i];
+            if (r < 0 || r >= e->R) return fail(e, VGX_ERR_ARG, "vgx_get_milestones: replicate index out of range");
+            if (seen[(size_t)r]) return fail(e, VGX_ERR_ARG, "vgx_get_milestones: replicates must be distinct");
+            seen[(size_t)r] = 1;
+            const VgxRepScalars &s = e->sc_host[(size_t)r];
+            const int64_t first = s.restarts > 0 ? 0 : ((size_t)r < e->call_ev0.size() ? e->call_ev0[(size_t)r] : e->ev_ptr0);
+            if (first != 0 || e->ev_base != 0)
+                return fail(e, VGX_ERR_ARG, "vgx_get_milestones: replicate " + std::to_string(r) + ": its chain does not start in the last call's device log (the model held " +
+                                                std::to_string(e->ev_base != 0 ? e->ev_base : first) + " events when the ensemble started)");
+            if (s.ev_ptr >= VGX_MS_MAX_EVENTS)
+                return fail(e, VGX_ERR_ARG, "vgx_get_milestones: replicate " + std::to_string(r) + " holds a chain of " + std::to_string(s.ev_ptr) + " events (2^30 or more)");
+            if (s.ev_ptr < 0 || s.ev_ptr > e->evcap)
+                return fail(e, VGX_ERR_ARG, "vgx_get_milestones: event range of replicate " + std::to_string(r) + " outside the device log");
+            n_ev[(size_t)i] = (int32_t)s.ev_ptr;
+        }
+    }
+    if (n == 0) {
+        io->ms[2] = wall();
+        return VGX_OK;
+    }
+    // the start of a chain folded through variant_of, the row of all populations behind the population rows
+    std::vector<int32_t> start((size_t)(n * pv));
+    std::vector<int32_t> start_all[2] = {std::vector<int32_t>((size_t)cells), std::vector<int32_t>((size_t)cells)};
+    {
+        std::vector<int64_t> fold[2] = {std::vector<int64_t>((size_t)cells, 0), std::vector<int64_t>((size_t)cells, 0)};
+        const std::vector<int64_t> *src[2] = {&e->hs.infectious, &e->hs.initial_infectious};
+        for (int k = 0; k < 2; k++) {
+            for (int64_t pn = 0; pn < P; pn++)
+                for (int64_t h = 0; h < H; h++)
+                    if (io->variant_of[h] >= 0) {
+                        fold[k][(size_t)(pn * V + io->variant_of[h])] += (*src[k])[(size_t)(pn * H + h)];
+                        fold[k][(size_t)(pv + io->variant_of[h])] += (*src[k])[(size_t)(pn * H + h)];
+                    }
+            for (int64_t c = 0; c < cells; c++) {
+                if (fold[k][(size_t)c] < 0 || fold[k][(size_t)c] > INT32_MAX) return fail(e, VGX_ERR_ARG, "vgx_get_milestones: a start value outside [0, 2^31)");
+                start_all[k][(size_t)c] = (int32_t)fold[k][(size_t)c];
+            }
+        }
+        for (int64_t i = 0; i < n; i++) {
+            const std::vector<int32_t> &f = start_all[e->sc_host[(size_t)io->replicates[i]].restarts > 0 ? 1 : 0];
+            for (int64_t c = 0; c < pv; c++) start[(size_t)(i * pv + c)] = f[(size_t)c];
+        }
+    }
+    int64_t tile = VGX_MS_TILE_DEFAULT;
+    if (const char *tb = getenv("VGX_MILESTONES_TILE_EVENTS")) tile = std::min<int64_t>(std::max<int64_t>(atoll(tb), 1), VGX_MS_MAX_EVENTS);
+    const char *wv = getenv("VGX_MILESTONES_WAVES");      // diagnostic: 4 = four wavefronts per tile taking rounds in turn
+    const int waves = wv && atoi(wv) == 4 ? 4 : 1;
+    HIPCHECK(e, hipSetDevice(e->device));
+    size_t free_b = 0, total_b = 0;
+    HIPCHECK(e, hipMemGetInfo(&free_b, &total_b));
+    auto up8 = [](int64_t b) { return (b + 255) / 256 * 256; };
+    auto dev_free = [](char *p) { (void)hipFree(p); };
+    // what stays for the whole call: [rep | n_ev | variant_of | start | peak | last_pos | first]
+    const int64_t peak_bytes = n * cells * 8, last_bytes = n * cells * 4, first_bytes = n * K * cells * 4;
+    const int64_t o_rep = 0, o_nev = o_rep + up8(n * 8), o_map = o_nev + up8(n * 4), o_start = o_map + up8(H * 4), o_peak = o_start + up8(n * pv * 4),
+                  o_last = o_peak + up8(peak_bytes), o_first = o_last + up8(last_bytes), keep_total = o_first + up8(first_bytes) + 256;
+    if (keep_total > (int64_t)(free_b / 2))
+        return fail(e, VGX_ERR_ARG, "vgx_get_milestones: the block of " + std::to_string(n) + " x " + std::to_string(P + 1) + " x " + std::to_string(V) + " records of " +
+                                        std::to_string(K) + " thresholds and its start take " + std::to_string(keep_total) + " bytes, above half of the " +
+                                        std::to_string((int64_t)free_b) + " bytes of free device memory: select fewer replicates per call");
+    const int64_t share = (int64_t)(free_b / 2) - keep_total + 4096;
+    // the bases of one replicate: its bounds, a running sum per (tile, population, class) and the final row
+    const int64_t tile_bytes = pv * 4 + 4;
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t tiles = std::max<int64_t>((n_ev[(size_t)i] + tile - 1) / tile, 1);
+        const int64_t need = (int64_t)n_ev[(size_t)i] * 12 + 64 + tiles * tile_bytes + pv * 4 + 1024;
+        if (need > share)
+            return fail(e, VGX_ERR_ARG, "vgx_get_milestones: replicate " + std::to_string(io->replicates[i]) + ": the bases of its " + std::to_string(tiles) + " tiles of " +
+                                            std::to_string(tile) + " events (" + std::to_string(tiles * tile_bytes) + " bytes) and its clock take " + std::to_string(need) +
+                                            " bytes, above the " + std::to_string(share) + " bytes of device memory the call may use: raise VGX_MILESTONES_TILE_EVENTS");
+    }
+    char *kws = nullptr;
+    hipError_t er = hipMalloc((void **)&kws, (size_t)keep_total);
+    if (er != hipSuccess) return fail(e, VGX_ERR_HIP, "vgx_get_milestones: hipMalloc of " + std::to_string(keep_total) + " bytes: " + hipGetErrorString(er));
+    std::unique_ptr<char, void (*)(char *)> khold(kws, dev_free);
+    std::vector<int64_t> reps_all(io->replicates, io->replicates + n);
+    // the block before any tile: the start offers itself at event -1
+    std::vector<uint64_t> h_peak((size_t)(n * cells));
+    std::vector<int32_t> h_last((size_t)(n * cells)), h_first((size_t)(n * std::max<int64_t>(K, 1) * cells));
+    for (int64_t i = 0; i < n; i++) {
+        const std::vector<int32_t> &f = start_all[e->sc_host[(size_t)io->replicates[i]].restarts > 0 ? 1 : 0];
+        const VgxMsBlock b{h_peak.data() + i * cells, h_last.data() + i * cells, h_first.data() + i * K * cells};
+        for (int64_t c = 0; c < cells; c++) vgx_ms_init_cell(b, (int32_t)c, (int32_t)cells, f[(size_t)c], io->thresholds, (int32_t)K);
+    }
+    HIPCHECK(e, hipMemcpyAsync(kws + o_rep, reps_all.data(), (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_nev, n_ev.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_map, io->variant_of, (size_t)H * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_start, start.data(), (size_t)(n * pv) * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_peak, h_peak.data(), (size_t)peak_bytes, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_last, h_last.data(), (size_t)last_bytes, hipMemcpyHostToDevice, e->stream));
+    if (K > 0) HIPCHECK(e, hipMemcpyAsync(kws + o_first, h_first.data(), (size_t)first_bytes, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipStreamSynchronize(e->stream));
+
+    std::vector<std::vector<double>> tms((size_t)n);      // the event times of the chunk's replicates, until their indices are known
+    const int rc_chunks = clock_chunks(e, "vgx_get_milestones", reps_all, n_ev, (const int64_t *)(kws + o_rep), (const int32_t *)(kws + o_nev), share, io->ms,
+        // host: a replicate's event times are kept until the chunk's event indices come back
+        [&](int64_t gi, const std::vector<double> &times) { tms[(size_t)gi] = times; },
+        // device: pass A over the tile edges, then the walk of every (replicate, tile); host: indices -> results and times
+        [&](int64_t i0, int64_t i1, int64_t max_n) -> int {
+            const int64_t m = i1 - i0, T = std::max<int64_t>((max_n + tile - 1) / tile, 1);
+            std::vector<int32_t> bounds((size_t)(m * (T + 2)));
+            for (int64_t j = 0; j < m; j++)
+                for (int64_t k = 0; k <= T + 1; k++) bounds[(size_t)(j * (T + 2) + k)] = (int32_t)std::min<int64_t>(k * tile, n_ev[(size_t)(i0 + j)]);
+            const int64_t c_bnd = 0, c_val = c_bnd + up8(m * (T + 2) * 4), c_fin = c_val + up8(m * T * pv * 4), c_total = c_fin + up8(m * pv * 4);
+            char *cws = nullptr;
+            if ((er = hipMalloc((void **)&cws, (size_t)c_total)) != hipSuccess)
+                return fail(e, VGX_ERR_HIP, "vgx_get_milestones: hipMalloc of " + std::to_string(c_total) + " bytes: " + hipGetErrorString(er));
+            std::unique_ptr<char, void (*)(char *)> chold(cws, dev_free);
+            HIPCHECK(e, hipMemcpyAsync(cws + c_bnd, bounds.data(), bounds.size() * 4, hipMemcpyHostToDevice, e->stream));
+            HIPCHECK(e, hipMemsetAsync(cws + c_val, 0, (size_t)(c_total - c_val), e->stream));   // val and fin
+            HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
+            VgxMsLaunch g{};
+            VgxPrevLaunch &a = g.a;
+            a.m = m;
+            a.log = (const int32_t *)e->r_evcols.p; a.evcap = e->evcap;
+            a.rep = (const int64_t *)(kws + o_rep) + i0; a.n_ev = (const int32_t *)(kws + o_nev) + i0;
+            a.bound = (const int32_t *)(cws + c_bnd);
+            a.T = (int32_t)T; a.P = (int32_t)P; a.hapNum = (int32_t)H; a.V = (int32_t)V;
+            a.variant_of = (const int32_t *)(kws + o_map);
+            a.tile = (int32_t)tile; a.max_n = max_n;
+            a.val = (int32_t *)(cws + c_val);
+            a.fin = (int32_t *)(cws + c_fin);
+            a.start = (const int32_t *)(kws + o_start) + i0 * pv;
+            g.K = (int32_t)K;
+            for (int64_t k = 0; k < K; k++) g.theta[k] = io->thresholds[k];
+            g.peak = (uint64_t *)(kws + o_peak) + i0 * cells;
+            g.last_pos = (int32_t *)(kws + o_last) + i0 * cells;
+            g.first = (int32_t *)(kws + o_first) + i0 * K * cells;
+            HIPCHECK(e, vgxi_prev_count(&a, e->stream));
+            HIPCHECK(e, vgxi_prev_scan(&a, e->stream));
+            HIPCHECK(e, vgxi_ms_walk(&g, waves, e->stream));
+            if (max_n > 0) io->passes += 1;
+            HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
+            std::vector<int32_t> fin((size_t)(m * pv));
+            HIPCHECK(e, hipMemcpyAsync(fin.data(), cws + c_fin, (size_t)(m * pv) * 4, hipMemcpyDeviceToHost, e->stream));
+            HIPCHECK(e, hipMemcpyAsync(h_peak.data() + i0 * cells, kws + o_peak + i0 * cells * 8, (size_t)(m * cells) * 8, hipMemcpyDeviceToHost, e->stream));
+            HIPCHECK(e, hipMemcpyAsync(h_last.data() + i0 * cells, kws + o_last + i0 * cells * 4, (size_t)(m * cells) * 4, hipMemcpyDeviceToHost, e->stream));
+            if (K > 0)
+                HIPCHECK(e, hipMemcpyAsync(h_first.data() + i0 * K * cells, kws + o_first + i0 * K * cells * 4, (size_t)(m * K * cells) * 4, hipMemcpyDeviceToHost, e->stream));
+            if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)
+                return fail(e, VGX_ERR_HIP, std::string("vgx_get_milestones: counting, scan or walk kernel failed: ") + hipGetErrorString(er));
+            float kms = 0.f;
+            HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
+            io->ms[0] += kms;
+            for (int64_t j = 0; j < m; j++) {
+                const int64_t gi = i0 + j, r = reps_all[(size_t)gi];
+                const VgxMsBlock b{h_peak.data() + gi * cells, h_last.data() + gi * cells, h_first.data() + gi * K * cells};
+                auto at = [&](auto *p, int64_t per) { return p ? p + gi * per : p; };
+                const VgxMsOut out{at(io->final, cells), at(io->peak, cells), at(io->peak_event, cells), at(io->last_positive_event, cells),
+                                   at(io->first_event, K * cells), at(io->peak_time, cells), at(io->extinction_time, cells), at(io->first_time, K * cells)};
+                // index -1: what the host clock opens this chain's run with (clock_build)
+                const double t_start = e->sc_host[(size_t)r].restarts > 0 ? 0.0 : e->call_t0[(size_t)r];
+                vgx_ms_outputs(b, fin.data() + j * pv, (int32_t)P, (int32_t)V, (int32_t)K, n_ev[(size_t)gi], tms[(size_t)gi].data(), t_start, out);
+                std::vector<double>().swap(tms[(size_t)gi]);
+            }
+            return VGX_OK;
+        }, tile, tile_bytes);
+    if (rc_chunks) return rc_chunks;
     io->ms[2] = wall();
     return VGX_OK;
 }

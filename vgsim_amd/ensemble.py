@@ -301,6 +301,49 @@ class Susceptibles:
         return out
 
 
+class Milestones:
+    """What ``Ensemble.milestones`` returns: peaks, first passages and extinctions per selected replicate, key and variant class,
+    exact over every event of the chain.  The key axis holds the populations 0 .. P-1 and, at index P (or -1), all populations
+    together.  Event indices count the chain's events from 0; -1 is the chain's start.
+
+    ``peak``, ``peak_event``, ``peak_time`` [n, P+1, V]: the largest value, the first event that attains it and its time;
+    ``final`` [n, P+1, V] the value after the whole chain; ``last_positive_event`` [n, P+1, V] the last event after which the cell
+    holds a host (-2: never); ``first_event``, ``first_time``, ``reached`` [n, K, P+1, V]: the first event at or above
+    ``thresholds[k]`` (``NEVER`` and NaN where none is, ``reached`` False); ``thresholds`` [K] int32; ``variant_of`` [H];
+    ``replicates`` [n]; ``passes``, ``kernel_ms``, ``clock_ms``, ``wall_ms``.  Integer arrays are int32, times float64."""
+
+    NEVER = _capi.MS_NEVER
+
+    @property
+    def extinct(self):
+        """[n, P+1, V] bool: the cell held a host at some event and holds none at the end (a chain that stops at its iteration
+        cap with hosts left is not extinct)."""
+        return (self.last_positive_event >= -1) & (self.final == 0)
+
+    @property
+    def never_present(self):
+        """[n, P+1, V] bool: the cell never held a host, the start included."""
+        return self.last_positive_event == -2
+
+    @property
+    def extinction_event(self):
+        """[n, P+1, V] int32: the event that emptied the cell for good, ``last_positive_event + 1``; meaningful where ``extinct``."""
+        return self.last_positive_event + np.int32(1)
+
+    def extinction_probability(self, by='auto'):
+        """The share of the selected replicates of every group in which the cell is extinct, [G, P+1, V] float64 (NaN for a group
+        without selected replicates).  ``by`` as ``trajectory_summary`` takes it: 'auto' is one group per scenario of a scenario
+        ensemble, one group otherwise; or one integer label per replicate of the ensemble."""
+        group_of, G = _summary_groups(by, None, self._R, self._scenario_of, self._n_scenarios)
+        g = group_of[self.replicates]
+        ext = self.extinct
+        out = np.full((G,) + ext.shape[1:], np.nan)
+        for k in range(G):
+            if (g == k).any():
+                out[k] = ext[g == k].mean(axis=0)
+        return out
+
+
 def _prevalence_grid(times, points, window):
     """The grid of a ``prevalence`` call as a float64 array; ValueError for bad arguments."""
     if (times is None) == (points is None):
@@ -993,6 +1036,57 @@ class Ensemble:
         pv.summary = done() if done is not None else None
         pv.passes, pv.kernel_ms, pv.clock_ms, pv.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
         return pv
+
+    def milestones(self, variants=None, thresholds=(), replicates=None):
+        """Peaks, first passages and extinctions of every selected replicate of the last direct ``simulate(record_events=True)``
+        call, per population, over all populations and per variant class, exact over every event and on the device
+        (``vgx_get_milestones``): one pass gives every tile of a chain its start values, an ordered walk of the log where the
+        kernel left it keeps the running maximum, the first event at or above every threshold and the last event with a host, and
+        the tiles are merged with integer atomics.  Returns a :class:`Milestones`.
+
+        ``variants``: as ``prevalence()`` takes them.  ``thresholds``: up to 16 integers in int32 (host counts; any sign).
+        ``replicates``: indices (default all, in order).  Direct chains only."""
+        if self._last_call is None:
+            raise ValueError("milestones() needs a direct simulate(record_events=True) call first")
+        if self._last_call[0] != 'direct':
+            raise ValueError("milestones() walks direct chains only: the last call was simulate_tau")
+        if not self._last_call[1]:
+            raise ValueError("milestones() needs the event log: the last call had record_events=False")
+        reps = self._selected_replicates(replicates)
+        vo, V = _capi.variant_map(variants, self.model.hapNum)
+        th = _capi.milestone_thresholds(thresholds)
+        n, K, P = len(reps), len(th), self.model.popNum
+        _capi.milestones_lds_check(P, V, K)
+        eng = self.engine
+        for r in reps:
+            c = eng.counters(int(r))
+            if c.ev_first_new != 0:
+                raise ValueError("replicate %d: its chain does not start in the last call's device log (the model held %d events "
+                                 "when the ensemble started)" % (r, c.ev_first_new))
+        ms = Milestones()
+        ints = {k: np.zeros((n, P + 1, V), dtype=np.int32) for k in ("final", "peak", "peak_event", "last_positive_event")}
+        ms.first_event = np.full((n, K, P + 1, V), Milestones.NEVER, dtype=np.int32)
+        ms.peak_time, ext_time = np.full((n, P + 1, V), np.nan), np.full((n, P + 1, V), np.nan)
+        ms.first_time = np.full((n, K, P + 1, V), np.nan)
+        i32 = C.POINTER(C.c_int32)
+        io = _capi.VgxMilestonesIO()
+        io.n, io.replicates, io.V, io.variant_of, io.K = n, _capi._p(reps), V, vo.ctypes.data_as(i32), K
+        io.thresholds = th.ctypes.data_as(i32) if K else None
+        if n:
+            for k, a in ints.items():
+                setattr(io, k, a.ctypes.data_as(i32))
+            io.first_event = ms.first_event.ctypes.data_as(i32) if K else None
+            io.peak_time, io.extinction_time = _capi._p(ms.peak_time), _capi._p(ext_time)
+            io.first_time = _capi._p(ms.first_time) if K else None
+        eng._check(eng.lib.vgx_get_milestones(eng.handle, C.byref(io)))
+        ms.final, ms.peak, ms.peak_event, ms.last_positive_event = (ints[k] for k in ("final", "peak", "peak_event", "last_positive_event"))
+        ms.extinction_time = ext_time
+        ms.reached = ms.first_event != Milestones.NEVER
+        ms.thresholds, ms.variant_of, ms.replicates = th, vo, reps
+        ms._R, ms._scenario_of = self.R, self.scenario_of
+        ms._n_scenarios = len(self.scenarios) if self.scenarios is not None else 1
+        ms.passes, ms.kernel_ms, ms.clock_ms, ms.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
+        return ms
 
     def _prevalence_request(self, g, variants, replicates, summary, values, cell_bytes, scenario_of, n_scenarios):
         """What ``prevalence()`` and ``tau_prevalence()`` share: the checks on ``replicates``, ``variants``, the LDS limit (cells of
