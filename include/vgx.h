@@ -37,6 +37,8 @@
  *   VGX_PREVALENCE_TILE_EVENTS=n   vgx_get_prevalence / vgx_get_tau_prevalence and vgx_get_susceptibles / vgx_get_tau_susceptibles: consecutive events (rows) a counting workgroup takes (default 4096; no result depends on it)
  *   VGX_MILESTONES_TILE_EVENTS=n   vgx_get_milestones: consecutive events a walking workgroup takes, and pass A's tile (default 4096; no result depends on it)
  *   VGX_MILESTONES_WAVES=4         vgx_get_milestones, diagnostic: four wavefronts per (replicate, tile) taking rounds in turn behind a barrier instead of one (same results)
+ *   VGX_TAU_MILESTONES_TILE_ROWS=n vgx_get_tau_milestones: rows of a tile of whole events that a walking workgroup takes (default 4096; no result depends on it)
+ *   VGX_TAU_MILESTONES_WAVES=4     vgx_get_tau_milestones, diagnostic: workgroups of four wavefronts (256 threads) instead of one (same results)
  */
 #ifndef VGX_H
 #define VGX_H
@@ -910,6 +912,96 @@ int vgx_test_milestones(const double *times, const int64_t *types, const int64_t
                         double t_start, int32_t *final, int32_t *peak, int32_t *peak_event, int32_t *last_positive_event,
                         int32_t *first_event, double *peak_time, double *extinction_time, double *first_time, char *errbuf,
                         int64_t errcap);
+
+/* ---- milestones of tau replicates ---------------------------------------------------------------- */
+/* vgx_get_milestones for the replicates of the last vgx_simulate_tau call that recorded its multievent rows.
+ * Chain and events.  The chain is vgx_get_tau_prevalence's: a replicate that did not restart and whose model held events carries
+ * the prefix (vgx_timelines_prefix, flattened: a direct event is one row with num = 1), its own steps follow; a restarted
+ * replicate has its own steps only.  An EVENT is a direct event of the prefix or one step.  Events are numbered from 0 along the
+ * chain: own step k of a replicate with a prefix of pre_ev events is event pre_ev + k.  An event's time is the time of its log
+ * record, prefix->ev_times[i] or the step's.
+ * Cells.  vgx_get_milestones's: keys 0 .. P-1 and key P for all populations together, classes through variant_of, (P + 1) * V
+ * cells.  A row changes the population cells exactly as vgx_get_tau_prevalence says (sign * num, VGX_TL_ROW_DIRECT masked off, a
+ * field that is not a 32-bit index matches nothing, num <= 0 changes nothing), and every change to (p, c) is also made to (P, c).
+ * Values.  x[-1] is start_r of vgx_get_tau_prevalence (the initial state for a replicate that restarted or a prefix that is not
+ * empty, else the state the call started from), row P the sum over the populations.  x[i] is the value after ALL rows of event
+ * i; the state inside a step is not a value: a step whose rows add 5 to a cell and take 5 from it leaves x unchanged, meets no
+ * threshold and moves no peak, and a cell at 1 that gets -1 and +1 in one step has not gone extinct.  Values are int64, compared
+ * signed; sums wrap as unsigned 64-bit integers do.
+ * Results per (replicate, key, class), defined as in vgx_get_milestones over this x: final and peak int64; peak_event (int32) the
+ * smallest i >= -1 that attains the peak; first_event[k] (int32) for each of the K thresholds theta_k (int64, any sign,
+ * 0 <= K <= 16) the smallest i >= -1 with x[i] >= theta_k, else VGX_MS_NEVER; last_positive_event (int32) the largest i with
+ * x[i] > 0, -2 if there is none.  Times are doubles: index i >= 0 gives event i's time; index -1 gives 0.0 for a chain that starts
+ * at the beginning of the model's history (a restart, or a prefix that is not empty), else the time the call's first step started
+ * from; VGX_MS_NEVER and -2 give NaN.  extinction_time is the time of event last_positive + 1 where last_positive >= -1 and
+ * final == 0, NaN elsewhere.  No host clock runs: step times are host doubles already.
+ * The device passes.  Tiles are runs of whole events: the host cuts every chain so that a tile holds about
+ * VGX_TAU_MILESTONES_TILE_ROWS rows (default 4096) and at most as many events; a tile never splits an event, a step with more
+ * rows is a tile of its own.  Pass A: vgx_get_tau_prevalence's int64 counting and scan kernels with the tile edges in row space
+ * as bounds give every tile its base, the values at its first event.  Pass B, the walk: one workgroup takes a (chain, tile); LDS
+ * holds one record per cell (value, the event's net change, peak: int64; the peak's event, the last positive event, K first
+ * events, a touched-list entry and its mark: int32; (P + 1) * V * (40 + 4 K) + 16 bytes).  The events of the tile run in order;
+ * for each, the threads stride over its rows and add the signed num to the net change of its cells with LDS atomics, noting a
+ * cell the first time it is hit; behind a barrier they stride over the touched population cells, settle each (new value, peak,
+ * first events, last positive event; a cell taken from above zero to zero or below offers the event before) and pass its net
+ * change on to row P, whose touched cells are settled behind another barrier.  Events without rows are not visited.  At the
+ * tile's end event indices are merged into the chain's block with 32-bit atomicMin / atomicMax; the tile's peak and its event go
+ * to a slot [chain][tile][cell], and a small kernel reduces the slots in tile order, a strictly greater value winning, so among
+ * equals the earliest event stays.  The prefix is walked ONCE per call as a chain of its own from the initial state; its block
+ * and its final values are what every replicate that carries it starts from.  The host initialises the other blocks from the
+ * start (peak = x[-1] at event -1, thresholds met at -1, last_positive = -1 where the start is positive) and gives a cell that
+ * ends positive last_positive = events - 1.  Every result is an extremum over candidates that hold whatever tile offers them: no
+ * result depends on the tile size, the workgroup shape (VGX_TAU_MILESTONES_WAVES), the chunking (VGX_TIMELINES_CHUNK_BYTES: the
+ * event tables, tile bases and peak slots of a chunk of replicates fit the share) or the order in which workgroups finish.
+ * Any output pointer may be NULL (not written).  passes counts the launches of the walk, the prefix's as one; ms: kernels, the
+ * host's tile and row tables, whole call.
+ * Refusals (VGX_ERR_ARG, worded alike behind "vgx_get_tau_milestones: "): the last call was not vgx_simulate_tau; it recorded no
+ * rows; a replicate that did not restart continues a log of another length than prefix->ev_ptr; prefix plus own rows reach 2^31;
+ * a null prefix column; replicates out of range or given twice; V < 1 or a variant_of value outside [-1, V); K outside [0, 16];
+ * a chain of 2^30 events or more; records above the 65536 bytes of LDS a walking workgroup may use (the message names popNum, V,
+ * K and the bytes); a replicate whose tile bases and peak slots alone do not fit the call's share of device memory. */
+typedef struct vgx_tau_milestones_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    int64_t V; const int32_t *variant_of;        /* [hapNum], values in [-1, V) */
+    int64_t K; const int64_t *thresholds;        /* [K], 0 <= K <= 16 */
+    int64_t *final;                              /* NULL or host [n][P+1][V] */
+    int64_t *peak;                               /* NULL or host [n][P+1][V] */
+    int32_t *peak_event;                         /* NULL or host [n][P+1][V] */
+    int32_t *last_positive_event;                /* NULL or host [n][P+1][V] */
+    int32_t *first_event;                        /* NULL or host [n][K][P+1][V] */
+    double *peak_time;                           /* NULL or host [n][P+1][V] */
+    double *extinction_time;                     /* NULL or host [n][P+1][V] */
+    double *first_time;                          /* NULL or host [n][K][P+1][V] */
+    int64_t passes; double ms[3];                /* out: launches of the walk; kernels, host tile and row tables, whole call */
+} vgx_tau_milestones_io;
+int vgx_get_tau_milestones(vgx_engine *e, vgx_tau_milestones_io *io, const vgx_timelines_prefix *prefix);
+/* Test hook: the flattening, tile edges, pass A, the walk (the same settle, event by event over the touched cells), the merge in
+ * tile order and the outputs of vgx_get_tau_milestones compiled for the host, on one chain given as event columns and multievent
+ * columns as vgx_tau_prevalence_chain gives them (no device, no engine), tile after tile of about `tile` rows (0: the default).
+ * The last n_own_events events play the replicate's own steps (-1: the chain's trailing MULTITYPE events), everything before
+ * them the prefix, which is walked once as a chain of its own; the own events start from its block and its final values, as on
+ * the device.  start [P][V]: x[-1] of the population rows.  t_start: the time of index -1.  The outputs ([P+1][V], first_*
+ * [K][P+1][V]) are overwritten.  Refused with the message in errbuf: K outside [0, 16], the LDS budget, a chain of 2^30 events, a
+ * bad V or variant_of, a MULTITYPE row range outside the multievent log, a prefix row out of range. */
+typedef struct vgx_tau_milestones_chain {
+    int64_t popNum, hapNum;
+    int64_t ev_ptr;
+    const double *ev_times;
+    const int64_t *ev_types, *ev_haplotypes, *ev_populations, *ev_newHaplotypes, *ev_newPopulations;
+    int64_t mev_rows;
+    const int64_t *mev_num, *mev_types, *mev_haplotypes, *mev_populations, *mev_newHaplotypes, *mev_newPopulations;
+    int64_t V; const int32_t *variant_of;        /* [hapNum] */
+    const int64_t *start;                        /* [P][V] */
+    int64_t K; const int64_t *thresholds;        /* [K] */
+    int64_t tile, n_own_events;
+    double t_start;
+    int64_t *final, *peak;                       /* out [P+1][V] */
+    int32_t *peak_event, *last_positive_event;   /* out [P+1][V] */
+    int32_t *first_event;                        /* out [K][P+1][V] */
+    double *peak_time, *extinction_time;         /* out [P+1][V] */
+    double *first_time;                          /* out [K][P+1][V] */
+} vgx_tau_milestones_chain;
+int vgx_test_tau_milestones(vgx_tau_milestones_chain *io, char *errbuf, int64_t errcap);
 
 /* ---- kernel choice of the direct path ------------------------------------------------------- */
 /* What the choice of a direct call's kernel reads: the model's dimensions, the state the call starts from and two diagnostic

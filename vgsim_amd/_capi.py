@@ -151,6 +151,27 @@ class VgxMilestonesIO(C.Structure):
                 ("passes", C.c_int64), ("ms", C.c_double * 3)]
 
 
+class VgxTauMilestonesIO(C.Structure):
+    _fields_ = [("n", C.c_int64), ("replicates", _I), ("V", C.c_int64), ("variant_of", C.POINTER(C.c_int32)),
+                ("K", C.c_int64), ("thresholds", _I),
+                ("final", _I), ("peak", _I), ("peak_event", C.POINTER(C.c_int32)),
+                ("last_positive_event", C.POINTER(C.c_int32)), ("first_event", C.POINTER(C.c_int32)),
+                ("peak_time", _F), ("extinction_time", _F), ("first_time", _F),
+                ("passes", C.c_int64), ("ms", C.c_double * 3)]
+
+
+class VgxTauMilestonesChain(C.Structure):
+    _fields_ = [("popNum", C.c_int64), ("hapNum", C.c_int64), ("ev_ptr", C.c_int64),
+                ("ev_times", _F), ("ev_types", _I), ("ev_haplotypes", _I), ("ev_populations", _I),
+                ("ev_newHaplotypes", _I), ("ev_newPopulations", _I),
+                ("mev_rows", C.c_int64), ("mev_num", _I), ("mev_types", _I), ("mev_haplotypes", _I), ("mev_populations", _I),
+                ("mev_newHaplotypes", _I), ("mev_newPopulations", _I),
+                ("V", C.c_int64), ("variant_of", C.POINTER(C.c_int32)), ("start", _I), ("K", C.c_int64), ("thresholds", _I),
+                ("tile", C.c_int64), ("n_own_events", C.c_int64), ("t_start", C.c_double),
+                ("final", _I), ("peak", _I), ("peak_event", C.POINTER(C.c_int32)), ("last_positive_event", C.POINTER(C.c_int32)),
+                ("first_event", C.POINTER(C.c_int32)), ("peak_time", _F), ("extinction_time", _F), ("first_time", _F)]
+
+
 class VgxTauIncidenceIO(C.Structure):
     _fields_ = [("n", C.c_int64), ("replicates", _I), ("T", C.c_int64), ("edges", _F), ("hap_mask", C.POINTER(C.c_uint32)),
                 ("counts", _I), ("outside", _I), ("summary", C.POINTER(VgxTrajSummaryIO)),
@@ -290,6 +311,8 @@ SIGNATURES = {
     "vgx_test_milestones": (C.c_int, [_F, _I, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int64, _I,
                                       C.POINTER(C.c_int32), C.c_int64, C.c_int64, C.c_double] + [C.POINTER(C.c_int32)] * 5 + [_F] * 3 +
                             [C.c_char_p, C.c_int64]),
+    "vgx_get_tau_milestones": (C.c_int, [_H, C.POINTER(VgxTauMilestonesIO), C.POINTER(VgxTimelinesPrefix)]),
+    "vgx_test_tau_milestones": (C.c_int, [C.POINTER(VgxTauMilestonesChain), C.c_char_p, C.c_int64]),
     "vgx_get_tau_incidence": (C.c_int, [_H, C.POINTER(VgxTauIncidenceIO), C.POINTER(VgxTimelinesPrefix)]),
     "vgx_test_tau_incidence": (C.c_int, [C.POINTER(VgxTauIncidenceChain), C.c_char_p, C.c_int64]),
     "vgx_get_tau_prevalence": (C.c_int, [_H, C.POINTER(VgxTauPrevalenceIO), C.POINTER(VgxTimelinesPrefix)]),
@@ -1011,6 +1034,86 @@ def replay_milestones(times, types, haplotypes, populations, newHaplotypes, newP
         *[_p(out[k]) for k in ("peak_time", "extinction_time", "first_time")], err, 512)
     if rc != VGX_OK:
         raise ValueError(err.value.decode() or "vgx_test_milestones failed")
+    for k in ("first_event", "first_time"):
+        out[k] = out[k][:K]
+    return out
+
+
+def tau_milestone_thresholds(thresholds):
+    """``thresholds`` of ``Ensemble.tau_milestones`` as an int64 array [K], K <= 16; ValueError for anything else."""
+    th = np.asarray(thresholds if thresholds is not None else ())
+    if th.ndim != 1:
+        raise ValueError("thresholds must be a sequence of integers")
+    if len(th) and th.dtype != object and not np.issubdtype(th.dtype, np.integer):
+        raise ValueError("thresholds must be integers")
+    if len(th) > MS_MAX_K:
+        raise ValueError("K = %d thresholds: at most %d" % (len(th), MS_MAX_K))
+    th = th.astype(object) if len(th) else th
+    if len(th) and not all(isinstance(t, (int, np.integer)) and not isinstance(t, bool) for t in th):
+        raise ValueError("thresholds must be integers")
+    if len(th) and (min(th) < -2 ** 63 or max(th) > 2 ** 63 - 1):
+        raise ValueError("thresholds must be integers in int64")
+    return np.ascontiguousarray(th, dtype=np.int64)
+
+
+def tau_milestones_lds_check(P, V, K):
+    """The LDS limit of the tau walk (vgx_tau_ms_lds_bytes), worded as the library words it; ValueError above it."""
+    need = (P + 1) * V * (40 + 4 * K) + 16
+    if need > 65536:
+        raise ValueError("%d populations (and their total) x %d classes x %d thresholds need %d bytes of records, above the 65536 bytes of "
+                         "LDS a walking workgroup may use" % (P, V, K, need))
+
+
+def replay_tau_milestones(events, mev, popNum, hapNum, variant_of, V, start, thresholds=(), tile=0, n_own_events=-1, t_start=0.0):
+    """The results of ``Ensemble.tau_milestones`` for one chain through ``vgx_test_tau_milestones``: the device's flattening, tile
+    edges, tile bases, settle, merge in tile order and outputs (vgx_tau_milestones.h) compiled for the host, tile after tile of about
+    ``tile`` rows (0: the default); no GPU.  ``events`` and ``mev`` as ``replay_tau_incidence`` takes them; the last ``n_own_events``
+    events play the replicate's own steps (-1: the trailing MULTITYPE events), everything before them the prefix, which is walked
+    once as a chain of its own.  ``variant_of`` [hapNum] with values in [-1, V); ``start`` [P, V] the chain's start folded through
+    it; ``thresholds`` int64; ``t_start`` the time of event index -1.  Returns a dict of final, peak [P + 1, V] int64, peak_event,
+    last_positive_event [P + 1, V] int32, first_event [K, P + 1, V] int32, peak_time, extinction_time [P + 1, V] and first_time
+    [K, P + 1, V] float64; a refusal raises ``ValueError`` with the library's message."""
+    times = np.ascontiguousarray(events[0], dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.int64) for c in events[1:6]]
+    n = len(times)
+    if len(cols) != 5 or any(len(c) != n for c in cols):
+        raise ValueError("event columns of different lengths")
+    mcols = [np.ascontiguousarray(mev[c] if mev is not None else [], dtype=np.int64) for c in MEV_COLUMNS]
+    if len({len(c) for c in mcols}) != 1:
+        raise ValueError("multievent columns of different lengths")
+    P, V = int(popNum), int(V)
+    vo = np.ascontiguousarray(variant_of, dtype=np.int32)
+    if len(vo) != int(hapNum):
+        raise ValueError("variant_of must hold hapNum values")
+    start = np.ascontiguousarray(start, dtype=np.int64)
+    if start.shape != (P, V):
+        raise ValueError("start must have the shape [P, V]")
+    th = np.ascontiguousarray(thresholds, dtype=np.int64).ravel()
+    K = len(th)
+    shape, kshape = (P + 1, max(V, 1)), (max(K, 1), P + 1, max(V, 1))
+    out = {k: np.zeros(shape, dtype=np.int64) for k in ("final", "peak")}
+    out.update({k: np.zeros(shape, dtype=np.int32) for k in ("peak_event", "last_positive_event")})
+    out["first_event"] = np.zeros(kshape, dtype=np.int32)
+    out["peak_time"], out["extinction_time"] = np.zeros(shape), np.zeros(shape)
+    out["first_time"] = np.zeros(kshape)
+    i32 = C.POINTER(C.c_int32)
+    io = VgxTauMilestonesChain()
+    io.popNum, io.hapNum, io.ev_ptr, io.ev_times = P, int(hapNum), n, _p(times)
+    for name, col in zip(("types", "haplotypes", "populations", "newHaplotypes", "newPopulations"), cols):
+        setattr(io, "ev_" + name, _p(col))
+    io.mev_rows = len(mcols[0])
+    for name, col in zip(MEV_COLUMNS, mcols):
+        setattr(io, "mev_" + name, _p(col))
+    io.V, io.variant_of, io.start, io.K, io.thresholds = V, vo.ctypes.data_as(i32), _p(start), K, _p(th)
+    io.tile, io.n_own_events, io.t_start = int(tile), int(n_own_events), float(t_start)
+    io.final, io.peak = _p(out["final"]), _p(out["peak"])
+    for k in ("peak_event", "last_positive_event", "first_event"):
+        setattr(io, k, out[k].ctypes.data_as(i32))
+    for k in ("peak_time", "extinction_time", "first_time"):
+        setattr(io, k, _p(out[k]))
+    err = C.create_string_buffer(512)
+    if load_library().vgx_test_tau_milestones(C.byref(io), err, 512) != VGX_OK:
+        raise ValueError(err.value.decode() or "vgx_test_tau_milestones failed")
     for k in ("first_event", "first_time"):
         out[k] = out[k][:K]
     return out

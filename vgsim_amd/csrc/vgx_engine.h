@@ -65,6 +65,7 @@ extern "C" hipError_t vgxi_sus_count(const VgxPrevLaunch *a, hipStream_t s);   /
 struct VgxTauPrevLaunch;
 extern "C" hipError_t vgxi_tau_prev_init(int64_t m, int64_t tc, int64_t cells, const int32_t *with, const int64_t *pre_val, const int64_t *pre_fin,
                                          const int64_t *pre_out, int64_t *val, int64_t *fin, int64_t *outside, hipStream_t s);
+extern "C" hipError_t vgxi_tau_prev_count(const VgxTauPrevLaunch *a, hipStream_t s);   // (vgx_tau_milestones.hip: pass A over tile edges)
 extern "C" hipError_t vgxi_tau_prev_scan(const VgxTauPrevLaunch *a, hipStream_t s);
 extern "C" hipError_t vgxi_tau_prev_minmax(int64_t total, const int64_t *src, int32_t *dst, uint64_t *mm, hipStream_t s);
 // the column summary of vgx_colsummary.hip on a device int32 matrix x[R][N] of values in [0, 2^31) (a refusal's message goes to errbuf)

@@ -221,6 +221,8 @@ extern "C" hipError_t vgxi_tau_prev_init(int64_t m, int64_t tc, int64_t cells, c
     return hipGetLastError();
 }
 
+extern "C" hipError_t vgxi_tau_prev_count(const VgxTauPrevLaunch *a, hipStream_t s) { return launch_count(a, s); }
+
 extern "C" hipError_t vgxi_tau_prev_scan(const VgxTauPrevLaunch *a, hipStream_t s) { return launch_scan(a, s); }
 
 extern "C" hipError_t vgxi_tau_prev_minmax(int64_t total, const int64_t *src, int32_t *dst, uint64_t *mm, hipStream_t s) {

@@ -310,7 +310,11 @@ class Milestones:
     ``final`` [n, P+1, V] the value after the whole chain; ``last_positive_event`` [n, P+1, V] the last event after which the cell
     holds a host (-2: never); ``first_event``, ``first_time``, ``reached`` [n, K, P+1, V]: the first event at or above
     ``thresholds[k]`` (``NEVER`` and NaN where none is, ``reached`` False); ``thresholds`` [K] int32; ``variant_of`` [H];
-    ``replicates`` [n]; ``passes``, ``kernel_ms``, ``clock_ms``, ``wall_ms``.  Integer arrays are int32, times float64."""
+    ``replicates`` [n]; ``passes``, ``kernel_ms``, ``clock_ms``, ``wall_ms``.  Integer arrays are int32, times float64.
+
+    ``Ensemble.tau_milestones`` returns the same object for tau replicates: an event is a direct event of the model's earlier
+    history or one whole tau step, values are taken after all rows of a step, and ``final``, ``peak`` and ``thresholds`` are
+    int64 (``clock_ms`` is the host's time for the tile and row tables)."""
 
     NEVER = _capi.MS_NEVER
 
@@ -1085,6 +1089,51 @@ class Ensemble:
         ms.thresholds, ms.variant_of, ms.replicates = th, vo, reps
         ms._R, ms._scenario_of = self.R, self.scenario_of
         ms._n_scenarios = len(self.scenarios) if self.scenarios is not None else 1
+        ms.passes, ms.kernel_ms, ms.clock_ms, ms.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
+        return ms
+
+    def tau_milestones(self, variants=None, thresholds=(), replicates=None):
+        """``milestones()`` for the replicates of the last ``simulate_tau(record_events=True)`` call (``vgx_get_tau_milestones``):
+        the same arguments and :class:`Milestones`, with ``final`` and ``peak`` int64 and ``thresholds`` up to 16 integers in int64.
+
+        A replicate's chain is ``tau_prevalence()``'s: the model's chain before the tau call (a replicate that restarted has none),
+        then its own steps.  An event is a direct event of that earlier chain or one whole step, numbered from 0 along the chain;
+        a value is taken after ALL rows of a step, so a step that adds hosts to a cell and takes as many away meets no threshold
+        and moves no peak, and a cell whose last host is replaced within a step is not extinct.  The values start as
+        ``tau_prevalence()``'s do; event -1 has the time 0.0 for a chain that starts at the beginning of the model's history,
+        else the time the call started from.  The shared earlier chain is walked once per call on the device."""
+        if self._last_call is None:
+            raise ValueError("tau_milestones() needs a simulate_tau(record_events=True) call first")
+        if self._last_call[0] != 'tau':
+            raise ValueError("tau_milestones() walks tau chains only: the last call was a direct simulate()")
+        if not self._last_call[1]:
+            raise ValueError("tau_milestones() needs the multievent rows: the last call had record_events=False")
+        reps = self._selected_replicates(replicates)
+        vo, V = _capi.variant_map(variants, self.model.hapNum)
+        th = _capi.tau_milestone_thresholds(thresholds)
+        n, K, P = len(reps), len(th), self.model.popNum
+        _capi.tau_milestones_lds_check(P, V, K)
+        ms = Milestones()
+        ms.final, ms.peak = np.zeros((n, P + 1, V), dtype=np.int64), np.zeros((n, P + 1, V), dtype=np.int64)
+        ms.peak_event, ms.last_positive_event = np.zeros((n, P + 1, V), dtype=np.int32), np.zeros((n, P + 1, V), dtype=np.int32)
+        ms.first_event = np.full((n, K, P + 1, V), Milestones.NEVER, dtype=np.int32)
+        ms.peak_time, ms.extinction_time = np.full((n, P + 1, V), np.nan), np.full((n, P + 1, V), np.nan)
+        ms.first_time = np.full((n, K, P + 1, V), np.nan)
+        i32 = C.POINTER(C.c_int32)
+        io = _capi.VgxTauMilestonesIO()
+        io.n, io.replicates, io.V, io.variant_of, io.K = n, _capi._p(reps), V, vo.ctypes.data_as(i32), K
+        io.thresholds = _capi._p(th) if K else None
+        if n:
+            io.final, io.peak = _capi._p(ms.final), _capi._p(ms.peak)
+            io.peak_event, io.last_positive_event = ms.peak_event.ctypes.data_as(i32), ms.last_positive_event.ctypes.data_as(i32)
+            io.first_event = ms.first_event.ctypes.data_as(i32) if K else None
+            io.peak_time, io.extinction_time = _capi._p(ms.peak_time), _capi._p(ms.extinction_time)
+            io.first_time = _capi._p(ms.first_time) if K else None
+        eng, pre = self.engine, self._tau_prefix_struct()
+        eng._check(eng.lib.vgx_get_tau_milestones(eng.handle, C.byref(io), C.byref(pre)))
+        ms.reached = ms.first_event != Milestones.NEVER
+        ms.thresholds, ms.variant_of, ms.replicates = th, vo, reps
+        ms._R, ms._scenario_of, ms._n_scenarios = self.R, None, 1
         ms.passes, ms.kernel_ms, ms.clock_ms, ms.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
         return ms
 
