@@ -39,6 +39,9 @@
  *   VGX_MILESTONES_WAVES=4         vgx_get_milestones, diagnostic: four wavefronts per (replicate, tile) taking rounds in turn behind a barrier instead of one (same results)
  *   VGX_TAU_MILESTONES_TILE_ROWS=n vgx_get_tau_milestones: rows of a tile of whole events that a walking workgroup takes (default 4096; no result depends on it)
  *   VGX_TAU_MILESTONES_WAVES=4     vgx_get_tau_milestones, diagnostic: workgroups of four wavefronts (256 threads) instead of one (same results)
+ *   VGX_FLOWS_TILE_EVENTS=n        vgx_get_flows: consecutive events a counting workgroup takes (default 4096; no result depends on it)
+ *   VGX_FLOWS_FORM=dense|split     vgx_get_flows: the table a counting workgroup keeps in LDS, all popNum^2 * V cells or the diagonal alone
+ *                                  (default: dense where it fits, else split; no result depends on it; a form that does not fit is refused)
  */
 #ifndef VGX_H
 #define VGX_H
@@ -570,6 +573,56 @@ int vgx_test_incidence(const double *times, const int64_t *types, const int64_t 
                        const int64_t *newHaplotypes, const int64_t *newPopulations, int64_t n_ev, int64_t P, int64_t hapNum,
                        const double *edges, int64_t T, const uint32_t *hap_mask, int64_t tile, int32_t *counts, int64_t *outside,
                        char *errbuf, int64_t errcap);
+
+/* ---- flows: who infects whom per time bin and variant class ------------------------------------ */
+/* What a multi-population model is built for: who seeds whom.  Every new infection in the log names its source, so the whole
+ * transmission matrix per time bin and variant class is one pass over the records vgx_get_incidence streams.
+ * The caller gives the bin edges of vgx_get_incidence (edges[0 .. T], the same cuts, bins and outside[r] = (cut[0], n_ev - cut[T]))
+ * and the map of vgx_get_prevalence (variant_of[hapNum] with values in [-1, V), -1 = not tracked).  A log record
+ * (type, haplotype, population, newHaplotype, newPopulation) counts +1, with c = variant_of[haplotype], in the cell
+ *   BIRTH       (src, dst, c) = (population, population, c)        a transmission within; skipped when `within` is 0
+ *   MIGRATION   (src, dst, c) = (population, newPopulation, c)     a transmission across, literally: equal keys land on the diagonal
+ * of its bin and every other type nowhere.  A type outside 0..5, c < 0, a haplotype outside [0, hapNum) or either key outside
+ * [0, popNum) counts nowhere.  The block is counts[n][T][popNum][popNum][V] in src, dst, class order.  With hap_mask = the members
+ * of class c, its margins are vgx_get_incidence's channels: the sum over src is 0 + 5, the off-diagonal sum over dst is 6, and
+ * the diagonal is 0 unless a MIGRATION has equal keys.
+ * The device reads every selected replicate's log in place with the geometry of vgx_get_incidence: a workgroup takes one
+ * replicate and a tile of consecutive events (VGX_FLOWS_TILE_EVENTS, default 4096), finds its first bin by a search in the
+ * replicate's cuts, and adds the nonzero cells it keeps in LDS to the block in device memory at every bin change and at the
+ * tile's end.  Two forms of that walk: dense keeps all popNum^2 * V int32 cells in LDS (possible up to 65536 bytes), split keeps
+ * the popNum * V cells of the diagonal and adds a record off the diagonal to its cell in device memory at once.  Dense runs where
+ * it fits, else split; VGX_FLOWS_FORM=dense|split forces one; `form` reports the one that ran (1 dense, 2 split).  All of it is
+ * integer work: no result depends on the form, the tile size, the launch geometry or the chunking.  The host clock runs as in
+ * vgx_get_incidence (VGX_TIMELINES_CHUNK_BYTES); the log itself is never copied.  `summary`, when given, is the column summary
+ * of vgx_get_trajectory_summary over the block as a matrix [n][T * popNum * popNum * V] where it lies (group_of has n entries,
+ * one per SELECTED replicate in the order of `replicates`); `counts` may then be NULL and the block is not copied to the host.
+ * Preconditions as vgx_get_incidence: the last call was direct and recorded events; every selected chain starts at log index 0.
+ * Refusals (VGX_ERR_ARG, worded alike behind "vgx_get_flows: "): those; replicates out of range or given twice; edges that are
+ * not finite or do not increase; T outside [1, 2^24); V < 1 or a variant_of value outside [-1, V); popNum * V * 4 bytes of
+ * diagonal cells above the 65536 bytes of LDS a counting workgroup may use, or the dense form forced where popNum^2 * V * 4
+ * bytes are (the message gives the bytes); a value of VGX_FLOWS_FORM that is neither; a block of n x T x P x P x V counts above
+ * half of the free device memory (the message gives the bytes: select fewer replicates); a chain of 2^30 events or more.
+ * vgx_clock_mismatches counts every selected replicate once. */
+typedef struct vgx_flows_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    int64_t T; const double *edges;              /* [T + 1] strictly increasing */
+    int64_t V; const int32_t *variant_of;        /* [hapNum], values in [-1, V) */
+    int32_t within;                              /* 1: births count on the diagonal; 0: migrations alone */
+    int32_t *counts;                             /* NULL or host [n][T][P][P][V] */
+    int64_t *outside;                            /* [n][2] events before / after the window */
+    vgx_traj_summary_io *summary;                /* NULL or the summary of the [n][T*P*P*V] block; group_of has n entries */
+    int64_t form, passes; double ms[3];          /* out: the form that ran (1 dense, 2 split); launches of the counting kernel; kernels, host clock, whole call */
+} vgx_flows_io;
+int vgx_get_flows(vgx_engine *e, vgx_flows_io *io);
+/* Test hook: the rule and the tile walk of vgx_get_flows compiled for the host, on one chain given as arrays (no device, no
+ * engine), tile after tile with `tile` events each (0: the default), in the form `form` asks for (0: the automatic choice,
+ * 1 dense, 2 split; the hist of a tile holds that form's cells).  counts [T][P][P][V] and outside [2] are overwritten, *form_ran
+ * (may be NULL) gets the form that ran.  The same limits: a form that does not fit the LDS budget, a chain of 2^30 events, bad
+ * edges, V or variant_of are refused with the message in errbuf. */
+int vgx_test_flows(const double *times, const int64_t *types, const int64_t *haplotypes, const int64_t *populations,
+                   const int64_t *newHaplotypes, const int64_t *newPopulations, int64_t n_ev, int64_t P, int64_t hapNum,
+                   const double *edges, int64_t T, const int32_t *variant_of, int64_t V, int32_t within, int64_t tile, int64_t form,
+                   int32_t *counts, int64_t *outside, int64_t *form_ran, char *errbuf, int64_t errcap);
 
 /* ---- prevalence: infectious hosts per variant class on a common grid --------------------------- */
 /* How many hosts carry which variant, when: the stock where vgx_get_incidence gives the flows, on ONE grid for all replicates

@@ -142,6 +142,12 @@ class VgxPrevalenceIO(C.Structure):
                 ("passes", C.c_int64), ("ms", C.c_double * 3)]
 
 
+class VgxFlowsIO(C.Structure):
+    _fields_ = [("n", C.c_int64), ("replicates", _I), ("T", C.c_int64), ("edges", _F), ("V", C.c_int64), ("variant_of", C.POINTER(C.c_int32)),
+                ("within", C.c_int32), ("counts", C.POINTER(C.c_int32)), ("outside", _I), ("summary", C.POINTER(VgxTrajSummaryIO)),
+                ("form", C.c_int64), ("passes", C.c_int64), ("ms", C.c_double * 3)]
+
+
 class VgxMilestonesIO(C.Structure):
     _fields_ = [("n", C.c_int64), ("replicates", _I), ("V", C.c_int64), ("variant_of", C.POINTER(C.c_int32)),
                 ("K", C.c_int64), ("thresholds", C.POINTER(C.c_int32)),
@@ -307,6 +313,9 @@ SIGNATURES = {
     "vgx_get_prevalence": (C.c_int, [_H, C.POINTER(VgxPrevalenceIO)]),
     "vgx_test_prevalence": (C.c_int, [_F, _I, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, _F, C.c_int64, C.POINTER(C.c_int32), C.c_int64, _I,
                                       C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, C.c_char_p, C.c_int64]),
+    "vgx_get_flows": (C.c_int, [_H, C.POINTER(VgxFlowsIO)]),
+    "vgx_test_flows": (C.c_int, [_F, _I, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, _F, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int32,
+                                 C.c_int64, C.c_int64, C.POINTER(C.c_int32), _I, _I, C.c_char_p, C.c_int64]),
     "vgx_get_milestones": (C.c_int, [_H, C.POINTER(VgxMilestonesIO)]),
     "vgx_test_milestones": (C.c_int, [_F, _I, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int64, _I,
                                       C.POINTER(C.c_int32), C.c_int64, C.c_int64, C.c_double] + [C.POINTER(C.c_int32)] * 5 + [_F] * 3 +
@@ -970,6 +979,41 @@ def replay_prevalence(times, types, haplotypes, populations, newHaplotypes, newP
     if rc != VGX_OK:
         raise ValueError(err.value.decode() or "vgx_test_prevalence failed")
     return values, final, outside
+
+
+FLOW_FORMS = {None: 0, 'auto': 0, 'dense': 1, 'split': 2}   # VGX_FLOW_AUTO, VGX_FLOW_DENSE, VGX_FLOW_SPLIT
+FLOW_FORM_NAMES = {0: None, 1: 'dense', 2: 'split'}
+
+
+def replay_flows(times, types, haplotypes, populations, newHaplotypes, newPopulations, popNum, hapNum, edges, variant_of, V, within=True,
+                 tile=0, form=None):
+    """The block of ``Ensemble.flows`` for one chain given as arrays through ``vgx_test_flows``: the device's rule and tile walk
+    (vgx_flows.h) compiled for the host, tile after tile of ``tile`` events (0: the default), in the form ``form`` asks for
+    (None: the automatic choice, 'dense', 'split'); no GPU.  ``variant_of`` [hapNum] with values in [-1, V).  Returns (counts
+    [T, P, P, V] int32 in src, dst, class order, outside [2] int64, the form that ran); a refusal raises ``ValueError`` with the
+    library's message."""
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.int64) for c in (types, haplotypes, populations, newHaplotypes, newPopulations)]
+    n = len(times)
+    if any(len(c) != n for c in cols):
+        raise ValueError("event columns of different lengths")
+    if form not in FLOW_FORMS:
+        raise ValueError("form must be None, 'dense' or 'split'")
+    edges = np.ascontiguousarray(edges, dtype=np.float64)
+    T, P, V = len(edges) - 1, int(popNum), int(V)
+    vo = np.ascontiguousarray(variant_of, dtype=np.int32)
+    if len(vo) != int(hapNum):
+        raise ValueError("variant_of must hold hapNum values")
+    counts = np.zeros((max(T, 1), max(P, 1), max(P, 1), max(V, 1)), dtype=np.int32)
+    outside = np.zeros(2, dtype=np.int64)
+    ran = np.zeros(1, dtype=np.int64)
+    err = C.create_string_buffer(512)
+    i32 = C.POINTER(C.c_int32)
+    rc = load_library().vgx_test_flows(_p(times), *[_p(c) for c in cols], n, P, int(hapNum), _p(edges), T, vo.ctypes.data_as(i32), V,
+                                       1 if within else 0, int(tile), FLOW_FORMS[form], counts.ctypes.data_as(i32), _p(outside), _p(ran), err, 512)
+    if rc != VGX_OK:
+        raise ValueError(err.value.decode() or "vgx_test_flows failed")
+    return counts, outside, FLOW_FORM_NAMES[int(ran[0])]
 
 
 MS_NEVER = 2 ** 31 - 1     # VGX_MS_NEVER: first_event of a threshold no value reaches

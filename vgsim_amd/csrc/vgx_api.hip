@@ -1807,6 +1807,145 @@ extern "C" int vgx_get_incidence(vgx_engine *e, vgx_incidence_io *io) {
     return VGX_OK;
 }
 
+// ---- who infects whom per time bin and variant class of many replicates (vgx_flows.hip, vgx_flows.h) ------------
+// vgx_get_incidence step for step, with the block [n][T][P][P][V] and vgx_get_prevalence's variant_of in place of the mask: the
+// host clock turns every replicate's times into T + 1 cuts, the device counts over the log in place in the form that fits, and
+// the column summary reads the block where it lies.
+extern "C" int vgx_get_flows(vgx_engine *e, vgx_flows_io *io) {
+    if (!e || !io || io->n < 0 || (io->n > 0 && (!io->replicates || !io->outside))) return VGX_ERR_ARG;
+    const auto t_call = std::chrono::steady_clock::now();
+    auto wall = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(); };
+    io->passes = 0;
+    io->form = 0;
+    io->ms[0] = io->ms[1] = io->ms[2] = 0.0;
+    if (e->last_was_tau) return fail(e, VGX_ERR_ARG, "vgx_get_flows: the last call was vgx_simulate_tau (counts direct chains only)");
+    if (!e->sc_host_valid || !e->dev_state_valid) return fail(e, VGX_ERR_ARG, "vgx_get_flows: needs a direct vgx_simulate_direct call with the event log first");
+    if (!e->call_recorded) return fail(e, VGX_ERR_ARG, "vgx_get_flows: the last call did not record events");
+    const int64_t n = io->n, P = e->d.popNum, H = e->d.hapNum, T = io->T, V = io->V;
+    if (T < 1 || T >= VGX_FLOW_MAX_BINS || !io->edges) return fail(e, VGX_ERR_ARG, "vgx_get_flows: T = " + std::to_string(T) + " bins: at least 1, below 2^24, with edges");
+    for (int64_t k = 0; k <= T; k++) {
+        if (!std::isfinite(io->edges[k])) return fail(e, VGX_ERR_ARG, "vgx_get_flows: edges[" + std::to_string(k) + "] is not finite");
+        if (k > 0 && !(io->edges[k - 1] < io->edges[k]))
+            return fail(e, VGX_ERR_ARG, "vgx_get_flows: edges must increase strictly (edges[" + std::to_string(k) + "])");
+    }
+    if (V < 1 || V > INT32_MAX || !io->variant_of) return fail(e, VGX_ERR_ARG, "vgx_get_flows: V = " + std::to_string(V) + " classes: at least 1, with variant_of");
+    for (int64_t h = 0; h < H; h++)
+        if (io->variant_of[h] < -1 || io->variant_of[h] >= V)
+            return fail(e, VGX_ERR_ARG, "vgx_get_flows: variant_of[" + std::to_string(h) + "] = " + std::to_string(io->variant_of[h]) + " is outside [-1, " + std::to_string(V) + ")");
+    int asked = VGX_FLOW_AUTO;
+    if (const char *fm = getenv("VGX_FLOWS_FORM")) {
+        if (!strcmp(fm, "dense")) asked = VGX_FLOW_DENSE;
+        else if (!strcmp(fm, "split")) asked = VGX_FLOW_SPLIT;
+        else if (*fm) return fail(e, VGX_ERR_ARG, std::string("vgx_get_flows: VGX_FLOWS_FORM=") + fm + " is neither dense nor split");
+    }
+    const int form = vgx_flow_form(asked, P, V);
+    if (!form) {
+        char why[256];
+        vgx_flow_refusal(asked, P, V, why, sizeof why);
+        return fail(e, VGX_ERR_ARG, std::string("vgx_get_flows: ") + why);
+    }
+    io->form = form;
+    const int64_t cells = P * P * V;   // (P * V <= 2^14 and P <= 2^14: below 2^28)
+    std::vector<int32_t> n_ev((size_t)n);
+    {
+        std::vector<char> seen((size_t)e->R, 0);
+        for (int64_t i = 0; i < n; i++) {
+            const int64_t r = io->replicates[i];
+            if (r < 0 || r >= e->R) return fail(e, VGX_ERR_ARG, "vgx_get_flows: replicate index out of range");
+            if (seen[(size_t)r]) return fail(e, VGX_ERR_ARG, "vgx_get_flows: replicates must be distinct");
+            seen[(size_t)r] = 1;
+            const VgxRepScalars &s = e->sc_host[(size_t)r];
+            const int64_t first = s.restarts > 0 ? 0 : ((size_t)r < e->call_ev0.size() ? e->call_ev0[(size_t)r] : e->ev_ptr0);
+            if (first != 0 || e->ev_base != 0)
+                return fail(e, VGX_ERR_ARG, "vgx_get_flows: replicate " + std::to_string(r) + ": its chain does not start in the last call's device log (the model held " +
+                                                std::to_string(e->ev_base != 0 ? e->ev_base : first) + " events when the ensemble started)");
+            if (s.ev_ptr >= VGX_FLOW_MAX_EVENTS)
+                return fail(e, VGX_ERR_ARG, "vgx_get_flows: replicate " + std::to_string(r) + " holds a chain of " + std::to_string(s.ev_ptr) + " events (2^30 or more)");
+            if (s.ev_ptr < 0 || s.ev_ptr > e->evcap)
+                return fail(e, VGX_ERR_ARG, "vgx_get_flows: event range of replicate " + std::to_string(r) + " outside the device log");
+            n_ev[(size_t)i] = (int32_t)s.ev_ptr;
+        }
+    }
+    if (n == 0) {
+        io->ms[2] = wall();
+        return VGX_OK;
+    }
+    int64_t tile = VGX_FLOW_TILE_DEFAULT;
+    if (const char *tb = getenv("VGX_FLOWS_TILE_EVENTS")) tile = std::min<int64_t>(std::max<int64_t>(atoll(tb), 1), VGX_FLOW_MAX_EVENTS);
+    HIPCHECK(e, hipSetDevice(e->device));
+    size_t free_b = 0, total_b = 0;
+    HIPCHECK(e, hipMemGetInfo(&free_b, &total_b));
+    auto up8 = [](int64_t b) { return (b + 255) / 256 * 256; };
+    auto dev_free = [](char *p) { (void)hipFree(p); };
+    // what stays for the whole call: [rep | n_ev | cut | variant_of | counts]
+    if (T * cells >= ((int64_t)1 << 40) / std::max<int64_t>(n, 1))
+        return fail(e, VGX_ERR_ARG, "vgx_get_flows: the block of " + std::to_string(n) + " x " + std::to_string(T) + " x " + std::to_string(P) + " x " + std::to_string(P) +
+                                        " x " + std::to_string(V) + " counts holds 2^40 cells or more: select fewer replicates per call");
+    const int64_t block_bytes = n * T * cells * 4;
+    const int64_t o_rep = 0, o_nev = o_rep + up8(n * 8), o_cut = o_nev + up8(n * 4), o_map = o_cut + up8(n * (T + 1) * 4),
+                  o_cnt = o_map + up8(H * 4), keep_total = o_cnt + up8(block_bytes);
+    if (keep_total > (int64_t)(free_b / 2))
+        return fail(e, VGX_ERR_ARG, "vgx_get_flows: the block of " + std::to_string(n) + " x " + std::to_string(T) + " x " + std::to_string(P) + " x " + std::to_string(P) +
+                                        " x " + std::to_string(V) + " counts and its cuts take " + std::to_string(keep_total) + " bytes, above half of the " +
+                                        std::to_string((int64_t)free_b) + " bytes of free device memory: select fewer replicates per call");
+    char *kws = nullptr;
+    hipError_t er = hipMalloc((void **)&kws, (size_t)keep_total);
+    if (er != hipSuccess) return fail(e, VGX_ERR_HIP, "vgx_get_flows: hipMalloc of " + std::to_string(keep_total) + " bytes: " + hipGetErrorString(er));
+    std::unique_ptr<char, void (*)(char *)> khold(kws, dev_free);
+    std::vector<int64_t> reps_all(io->replicates, io->replicates + n);
+    HIPCHECK(e, hipMemcpyAsync(kws + o_rep, reps_all.data(), (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_nev, n_ev.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_map, io->variant_of, (size_t)H * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemsetAsync(kws + o_cnt, 0, (size_t)block_bytes, e->stream));   // zeroed once
+
+    const int64_t share = (int64_t)(free_b / 2) - keep_total + 4096;
+    std::vector<int32_t> cuts((size_t)(n * (T + 1)));
+    const int rc_chunks = clock_chunks(e, "vgx_get_flows", reps_all, n_ev, (const int64_t *)(kws + o_rep), (const int32_t *)(kws + o_nev), share, io->ms,
+        // host: a replicate's event times -> its T + 1 cuts
+        [&](int64_t gi, const std::vector<double> &times) {
+            int32_t *cut = cuts.data() + gi * (T + 1);
+            VgxIncCutter ct{io->edges, T, cut};
+            for (size_t k = 0; k < times.size(); k++) ct.event((int64_t)k, times[k]);
+            ct.finish((int64_t)times.size());
+            io->outside[2 * gi] = cut[0];
+            io->outside[2 * gi + 1] = (int64_t)times.size() - cut[(size_t)T];
+        },
+        // device: the count of the chunk's replicates into their rows of the block
+        [&](int64_t i0, int64_t i1, int64_t max_n) -> int {
+            const int64_t m = i1 - i0;
+            HIPCHECK(e, hipMemcpyAsync(kws + o_cut + i0 * (T + 1) * 4, cuts.data() + i0 * (T + 1), (size_t)(m * (T + 1)) * 4, hipMemcpyHostToDevice, e->stream));
+            HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
+            VgxFlowLaunch a{};
+            a.m = m;
+            a.log = (const int32_t *)e->r_evcols.p; a.evcap = e->evcap;
+            a.rep = (const int64_t *)(kws + o_rep) + i0; a.n_ev = (const int32_t *)(kws + o_nev) + i0;
+            a.cut = (const int32_t *)(kws + o_cut) + i0 * (T + 1);
+            a.T = (int32_t)T; a.P = (int32_t)P; a.hapNum = (int32_t)H; a.V = (int32_t)V;
+            a.variant_of = (const int32_t *)(kws + o_map);
+            a.within = io->within ? 1 : 0; a.form = form;
+            a.tile = (int32_t)tile; a.max_n = max_n;
+            a.counts = (int32_t *)(kws + o_cnt) + i0 * T * cells;
+            HIPCHECK(e, vgxi_flow_count(&a, e->stream));
+            if (max_n > 0) io->passes += 1;
+            HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
+            if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)
+                return fail(e, VGX_ERR_HIP, std::string("vgx_get_flows: counting kernel failed: ") + hipGetErrorString(er));
+            float kms = 0.f;
+            HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
+            io->ms[0] += kms;
+            return VGX_OK;
+        });
+    if (rc_chunks) return rc_chunks;
+    if (io->summary) {
+        char msg[512] = "";
+        const int rc = vgxi_column_summary_i32("vgx_get_flows: summary", (const int32_t *)(kws + o_cnt), n, T * cells, io->summary, e->stream, msg, sizeof msg);
+        if (rc) return fail(e, rc, msg);
+    }
+    if (io->counts) HIPCHECK(e, hipMemcpy(io->counts, kws + o_cnt, (size_t)block_bytes, hipMemcpyDeviceToHost));
+    io->ms[2] = wall();
+    return VGX_OK;
+}
+
 // ---- infectious hosts per variant class of many replicates at the times of one grid (vgx_prevalence.hip, vgx_prevalence.h)
 // The split of vgx_get_incidence: the host clock turns every replicate's times into T + 2 bounds, the device forms the net change
 // of every (interval, population, class) over the log in place and sums the intervals up per column; the column summary reads the

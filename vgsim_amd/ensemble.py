@@ -255,6 +255,41 @@ def _incidence_edges(edges, bins, window):
     return np.ascontiguousarray(e)
 
 
+class Flows:
+    """What ``Ensemble.flows`` returns: new infections per selected replicate, time bin, source population, destination
+    population and variant class.
+
+    ``counts`` [n, T, P, P, V] int32 indexed ``[r, b, src, dst, c]`` (None when the call had ``counts=False``): a birth in p counts
+    at (p, p), a migration at (population, newPopulation); ``edges`` [T + 1] the bin edges (bin b holds edges[b] <= t <
+    edges[b + 1]); ``variant_of`` [H] the class of every haplotype (-1: not tracked); ``outside`` [n, 2] the events of every
+    replicate before ``edges[0]`` and from ``edges[T]`` on; ``replicates`` [n]; ``summary`` a :class:`TrajectorySummary` over the
+    [T, P, P, V] columns, or None; ``form`` the table the counting workgroups kept ('dense' or 'split': no value depends on it);
+    ``passes``, ``kernel_ms``, ``clock_ms``, ``wall_ms``."""
+
+    def local(self):
+        """Transmissions within a population, [n, T, P, V]: the diagonal."""
+        return np.ascontiguousarray(np.moveaxis(np.diagonal(self.counts, axis1=2, axis2=3), -1, 2))
+
+    def new_infections(self):
+        """New infections per destination, [n, T, dst, V]: the sum over src, the diagonal included."""
+        return self.counts.sum(axis=2, dtype=np.int64)
+
+    def imports(self):
+        """New infections a population received from the others, [n, T, dst, V]: the off-diagonal sum over src."""
+        return self.new_infections() - self.local()
+
+    def exports(self):
+        """New infections a population caused in the others, [n, T, src, V]: the off-diagonal sum over dst."""
+        return self.counts.sum(axis=3, dtype=np.int64) - self.local()
+
+    def imported_share(self):
+        """``imports() / new_infections()``, [n, T, dst, V] float64; NaN where there are no new infections."""
+        total = self.new_infections()
+        out = np.full(total.shape, np.nan, dtype=np.float64)
+        np.divide(self.imports(), total, out=out, where=total != 0)
+        return out
+
+
 class Prevalence:
     """What ``Ensemble.prevalence`` returns: infectious hosts per selected replicate, grid time, population and variant class.
 
@@ -993,6 +1028,60 @@ class Ensemble:
         finish = self._incidence_request(io, e, replicates, haplotypes, summary, counts, np.int64, None, 1)
         eng, pre = self.engine, self._tau_prefix_struct()
         return finish(lambda: eng._check(eng.lib.vgx_get_tau_incidence(eng.handle, C.byref(io), C.byref(pre))))
+
+    def flows(self, edges=None, bins=None, window=None, variants=None, within=True, replicates=None, summary=None, counts=True):
+        """Who infects whom: new infections per time bin, source population, destination population and variant class of every
+        selected replicate of the last direct ``simulate(record_events=True)`` call, on ONE grid for all replicates and on the
+        device (``vgx_get_flows``): one streaming pass over every replicate's log where the kernel left it.  Returns a
+        :class:`Flows`.
+
+        Every new infection in the log names its source: a birth in p is a transmission within p and counts at
+        ``[src, dst] = [p, p]``, a migration is a transmission across and counts at ``[population, newPopulation]``.
+        ``within=False`` leaves the births out.  The grid as ``incidence()`` takes it: ``edges`` [T + 1], or ``bins`` and
+        ``window=(t0, t1)``.  ``variants`` as ``prevalence()`` takes them: None (every haplotype its own class), an integer
+        array [H] of classes with -1 for haplotypes that are not tracked, or a sequence of sequences of haplotype indices; a new
+        infection counts in the class of its haplotype.  ``replicates``, ``summary`` and ``counts=False`` as in ``incidence()``.
+        With ``haplotypes`` = the members of class c, ``incidence()``'s channels are this block's margins: births the diagonal,
+        arrivals the off-diagonal sum over src, departures the off-diagonal sum over dst.  Direct chains only."""
+        e = _incidence_edges(edges, bins, window)
+        if self._last_call is None:
+            raise ValueError("flows() needs a direct simulate(record_events=True) call first")
+        if self._last_call[0] != 'direct':
+            raise ValueError("flows() counts direct chains only: the last call was simulate_tau")
+        if not self._last_call[1]:
+            raise ValueError("flows() needs the event log: the last call had record_events=False")
+        m, eng = self.model, self.engine
+        reps = self._selected_replicates(replicates)
+        n = len(reps)
+        vo, V = _capi.variant_map(variants, m.hapNum)
+        T, P = len(e) - 1, m.popNum
+        if 4 * P * V > 65536:
+            raise ValueError("%d populations x %d classes need %d bytes of cells, above the 65536 bytes of LDS a counting workgroup may use"
+                             % (P, V, 4 * P * V))
+        sio, done = self._block_summary(summary, reps, (T, P, P, V), self.scenario_of, len(self.scenarios) if self.scenarios is not None else 1)
+        if summary is None and not counts:
+            raise ValueError("counts=False needs summary=: the call would return nothing")
+        for r in reps:
+            c = eng.counters(int(r))
+            if c.ev_first_new != 0:
+                raise ValueError("replicate %d: its chain does not start in the last call's device log (the model held %d events "
+                                 "when the ensemble started)" % (r, c.ev_first_new))
+        block = np.zeros((n, T, P, P, V), dtype=np.int32) if counts else None
+        outside = np.zeros((max(n, 1), 2), dtype=np.int64)
+        i32 = C.POINTER(C.c_int32)
+        io = _capi.VgxFlowsIO()
+        io.n, io.replicates, io.T, io.edges, io.V, io.variant_of = n, _capi._p(reps), T, _capi._p(e), V, vo.ctypes.data_as(i32)
+        io.within = 1 if within else 0
+        io.counts = block.ctypes.data_as(i32) if counts and n else None
+        io.outside = _capi._p(outside)
+        io.summary = C.pointer(sio) if sio is not None and n else None
+        eng._check(eng.lib.vgx_get_flows(eng.handle, C.byref(io)))
+        fl = Flows()
+        fl.counts, fl.edges, fl.variant_of, fl.outside, fl.replicates = block, e, vo, outside[:n], reps
+        fl.summary = done() if done is not None else None
+        fl.form = _capi.FLOW_FORM_NAMES[int(io.form)]
+        fl.passes, fl.kernel_ms, fl.clock_ms, fl.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
+        return fl
 
     def prevalence(self, times=None, points=None, window=None, variants=None, replicates=None, summary=None, values=True):
         """Infectious hosts per grid time, population and variant class of every selected replicate of the last direct
