@@ -37,3 +37,6 @@ if tl[6] > 0:
 if tl[7] + tl[8] > 0:
     print("choices over a multi-tile list: %.2f %% took the tile from the row's end-of-tile sums, %.2f %% streamed; long-form iterations in which "
           "no row streamed: %.2f %%" % (100 * tl[7] / (tl[7] + tl[8]), 100 * tl[8] / (tl[7] + tl[8]), 100 * tl[9] / long_iters))
+    print("choices over a multi-tile list: %.3f %% over a list of more than 256 entries, %.3f %% of more than 512" % (
+        100 * tl[10] / (tl[7] + tl[8]), 100 * tl[11] / (tl[7] + tl[8])))
+    print("long-form iterations in which some row chooses from a list of 1 to 64 entries: %.2f %%" % (100 * tl[12] / long_iters))

@@ -512,8 +512,9 @@ static __device__ __forceinline__ void quad_body() {
     // the row needs up to its hit, [3] the most any row of the wave needs (= tiles streamed) — per haplotype choice that took the
     // long form; [4] / [5] the same pair for the rate refresh; [6] refreshes that took the long form; [7] / [8] choices over a
     // multi-tile list that found / did not find the row's end-of-tile sums in its register; [9] long-form choices (per wavefront:
-    // row 0 counts) in which no row streamed
-    int prof_tiles[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    // row 0 counts) in which no row streamed; [10] / [11] choices over a list of more than 4 / more than 8 tiles (256 / 512 entries);
+    // [12] long-form choices (row 0 counts) in which some row chooses from a list of 1 to 64 entries
+    int prof_tiles[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #endif
     while (true) {
         QPROF(0);
@@ -723,6 +724,8 @@ static __device__ __forceinline__ void quad_body() {
                     const bool hit_ = n_sel > 64 && tc_pi == pi, miss_ = n_sel > 64 && tc_pi != pi;
                     prof_tiles[7] += hit_; prof_tiles[8] += miss_;
                     if (!__ballot(miss_) && row == 0) prof_tiles[9] += 1;
+                    prof_tiles[10] += n_sel > 256; prof_tiles[11] += n_sel > 512;
+                    if (__ballot(n_sel > 0 && n_sel <= 64) && row == 0) prof_tiles[12] += 1;
                 }
 #endif
                 QSel sel;
@@ -762,9 +765,12 @@ static __device__ __forceinline__ void quad_body() {
                 if (rl == 0) { s_ts[pi] = ts_pi - 1.0; s_ti[pi] = ti_pi + 1.0; }
                 gI += 1.0; QBUMP(QC_B);
                 if (live && rl == 0) { l3[k_hit] = (int32_t)(cnt_hit + 1); if (QT >= 4) { L8(pi)[k_hit] = B8(cnt_hit + 1); if (n_sel > 64) lt[k_hit >> 6] += 1; } }
+                // (ch_cn is read by a refresh with ch_pi == pi only, and ch_pi is set by the register path of the choice alone)
+                if (QT >= 4 || maxn <= 64) {
 #pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    if (c == (k_hit >> 4) && rl == (k_hit & 15)) ch_cn[c] += 1;
+                    for (int c = 0; c < 4; ++c)
+                        if (c == (k_hit >> 4) && rl == (k_hit & 15)) ch_cn[c] += 1;
+                }
                 e_type = QEV_BIRTH; e_hap = hap_hit; e_pop = pi; e_nh = 0; e_np = H;
                 u_lo = pi; u_hi = pi + 1;
             }
@@ -778,9 +784,11 @@ static __device__ __forceinline__ void quad_body() {
                 else {
                     if (live && rl == 0) { l3[k_hit] = (int32_t)(cnt_hit - 1); if (QT >= 4) { L8(pi)[k_hit] = B8(cnt_hit - 1); if (n_sel > 64) lt[k_hit >> 6] -= 1; } }
                     if (QT >= 4 && cnt_hit == 1 && rl == 0) s_zero[pi] += 1;
+                    if (QT >= 4 || maxn <= 64) {
 #pragma unroll
-                    for (int c = 0; c < 4; ++c)
-                        if (c == (k_hit >> 4) && rl == (k_hit & 15)) ch_cn[c] -= 1;
+                        for (int c = 0; c < 4; ++c)
+                            if (c == (k_hit >> 4) && rl == (k_hit & 15)) ch_cn[c] -= 1;
+                    }
                 }
                 e_hap = hap_hit; e_pop = pi; e_nh = 0; e_np = 0;
                 u_lo = pi; u_hi = pi + 1;
@@ -1149,7 +1157,10 @@ static __device__ __forceinline__ void quad_body() {
                         // size: no overflow or underflow inside the reciprocal sequence (the latency kernels' range: vgx_flat.h)
                         const double t = x * m * m * k_cd[pn];
                         tv4[s] = RCPDIV ? div_by_const(t, k_as[pn], k_rcp[pn]) : t / k_as[pn];
-                        if (pn >= P) tv4[s] = 0.0;
+                        // A lane beyond P needs no select: its term is +0.0 as it stands.  x, m (read at a clamped index) and the
+                        // product are finite and >= +0.0, cd = +0.0 makes t = +0.0, and +0.0 / 1.0 = +0.0 by the division and by
+                        // the reciprocal sequence alike (as = 1 / as = 1.0: every fma there is (+-0.0) * 1.0 + (+0.0) = +0.0).
+                        if (QT >= 4 && pn >= P) tv4[s] = 0.0;      // (the long-list kernel's code is left as it was)
                     }
                 }
 #pragma unroll
@@ -1216,7 +1227,8 @@ static __device__ __forceinline__ void quad_body() {
                     if (s < nslot) {
                         const int pn = s * 16 + rl;     // lanes beyond P: maxEBM = +0.0, counts 0
                         w4[s] = k_mebm[pn] * s_ts[pn] * (gI - s_ti[pn]);
-                        if (pn >= P) w4[s] = 0.0;
+                        // no select for the lanes beyond P either: +0.0 * 0.0 * (gI - 0.0) = +0.0 (gI is finite and >= +0.0)
+                        if (QT >= 4 && pn >= P) w4[s] = 0.0;      // (the long-list kernel's code is left as it was)
                     }
                 }
 #pragma unroll
@@ -1306,7 +1318,7 @@ static __device__ __forceinline__ void quad_body() {
     if (lane == 0 && r.prof)
         for (int i = 0; i < VGX_PROF_SLOTS; ++i) r.prof[rep * VGX_PROF_SLOTS + i] = prof_acc[i];
     // the tile counters, summed over the four rows, in the buffer of the wavefront's second replicate
-    for (int i = 0; i < 10; ++i) {
+    for (int i = 0; i < 13; ++i) {
         const long long t4 = (long long)__builtin_amdgcn_readlane(prof_tiles[i], 0) + __builtin_amdgcn_readlane(prof_tiles[i], 16) +
                              __builtin_amdgcn_readlane(prof_tiles[i], 32) + __builtin_amdgcn_readlane(prof_tiles[i], 48);
         if (lane == 0 && r.prof && rep_raw + 1 < R) r.prof[(rep_raw + 1) * VGX_PROF_SLOTS + i] = (unsigned long long)t4;
