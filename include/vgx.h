@@ -39,8 +39,8 @@
  *   VGX_MILESTONES_WAVES=4         vgx_get_milestones, diagnostic: four wavefronts per (replicate, tile) taking rounds in turn behind a barrier instead of one (same results)
  *   VGX_TAU_MILESTONES_TILE_ROWS=n vgx_get_tau_milestones: rows of a tile of whole events that a walking workgroup takes (default 4096; no result depends on it)
  *   VGX_TAU_MILESTONES_WAVES=4     vgx_get_tau_milestones, diagnostic: workgroups of four wavefronts (256 threads) instead of one (same results)
- *   VGX_FLOWS_TILE_EVENTS=n        vgx_get_flows: consecutive events a counting workgroup takes (default 4096; no result depends on it)
- *   VGX_FLOWS_FORM=dense|split     vgx_get_flows: the table a counting workgroup keeps in LDS, all popNum^2 * V cells or the diagonal alone
+ *   VGX_FLOWS_TILE_EVENTS=n        vgx_get_flows / vgx_get_tau_flows: consecutive events (rows) a counting workgroup takes (default 4096; no result depends on it)
+ *   VGX_FLOWS_FORM=dense|split     vgx_get_flows / vgx_get_tau_flows: the table a counting workgroup keeps in LDS, all popNum^2 * V cells or the diagonal alone
  *                                  (default: dense where it fits, else split; no result depends on it; a form that does not fit is refused)
  */
 #ifndef VGX_H
@@ -735,6 +735,66 @@ typedef struct vgx_tau_incidence_chain {
     int64_t *outside;                            /* out [2] */
 } vgx_tau_incidence_chain;
 int vgx_test_tau_incidence(vgx_tau_incidence_chain *io, char *errbuf, int64_t errcap);
+
+/* vgx_get_flows for many replicates of the last vgx_simulate_tau call (with the event log), on the device.
+ * The chain, the events, the cuts in row index space and `outside` are vgx_get_tau_incidence's, unchanged: `prefix` flattened,
+ * then the replicate's own rows where the tau kernels left them; a replicate that restarted has no prefix; an event is a direct
+ * event or a whole step at the time of its MULTITYPE record; outside[r] = (sum of num over the rows before cut[0], over the rows
+ * from cut[T] on), over num > 0, unfiltered.  A row (num, type, haplotype, population, newHaplotype, newPopulation) counts `num`
+ * times in the one cell vgx_get_flows gives for its five fields (VGX_TL_ROW_DIRECT masked off the type; variant_of, `within`, a
+ * BIRTH on the diagonal, a MIGRATION at (population, newPopulation) literally); num <= 0 counts nothing, a field that is not a
+ * 32-bit index matches nothing.  The block is int64 counts[n][T][popNum][popNum][V]; with hap_mask = the members of class c its
+ * margins are vgx_get_tau_incidence's channels (sum over src = 0 + 5, off-diagonal sum over dst = 6, diagonal = 0 unless a
+ * MIGRATION has equal keys).
+ * The two forms of vgx_get_flows with 8-byte cells: dense keeps popNum^2 * V int64 cells in LDS (popNum <= 90 at V = 1), split
+ * the popNum * V cells of the diagonal, a row off the diagonal then adding num to its cell in device memory at once.  Dense runs
+ * where it fits, else split; VGX_FLOWS_FORM=dense|split forces one; `form` reports the one that ran (1 dense, 2 split).  A
+ * workgroup takes one chain and a tile of VGX_FLOWS_TILE_EVENTS consecutive rows (default 4096).  All of it is integer work: no
+ * result depends on the form, the tile size, the launch geometry or the chunking.  No host clock runs.  The prefix is flattened,
+ * uploaded and counted ONCE per call into a block of its own; the block of every replicate that did not restart starts from it.
+ * Replicates go in chunks under VGX_TIMELINES_CHUNK_BYTES.  `summary` as in vgx_get_tau_incidence: a device pass narrows the block
+ * to int32 for it; if a count is 2^31 or more the summary is refused (VGX_ERR_ARG, the largest count in the message) after
+ * `counts`, if asked for, has been written; with counts = NULL no block is copied to the host.  ms[1] is the host's cut search.
+ * Refusals (VGX_ERR_ARG, worded alike behind "vgx_get_tau_flows: "): the last call was not vgx_simulate_tau; it recorded no rows;
+ * a replicate that did not restart continues a log of another length than prefix->ev_ptr; prefix plus own rows reach 2^31; a null
+ * prefix column; bad edges; T outside [1, 2^24); replicates out of range or given twice; V < 1 or a variant_of value outside
+ * [-1, V); popNum * V * 8 bytes of diagonal cells above the 65536 bytes of LDS a counting workgroup may use, or the dense form
+ * forced where popNum^2 * V * 8 bytes are (the message gives the bytes); a value of VGX_FLOWS_FORM that is neither; a block of
+ * 2^40 cells or more; the block (8 bytes per cell, 4 more with a summary) and the prefix block above half of the free device
+ * memory (the message gives the bytes: select fewer replicates). */
+typedef struct vgx_tau_flows_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    int64_t T; const double *edges;              /* [T + 1] strictly increasing, finite */
+    int64_t V; const int32_t *variant_of;        /* [hapNum], values in [-1, V) */
+    int32_t within;                              /* 1: births count on the diagonal; 0: migrations alone */
+    int64_t *counts;                             /* NULL or host [n][T][P][P][V] */
+    int64_t *outside;                            /* [n][2] */
+    vgx_traj_summary_io *summary;                /* NULL or the summary of the [n][T*P*P*V] block; group_of has n entries */
+    int64_t form, passes; double ms[3];          /* out: the form that ran (1 dense, 2 split); counting launches; kernels, host cut search, whole call */
+} vgx_tau_flows_io;
+int vgx_get_tau_flows(vgx_engine *e, vgx_tau_flows_io *io, const vgx_timelines_prefix *prefix);
+/* Test hook: the flattening, cuts, cell and tile walk of vgx_get_tau_flows compiled for the host, on one chain given as event
+ * columns and multievent columns (no device, no engine), tile after tile of `tile` rows (0: the default), in the form `form` asks
+ * for (0: the automatic choice, 1 dense, 2 split).  n_own_events, the prefix and the own rows as in vgx_test_tau_incidence: the
+ * prefix is counted once as a chain of its own and added, as on the device.  counts [T][P][P][V] and outside [2] are overwritten,
+ * form_ran gets the form that ran.  Refused with the message in errbuf: bad edges, V or variant_of, a form that does not fit the
+ * LDS budget, a negative tile, a MULTITYPE row range outside the multievent log, a prefix row the flattening refuses. */
+typedef struct vgx_tau_flows_chain {
+    int64_t popNum, hapNum;
+    int64_t ev_ptr;
+    const double *ev_times;
+    const int64_t *ev_types, *ev_haplotypes, *ev_populations, *ev_newHaplotypes, *ev_newPopulations;
+    int64_t mev_rows;
+    const int64_t *mev_num, *mev_types, *mev_haplotypes, *mev_populations, *mev_newHaplotypes, *mev_newPopulations;
+    int64_t T; const double *edges;              /* [T + 1] */
+    int64_t V; const int32_t *variant_of;        /* [hapNum], values in [-1, V) */
+    int64_t within;                              /* 0: migrations alone */
+    int64_t tile, form, n_own_events;
+    int64_t *counts;                             /* out [T][P][P][V] */
+    int64_t *outside;                            /* out [2] */
+    int64_t form_ran;                            /* out: 1 dense, 2 split */
+} vgx_tau_flows_chain;
+int vgx_test_tau_flows(vgx_tau_flows_chain *io, char *errbuf, int64_t errcap);
 
 /* vgx_get_prevalence for many replicates of the last vgx_simulate_tau call (with the event log), on the device.
  * The chain is that of vgx_get_tau_incidence: weighted rows (num, type, haplotype, population, newHaplotype, newPopulation), six

@@ -194,6 +194,23 @@ class VgxTauIncidenceChain(C.Structure):
                 ("counts", _I), ("outside", _I)]
 
 
+class VgxTauFlowsIO(C.Structure):
+    _fields_ = [("n", C.c_int64), ("replicates", _I), ("T", C.c_int64), ("edges", _F), ("V", C.c_int64), ("variant_of", C.POINTER(C.c_int32)),
+                ("within", C.c_int32), ("counts", _I), ("outside", _I), ("summary", C.POINTER(VgxTrajSummaryIO)),
+                ("form", C.c_int64), ("passes", C.c_int64), ("ms", C.c_double * 3)]
+
+
+class VgxTauFlowsChain(C.Structure):
+    _fields_ = [("popNum", C.c_int64), ("hapNum", C.c_int64), ("ev_ptr", C.c_int64),
+                ("ev_times", _F), ("ev_types", _I), ("ev_haplotypes", _I), ("ev_populations", _I),
+                ("ev_newHaplotypes", _I), ("ev_newPopulations", _I),
+                ("mev_rows", C.c_int64), ("mev_num", _I), ("mev_types", _I), ("mev_haplotypes", _I), ("mev_populations", _I),
+                ("mev_newHaplotypes", _I), ("mev_newPopulations", _I),
+                ("T", C.c_int64), ("edges", _F), ("V", C.c_int64), ("variant_of", C.POINTER(C.c_int32)), ("within", C.c_int64),
+                ("tile", C.c_int64), ("form", C.c_int64), ("n_own_events", C.c_int64), ("counts", _I), ("outside", _I),
+                ("form_ran", C.c_int64)]
+
+
 class VgxTauPrevalenceIO(C.Structure):
     _fields_ = [("n", C.c_int64), ("replicates", _I), ("T", C.c_int64), ("grid", _F), ("V", C.c_int64), ("variant_of", C.POINTER(C.c_int32)),
                 ("values", _I), ("final", _I), ("outside", _I), ("summary", C.POINTER(VgxTrajSummaryIO)),
@@ -324,6 +341,8 @@ SIGNATURES = {
     "vgx_test_tau_milestones": (C.c_int, [C.POINTER(VgxTauMilestonesChain), C.c_char_p, C.c_int64]),
     "vgx_get_tau_incidence": (C.c_int, [_H, C.POINTER(VgxTauIncidenceIO), C.POINTER(VgxTimelinesPrefix)]),
     "vgx_test_tau_incidence": (C.c_int, [C.POINTER(VgxTauIncidenceChain), C.c_char_p, C.c_int64]),
+    "vgx_get_tau_flows": (C.c_int, [_H, C.POINTER(VgxTauFlowsIO), C.POINTER(VgxTimelinesPrefix)]),
+    "vgx_test_tau_flows": (C.c_int, [C.POINTER(VgxTauFlowsChain), C.c_char_p, C.c_int64]),
     "vgx_get_tau_prevalence": (C.c_int, [_H, C.POINTER(VgxTauPrevalenceIO), C.POINTER(VgxTimelinesPrefix)]),
     "vgx_test_tau_prevalence": (C.c_int, [C.POINTER(VgxTauPrevalenceChain), C.c_char_p, C.c_int64]),
     "vgx_get_susceptibles": (C.c_int, [_H, C.POINTER(VgxSusceptiblesIO)]),
@@ -1201,6 +1220,58 @@ def replay_tau_incidence(events, mev, popNum, hapNum, edges, hap_mask=None, tile
     if load_library().vgx_test_tau_incidence(C.byref(io), err, 512) != VGX_OK:
         raise ValueError(err.value.decode() or "vgx_test_tau_incidence failed")
     return counts, outside
+
+
+def tau_flows_lds_check(P, V):
+    """The LDS limit of the split form of ``vgx_get_tau_flows`` (8-byte cells), worded as the library words it; ValueError above it."""
+    need = 8 * P * V
+    if need > 65536:
+        raise ValueError("%d populations x %d classes need %d bytes of 8-byte cells in the split form, above the 65536 bytes of LDS a "
+                         "counting workgroup may use" % (P, V, need))
+
+
+def replay_tau_flows(events, mev, P, H, edges, variant_of, V, within=True, tile=0, form=0, n_own=-1):
+    """The block of ``Ensemble.tau_flows`` for one chain through ``vgx_test_tau_flows``: the device's flattening, cuts, cell and
+    tile walk (vgx_tau_flows.h) compiled for the host, tile after tile of ``tile`` rows (0: the default), in the form ``form`` asks
+    for (0 or None: the automatic choice, 1 or 'dense', 2 or 'split'); no GPU.  ``events`` and ``mev`` as ``replay_tau_incidence``
+    takes them; the last ``n_own`` events play the replicate's own steps (-1: the trailing MULTITYPE events), everything before them
+    the prefix, which is counted once and added as on the device.  ``variant_of`` [H] with values in [-1, V).  Returns (counts
+    [T, P, P, V] int64 in src, dst, class order, outside [2] int64, the form that ran: 'dense' or 'split'); a refusal raises
+    ``ValueError`` with the library's message."""
+    times = np.ascontiguousarray(events[0], dtype=np.float64)
+    cols = [np.ascontiguousarray(c, dtype=np.int64) for c in events[1:6]]
+    n = len(times)
+    if len(cols) != 5 or any(len(c) != n for c in cols):
+        raise ValueError("event columns of different lengths")
+    mcols = [np.ascontiguousarray(mev[c] if mev is not None else [], dtype=np.int64) for c in MEV_COLUMNS]
+    if len({len(c) for c in mcols}) != 1:
+        raise ValueError("multievent columns of different lengths")
+    if form is None or isinstance(form, str):
+        if form not in FLOW_FORMS:
+            raise ValueError("form must be None, 'dense' or 'split'")
+        form = FLOW_FORMS[form]
+    edges = np.ascontiguousarray(edges, dtype=np.float64)
+    T, P, H, V = len(edges) - 1, int(P), int(H), int(V)
+    vo = np.ascontiguousarray(variant_of, dtype=np.int32)
+    if len(vo) != H:
+        raise ValueError("variant_of must hold hapNum values")
+    fits = 0 < P and 0 < V and 8 * P * V <= 65536   # (what does not fit is refused by the hook before it writes)
+    counts = np.zeros((max(T, 1), P, P, V) if fits else (1,), dtype=np.int64)
+    outside = np.zeros(2, dtype=np.int64)
+    io = VgxTauFlowsChain()
+    io.popNum, io.hapNum, io.ev_ptr, io.ev_times = P, H, n, _p(times)
+    for name, col in zip(("types", "haplotypes", "populations", "newHaplotypes", "newPopulations"), cols):
+        setattr(io, "ev_" + name, _p(col))
+    io.mev_rows = len(mcols[0])
+    for name, col in zip(MEV_COLUMNS, mcols):
+        setattr(io, "mev_" + name, _p(col))
+    io.T, io.edges, io.V, io.variant_of = T, _p(edges), V, vo.ctypes.data_as(C.POINTER(C.c_int32))
+    io.within, io.tile, io.form, io.n_own_events = 1 if within else 0, int(tile), int(form), int(n_own)
+    io.counts, io.outside = _p(counts), _p(outside)
+    err = C.create_string_buffer(512)
+    if load_library().vgx_test_tau_flows(C.byref(io), err, 512) != VGX_OK:
+        raise ValueError(err.value.decode() or "vgx_test_tau_flows failed")
+    return counts, outside, FLOW_FORM_NAMES[int(io.form_ran)]
 
 
 def replay_tau_prevalence(events, mev, popNum, hapNum, grid, variant_of, V, start, tile=0, n_own_events=-1):

@@ -70,6 +70,11 @@ extern "C" hipError_t vgxi_tau_prev_init(int64_t m, int64_t tc, int64_t cells, c
 extern "C" hipError_t vgxi_tau_prev_count(const VgxTauPrevLaunch *a, hipStream_t s);   // (vgx_tau_milestones.hip: pass A over tile edges)
 extern "C" hipError_t vgxi_tau_prev_scan(const VgxTauPrevLaunch *a, hipStream_t s);
 extern "C" hipError_t vgxi_tau_prev_minmax(int64_t total, const int64_t *src, int32_t *dst, uint64_t *mm, hipStream_t s);
+// vgx_tau_flows.hip: the weighted-row count (a->form is the form that runs) and the start of m blocks of tc cells from the prefix's
+struct VgxTauFlowLaunch;
+extern "C" hipError_t vgxi_tau_flow_count(const VgxTauFlowLaunch *a, hipStream_t s);
+extern "C" hipError_t vgxi_tau_flow_init(int64_t m, int64_t tc, const int32_t *with, const int64_t *pre, const int64_t *pre_out, int64_t *counts,
+                                         int64_t *outside, hipStream_t s);
 // the column summary of vgx_colsummary.hip on a device int32 matrix x[R][N] of values in [0, 2^31) (a refusal's message goes to errbuf)
 extern "C" int vgxi_column_summary_i32(const char *what, const int32_t *x, int64_t R, int64_t N, vgx_traj_summary_io *io, hipStream_t stream,
                                        char *errbuf, int64_t errcap);

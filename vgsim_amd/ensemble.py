@@ -259,7 +259,7 @@ class Flows:
     """What ``Ensemble.flows`` returns: new infections per selected replicate, time bin, source population, destination
     population and variant class.
 
-    ``counts`` [n, T, P, P, V] int32 indexed ``[r, b, src, dst, c]`` (None when the call had ``counts=False``): a birth in p counts
+    ``counts`` [n, T, P, P, V] int32 (int64 from ``tau_flows``) indexed ``[r, b, src, dst, c]`` (None when the call had ``counts=False``): a birth in p counts
     at (p, p), a migration at (population, newPopulation); ``edges`` [T + 1] the bin edges (bin b holds edges[b] <= t <
     edges[b + 1]); ``variant_of`` [H] the class of every haplotype (-1: not tracked); ``outside`` [n, 2] the events of every
     replicate before ``edges[0]`` and from ``edges[T]`` on; ``replicates`` [n]; ``summary`` a :class:`TrajectorySummary` over the
@@ -1076,6 +1076,52 @@ class Ensemble:
         io.outside = _capi._p(outside)
         io.summary = C.pointer(sio) if sio is not None and n else None
         eng._check(eng.lib.vgx_get_flows(eng.handle, C.byref(io)))
+        fl = Flows()
+        fl.counts, fl.edges, fl.variant_of, fl.outside, fl.replicates = block, e, vo, outside[:n], reps
+        fl.summary = done() if done is not None else None
+        fl.form = _capi.FLOW_FORM_NAMES[int(io.form)]
+        fl.passes, fl.kernel_ms, fl.clock_ms, fl.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
+        return fl
+
+    def tau_flows(self, edges=None, bins=None, window=None, variants=None, within=True, replicates=None, summary=None, counts=True):
+        """``flows()`` for the replicates of the last ``simulate_tau(record_events=True)`` call (``vgx_get_tau_flows``): the same
+        grid arguments, ``variants``, ``within``, ``replicates``, ``summary`` and :class:`Flows`, with ``counts``
+        [n, T, P, P, V] int64 (a bin sums the multiplicities of many steps) and ``outside`` the summed multiplicities before and
+        after the window.
+
+        The chain is ``tau_incidence()``'s: the model's chain before the tau call (a replicate that restarted has none), then
+        the replicate's own steps, every multievent row counting ``num`` times in the one cell ``flows()`` gives it; all events
+        of a step fall into the bin of the step's MULTITYPE record.  The shared part is counted once per call on the device; no
+        host clock runs.  With ``haplotypes`` = the members of class c, ``tau_incidence()``'s channels are this block's margins.
+        ``summary``: refused by the library when a count reaches 2^31 (``counts`` stays available: call again without
+        ``summary``).  ``by='auto'`` is one group (scenario ensembles have no ``simulate_tau``)."""
+        e = _incidence_edges(edges, bins, window)
+        if self._last_call is None:
+            raise ValueError("tau_flows() needs a simulate_tau(record_events=True) call first")
+        if self._last_call[0] != 'tau':
+            raise ValueError("tau_flows() counts tau chains only: the last call was a direct simulate()")
+        if not self._last_call[1]:
+            raise ValueError("tau_flows() needs the multievent rows: the last call had record_events=False")
+        m, eng = self.model, self.engine
+        reps = self._selected_replicates(replicates)
+        n = len(reps)
+        vo, V = _capi.variant_map(variants, m.hapNum)
+        T, P = len(e) - 1, m.popNum
+        _capi.tau_flows_lds_check(P, V)
+        sio, done = self._block_summary(summary, reps, (T, P, P, V), None, 1)
+        if summary is None and not counts:
+            raise ValueError("counts=False needs summary=: the call would return nothing")
+        block = np.zeros((n, T, P, P, V), dtype=np.int64) if counts else None
+        outside = np.zeros((max(n, 1), 2), dtype=np.int64)
+        io = _capi.VgxTauFlowsIO()
+        io.n, io.replicates, io.T, io.edges = n, _capi._p(reps), T, _capi._p(e)
+        io.V, io.variant_of = V, vo.ctypes.data_as(C.POINTER(C.c_int32))
+        io.within = 1 if within else 0
+        io.counts = _capi._p(block) if counts and n else None
+        io.outside = _capi._p(outside)
+        io.summary = C.pointer(sio) if sio is not None and n else None
+        pre = self._tau_prefix_struct()
+        eng._check(eng.lib.vgx_get_tau_flows(eng.handle, C.byref(io), C.byref(pre)))
         fl = Flows()
         fl.counts, fl.edges, fl.variant_of, fl.outside, fl.replicates = block, e, vo, outside[:n], reps
         fl.summary = done() if done is not None else None
