@@ -1183,7 +1183,10 @@ int vgx_get_list_tile_sums(vgx_engine *e, int64_t replicate, int64_t population,
 /* For callers that hold the reference's dense per-population arrays: the infect branch of UpdateRates (pyx:518-528:
  * BirthRate, tEventHapPopRate, hapPopRate, infectPopRate) followed by fastChoose over hapPopRate (fast_choose.pxi:18-31)
  * for `rows` independent (replicate, population) rows at once.  FAST-mode arithmetic: BirthRate factored
- * through rowContact = sum_pn m[pi,pn]^2 * cd[pn] / actualSizes[pn], tree-order sums.  All pointers are host arrays. */
+ * through rowContact = sum_pn m[pi,pn]^2 * cd[pn] / actualSizes[pn], tree-order sums.  All pointers are host arrays.
+ * The chosen entry always has a positive hapPopRate: u = 0 gives the row's first positive entry (rnOut 0), an r that rounding
+ * leaves above every running sum its last positive one.  A row whose rowTotal is 0 has nothing to choose: chosen is H - 1 and
+ * rnOut is NaN there, and neither may be used.  rows, H or S below 1: VGX_ERR_ARG, the message names the three. */
 typedef struct vgx_rowscan {
     int64_t rows, H, S;
     const int64_t *infectious;       /* [rows][H]      infectious[pi, :]                                   in  */

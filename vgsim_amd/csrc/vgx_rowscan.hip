@@ -22,6 +22,7 @@
 // half the row is read, as in the reference's linear scan.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string>
 #include <vector>
 #include "../../include/vgx.h"
 #include "vgx_wave.h"
@@ -154,8 +155,10 @@ extern "C" __global__ void __launch_bounds__(RS_TB) vgx_rowscan_choose_kernel(Ro
         const double part = ((w[0] + w[1]) + w[2]) + w[3];
         double tot;
         const double incl = block_scan(part, wsum, tot) + carry;      // running sum through this thread's four entries
-        // the first entry whose running sum reaches r lies in the first thread whose inclusive sum does
-        const unsigned long long hitmask = __ballot(!(incl < r));
+        if (!(total > 0.0)) break;   // nothing to choose from (vgx.h): do not walk the row (tested here, where the load of total is first waited for)
+        // the first entry whose running sum reaches r lies in the first thread whose inclusive sum does.  A thread of four zeros holds no
+        // entry to choose: its sum is its neighbour's exact sum in another tree order and may reach r an ulp before it
+        const unsigned long long hitmask = __ballot(!(incl < r) && part > 0.0);
         if ((threadIdx.x & 63) == 0) s_first[threadIdx.x >> 6] = hitmask ? (int)(threadIdx.x + __ffsll((long long)hitmask) - 1) : RS_TB;
         if ((threadIdx.x & 63) == 63) s_wincl[threadIdx.x >> 6] = incl;   // for the first lane of the next wavefront
         double prev = __shfl_up(incl, 1);
@@ -166,10 +169,14 @@ extern "C" __global__ void __launch_bounds__(RS_TB) vgx_rowscan_choose_kernel(Ro
         if ((int)threadIdx.x == first) {
             // running sum before this thread's entries: the previous thread's inclusive sum (the same bits it compared)
             double run = (threadIdx.x & 63) ? prev : (threadIdx.x ? s_wincl[(threadIdx.x >> 6) - 1] : carry);
+            // the serial sums below may stay under r where the tree-order incl reached it: the thread's last positive entry ends the walk
+            int last = 0;
+#pragma unroll
+            for (int k = 1; k < RS_PER; ++k) if (w[k] > 0.0) last = k;
             int j = 0;
-            for (; j < RS_PER - 1; ++j) { if (!(run + w[j] < r)) break; run += w[j]; }
+            for (; j < last; ++j) { if (!(run + w[j] < r)) break; run += w[j]; }
             // zero weights never stop the reference's scan either (total < rn is strict, fc:26): skip forward to a positive one
-            while (j < RS_PER - 1 && w[j] == 0.0) ++j;
+            while (j < last && w[j] == 0.0) ++j;
             s_hit = h0 + j; s_pre = run + w[j]; s_w = w[j];
         }
         __syncthreads();
@@ -179,8 +186,10 @@ extern "C" __global__ void __launch_bounds__(RS_TB) vgx_rowscan_choose_kernel(Ro
     if (threadIdx.x == 0) {
         int64_t hit = s_hit;
         double pre = s_pre, wi = s_w;
-        if (hit < 0) {   // rounding left the tree-order total below r: clamp at the end like fc:26
-            hit = H - 1; pre = carry; wi = hpr[H - 1];
+        if (hit < 0) {   // rounding left the tree-order total below r: clamp at the end like fc:26, in front of the row's trailing zeros
+            hit = H - 1; pre = carry;
+            if (total > 0.0) while (hit > 0 && hpr[hit] == 0.0) --hit;
+            wi = hpr[hit];   // a row of total 0: H - 1 and 0 / 0
         }
         a.chosen[row] = hit;
         a.rnOut[row] = (r - (pre - wi)) / wi;           // fc:31
@@ -203,7 +212,11 @@ extern "C" const char *vgx_propensity_scan_error(void) { return g_rowscan_error.
 
 static int rowscan_run(const vgx_rowscan *io, int repeats, double *ms_update, double *ms_choose, bool synthetic) {
     std::vector<void *> bufs;
-    if (!io || io->rows < 1 || io->H < 1 || io->S < 1) { g_rowscan_error = "vgx_propensity_scan: bad dimensions"; return VGX_ERR_ARG; }
+    if (!io || io->rows < 1 || io->H < 1 || io->S < 1) {
+        g_rowscan_error = "vgx_propensity_scan: bad dimensions";
+        if (io) g_rowscan_error += " (rows = " + std::to_string(io->rows) + ", H = " + std::to_string(io->H) + ", S = " + std::to_string(io->S) + ", each must be at least 1)";
+        return VGX_ERR_ARG;
+    }
     const int64_t R = io->rows, H = io->H, S = io->S;
     RowScanDev d{};
     d.rows = R; d.H = H; d.S = S;
