@@ -145,6 +145,8 @@ typedef struct vgx_run_opts {
                                 tests/test_direct_plan.py has the table. */
     int64_t reserved[2];     /* [0] tau path: 1 = run every try of the halving loop (pyx:2316-2321) instead of starting at the
                                 first try that is not certain to be rejected (same accepted steps either way);
+                                2 = with several parameter sets installed (vgx_set_param_sets): run every replicate under its own
+                                set on the on-device step loop (without it such a call is refused; ignored with one set);
                                 [1] tau path, how a try's deltas are kept and checked (same draws and decisions in every mode):
                                 0 = sparse (default): a list of moves, own deltas checked where they are drawn, no dense arrays;
                                 2 = dense delta arrays written by every try, the fused own-delta / arrival tests;
@@ -177,7 +179,12 @@ int vgx_set_params(vgx_engine *e, const vgx_params *p);
  * Replicate r of the next vgx_simulate_direct call is, bit for bit, the run of an engine that was given sets[set_of[r]] through
  * vgx_set_params, the same state and seed r: one launch of the one-replicate-per-wavefront kernel runs all of them, every wavefront
  * reading its own set's tables (classes of identical rate rows, actualSizes, the recomputed migration diagonal, suscepCumul,
- * maxEffectiveBirth are built per set).  n_sets == 1 is vgx_set_params(e, &sets[0]); a later vgx_set_params returns the engine to one
+ * maxEffectiveBirth are built per set).  So is replicate r of a vgx_simulate_tau call that asks for the sets
+ * (vgx_run_opts.reserved[0] = 2; a call that does not is refused, as every tau call under sets used to be), where the on-device
+ * step loop runs it
+ * (one workgroup per replicate, every workgroup under its own set: compartments, counters, times, restarts, lockdown state and
+ * records, multievent rows, step times and trajectories equal that engine's run on the on-device loop; the preparation's lockdown
+ * check, swapLockdown and the non-zero-rate guards of the start and of a Restart are each set's own).  n_sets == 1 is vgx_set_params(e, &sets[0]); a later vgx_set_params returns the engine to one
  * set.  Like vgx_set_params the call invalidates the device state.  Dimensions, start state and recombination settings are the
  * engine's, shared by all sets; so `sizes` must be bitwise equal in all sets (VGX_ERR_ARG otherwise).  One value of the state is a
  * set's own: a replicate starts with contactDensityAfterLockdown of its set in the populations whose lockdownON is set in the start
@@ -187,7 +194,14 @@ int vgx_set_params(vgx_engine *e, const vgx_params *p);
  * logs, vgx_get_genealogies, vgx_get_timelines and the trajectories read logs and state only and work unchanged.
  * Limits while more than one set is installed (each refused with VGX_ERR_ARG and a message naming it): vgx_simulate_direct runs in
  * mode 0 on kernel 0 or 1 only (the row, latency and lane kernels, FAST and the counter-based stream read one shared parameter
- * copy); vgx_simulate_tau and vgx_stage_tau are refused.  Device memory: one copy of every parameter array per set. */
+ * copy).  vgx_simulate_tau runs only when vgx_run_opts.reserved[0] = 2 asks for it, and then on the on-device step loop only, whatever the ensemble's size (the step kernels of large states
+ * read one shared copy), and is refused where that loop does not run, the message naming the number: popNum * hapNum above 8192,
+ * popNum above 64, susNum above 8, more than 15 sites, more than 256 rate classes or 64 transmission classes in the largest set,
+ * more than 150 KiB of LDS per replicate, VGX_TAU_STEP_KERNELS=1, VGX_TAU_LARGE_MODEL_THRESHOLDS=1, the step kernels' validation
+ * modes (vgx_run_opts.reserved[1]), or a step log (replicates x steps x 24 bytes) above 8e9 bytes.  A refused call leaves the engine
+ * usable.  vgx_stage_tau is refused.  The tau getters (states, multievent rows, lockdowns, timelines, genealogies, incidence,
+ * prevalence, susceptibles, milestones, flows) read logs and state only and work unchanged.
+ * Device memory: one copy of every parameter array per set. */
 int vgx_set_param_sets(vgx_engine *e, int64_t n_sets, const vgx_params *sets /* [n_sets] */,
                        const int32_t *set_of /* [n_replicates], values in [0, n_sets) */);
 /* Recombination branch of Birth (pyx:575-596): `recombination_probability` (pyx:93, set_coinfection_parameters

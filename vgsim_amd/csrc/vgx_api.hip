@@ -185,6 +185,26 @@ static int build_param_tables(const vgx_dims &d, const vgx_params *p, const std:
     return VGX_OK;
 }
 
+// What the start of a tau call reads of one parameter set beyond its device block: which rate classes have any positive rate, and
+// the table of the uniform mutation model (every haplotype with the same mRate / hapMutType rows)
+static void tau_set_tables(const vgx_dims &d, const vgx_params *p, const ParamTables &t, TauSetTables &out) {
+    const int64_t H = d.hapNum, sites = d.sites;
+    out.cls = t.cls;
+    out.suscepCumul = t.suscepCumul;
+    out.class_pos.assign(t.c_d.size(), 0);
+    for (size_t c = 0; c < t.c_d.size(); c++)
+        out.class_pos[c] = (t.c_d[c] > 0.0 || t.c_s[c] > 0.0 || t.c_tm[c] > 0.0 || t.cb_b[(size_t)t.c_bidx[c]] > 0.0) ? 1 : 0;
+    out.mut_uniform = true;
+    for (int64_t h = 1; h < H && out.mut_uniform; h++)
+        if (memcmp(p->mRate + h * sites, p->mRate, (size_t)sites * 8) != 0 ||
+            memcmp(p->hapMutType + h * sites * 3, p->hapMutType, (size_t)sites * 24) != 0)
+            out.mut_uniform = false;
+    for (int64_t s2 = 0; s2 < sites && s2 < 16; s2++) {
+        const double *hm = p->hapMutType + s2 * 3;
+        for (int i = 0; i < 3; i++) out.mutp[s2][i] = p->mRate[s2] * hm[i] / (hm[0] + hm[1] + hm[2]);
+    }
+}
+
 extern "C" int vgx_set_params(vgx_engine *e, const vgx_params *p) {
     if (!e || !p) return VGX_ERR_ARG;
     HIPCHECK(e, hipSetDevice(e->device));
@@ -296,9 +316,9 @@ extern "C" int vgx_set_params(vgx_engine *e, const vgx_params *p) {
         }
         e->h_so_ncls = (int)cmap.size();
     }
-    e->h_class_pos.assign(c_d.size(), 0);
-    for (size_t c = 0; c < c_d.size(); c++)
-        e->h_class_pos[c] = (c_d[c] > 0.0 || c_s[c] > 0.0 || c_tm[c] > 0.0 || cb_b[(size_t)c_bidx[c]] > 0.0) ? 1 : 0;
+    TauSetTables ts;
+    tau_set_tables(e->d, p, t, ts);
+    e->h_class_pos = ts.class_pos;
 
     e->suscepCumul = t.suscepCumul;
     e->mig = t.mig;
@@ -314,19 +334,11 @@ extern "C" int vgx_set_params(vgx_engine *e, const vgx_params *p) {
             if (i != j && p->migrationRates[i * P + j] != 0.0) e->h_has_mig = true;
     if (S > 64) return fail(e, VGX_ERR_ARG, "vgx_set_params: at most 64 susceptibility groups are supported");
     // uniform mutation model (every haplotype has the same mRate / hapMutType rows): table for the tau kernels
-    e->h_mut_uniform = true;
-    for (int64_t h = 1; h < H && e->h_mut_uniform; h++)
-        if (memcmp(p->mRate + h * sites, p->mRate, (size_t)sites * 8) != 0 ||
-            memcmp(p->hapMutType + h * sites * 3, p->hapMutType, (size_t)sites * 24) != 0)
-            e->h_mut_uniform = false;
+    e->h_mut_uniform = ts.mut_uniform;
+    memcpy(e->h_mutp, ts.mutp, sizeof(e->h_mutp));
     e->h_mut_total = 0.0;
-    for (int64_t s2 = 0; s2 < sites && s2 < 16; s2++) {
-        const double *hm = p->hapMutType + s2 * 3;
-        for (int i = 0; i < 3; i++) {
-            e->h_mutp[s2][i] = sites > 0 ? p->mRate[s2] * hm[i] / (hm[0] + hm[1] + hm[2]) : 0.0;
-            e->h_mut_total += e->h_mutp[s2][i];
-        }
-    }
+    for (int64_t s2 = 0; s2 < sites && s2 < 16; s2++)
+        for (int i = 0; i < 3; i++) e->h_mut_total += e->h_mutp[s2][i];
     const double maxEffectiveBirth = t.maxEffectiveBirth;
 
     int rc = 0;
@@ -513,6 +525,9 @@ extern "C" int vgx_set_param_sets(vgx_engine *e, int64_t n_sets, const vgx_param
     if (rc) return rc;
     HIPCHECK(e, hipMemcpy(e->ps_setof.p, set_of, (size_t)R * 4, hipMemcpyHostToDevice));
     e->sets_C = maxC; e->sets_CB = maxCB;
+    e->h_setof.assign(set_of, set_of + R);
+    e->h_sets.assign((size_t)n_sets, TauSetTables{});
+    for (int64_t g = 0; g < n_sets; g++) tau_set_tables(e->d, &sets[g], tabs[(size_t)g], e->h_sets[(size_t)g]);
     e->n_sets = n_sets;
     return VGX_OK;
 }

@@ -46,6 +46,7 @@ extern "C" hipError_t vgxi_launch_counts64(const int32_t *c32, int64_t *c64, int
 extern "C" hipError_t vgxi_launch_quad_prep(const VgxDevParams *p, const double *cd, double *effMig, double *maxEBM, int32_t *has_mig, hipStream_t stream);
 extern "C" hipError_t vgxi_launch_quadf(const VgxDirectArgs *a, const double *cd, double *effMig, double *maxEBM, int32_t *has_mig, hipStream_t stream);
 extern "C" hipError_t vgxi_launch_taus(const VgxTausArgs *a, hipStream_t s);
+extern "C" hipError_t vgxi_launch_taus_sets(const VgxTausSetsArgs *sa, int max_C, int max_CB, hipStream_t s);
 extern "C" hipError_t vgxi_launch_quadg(const VgxDirectArgs *a, const VgxQuadgArgs *qa, hipStream_t stream);
 extern "C" hipError_t vgxi_launch_solo(const VgxDirectArgs *a, const VgxSoloArgs *sa, int clock, hipStream_t stream);
 extern "C" hipError_t vgxi_launch_lone(const VgxDirectArgs *a, const VgxLoneArgs *la, int clock, hipStream_t stream);
@@ -105,6 +106,16 @@ struct HostState {
     int64_t ev_ptr = 0, ev_size = 0;
 };
 
+// What the start of a tau call reads of one parameter set on the host (the engine's h_class_pos, suscepCumul, h_mut_uniform and
+// h_mutp hold set 0's): filled for every set by vgx_set_param_sets
+struct TauSetTables {
+    std::vector<int32_t> cls;            // [H] rate class of a haplotype
+    std::vector<char> class_pos;         // [C] the class has a positive recovery, sampling, mutation or transmission rate
+    std::vector<double> suscepCumul;     // [S]
+    bool mut_uniform = false;
+    double mutp[16][3] = {};             // mRate[s] * w[s][i] / (w[s][0] + w[s][1] + w[s][2]) of haplotype 0's rows
+};
+
 struct DevBuf {
     void *p = nullptr;
     size_t bytes = 0;
@@ -148,6 +159,9 @@ struct vgx_engine {
     std::vector<double> sets_startLD;    // [n_sets][P]
     std::vector<VgxDevParams> h_psets;   // [n_sets] the blocks as uploaded: pointers into ps_blob
     DevBuf ps_blob, ps_blocks, ps_setof;
+    std::vector<int32_t> h_setof;        // [R] the map as installed
+    std::vector<TauSetTables> h_sets;    // [n_sets] what the start of a tau call reads of every set (vgx_tau_run.hip)
+    DevBuf ps_taurec;                    // [n_sets] VgxTausSetRec of the last tau call
     int max_C() const { return n_sets > 1 ? sets_C : C; }
     int max_CB() const { return n_sets > 1 ? sets_CB : CB; }
     double recombination = 0.0;          // pyx:93, 1422-1426

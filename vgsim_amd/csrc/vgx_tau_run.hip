@@ -91,18 +91,26 @@ extern "C" int vgx_stage_tau(vgx_engine *e) {
 }
 
 // The first `n` lockdown records and times of replicate `src` on the device onto the lockdown log of replicates [dst0, dst1)
-static int drain_lockdown_log(vgx_engine *e, int64_t src, int64_t n, int64_t dst0, int64_t dst1) {
+static int read_lockdown_log(vgx_engine *e, int64_t src, int64_t n, std::vector<int32_t> &rec, std::vector<double> &tt) {
     if (n <= 0) return VGX_OK;
-    std::vector<int32_t> rec((size_t)n * 2);
-    std::vector<double> tt((size_t)n);
+    rec.resize((size_t)n * 2);
+    tt.resize((size_t)n);
     HIPCHECK(e, hipMemcpy(rec.data(), (int32_t *)e->r_locrec.p + src * VGX_LOC_CAP * 2, (size_t)n * 8, hipMemcpyDeviceToHost));
     HIPCHECK(e, hipMemcpy(tt.data(), (double *)e->r_loctime.p + src * VGX_LOC_CAP, (size_t)n * 8, hipMemcpyDeviceToHost));
-    for (int64_t r = dst0; r < dst1; r++)
-        for (int64_t i = 0; i < n; i++) {
-            e->tau_loc_state[(size_t)r].push_back(rec[(size_t)(i * 2)]);
-            e->tau_loc_pop[(size_t)r].push_back(rec[(size_t)(i * 2 + 1)]);
-            e->tau_loc_time[(size_t)r].push_back(tt[(size_t)i]);
-        }
+    return VGX_OK;
+}
+static void append_lockdown_log(vgx_engine *e, int64_t r, int64_t n, const std::vector<int32_t> &rec, const std::vector<double> &tt) {
+    for (int64_t i = 0; i < n; i++) {
+        e->tau_loc_state[(size_t)r].push_back(rec[(size_t)(i * 2)]);
+        e->tau_loc_pop[(size_t)r].push_back(rec[(size_t)(i * 2 + 1)]);
+        e->tau_loc_time[(size_t)r].push_back(tt[(size_t)i]);
+    }
+}
+static int drain_lockdown_log(vgx_engine *e, int64_t src, int64_t n, int64_t dst0, int64_t dst1) {
+    std::vector<int32_t> rec;
+    std::vector<double> tt;
+    TAU_TRY(read_lockdown_log(e, src, n, rec, tt));
+    for (int64_t r = dst0; r < dst1 && n > 0; r++) append_lockdown_log(e, r, n, rec, tt);
     return VGX_OK;
 }
 
@@ -135,7 +143,7 @@ static int64_t host_check_lockdown(vgx_engine *e, const std::vector<int64_t> &to
 static bool taus_shape_ok(const vgx_engine *e, bool sparse_default) {
     const int64_t H = e->d.hapNum, P = e->d.popNum, S = e->d.susNum;
     return P * H <= VGX_TAUS_MAX_CELLS && P <= VGX_TAUS_MAX_P && S <= VGX_TAUS_MAX_S && e->d.sites <= 15 && sparse_default &&
-           e->C <= VGX_TAUS_MAX_C && e->CB <= VGX_TAUS_MAX_CB && vgx_taus_lds_bytes(P, H, S, e->C, e->CB) <= 150 * 1024;
+           e->max_C() <= VGX_TAUS_MAX_C && e->max_CB() <= VGX_TAUS_MAX_CB && vgx_taus_lds_bytes(P, H, S, e->max_C(), e->max_CB()) <= 150 * 1024;
 }
 
 static int halving_guard(vgx_engine *e, int tries) {
@@ -158,6 +166,12 @@ struct __attribute__((visibility("hidden"))) TauRun {
     // the start state (staged: vgx_stage_tau already did the snapshot, the count and the upload of this start state)
     bool staged = false, start_ok = false, rates_nonzero_initial = false;
     int64_t occupied = 0;
+    // several parameter sets (vgx_set_param_sets; the on-device loop only): what the preparation found per set and per replicate
+    const bool sets = e->n_sets > 1;
+    std::vector<int32_t> set_start_ok, set_rates_nonzero_initial;   // [n_sets]
+    std::vector<int64_t> set_swaps;                                 // [n_sets] swapLockdown after the preparation
+    std::vector<double> rep_cd, rep_total_rate, rep_total_mig;      // [R][P], [R], [R]
+    std::vector<int32_t> rep_lock;                                  // [R][P]
     // the workspace: capacities (the growable ones: inc_cap, big_cap, q_scap, mev_cap) and what they were sized from
     int64_t mev_max = 0, mev_cap = 0, Ppad = 0, q_shards = 0, q_shard_max = 0, q_scap = 0, big_cap = 0, suspect_cap = 0, st_size = 64, inc_cap = 0;
     bool sparse_default = true, dense_ready = false;
@@ -189,6 +203,39 @@ struct __attribute__((visibility("hidden"))) TauRun {
         t_last = now;
     }
 
+    // records of accepted steps a replicate can write in this call (a Restart rewinds the log to 0)
+    int64_t step_log_rows() const {
+        return std::max<int64_t>(ev_size - ((ev_ptr_start <= 100 && iterations > 100) ? 0 : ev_ptr_start), 1);
+    }
+
+    // Several parameter sets (vgx_set_param_sets) run on the on-device loop of vgx_taus.hip alone, whatever the ensemble's size: the
+    // step kernels take one set.  A call that loop would not run is refused before anything is prepared.
+    int check_sets() {
+        const std::string who = "vgx_simulate_tau: " + std::to_string(e->n_sets) + " parameter sets are installed (vgx_set_param_sets), which run "
+                                "on the on-device step loop only: ";
+        auto over = [&](const char *what, int64_t v, int64_t limit) {
+            return fail(e, VGX_ERR_ARG, who + what + " = " + std::to_string(v) + " is above the loop's limit of " + std::to_string(limit));
+        };
+        if (P * H > VGX_TAUS_MAX_CELLS) return over("popNum x hapNum", P * H, VGX_TAUS_MAX_CELLS);
+        if (P > VGX_TAUS_MAX_P) return over("popNum", P, VGX_TAUS_MAX_P);
+        if (S > VGX_TAUS_MAX_S) return over("susNum", S, VGX_TAUS_MAX_S);
+        if (e->d.sites > 15) return over("sites", e->d.sites, 15);
+        if (e->max_C() > VGX_TAUS_MAX_C) return over("the rate classes of the largest set", e->max_C(), VGX_TAUS_MAX_C);
+        if (e->max_CB() > VGX_TAUS_MAX_CB) return over("the transmission classes of the largest set", e->max_CB(), VGX_TAUS_MAX_CB);
+        const int64_t lds = (int64_t)vgx_taus_lds_bytes(P, H, S, e->max_C(), e->max_CB());
+        if (lds > 150 * 1024) return over("the LDS bytes of a replicate", lds, 150 * 1024);
+        if (o.reserved[1] == 1 || o.reserved[1] == 2)
+            return fail(e, VGX_ERR_ARG, who + "vgx_run_opts.reserved[1] = " + std::to_string(o.reserved[1]) + " asks for a validation mode of the step kernels");
+        const char *fs = getenv("VGX_TAU_STEP_KERNELS"), *th = getenv("VGX_TAU_LARGE_MODEL_THRESHOLDS");
+        if (fs && fs[0] == '1') return fail(e, VGX_ERR_ARG, who + "VGX_TAU_STEP_KERNELS=1 asks for the step kernels");
+        if (th && th[0] == '1') return fail(e, VGX_ERR_ARG, who + "VGX_TAU_LARGE_MODEL_THRESHOLDS=1 asks for the step kernels");
+        const int64_t rows = step_log_rows();
+        if ((double)R * (double)rows * 24.0 > 8e9)
+            return fail(e, VGX_ERR_ARG, who + "the step log of " + std::to_string(R) + " replicates x " + std::to_string(rows) +
+                                            " steps x 24 bytes is above the loop's limit of 8000000000 bytes");
+        return VGX_OK;
+    }
+
     // PrepareParameters (pyx:2298): first-call snapshot on the host, then CheckLockdown for every population and
     // UpdateAllRates.  The tau steps never read the direct path's rate caches; what the driver needs from
     // UpdateAllRates is only whether totalRate + totalMigrationRate is non-zero (pyx:2311).  For moderately
@@ -210,7 +257,10 @@ struct __attribute__((visibility("hidden"))) TauRun {
         // (the device's UpdateAllRates for the start state — exact totalRate, lockdown switches — where building the direct kernels' occupancy
         // lists from the dense host arrays is cheap: at config 4's size that scan of 2.7e8 compartments is 0.3 s per call, and the host form
         // below — what a densely occupied state takes anyway — stands in)
-        if (occupied <= ((int64_t)1 << 18) && P * H <= ((int64_t)1 << 24)) {
+        if (sets) {
+            TAU_TRY(prepare_start_sets());
+            rates_nonzero = set_start_ok[(size_t)e->h_setof[0]] != 0;
+        } else if (occupied <= ((int64_t)1 << 18) && P * H <= ((int64_t)1 << 24)) {
             vgx_run_opts po{};
             po.record_events = 0;
             TAU_TRY(direct_core(e, 0, -1, -1.0f, 0, &po));
@@ -244,18 +294,79 @@ struct __attribute__((visibility("hidden"))) TauRun {
         if (e->C > 256 && (e->CB > 16 || S > 64)) return fail(e, VGX_ERR_CLASSES, "vgx_simulate_tau: more than 16 transmission classes together with more than 256 rate classes is not supported");
         start_ok = rates_nonzero && h.globalInfectious != 0;
         // the same guard for the state a Restart restores: does an infected host of the initial state have any event rate?
-        for (int64_t pn = 0; pn < P && !rates_nonzero_initial; pn++) {
-            for (int64_t hn = 0; hn < H && !rates_nonzero_initial; hn++) {
+        rates_nonzero_initial = initial_rates_nonzero(e->cls, e->h_class_pos, e->suscepCumul);
+        for (int64_t g = 0; sets && g < e->n_sets; g++) {
+            const TauSetTables &t = e->h_sets[(size_t)g];
+            set_rates_nonzero_initial[(size_t)g] = initial_rates_nonzero(t.cls, t.class_pos, t.suscepCumul) ? 1 : 0;
+        }
+        lap("PrepareParameters");
+        return VGX_OK;
+    }
+
+    // pyx:2311 on the state a Restart restores, under one set's class tables and suscepCumul
+    bool initial_rates_nonzero(const std::vector<int32_t> &cls, const std::vector<char> &class_pos, const std::vector<double> &cumul) const {
+        bool nonzero = false;
+        for (int64_t pn = 0; pn < P && !nonzero; pn++) {
+            for (int64_t hn = 0; hn < H && !nonzero; hn++) {
                 if (h.initial_infectious[(size_t)(pn * H + hn)] == 0) continue;
                 // any positive recovery / sampling / mutation / transmission rate of the haplotype's class makes tEventHapPopRate,
                 // hence totalRate, non-zero (transmission additionally needs a susceptible host; a model without the other
                 // three rates and without susceptibles has nothing left to simulate either way)
-                if (e->h_class_pos[(size_t)e->cls[(size_t)hn]]) rates_nonzero_initial = true;
+                if (class_pos[(size_t)cls[(size_t)hn]]) nonzero = true;
             }
             for (int64_t sn = 0; sn < S; sn++)
-                if (e->suscepCumul[(size_t)sn] * (double)h.initial_susceptible[(size_t)(pn * S + sn)] != 0.0) rates_nonzero_initial = true;
+                if (cumul[(size_t)sn] * (double)h.initial_susceptible[(size_t)(pn * S + sn)] != 0.0) nonzero = true;
         }
-        lap("PrepareParameters");
+        return nonzero;
+    }
+
+    // The preparation under several parameter sets: the same launch (the scenario form of the wavefront kernel, zero attempts) prepares
+    // every replicate under its own set.  Replicates of one set start from one state under one set of parameters and draw nothing, so
+    // they find the same: the first replicate of a set stands for the set (start_ok, swapLockdown, the lockdown records), and every
+    // replicate's contact densities and lockdown states are read from its own block.
+    int prepare_start_sets() {
+        const int64_t G = e->n_sets;
+        vgx_run_opts po{};
+        po.record_events = 0;
+        TAU_TRY(direct_core(e, 0, -1, -1.0f, 0, &po));
+        std::vector<double> popD((size_t)(R * PD_COUNT * P));
+        std::vector<int64_t> popI((size_t)(R * PI_COUNT * P));
+        HIPCHECK(e, hipMemcpy(popD.data(), e->r_popD.p, popD.size() * 8, hipMemcpyDeviceToHost));
+        HIPCHECK(e, hipMemcpy(popI.data(), e->r_popI.p, popI.size() * 8, hipMemcpyDeviceToHost));
+        rep_cd.resize((size_t)(R * P)); rep_lock.resize((size_t)(R * P));
+        rep_total_rate.resize((size_t)R); rep_total_mig.resize((size_t)R);
+        for (int64_t r = 0; r < R; r++) {
+            for (int64_t pn = 0; pn < P; pn++) {
+                rep_cd[(size_t)(r * P + pn)] = popD[(size_t)((r * PD_COUNT + PD_CD) * P + pn)];
+                rep_lock[(size_t)(r * P + pn)] = (int32_t)popI[(size_t)((r * PI_COUNT + PI_LOCK) * P + pn)];
+            }
+            rep_total_rate[(size_t)r] = e->sc_host[(size_t)r].totalRate;
+            rep_total_mig[(size_t)r] = e->sc_host[(size_t)r].totalMig;
+        }
+        set_start_ok.assign((size_t)G, 0); set_swaps.assign((size_t)G, 0); set_rates_nonzero_initial.assign((size_t)G, 0);
+        std::vector<int64_t> first((size_t)G, -1);
+        for (int64_t r = R - 1; r >= 0; r--) first[(size_t)e->h_setof[(size_t)r]] = r;
+        std::vector<int32_t> rec;
+        std::vector<double> tt;
+        for (int64_t g = 0; g < G; g++) {
+            const int64_t r0 = first[(size_t)g];
+            if (r0 < 0) continue;      // (a set without replicates)
+            const VgxRepScalars &prep = e->sc_host[(size_t)r0];
+            set_start_ok[(size_t)g] = (prep.totalRate + prep.totalMig != 0.0 && h.globalInfectious != 0) ? 1 : 0;
+            set_swaps[(size_t)g] = prep.swapLockdown;
+            const int64_t n = std::min<int64_t>(prep.loc_n, e->loc_cap);
+            TAU_TRY(read_lockdown_log(e, r0, n, rec, tt));
+            for (int64_t r = r0; r < R; r++)
+                if (e->h_setof[(size_t)r] == g) append_lockdown_log(e, r, n, rec, tt);
+        }
+        // (the host's one copy of the state: replicate 0's, as a call under one set leaves it)
+        for (int64_t pn = 0; pn < P; pn++) {
+            h.contactDensity[(size_t)pn] = rep_cd[(size_t)pn];
+            h.lockdownON[(size_t)pn] = rep_lock[(size_t)pn];
+        }
+        h.swapLockdown = e->sc_host[0].swapLockdown;
+        h.totalRate = rep_total_rate[0];
+        h.totalMigrationRate = rep_total_mig[0];
         return VGX_OK;
     }
 
@@ -375,8 +486,13 @@ struct __attribute__((visibility("hidden"))) TauRun {
         for (int64_t pn = 0; pn < P; pn++) lock32[(size_t)pn] = (int32_t)h.lockdownON[(size_t)pn];
         for (int64_t r = 0; r < R; r++) {
             if (!staged) TAU_TRY(tau_upload_state(e, r, h.infectious, h.susceptible));
+            if (sets) continue;
             HIPCHECK(e, hipMemcpy((double *)e->t_cd.p + r * P, h.contactDensity.data(), (size_t)P * 8, hipMemcpyHostToDevice));
             HIPCHECK(e, hipMemcpy((int32_t *)e->t_lock.p + r * P, lock32.data(), (size_t)P * 4, hipMemcpyHostToDevice));
+        }
+        if (sets) {    // every replicate's own, as its set's preparation left them
+            HIPCHECK(e, hipMemcpy(e->t_cd.p, rep_cd.data(), (size_t)(R * P) * 8, hipMemcpyHostToDevice));
+            HIPCHECK(e, hipMemcpy(e->t_lock.p, rep_lock.data(), (size_t)(R * P) * 4, hipMemcpyHostToDevice));
         }
         lap("memsets + state upload");
         return VGX_OK;
@@ -559,7 +675,8 @@ struct __attribute__((visibility("hidden"))) TauRun {
     // Small models: the whole step loop on the device, one workgroup per replicate (vgx_taus.hip).  VGX_TAU_STEP_KERNELS=1 and the
     // test switches of the step kernels (dense validation modes, the large-model draw thresholds) keep the step kernels.
     bool choose_device_loop() {
-        slog_cap = std::max<int64_t>(ev_size - ((ev_ptr_start <= 100 && iterations > 100) ? 0 : ev_ptr_start), 1);
+        slog_cap = step_log_rows();
+        if (sets) return true;      // (check_sets has refused what the loop cannot run)
         // One workgroup (one CU) runs a replicate's whole loop: that wins where a step is launch-bound (up to ~2000 compartments at any
         // ensemble size) or where there are replicates to fill the chip with; few replicates of a larger model are faster spread over the
         // chip by the step kernels.  Measured in round 4 (tools/probe_tau_single.py, steps/s of ONE trajectory, step kernels / loop):
@@ -601,8 +718,27 @@ struct __attribute__((visibility("hidden"))) TauRun {
         ta.loc_rec = a.loc_rec; ta.loc_time = a.loc_time; ta.loc_n = a.loc_n;
         ta.res = (int64_t *)e->t_sres.p;
         ta.traj = a.traj; ta.traj_points = a.traj_points; ta.traj_t0 = a.traj_t0; ta.traj_dt = a.traj_dt;
+        VgxTausSetsArgs sa{};
+        if (sets) {    // what the one-set kernels read as one value of `ta`, per set
+            std::vector<VgxTausSetRec> recs((size_t)e->n_sets, VgxTausSetRec{});
+            for (int64_t g = 0; g < e->n_sets; g++) {
+                VgxTausSetRec &q = recs[(size_t)g];
+                const TauSetTables &t = e->h_sets[(size_t)g];
+                q.start_ok = set_start_ok[(size_t)g]; q.rates_nonzero_initial = set_rates_nonzero_initial[(size_t)g];
+                q.mut_uniform = (t.mut_uniform && sites_ok16(e)) ? 1 : 0;
+                memcpy(q.mutp, t.mutp, sizeof(q.mutp));
+                for (int i = 0; i < 8; i++) q.base_cnt[i] = base_cnt[(size_t)i];
+                q.base_cnt[6] = set_swaps[(size_t)g];
+            }
+            TAU_TRY(upload(e, e->ps_taurec, recs.data(), recs.size()));
+            HIPCHECK(e, hipStreamSynchronize(e->stream));    // (recs goes out of scope)
+            sa.a = ta;
+            sa.psets = (const VgxDevParams *)e->ps_blocks.p; sa.set_of = (const int32_t *)e->ps_setof.p;
+            sa.recs = (const VgxTausSetRec *)e->ps_taurec.p;
+        }
         HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
-        HIPCHECK(e, vgxi_launch_taus(&ta, e->stream));
+        if (sets) HIPCHECK(e, vgxi_launch_taus_sets(&sa, e->max_C(), e->max_CB(), e->stream));
+        else HIPCHECK(e, vgxi_launch_taus(&ta, e->stream));
         HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
         HIPCHECK(e, hipStreamSynchronize(e->stream));
         HIPCHECK(e, hipEventElapsedTime(&ms_total, e->ev0, e->ev1));
@@ -1050,6 +1186,7 @@ struct __attribute__((visibility("hidden"))) TauRun {
             const std::vector<int64_t> &c0 = cnt0[(size_t)r];
             const int64_t *c = &cnt[(size_t)r * 8];
             s.currentTime = tnow[(size_t)r]; s.totalRate = h.totalRate; s.totalMig = h.totalMigrationRate;
+            if (sets) { s.totalRate = rep_total_rate[(size_t)r]; s.totalMig = rep_total_mig[(size_t)r]; }
             s.tau_l = tau_h.empty() ? h.tau_l : tau_h[(size_t)r];
             s.globalInfectious = gI[(size_t)r];
             s.bCounter = c0[0] + c[0]; s.dCounter = c0[1] + c[1]; s.sCounter = c0[2] + c[2]; s.mCounter = c0[3] + c[3];
@@ -1085,11 +1222,17 @@ extern "C" int vgx_simulate_tau(vgx_engine *e, int64_t iterations, int64_t sampl
     if (!e) return VGX_ERR_ARG;
     e->traj_points = 0;    // (until this call has written its own: vgx_get_trajectories never returns the bins of an earlier call)
     if (!e->have_params || !e->have_state) return fail(e, VGX_ERR_ARG, "vgx_simulate_tau: set params and state first");
-    if (e->n_sets > 1) return fail(e, VGX_ERR_ARG, "vgx_simulate_tau: several parameter sets are installed (vgx_set_param_sets): tau-leaping runs one set only");
     HIPCHECK(e, hipSetDevice(e->device));
     TauRun run{e, e->hs, e->d.hapNum, e->d.popNum, e->d.susNum, e->R, iterations, sample_size, attempts, time, !(time == -1.0f), e->hs.ev_ptr, e->hs.ev_size};
     run.o.record_events = 1;
     if (opts) run.o = *opts;
+    if (run.sets) {
+        // (a call that does not ask for the sets is refused as it was before they could run: nothing a caller relied on changes)
+        if (run.o.reserved[0] != 2)
+            return fail(e, VGX_ERR_ARG, "vgx_simulate_tau: several parameter sets are installed (vgx_set_param_sets): tau-leaping runs one set only "
+                                        "unless vgx_run_opts.reserved[0] = 2 asks for one set per replicate on the on-device step loop");
+        TAU_TRY(run.check_sets());
+    }
     TAU_TRY(run.prepare_start());
     TAU_TRY(run.alloc_workspace());
     TAU_TRY(run.fill_args());

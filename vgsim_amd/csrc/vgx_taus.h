@@ -46,6 +46,23 @@ struct VgxTausArgs {
     double traj_t0, traj_dt;
 };
 
+// Scenario ensembles (vgx_set_param_sets): what a replicate takes from its own set where the one-set kernels read one value from
+// VgxTausArgs.  The fields carry the names they have there: the body reads them through one reference, whichever the kernel.
+struct VgxTausSetRec {
+    int32_t start_ok, rates_nonzero_initial, mut_uniform, pad_;
+    int64_t base_cnt[8];              // ([6], swapLockdown: the preparation's lockdown check runs under the set's own thresholds)
+    double mutp[16][3];
+};
+
+// The scenario entry points of vgx_taus.hip: replicate r runs under psets[set_of[r]] instead of a.p, with recs[set_of[r]].  A wrapper, so
+// that VgxTausArgs, the kernarg block of the one-set kernels, keeps its layout (a is its first member: the body reads it at the same place).
+struct VgxTausSetsArgs {
+    VgxTausArgs a;
+    const VgxDevParams *psets;        // [n_sets] device
+    const int32_t *set_of;            // [R] device, values in [0, n_sets)
+    const VgxTausSetRec *recs;        // [n_sets] device
+};
+
 enum { TS_TAU = 0, TS_GI, TS_CNT0, TS_EVPTR = 10, TS_ATT, TS_GOOD, TS_RESTARTS, TS_STEPS, TS_MEVROWS, TS_ERROR, TS_TIME, TS_EVPTR0, TS_TRIES };
 
 #define VGX_TAUS_MAX_C 256

@@ -58,10 +58,31 @@ static __device__ __forceinline__ double taus_traj_grid(double t0, double dt, in
 // (the arguments are read through the kernarg segment pointer, as in vgx_solo.hip / vgx_quadg.hip: by-value parameters referenced all over
 // the loop were held in scalar registers for the whole kernel, 330 of them spilled)
 typedef const VgxTausArgs __attribute__((address_space(4))) *TausKA;
-template <int TT>
+// SETS (scenario ensembles): the replicate's parameters are block set_of[replicate] of psets instead of a.p, and what the preparation
+// found under that set (VgxTausSetRec) stands where the one-set kernels read one value from the arguments.  Both are read in place
+// through the constant address space, as the kernel arguments are (nothing writes them while the kernel runs): one address per
+// workgroup, so scalar loads, and no copy of the block to hold in registers.  The body's statements are the same for both forms:
+// `p` and `q` are references of one type each, bound to what these two return.  (Pointers, not references: a reference returned
+// by a function tells the compiler that the whole object may be loaded ahead of a branch, and the one-set kernels' code moved.)
+typedef const VgxTausSetsArgs __attribute__((address_space(4))) *TausSetsKA;
+template <bool SETS>
+static __device__ __forceinline__ auto taus_params(TausKA a, int set) {
+    if constexpr (SETS) return (const VgxDevParams __attribute__((address_space(4))) *)(((TausSetsKA)a)->psets + set);
+    else return &a->p;
+}
+template <bool SETS>
+static __device__ __forceinline__ auto taus_per_set(TausKA a, int set) {
+    if constexpr (SETS) return (const VgxTausSetRec __attribute__((address_space(4))) *)(((TausSetsKA)a)->recs + set);
+    else return a;
+}
+template <int TT, bool SETS = false>
 static __device__ __forceinline__ void taus_body() {
     const auto &a = *(TausKA)__builtin_amdgcn_kernarg_segment_ptr();
-    const auto &p = a.p;
+    int set = 0;
+    if constexpr (SETS)    // (one value per workgroup, read by a scalar load)
+        set = __builtin_amdgcn_readfirstlane(((const int32_t __attribute__((address_space(4))) *)((TausSetsKA)&a)->set_of)[blockIdx.x]);
+    const auto &p = *taus_params<SETS>(&a, set);
+    const auto &q = *taus_per_set<SETS>(&a, set);     // start_ok, rates_nonzero_initial, mut_uniform, mutp, base_cnt
     const int rep = blockIdx.x;
     const int P = p.P, H = p.H, S = p.S, sites = p.sites, PH = P * H;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -101,7 +122,7 @@ static __device__ __forceinline__ void taus_body() {
     for (int i = tid; i < CB; i += TT) l_cbb[i] = p.cb_b[i];
     for (int i = tid; i < CB * S; i += TT) l_sig[i] = p.cb_sigma[i];
     for (int i = tid; i < H; i += TT) l_cls[i] = p.cls[i];
-    if (tid < 48) l_mutp[tid] = a.mutp[tid / 3][tid % 3];
+    if (tid < 48) l_mutp[tid] = q.mutp[tid / 3][tid % 3];
     if (tid == 0) { s_dirty = 1; s_flips = 0; s_fail = 0; s_tau = (unsigned long long)__double_as_longlong(1.0); }
     __syncthreads();
 
@@ -109,7 +130,7 @@ static __device__ __forceinline__ void taus_body() {
     double tnow = a.t0, tau_l = 0.0;
     long long gI = a.gI0, ev_ptr = a.ev_ptr0, good = a.good0, restarts = 0, steps = 0, mev_base = 0, tries_total = 0;
     long long cnt[8];
-    for (int i = 0; i < 8; ++i) cnt[i] = a.base_cnt[i];
+    for (int i = 0; i < 8; ++i) cnt[i] = q.base_cnt[i];
     int att = 0, err = 0;
     uint32_t step = 0;
     long long ev_ptr_start = a.ev_ptr0;
@@ -117,7 +138,7 @@ static __device__ __forceinline__ void taus_body() {
     const uint64_t seed = (uint64_t)a.seeds[rep];
     int64_t *slog = a.slog + (int64_t)rep * a.slog_cap * 3;
     int64_t *mev = a.mev + (int64_t)rep * (a.mev_cap > 0 ? a.mev_cap : 0) * 6;
-    bool running = a.attempts > 0 && a.start_ok;
+    bool running = a.attempts > 0 && q.start_ok;
     bool fresh = true, finished = a.attempts <= 0;
     int64_t guard = 0;
     // summary trajectories (as vgx_direct.hip's traj_emit): every grid point not yet written that lies before t_new gets the totals
@@ -203,7 +224,7 @@ static __device__ __forceinline__ void taus_body() {
                 tnow = 0.0; ev_ptr = 0; ev_ptr_start = 0; mev_base = 0; steps = 0;
                 traj_next = 0;      // (the bins describe the final attempt, as its log does)
                 att += 1;
-                if (att < a.attempts && err == 0) { running = g0 != 0 && a.rates_nonzero_initial; fresh = true; }
+                if (att < a.attempts && err == 0) { running = g0 != 0 && q.rates_nonzero_initial; fresh = true; }
                 else finished = true;
             } else {
                 good = att + 1;
@@ -258,7 +279,7 @@ static __device__ __forceinline__ void taus_body() {
                         if (In == 0) continue;
                         const int al = AS ^ x, i = AS - (AS > al ? 1 : 0);
                         double r;
-                        if (a.mut_uniform) r = l_mutp[s * 3 + i];
+                        if (q.mut_uniform) r = l_mutp[s * 3 + i];
                         else {
                             const double *hm = p.hapMutType + ((int64_t)nb * sites + s) * 3;
                             r = p.mRate[(int64_t)nb * sites + s] * hm[i] / (hm[0] + hm[1] + hm[2]);
@@ -369,7 +390,7 @@ static __device__ __forceinline__ void taus_body() {
                         } else if (ch < 2 + 3 * sites) {   // mutation (pyx:2497-2504): x0 = the mutant's haplotype
                             const int s2 = (ch - 2) / 3, i = (ch - 2) - 3 * s2;
                             double r;
-                            if (a.mut_uniform) r = l_mutp[s2 * 3 + i];
+                            if (q.mut_uniform) r = l_mutp[s2 * 3 + i];
                             else {
                                 const double *hm = p.hapMutType + ((int64_t)hn * sites + s2) * 3;
                                 r = p.mRate[(int64_t)hn * sites + s2] * hm[i] / (hm[0] + hm[1] + hm[2]);
@@ -557,8 +578,13 @@ extern "C" __global__ void __launch_bounds__(64) vgx_taus_kernel_t64(VgxTausArgs
 extern "C" __global__ void __launch_bounds__(256) vgx_taus_kernel_t256(VgxTausArgs) { taus_body<256>(); }
 extern "C" __global__ void __launch_bounds__(512) vgx_taus_kernel(VgxTausArgs) { taus_body<512>(); }
 
-extern "C" __attribute__((visibility("hidden"))) hipError_t vgxi_launch_taus(const VgxTausArgs *a, hipStream_t s) {
-    const size_t lds = vgx_taus_lds_bytes(a->p.P, a->p.H, a->p.S, a->p.C, a->p.CB);
+// the scenario forms: replicate r runs under psets[set_of[r]] with recs[set_of[r]]
+extern "C" __global__ void __launch_bounds__(64) vgx_taus_sets_kernel_t64(VgxTausSetsArgs) { taus_body<64, true>(); }
+extern "C" __global__ void __launch_bounds__(256) vgx_taus_sets_kernel_t256(VgxTausSetsArgs) { taus_body<256, true>(); }
+extern "C" __global__ void __launch_bounds__(512) vgx_taus_sets_kernel(VgxTausSetsArgs) { taus_body<512, true>(); }
+
+// The threads of a workgroup for R replicates of `lds` bytes each
+static int taus_threads(int64_t R, size_t lds) {
     // the workgroup size: see taus_body (VGX_TAUS_THREADS = 64 / 256 / 512 forces one, for comparisons)
     // (tools/probe_taus_threads.py, 16 x 3 / 64 x 4 / 256 x 5 models at 64 ... 4096 replicates: 512 threads lead below two workgroups per CU,
     // 256 from two to eight, 64 from eight on — whatever the model's size)
@@ -571,12 +597,32 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t vgxi_launch_taus(con
     }
     // workgroups a CU will hold at once: what the launch offers, and what fits its LDS (a model of 8192 compartments fills it alone)
     const int64_t fit = std::max<int64_t>(1, (int64_t)(160 * 1024) / (int64_t)std::max<size_t>(lds, 1));
-    const int64_t per_cu = std::min<int64_t>(std::max<int64_t>(a->R / cus, 1), fit);
+    const int64_t per_cu = std::min<int64_t>(std::max<int64_t>(R / cus, 1), fit);
     int tt = per_cu >= 8 ? 64 : per_cu >= 2 ? 256 : 512;
     if (const char *ft = getenv("VGX_TAUS_THREADS")) { const int v = atoi(ft); if (v == 64 || v == 256 || v == 512) tt = v; }
+    return tt;
+}
+
+extern "C" __attribute__((visibility("hidden"))) hipError_t vgxi_launch_taus(const VgxTausArgs *a, hipStream_t s) {
+    const size_t lds = vgx_taus_lds_bytes(a->p.P, a->p.H, a->p.S, a->p.C, a->p.CB);
+    const int tt = taus_threads(a->R, lds);
     void (*k)(VgxTausArgs) = tt == 64 ? vgx_taus_kernel_t64 : tt == 256 ? vgx_taus_kernel_t256 : vgx_taus_kernel;
     hipError_t err = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (err != hipSuccess) return err;
     hipLaunchKernelGGL(k, dim3((unsigned)a->R), dim3((unsigned)tt), lds, s, *a);
+    return hipGetLastError();
+}
+
+// The scenario form: the LDS of a workgroup is sized for the largest set (max_C rate classes, max_CB birth classes), and every workgroup
+// lays its tables out by its own set's counts; the workgroup size follows the same rule
+extern "C" __attribute__((visibility("hidden"))) hipError_t vgxi_launch_taus_sets(const VgxTausSetsArgs *sa, int max_C, int max_CB, hipStream_t s) {
+    if (!sa->psets || !sa->set_of || !sa->recs) return hipErrorInvalidValue;
+    const VgxTausArgs *a = &sa->a;
+    const size_t lds = vgx_taus_lds_bytes(a->p.P, a->p.H, a->p.S, max_C, max_CB);
+    const int tt = taus_threads(a->R, lds);
+    void (*k)(VgxTausSetsArgs) = tt == 64 ? vgx_taus_sets_kernel_t64 : tt == 256 ? vgx_taus_sets_kernel_t256 : vgx_taus_sets_kernel;
+    hipError_t err = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL(k, dim3((unsigned)a->R), dim3((unsigned)tt), lds, s, *sa);
     return hipGetLastError();
 }

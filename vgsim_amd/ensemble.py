@@ -420,9 +420,10 @@ class Ensemble:
         under ``scenarios[scenario_of[r]]`` (default ``arange(R) % len(scenarios)``) and is, bit for bit, the run of a single
         ``Simulator`` with that scenario's parameters, this start state and seed ``seeds[r]``; one launch runs all of them.
         Limits: the exact direct path on the one-replicate-per-wavefront kernel (``mode='exact'``, ``kernel`` 'auto' or 'wave');
-        no ``simulate_tau``; population sizes and recombination settings equal in all scenarios.  The contact densities a
-        replicate starts with are its own scenario's (``set_contact_density``, ``set_npi``) for the lockdown state of the start
-        state; a scenario whose model holds another value is refused by ``simulate``."""
+        ``simulate_tau(..., per_scenario=True)`` on the on-device step loop (models of up to 8192 compartments); population sizes and recombination
+        settings equal in all scenarios.  The contact densities a replicate starts with are its own scenario's
+        (``set_contact_density``, ``set_npi``) for the lockdown state of the start state; a scenario whose model holds another
+        value is refused by ``simulate`` and ``simulate_tau``."""
         self.model = getattr(simulator, "simulation", simulator)
         m = self.model
         self.R = int(n_replicates)
@@ -442,6 +443,30 @@ class Ensemble:
 
     def close(self):
         self.engine.close()
+
+    def _check_scenario_contact_densities(self):
+        """Every replicate of a scenario ensemble starts with its own scenario's contact densities for the lockdown state of the
+        start state (the engine takes them from the set's parameters): a scenario whose model holds anything else would not be
+        what runs, and is refused."""
+        m = self.model
+        for g, s in enumerate(self.scenarios):
+            cd = np.where(np.asarray(m.lockdownON) != 0, s.contactDensityAfterLockdown, s.contactDensityBeforeLockdown)
+            bad = np.nonzero(np.asarray(s.contactDensity, dtype=np.float64) != cd)[0]
+            if len(bad):
+                raise ValueError("scenario %d: the contact density of population %d is %r, its own settings give %r for the lockdown "
+                                 "state of the start state" % (g, bad[0], float(s.contactDensity[bad[0]]), float(cd[bad[0]])))
+
+    def _set_parameters(self):
+        """The parameters of the next simulate call into the engine: the model's, or (after the check above) every scenario's."""
+        if self.scenarios is None:
+            self.engine.set_params(self.model)
+            return
+        self._check_scenario_contact_densities()
+        self.engine.set_param_sets(self.scenarios, self.scenario_of)
+
+    def _scenario_groups(self):
+        """(scenario_of, number of scenarios) as the summaries' ``by='auto'`` takes them: (None, 1) without scenarios."""
+        return self.scenario_of, (len(self.scenarios) if self.scenarios is not None else 1)
 
     def simulate(self, iterations, sample_size=None, epidemic_time=-1, attempts=200, record_events=False,
                  traj_points=0, traj_window=(0.0, 1.0), seeds=None, mode='exact', kernel='auto'):
@@ -465,18 +490,7 @@ class Ensemble:
         # Events.CreateEvents bookkeeping on a scratch copy of the counters (the host model keeps its own log)
         ptr, size = m.events.ptr, m.events.size
         size = size + iterations if ptr == 0 else max(size, ptr + iterations)
-        if self.scenarios is not None:
-            # every replicate starts with its own scenario's contact densities for the lockdown state of the start state (the engine
-            # takes them from the set's parameters): a scenario whose model holds anything else would not be what runs
-            for g, s in enumerate(self.scenarios):
-                cd = np.where(np.asarray(m.lockdownON) != 0, s.contactDensityAfterLockdown, s.contactDensityBeforeLockdown)
-                bad = np.nonzero(np.asarray(s.contactDensity, dtype=np.float64) != cd)[0]
-                if len(bad):
-                    raise ValueError("scenario %d: the contact density of population %d is %r, its own settings give %r for the lockdown "
-                                     "state of the start state" % (g, bad[0], float(s.contactDensity[bad[0]]), float(cd[bad[0]])))
-            eng.set_param_sets(self.scenarios, self.scenario_of)
-        else:
-            eng.set_params(m)
+        self._set_parameters()
         saved = (m.events.ptr, m.events.size)
         m.events.size = size
         try:
@@ -503,14 +517,23 @@ class Ensemble:
         return res
 
     def simulate_tau(self, iterations, sample_size=None, epidemic_time=-1, attempts=200, record_events=False, seeds=None,
-                     traj_points=0, traj_window=(0.0, 1.0)):
+                     traj_points=0, traj_window=(0.0, 1.0), per_scenario=False):
         """Poisson tau-leaping for every replicate from the model's current state (``SimulatePopulation_tau``
         semantics per replicate, pyx:2293-2346).  ``EnsembleResult.events`` counts MULTITYPE records (steps);
         ``events_drawn`` the sum of the drawn channel multiplicities.  ``traj_points`` / ``traj_window``: summary
         trajectories as ``simulate`` bins them (a grid point gets the totals before the step that takes the time past it),
-        with or without the event log; read with ``trajectories()`` / ``gather_trajectories()``."""
-        if self.scenarios is not None:
-            raise ValueError("a scenario ensemble has no simulate_tau: tau-leaping runs one parameter set only")
+        with or without the event log; read with ``trajectories()`` / ``gather_trajectories()``.
+
+        ``per_scenario=True`` (scenario ensembles; without it they refuse the call, as they did before they could run it):
+        replicate r runs under ``scenarios[scenario_of[r]]`` and is, bit for bit, replicate k of a one-set ``Ensemble`` built on
+        that scenario (holding this start state) whose seed k is ``seeds[r]``: one launch of the on-device step loop runs all
+        scenarios.  The library refuses the call where that loop does not run (more than 8192 compartments,
+        ``VGX_TAU_STEP_KERNELS=1``)."""
+        if self.scenarios is not None and not per_scenario:
+            raise ValueError("simulate_tau on a scenario ensemble runs when it is asked to: pass per_scenario=True (every replicate "
+                             "under its own scenario, one launch of the on-device step loop)")
+        if per_scenario and self.scenarios is None:
+            raise ValueError("per_scenario=True needs a scenario ensemble (Ensemble(..., scenarios=[...]))")
         m, eng = self.model, self.engine
         if seeds is not None:
             self.seeds = np.ascontiguousarray(seeds, dtype=np.int64)
@@ -521,7 +544,7 @@ class Ensemble:
         ptr, size = m.events.ptr, m.events.size
         for _ in range(2):  # CreateEvents is called twice on the tau path (pyx:2298 -> pyx:434, pyx:2306)
             size = size + iterations if ptr == 0 else max(size, ptr + iterations)
-        eng.set_params(m)
+        self._set_parameters()
         saved = (m.events.ptr, m.events.size)
         m.events.size = size
         try:
@@ -541,6 +564,8 @@ class Ensemble:
         o.record_events = 1 if record_events else 0
         o.traj_points = int(traj_points)
         o.traj_t0, o.traj_t1 = float(traj_window[0]), float(traj_window[1])
+        if self.scenarios is not None and len(self.scenarios) > 1:
+            o.reserved[0] = 2     # the installed sets are meant: one per replicate
         rc = eng.lib.vgx_simulate_tau(eng.handle, int(iterations), int(sample_size), float(np.float32(epidemic_time)),
                                       int(attempts), C.byref(o))
         self._last_call = None
@@ -1016,7 +1041,7 @@ class Ensemble:
         of a step carry the time of the step's MULTITYPE record, which is where the reference's own replays place them, so a
         step falls into one bin whole.  The shared part is counted once per call on the device, not once per replicate; no
         host clock runs.  ``summary``: refused by the library when a count reaches 2^31 (``counts`` stays available: call
-        again without ``summary``).  ``by='auto'`` is one group (scenario ensembles have no ``simulate_tau``)."""
+        again without ``summary``).  ``by='auto'``: one group per scenario of a scenario ensemble."""
         e = _incidence_edges(edges, bins, window)
         if self._last_call is None:
             raise ValueError("tau_incidence() needs a simulate_tau(record_events=True) call first")
@@ -1025,7 +1050,7 @@ class Ensemble:
         if not self._last_call[1]:
             raise ValueError("tau_incidence() needs the multievent rows: the last call had record_events=False")
         io = _capi.VgxTauIncidenceIO()
-        finish = self._incidence_request(io, e, replicates, haplotypes, summary, counts, np.int64, None, 1)
+        finish = self._incidence_request(io, e, replicates, haplotypes, summary, counts, np.int64, *self._scenario_groups())
         eng, pre = self.engine, self._tau_prefix_struct()
         return finish(lambda: eng._check(eng.lib.vgx_get_tau_incidence(eng.handle, C.byref(io), C.byref(pre))))
 
@@ -1094,7 +1119,7 @@ class Ensemble:
         of a step fall into the bin of the step's MULTITYPE record.  The shared part is counted once per call on the device; no
         host clock runs.  With ``haplotypes`` = the members of class c, ``tau_incidence()``'s channels are this block's margins.
         ``summary``: refused by the library when a count reaches 2^31 (``counts`` stays available: call again without
-        ``summary``).  ``by='auto'`` is one group (scenario ensembles have no ``simulate_tau``)."""
+        ``summary``).  ``by='auto'``: one group per scenario of a scenario ensemble."""
         e = _incidence_edges(edges, bins, window)
         if self._last_call is None:
             raise ValueError("tau_flows() needs a simulate_tau(record_events=True) call first")
@@ -1108,7 +1133,7 @@ class Ensemble:
         vo, V = _capi.variant_map(variants, m.hapNum)
         T, P = len(e) - 1, m.popNum
         _capi.tau_flows_lds_check(P, V)
-        sio, done = self._block_summary(summary, reps, (T, P, P, V), None, 1)
+        sio, done = self._block_summary(summary, reps, (T, P, P, V), *self._scenario_groups())
         if summary is None and not counts:
             raise ValueError("counts=False needs summary=: the call would return nothing")
         block = np.zeros((n, T, P, P, V), dtype=np.int64) if counts else None
@@ -1268,7 +1293,7 @@ class Ensemble:
         eng._check(eng.lib.vgx_get_tau_milestones(eng.handle, C.byref(io), C.byref(pre)))
         ms.reached = ms.first_event != Milestones.NEVER
         ms.thresholds, ms.variant_of, ms.replicates = th, vo, reps
-        ms._R, ms._scenario_of, ms._n_scenarios = self.R, None, 1
+        ms._R, (ms._scenario_of, ms._n_scenarios) = self.R, self._scenario_groups()
         ms.passes, ms.kernel_ms, ms.clock_ms, ms.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
         return ms
 
@@ -1347,7 +1372,7 @@ class Ensemble:
         if not self._last_call[1]:
             raise ValueError("tau_susceptibles() needs the multievent rows: the last call had record_events=False")
         reps, n, co, G, T, P, sio, done = self._class_block_request(g, _capi.group_map, groups, self.model.susNum, replicates, summary, values, 8,
-                                                                    None, 1)
+                                                                    *self._scenario_groups())
         block = np.zeros((n, T, P, G), dtype=np.int64) if values else None
         final = np.zeros((n, P, G), dtype=np.int64)
         outside = np.zeros((max(n, 1), 2), dtype=np.int64)
@@ -1374,8 +1399,8 @@ class Ensemble:
         values start from the model's initial state when the chain starts at the beginning of the model's history (the model held
         events before the call, or the replicate restarted), else from the state the call started from.  The shared part is
         counted once per call on the device, not once per replicate; no host clock runs.  ``summary``: refused by the library
-        when a value is negative or reaches 2^31 (``values`` stays available: call again without ``summary``).  ``by='auto'`` is
-        one group (scenario ensembles have no ``simulate_tau``)."""
+        when a value is negative or reaches 2^31 (``values`` stays available: call again without ``summary``).  ``by='auto'``:
+        one group per scenario of a scenario ensemble."""
         g = _prevalence_grid(times, points, window)
         if self._last_call is None:
             raise ValueError("tau_prevalence() needs a simulate_tau(record_events=True) call first")
@@ -1383,7 +1408,7 @@ class Ensemble:
             raise ValueError("tau_prevalence() counts tau chains only: the last call was a direct simulate()")
         if not self._last_call[1]:
             raise ValueError("tau_prevalence() needs the multievent rows: the last call had record_events=False")
-        reps, n, vo, V, T, P, sio, done = self._prevalence_request(g, variants, replicates, summary, values, 8, None, 1)
+        reps, n, vo, V, T, P, sio, done = self._prevalence_request(g, variants, replicates, summary, values, 8, *self._scenario_groups())
         block = np.zeros((n, T, P, V), dtype=np.int64) if values else None
         final = np.zeros((n, P, V), dtype=np.int64)
         outside = np.zeros((max(n, 1), 2), dtype=np.int64)
