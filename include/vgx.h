@@ -163,8 +163,8 @@ typedef struct vgx_counters {
     int64_t error;                 /* VGX_* code raised inside the kernel for this replicate */
     int64_t multievent_rows;       /* tau: rows appended to the multievent log by this call */
     int64_t reserved[5];           /* [0] tau: events drawn; direct: [1] index of the last attempt that drew random
-                                      numbers (-1 none), [2] its loop iterations (2 uniforms each); [3] tau: tries of the
-                                      halving loop left out as certain rejections */
+                                      numbers (-1 none), [2] its loop iterations (2 uniforms each), [4] sCounter (the
+                                      cases sampled); [3] tau: tries of the halving loop left out as certain rejections */
 } vgx_counters;
 
 /* ---- lifecycle ------------------------------------------------------------------------------ */
@@ -694,6 +694,69 @@ int vgx_test_prevalence(const double *times, const int64_t *types, const int64_t
                         const int64_t *newHaplotypes, const int64_t *newPopulations, int64_t n_ev, int64_t P, int64_t hapNum,
                         const double *grid, int64_t T, const int32_t *variant_of, int64_t V, const int64_t *start, int64_t tile,
                         int32_t *values, int32_t *final, int64_t *outside, char *errbuf, int64_t errcap);
+
+/* ---- lineages: ancestral lineages of the sample per population and variant class on a common grid --- */
+/* The tree's counterpart of vgx_get_prevalence: how many ancestral lineages of the sampled cases are alive at each
+ * grid time, in which population, carrying which variant, for many replicates of the last vgx_simulate_direct call at once.  It
+ * cannot be rebuilt from what vgx_get_genealogies returns (a migration that moves a lineage without coalescing writes no record at
+ * its own event, and the haplotype a lineage carries between nodes appears nowhere), so it comes out of the walk itself.
+ * The walk is that of vgx_get_genealogies: the same draws in the same order from rng_state, the same status and the same
+ * generator state afterwards (rng_out).  Whenever it changes a lineage list it appends one lineage record of six int32 words,
+ * kind, hap, pop, newHap, newPop, ev (the event index), to a per-replicate log on the device.  Read forward in time, with
+ * c(h) = variant_of[h] and a side of class -1 skipped, a record changes
+ *   TIP       a SAMPLING pushes a lineage                                -1 at (pop, c(hap))
+ *   SPLIT     a BIRTH coalesces                                          +1 at (pop, c(hap))
+ *   SPLIT     a MIGRATION coalesces, pop = the event's newPopulation     +1 at (pop, c(hap))
+ *   MUTATION  a MUTATION takes a lineage                                 -1 at (pop, c(hap)), +1 at (pop, c(newHap)); equal classes change nothing
+ *   MOVE      a MIGRATION moves a lineage without coalescing             -1 at (pop, c(hap)), +1 at (newPop, c(hap))
+ * (the migration records vgx_get_genealogies' closing pass adds are no lineage records).  A replicate's log holds at most
+ * (2 sCounter - 1) + its MUTATION events + its MIGRATION events records, counted on the device; a full log sets status 9 and is
+ * never written past its end.
+ * The grid is vgx_get_prevalence's: grid[0 .. T-1] strictly increasing and finite, cut[j] = first event index i with
+ * grid[j] < t_i (strict; the position never goes back), from the host clock; a record with event index ev lies in interval k =
+ * 0 .. T when cut[k-1] <= ev < cut[k] (cut[-1] = 0, cut[T] = n_ev).  No lineage is alive after the last event, so
+ *   values[r][j][p][c] = -(net change of the intervals j+1 .. T),   root[r][p][c] = -(net change of all intervals)
+ * or values[j] = root + net of the intervals 0 .. j: prevalence's formula with `root` as the start.  With every haplotype tracked
+ * root sums to 1 for a walk that succeeded.  A replicate whose walk fails gets its status (vgx_genealogy_message gives the text)
+ * and zeros; it does not fail the call.
+ * On the device a pass is three kernels on the engine's stream: the walk (one replicate per wavefront), a binning kernel in
+ * vgx_get_prevalence's geometry over the lineage logs (a workgroup takes one replicate and a tile of VGX_LINEAGES_TILE_RECORDS
+ * consecutive records, default 4096, and keeps popNum * V int32 cells in LDS) and a suffix-sum kernel that turns the net block
+ * into values and root in place.  All work after the cuts is integer work: no result depends on the tile size, the launch
+ * geometry or the number of passes.  Replicates whose workspace exceeds half of the free device memory (or
+ * VGX_GENEALOGY_CHUNK_BYTES) are walked in several passes.  `summary`, when given, is the column summary of
+ * vgx_get_trajectory_summary over `values` as a matrix [n][T * popNum * V] where it lies (group_of has n entries, one per
+ * SELECTED replicate); if a replicate with group_of >= 0 has a nonzero status the summary is refused with their number in the
+ * message, after values, root, status, status_arg, records and rng_out have been written.  `values` may be NULL: the block is
+ * then not copied to the host.
+ * Preconditions as vgx_get_genealogies: the last call was direct and recorded events; every selected chain starts at log index 0.
+ * Refusals (VGX_ERR_ARG, worded alike behind "vgx_get_lineages: "): those; replicates out of range or given twice; a grid that is
+ * not finite or does not increase; T outside [1, 2^24); V < 1 or a variant_of value outside [-1, V); popNum * V * 4 bytes of cells
+ * above the 65536 bytes of LDS a binning workgroup may use; a block (4 n (T + 1) popNum V bytes) above half of the free device
+ * memory; a chain of 2^30 events or more.  vgx_clock_mismatches counts every selected replicate once. */
+typedef struct vgx_lineages_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    const uint64_t *rng_state;                   /* [n][4] PCG64 start of every walk: state hi, lo, increment hi, lo */
+    int64_t T; const double *grid;               /* [T] strictly increasing, finite */
+    int64_t V; const int32_t *variant_of;        /* [hapNum], values in [-1, V) */
+    int32_t *values;                             /* NULL or host [n][T][P][V] */
+    int32_t *root;                               /* host [n][P][V] */
+    int64_t *status, *status_arg;                /* [n] 0 or why the walk stopped, as vgx_genealogies_io */
+    int64_t *records;                            /* [n] lineage records of the walk (0 for a walk that failed) */
+    uint64_t *rng_out;                           /* [n][4] generator state after the walk */
+    vgx_traj_summary_io *summary;                /* NULL or the summary of [n][T*P*V]; group_of has n entries */
+    int64_t passes;                              /* out: walk passes */
+    double ms[3];                                /* out: kernels (device time), host clock, whole call */
+    double kernel_ms[3];                         /* out: the walk, binning and suffix-sum kernels of ms[0] apart */
+} vgx_lineages_io;
+int vgx_get_lineages(vgx_engine *e, vgx_lineages_io *io);
+/* Test hook: the walk of vgx_get_lineages with its observer, the tile walk and the suffix sum compiled for the host, on the chain,
+ * state and generator of a vgx_genealogy_io (its tree, mutation and migration outputs are not read or written; infectious is walked
+ * back in place and rng_state advanced as vgx_test_genealogy_walk does), tile after tile of `tile` records (0: the default).
+ * values [T][P][V] and root [P][V] are overwritten, *records gets the number of lineage records.  A walk that fails is refused with
+ * the message vgx_get_genealogy reports; a bad grid, V or variant_of and the LDS budget are refused as vgx_get_lineages does. */
+int vgx_test_lineages(vgx_genealogy_io *io, const double *grid, int64_t T, const int32_t *variant_of, int64_t V, int64_t tile,
+                      int32_t *values, int32_t *root, int64_t *records, char *errbuf, int64_t errcap);
 
 /* The same counts for many replicates of the last vgx_simulate_tau call (with the event log), on the device.
  * A tau replicate's chain is a list of weighted rows (num, type, haplotype, population, newHaplotype, newPopulation), six int64:

@@ -142,6 +142,13 @@ class VgxPrevalenceIO(C.Structure):
                 ("passes", C.c_int64), ("ms", C.c_double * 3)]
 
 
+class VgxLineagesIO(C.Structure):
+    _fields_ = [("n", C.c_int64), ("replicates", _I), ("rng_state", C.POINTER(C.c_uint64)), ("T", C.c_int64), ("grid", _F),
+                ("V", C.c_int64), ("variant_of", C.POINTER(C.c_int32)), ("values", C.POINTER(C.c_int32)), ("root", C.POINTER(C.c_int32)),
+                ("status", _I), ("status_arg", _I), ("records", _I), ("rng_out", C.POINTER(C.c_uint64)),
+                ("summary", C.POINTER(VgxTrajSummaryIO)), ("passes", C.c_int64), ("ms", C.c_double * 3), ("kernel_ms", C.c_double * 3)]
+
+
 class VgxFlowsIO(C.Structure):
     _fields_ = [("n", C.c_int64), ("replicates", _I), ("T", C.c_int64), ("edges", _F), ("V", C.c_int64), ("variant_of", C.POINTER(C.c_int32)),
                 ("within", C.c_int32), ("counts", C.POINTER(C.c_int32)), ("outside", _I), ("summary", C.POINTER(VgxTrajSummaryIO)),
@@ -330,6 +337,9 @@ SIGNATURES = {
     "vgx_get_prevalence": (C.c_int, [_H, C.POINTER(VgxPrevalenceIO)]),
     "vgx_test_prevalence": (C.c_int, [_F, _I, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, _F, C.c_int64, C.POINTER(C.c_int32), C.c_int64, _I,
                                       C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, C.c_char_p, C.c_int64]),
+    "vgx_get_lineages": (C.c_int, [_H, C.POINTER(VgxLineagesIO)]),
+    "vgx_test_lineages": (C.c_int, [C.POINTER(VgxGenealogyIO), _F, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int64, C.POINTER(C.c_int32),
+                                    C.POINTER(C.c_int32), _I, C.c_char_p, C.c_int64]),
     "vgx_get_flows": (C.c_int, [_H, C.POINTER(VgxFlowsIO)]),
     "vgx_test_flows": (C.c_int, [_F, _I, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, _F, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int32,
                                  C.c_int64, C.c_int64, C.POINTER(C.c_int32), _I, _I, C.c_char_p, C.c_int64]),
@@ -756,7 +766,9 @@ def genealogy_message(status, arg):
     return buf.value.decode()
 
 
-def _genealogy(entry, m, seed, rng_position, rng_raw, extra=()):
+def _genealogy_chain(m, seed, rng_position, rng_raw):
+    """A ``VgxGenealogyIO`` with the chain, the state and the generator start of a host model, its outputs not yet allocated:
+    (io, MUTATION events, MIGRATION events of the chain, multievent rows weighted)."""
     lib = load_library()
     ev, mv = m.events, m.multievents
     io = VgxGenealogyIO()
@@ -787,6 +799,12 @@ def _genealogy(entry, m, seed, rng_position, rng_raw, extra=()):
         lib.vgx_rng_position(int(m.user_seed), int(att), int(draws), C.byref(pos))
     for i in range(4):
         io.rng_state[i] = pos[i]
+    return io, n_mut, n_mig
+
+
+def _genealogy(entry, m, seed, rng_position, rng_raw, extra=()):
+    lib = load_library()
+    io, n_mut, n_mig = _genealogy_chain(m, seed, rng_position, rng_raw)
     nodes = max(2 * int(m.sCounter) - 1, 1)
     out = {"tree": np.zeros(nodes, dtype=np.int64), "tree_pop": np.zeros(nodes, dtype=np.int64), "times": np.zeros(nodes)}
     io.tree, io.tree_pop, io.times = _p(out["tree"]), _p(out["tree_pop"]), _p(out["times"])
@@ -998,6 +1016,32 @@ def replay_prevalence(times, types, haplotypes, populations, newHaplotypes, newP
     if rc != VGX_OK:
         raise ValueError(err.value.decode() or "vgx_test_prevalence failed")
     return values, final, outside
+
+
+def replay_lineages(m, seed, grid, variant_of, V, tile=0, rng_raw=None):
+    """The values of ``Ensemble.lineages`` for the chain and state of one host model through ``vgx_test_lineages``: the device's walk
+    with its observer, tile walk and suffix sum (vgx_gwalk.h, vgx_lineages.h) compiled for the host, tile after tile of ``tile``
+    lineage records (0: the default); no GPU.  ``seed`` and ``rng_raw`` as ``get_genealogy`` takes them (a direct chain;
+    ``seed=None`` without ``rng_raw`` starts at the simulation stream's origin); ``variant_of`` [hapNum] with values in [-1, V).
+    Walks ``m.infectious`` back in place.  Returns a dict: values [T, P, V] int32, root [P, V] int32, records, nodes_used,
+    rng_raw; a refusal or a walk that fails raises ``ValueError`` with the library's message."""
+    grid = np.ascontiguousarray(grid, dtype=np.float64)
+    T, P, V = len(grid), int(m.popNum), int(V)
+    vo = np.ascontiguousarray(variant_of, dtype=np.int32)
+    if len(vo) != int(m.hapNum):
+        raise ValueError("variant_of must hold hapNum values")
+    io, _, _ = _genealogy_chain(m, seed, None, rng_raw)
+    values = np.zeros((max(T, 1), max(P, 1), max(V, 1)), dtype=np.int32)
+    root = np.zeros((max(P, 1), max(V, 1)), dtype=np.int32)
+    records = np.zeros(1, dtype=np.int64)
+    err = C.create_string_buffer(512)
+    i32 = C.POINTER(C.c_int32)
+    rc = load_library().vgx_test_lineages(C.byref(io), _p(grid), T, vo.ctypes.data_as(i32), V, int(tile), values.ctypes.data_as(i32),
+                                          root.ctypes.data_as(i32), _p(records), err, 512)
+    if rc != VGX_OK:
+        raise ValueError(err.value.decode() or "vgx_test_lineages failed")
+    return {"values": values, "root": root, "records": int(records[0]), "nodes_used": int(io.nodes_used),
+            "rng_raw": tuple(int(io.rng_state[i]) for i in range(4)) + (0, 0)}
 
 
 FLOW_FORMS = {None: 0, 'auto': 0, 'dense': 1, 'split': 2}   # VGX_FLOW_AUTO, VGX_FLOW_DENSE, VGX_FLOW_SPLIT

@@ -794,7 +794,7 @@ extern "C" int vgx_get_counters(vgx_engine *e, int64_t replicate, vgx_counters *
     out->lockdown_records = s.loc_n;
     out->error = s.error;
     out->multievent_rows = s.mev_rows;
-    if (!e->last_was_tau) { out->reserved[1] = s.last_attempt; out->reserved[2] = s.last_attempt_loops; }
+    if (!e->last_was_tau) { out->reserved[1] = s.last_attempt; out->reserved[2] = s.last_attempt_loops; out->reserved[4] = s.sCounter; }
     else out->reserved[1] = -1;
     return VGX_OK;
 }
@@ -2111,6 +2111,236 @@ extern "C" int vgx_get_prevalence(vgx_engine *e, vgx_prevalence_io *io) {
             return fail(e, VGX_ERR_ARG, "vgx_get_prevalence: summary: a value of " + std::to_string(mm[0]) + " is not a whole number in [0, 2^31) (the log holds records outside the model)");
         char msg[512] = "";
         const int rc = vgxi_column_summary_i32("vgx_get_prevalence: summary", (const int32_t *)(kws + o_val), n, T * cells, io->summary, e->stream, msg, sizeof msg);
+        if (rc) return fail(e, rc, msg);
+    }
+    io->ms[2] = wall();
+    return VGX_OK;
+}
+
+// ---- ancestral lineages per variant class of many replicates at the times of one grid (vgx_lineages.hip, vgx_lineages.h)
+// vgx_get_genealogies' walk and vgx_get_prevalence's grid in one call: the sizing kernel counts every chain's MUTATION and
+// MIGRATION events, the host clock turns every replicate's times into T + 2 bounds, and pass by pass the device walks the selected
+// replicates with the logging observer, bins their lineage logs into the block of net changes and sums the intervals up where
+// they lie; the column summary reads the values there.
+extern "C" int vgx_get_lineages(vgx_engine *e, vgx_lineages_io *io) {
+    if (!e || !io || io->n < 0 ||
+        (io->n > 0 && (!io->replicates || !io->rng_state || !io->root || !io->status || !io->status_arg || !io->records || !io->rng_out)))
+        return VGX_ERR_ARG;
+    const auto t_call = std::chrono::steady_clock::now();
+    auto wall = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(); };
+    io->passes = 0;
+    io->ms[0] = io->ms[1] = io->ms[2] = 0.0;
+    io->kernel_ms[0] = io->kernel_ms[1] = io->kernel_ms[2] = 0.0;
+    if (!e->sc_host_valid || !e->dev_state_valid) return fail(e, VGX_ERR_ARG, "vgx_get_lineages: no direct simulate call yet");
+    if (e->last_was_tau) return fail(e, VGX_ERR_ARG, "vgx_get_lineages: the last call was vgx_simulate_tau (direct chains only)");
+    if (!e->call_recorded) return fail(e, VGX_ERR_ARG, "vgx_get_lineages: the last call did not record events");
+    const int64_t n = io->n, P = e->d.popNum, H = e->d.hapNum, T = io->T, V = io->V;
+    if (T < 1 || T >= VGX_PREV_MAX_POINTS || !io->grid) return fail(e, VGX_ERR_ARG, "vgx_get_lineages: T = " + std::to_string(T) + " grid points: at least 1, below 2^24, with grid");
+    for (int64_t k = 0; k < T; k++) {
+        if (!std::isfinite(io->grid[k])) return fail(e, VGX_ERR_ARG, "vgx_get_lineages: grid[" + std::to_string(k) + "] is not finite");
+        if (k > 0 && !(io->grid[k - 1] < io->grid[k]))
+            return fail(e, VGX_ERR_ARG, "vgx_get_lineages: grid must increase strictly (grid[" + std::to_string(k) + "])");
+    }
+    if (V < 1 || V > INT32_MAX || !io->variant_of) return fail(e, VGX_ERR_ARG, "vgx_get_lineages: V = " + std::to_string(V) + " classes: at least 1, with variant_of");
+    for (int64_t h = 0; h < H; h++)
+        if (io->variant_of[h] < -1 || io->variant_of[h] >= V)
+            return fail(e, VGX_ERR_ARG, "vgx_get_lineages: variant_of[" + std::to_string(h) + "] = " + std::to_string(io->variant_of[h]) + " is outside [-1, " + std::to_string(V) + ")");
+    if (vgx_prev_lds_bytes(P, V) > VGX_PREV_LDS_MAX)
+        return fail(e, VGX_ERR_ARG, "vgx_get_lineages: " + std::to_string(P) + " populations x " + std::to_string(V) + " classes need " + std::to_string(vgx_prev_lds_bytes(P, V)) +
+                                        " bytes of cells, above the " + std::to_string((int64_t)VGX_PREV_LDS_MAX) + " bytes of LDS a counting workgroup may use");
+    const int64_t cells = P * V;
+    std::vector<int32_t> n_ev((size_t)n);
+    std::vector<int64_t> n_ev64((size_t)n), sC((size_t)n);
+    {
+        std::vector<char> seen((size_t)e->R, 0);
+        for (int64_t i = 0; i < n; i++) {
+            const int64_t r = io->replicates[i];
+            if (r < 0 || r >= e->R) return fail(e, VGX_ERR_ARG, "vgx_get_lineages: replicate index out of range");
+            if (seen[(size_t)r]) return fail(e, VGX_ERR_ARG, "vgx_get_lineages: replicates must be distinct");
+            seen[(size_t)r] = 1;
+            const VgxRepScalars &s = e->sc_host[(size_t)r];
+            const int64_t first = s.restarts > 0 ? 0 : ((size_t)r < e->call_ev0.size() ? e->call_ev0[(size_t)r] : e->ev_ptr0);
+            if (first != 0 || e->ev_base != 0)
+                return fail(e, VGX_ERR_ARG, "vgx_get_lineages: the chain of replicate " + std::to_string(r) +
+                                                " does not start in the last call's device log (events.ptr was not 0 at its start)");
+            if (s.ev_ptr >= VGX_PREV_MAX_EVENTS)
+                return fail(e, VGX_ERR_ARG, "vgx_get_lineages: replicate " + std::to_string(r) + " holds a chain of " + std::to_string(s.ev_ptr) + " events (2^30 or more)");
+            if (s.ev_ptr < 0 || s.ev_ptr > e->evcap)
+                return fail(e, VGX_ERR_ARG, "vgx_get_lineages: event range of replicate " + std::to_string(r) + " outside the device log");
+            n_ev[(size_t)i] = (int32_t)s.ev_ptr;
+            n_ev64[(size_t)i] = s.ev_ptr;
+            sC[(size_t)i] = s.sCounter;
+        }
+    }
+    if (n == 0) {
+        io->ms[2] = wall();
+        return VGX_OK;
+    }
+    int64_t tile = VGX_LN_TILE_DEFAULT;
+    if (const char *tb = getenv("VGX_LINEAGES_TILE_RECORDS")) tile = std::min<int64_t>(std::max<int64_t>(atoll(tb), 1), VGX_PREV_MAX_EVENTS);
+    HIPCHECK(e, hipSetDevice(e->device));
+    const int32_t *log = (const int32_t *)e->r_evcols.p;
+    // the walk reads the 8-byte counts of the final occupancy lists
+    if (!e->counts64_valid) {
+        HIPCHECK(e, vgxi_launch_counts64(e->dr.lcnt32, e->dr.lcnt, e->R * P * e->cap, e->stream));
+        HIPCHECK(e, hipStreamSynchronize(e->stream));
+        e->counts64_valid = true;
+    }
+    size_t free_b = 0, total_b = 0;
+    HIPCHECK(e, hipMemGetInfo(&free_b, &total_b));
+    auto up8 = [](int64_t b) { return (b + 255) / 256 * 256; };
+    auto dev_free = [](char *p) { (void)hipFree(p); };
+    // what stays for the whole call: [rep | n_ev | n_ev (8 bytes) | event counts | bound | variant_of | val | fin | min, max]
+    const int64_t val_bytes = n * T * cells * 4, fin_bytes = n * cells * 4;
+    const int64_t o_rep = 0, o_nev = o_rep + up8(n * 8), o_nev64 = o_nev + up8(n * 4), o_cnt = o_nev64 + up8(n * 8), o_bnd = o_cnt + up8(n * 16),
+                  o_map = o_bnd + up8(n * (T + 2) * 4), o_val = o_map + up8(H * 4), o_fin = o_val + up8(val_bytes), o_mm = o_fin + up8(fin_bytes),
+                  keep_total = o_mm + 256;
+    if (keep_total > (int64_t)(free_b / 2))
+        return fail(e, VGX_ERR_ARG, "vgx_get_lineages: the block of " + std::to_string(n) + " x " + std::to_string(T + 1) + " x " + std::to_string(P) + " x " + std::to_string(V) +
+                                        " values (" + std::to_string(val_bytes + fin_bytes) + " bytes) and its cuts take " + std::to_string(keep_total) +
+                                        " bytes, above half of the " + std::to_string((int64_t)free_b) + " bytes of free device memory: select fewer replicates per call");
+    char *kws = nullptr;
+    hipError_t er = hipMalloc((void **)&kws, (size_t)keep_total);
+    if (er != hipSuccess) return fail(e, VGX_ERR_HIP, "vgx_get_lineages: hipMalloc of " + std::to_string(keep_total) + " bytes: " + hipGetErrorString(er));
+    std::unique_ptr<char, void (*)(char *)> khold(kws, dev_free);
+    std::vector<int64_t> reps_all(io->replicates, io->replicates + n);
+    HIPCHECK(e, hipMemcpyAsync(kws + o_rep, reps_all.data(), (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_nev, n_ev.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_nev64, n_ev64.data(), (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_map, io->variant_of, (size_t)H * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemsetAsync(kws + o_val, 0, (size_t)(o_mm - o_val), e->stream));   // val and fin, zeroed once
+    // the MUTATION and MIGRATION events of every chain: the capacity of its lineage log
+    std::vector<int64_t> cnt((size_t)n * 2);
+    HIPCHECK(e, vgxi_gw_count(log, e->evcap, (const int64_t *)(kws + o_rep), (const int64_t *)(kws + o_nev64), n, (int64_t *)(kws + o_cnt), e->stream));
+    HIPCHECK(e, hipMemcpyAsync(cnt.data(), kws + o_cnt, (size_t)n * 16, hipMemcpyDeviceToHost, e->stream));
+    if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)
+        return fail(e, VGX_ERR_HIP, std::string("vgx_get_lineages: counting pass: ") + hipGetErrorString(er));
+
+    // host: every replicate's event times -> its T + 2 bounds (the device work of a clock chunk comes later, pass by pass)
+    const int64_t share_clock = (int64_t)(free_b / 2) - keep_total + 4096;
+    std::vector<int32_t> bounds((size_t)(n * (T + 2)));
+    const int rc_chunks = clock_chunks(e, "vgx_get_lineages", reps_all, n_ev, (const int64_t *)(kws + o_rep), (const int32_t *)(kws + o_nev), share_clock, io->ms,
+        [&](int64_t gi, const std::vector<double> &times) {
+            VgxPrevCutter ct{io->grid, T, bounds.data() + gi * (T + 2)};
+            for (size_t k = 0; k < times.size(); k++) ct.event((int64_t)k, times[k]);
+            ct.finish((int64_t)times.size());
+        },
+        [&](int64_t, int64_t, int64_t) -> int { return VGX_OK; });
+    if (rc_chunks) return rc_chunks;
+    HIPCHECK(e, hipMemcpyAsync(kws + o_bnd, bounds.data(), bounds.size() * 4, hipMemcpyHostToDevice, e->stream));
+
+    // per-replicate workspace (elements), and the passes: every pass holds at most `share` bytes
+    std::vector<VgxLnDesc> desc((size_t)n);
+    std::vector<int64_t> bytes((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        VgxLnDesc &d = desc[(size_t)i];
+        d.rep = io->replicates[i];
+        d.n_ev = n_ev64[(size_t)i];
+        d.sCounter = sC[(size_t)i];
+        d.tsize = d.sCounter >= 2 ? vgx_gw_table_size(d.n_ev, P * H) : 0;
+        d.arena_cap = d.sCounter >= 2 ? d.n_ev : 0;
+        d.rec_cap = vgx_ln_capacity(d.sCounter, cnt[(size_t)(2 * i)], cnt[(size_t)(2 * i + 1)]);
+        for (int k = 0; k < 4; k++) d.rng[k] = io->rng_state[i * 4 + k];
+        const int64_t nodes = d.sCounter >= 2 ? 2 * d.sCounter - 1 : 0;
+        bytes[(size_t)i] = d.tsize * 28 + d.arena_cap * 4 + nodes * 4 + d.rec_cap * 24 + (int64_t)sizeof(VgxLnDesc) + 80;
+    }
+    int64_t share = std::max<int64_t>((int64_t)(free_b / 2) - keep_total, 1);
+    if (const char *cb = getenv("VGX_GENEALOGY_CHUNK_BYTES")) share = std::min<int64_t>(share, std::max<int64_t>(atoll(cb), 1));
+    struct Events {   // the stages of a pass, timed apart
+        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+        ~Events() { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); }
+    } tm;
+    for (hipEvent_t &x : tm.ev) HIPCHECK(e, hipEventCreate(&x));
+    int64_t i0 = 0;
+    while (i0 < n) {
+        int64_t i1 = i0, sum = 0;
+        while (i1 < n && (i1 == i0 || sum + bytes[(size_t)i1] <= share)) sum += bytes[(size_t)i1++];
+        const int64_t m = i1 - i0;
+        int64_t TB = 0, A = 0, N = 0, Rc = 0, max_rec = 0;
+        std::vector<VgxLnDesc> dp(desc.begin() + i0, desc.begin() + i1);
+        for (int64_t j = 0; j < m; j++) {
+            VgxLnDesc &d = dp[(size_t)j];
+            d.tab_off = TB; d.arena_off = A; d.node_off = N; d.rec_off = Rc;
+            TB += d.tsize; A += d.arena_cap; N += d.sCounter >= 2 ? 2 * d.sCounter - 1 : 0; Rc += d.rec_cap;
+            max_rec = std::max<int64_t>(max_rec, d.rec_cap);
+        }
+        // one allocation: [desc | res | rng | n_rec | key | cnt | base | len | lcap | arena | parents | lineage logs]
+        const int64_t o_desc = 0, o_res = o_desc + up8(m * (int64_t)sizeof(VgxLnDesc)), o_rng = o_res + up8(m * 40), o_nrec = o_rng + up8(m * 32),
+                      o_key = o_nrec + up8(m * 8), o_tcnt = o_key + up8(TB * 8), o_base = o_tcnt + up8(TB * 8), o_len = o_base + up8(TB * 4),
+                      o_lcap = o_len + up8(TB * 4), o_arena = o_lcap + up8(TB * 4), o_tree = o_arena + up8(A * 4), o_rec = o_tree + up8(N * 4),
+                      total = o_rec + up8(Rc * 24);
+        char *ws = nullptr;
+        er = hipMalloc((void **)&ws, (size_t)total);
+        if (er != hipSuccess)
+            return fail(e, VGX_ERR_HIP, "vgx_get_lineages: hipMalloc of " + std::to_string(total) + " bytes: " + hipGetErrorString(er));
+        std::unique_ptr<char, void (*)(char *)> hold(ws, dev_free);
+        VgxLnLaunch a{};
+        a.m = m;
+        a.desc = (const VgxLnDesc *)(ws + o_desc);
+        a.log = log; a.evcap = e->evcap;
+        a.nocc = e->dr.nocc; a.lhap = e->dr.lhap; a.lcnt = e->dr.lcnt;
+        a.P = P; a.H = H; a.cap = e->cap;
+        a.key = (int64_t *)(ws + o_key); a.cnt = (int64_t *)(ws + o_tcnt);
+        a.base = (int32_t *)(ws + o_base); a.len = (int32_t *)(ws + o_len); a.lcap = (int32_t *)(ws + o_lcap);
+        a.arena = (int32_t *)(ws + o_arena);
+        a.tree = (int32_t *)(ws + o_tree);
+        a.rec = (int32_t *)(ws + o_rec);
+        a.res = (int64_t *)(ws + o_res);
+        a.rng_out = (uint64_t *)(ws + o_rng);
+        a.n_rec = (int64_t *)(ws + o_nrec);
+        a.bound = (const int32_t *)(kws + o_bnd) + i0 * (T + 2);
+        a.T = (int32_t)T; a.V = (int32_t)V;
+        a.variant_of = (const int32_t *)(kws + o_map);
+        a.tile = (int32_t)tile; a.max_rec = max_rec;
+        a.val = (int32_t *)(kws + o_val) + i0 * T * cells;
+        a.fin = (int32_t *)(kws + o_fin) + i0 * cells;
+        HIPCHECK(e, hipMemcpyAsync(ws + o_desc, dp.data(), (size_t)m * sizeof(VgxLnDesc), hipMemcpyHostToDevice, e->stream));
+        if (TB > 0) HIPCHECK(e, hipMemsetAsync(a.key, 0xFF, (size_t)TB * 8, e->stream));   // every slot empty (-1)
+        HIPCHECK(e, hipEventRecord(tm.ev[0], e->stream));
+        HIPCHECK(e, vgxi_ln_walk(&a, e->stream));
+        HIPCHECK(e, hipEventRecord(tm.ev[1], e->stream));
+        HIPCHECK(e, vgxi_ln_bin(&a, e->stream));
+        HIPCHECK(e, hipEventRecord(tm.ev[2], e->stream));
+        HIPCHECK(e, vgxi_ln_scan(&a, e->stream));
+        HIPCHECK(e, hipEventRecord(tm.ev[3], e->stream));
+        std::vector<int64_t> res((size_t)m * 5), nrec((size_t)m);
+        HIPCHECK(e, hipMemcpyAsync(res.data(), a.res, (size_t)m * 40, hipMemcpyDeviceToHost, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(io->rng_out + i0 * 4, a.rng_out, (size_t)m * 32, hipMemcpyDeviceToHost, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(nrec.data(), a.n_rec, (size_t)m * 8, hipMemcpyDeviceToHost, e->stream));
+        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)   // before anything reads the outputs
+            return fail(e, VGX_ERR_HIP, std::string("vgx_get_lineages: walk, binning or scan kernel failed: ") + hipGetErrorString(er));
+        for (int k = 0; k < 3; k++) {
+            float kms = 0.f;
+            HIPCHECK(e, hipEventElapsedTime(&kms, tm.ev[k], tm.ev[k + 1]));
+            io->kernel_ms[k] += kms;
+            io->ms[0] += kms;
+        }
+        for (int64_t j = 0; j < m; j++) {
+            io->status[i0 + j] = res[(size_t)(j * 5)];
+            io->status_arg[i0 + j] = res[(size_t)(j * 5 + 1)];
+            io->records[i0 + j] = nrec[(size_t)j];
+        }
+        io->passes += 1;
+        i0 = i1;
+    }
+    if (io->values) HIPCHECK(e, hipMemcpy(io->values, kws + o_val, (size_t)val_bytes, hipMemcpyDeviceToHost));
+    HIPCHECK(e, hipMemcpy(io->root, kws + o_fin, (size_t)fin_bytes, hipMemcpyDeviceToHost));
+    if (io->summary) {
+        if (!io->summary->group_of) return fail(e, VGX_ERR_ARG, "vgx_get_lineages: summary: null group_of");
+        int64_t failed = 0;
+        for (int64_t i = 0; i < n; i++) failed += io->summary->group_of[i] >= 0 && io->status[i] != VGX_GW_OK;
+        if (failed > 0)
+            return fail(e, VGX_ERR_ARG, "vgx_get_lineages: summary: " + std::to_string(failed) + " replicate(s) of a group have a walk that failed (status is not 0): leave them out of the groups");
+        // the column summary sorts 32-bit keys of whole numbers in [0, 2^31)
+        int32_t mm[2] = {0, 0};
+        HIPCHECK(e, vgxi_prev_minmax((const int32_t *)(kws + o_val), n * T * cells, (int32_t *)(kws + o_mm), e->stream));
+        HIPCHECK(e, hipMemcpyAsync(mm, kws + o_mm, sizeof mm, hipMemcpyDeviceToHost, e->stream));
+        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)
+            return fail(e, VGX_ERR_HIP, std::string("vgx_get_lineages: min/max kernel failed: ") + hipGetErrorString(er));
+        if (mm[0] < 0)
+            return fail(e, VGX_ERR_ARG, "vgx_get_lineages: summary: a value of " + std::to_string(mm[0]) + " is not a whole number in [0, 2^31)");
+        char msg[512] = "";
+        const int rc = vgxi_column_summary_i32("vgx_get_lineages: summary", (const int32_t *)(kws + o_val), n, T * cells, io->summary, e->stream, msg, sizeof msg);
         if (rc) return fail(e, rc, msg);
     }
     io->ms[2] = wall();

@@ -27,6 +27,7 @@
 #include "vgx_prevalence.h"
 #include "vgx_milestones.h"
 #include "vgx_flows.h"
+#include "vgx_lineages.h"
 
 #pragma GCC visibility push(hidden)   // nothing here is part of the exported C ABI
 
@@ -62,6 +63,10 @@ extern "C" hipError_t vgxi_prev_scan(const VgxPrevLaunch *a, hipStream_t s);
 extern "C" hipError_t vgxi_prev_minmax(const int32_t *x, int64_t n, int32_t *out, hipStream_t s);   // out[0] = min, out[1] = max of x[0 .. n)
 extern "C" hipError_t vgxi_ms_walk(const VgxMsLaunch *g, int waves, hipStream_t s);   // vgx_milestones.hip: the ordered walk over the bases of pass A
 extern "C" hipError_t vgxi_sus_count(const VgxPrevLaunch *a, hipStream_t s);   // vgx_susceptible.hip: hapNum := susNum, V := G, variant_of := class_of
+// vgx_lineages.hip: the walk with the logging observer, the binning of the lineage logs, the suffix sum (one pass, one stream)
+extern "C" hipError_t vgxi_ln_walk(const VgxLnLaunch *a, hipStream_t s);
+extern "C" hipError_t vgxi_ln_bin(const VgxLnLaunch *a, hipStream_t s);
+extern "C" hipError_t vgxi_ln_scan(const VgxLnLaunch *a, hipStream_t s);
 extern "C" hipError_t vgxi_flow_count(const VgxFlowLaunch *a, hipStream_t s);   // vgx_flows.hip: a->form is the form that runs (dense or split)
 // the launchers of vgx_tau_prevalence.hip that vgx_tau_susceptible.hip shares (net blocks from the prefix's, the 64-bit running
 // sums, the narrowing min/max pass)

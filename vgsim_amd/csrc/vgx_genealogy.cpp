@@ -8,6 +8,8 @@
 // same operations on the same vectors in the same order, so trees, times and records are identical.
 // Random numbers: the wrapper's uniform() = PCG64 next_double (pyx:801 ...), numpy's random_hypergeometric on the
 // same bit generator for MULTITYPE thinning (pyx:905, 933, 950, 956).
+#include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -20,6 +22,7 @@
 #include "../../include/vgx.h"
 #include "vgx_gwalk.h"
 #include "vgx_gwalk_tau.h"
+#include "vgx_lineages.h"
 #include "vgx_logfact.h"
 #include "vgx_rng.h"
 
@@ -473,5 +476,93 @@ extern "C" int vgx_test_genealogy_walk(vgx_genealogy_io *io, char *errbuf, int64
     }
     io->nodes_used = res.nodes_used;
     io->rng_state[0] = g.sh; io->rng_state[1] = g.sl; io->rng_state[2] = g.ih; io->rng_state[3] = g.il;
+    return VGX_OK;
+}
+
+// ---- lineages on a grid (vgx_lineages.h): the walk with the logging observer, the tile walk and the suffix sum on one chain ------
+extern "C" int vgx_test_lineages(vgx_genealogy_io *io, const double *grid, int64_t T, const int32_t *variant_of, int64_t V, int64_t tile,
+                                 int32_t *values, int32_t *root, int64_t *records, char *errbuf, int64_t errcap) {
+    auto fail = [&](const std::string &m) {
+        if (errbuf && errcap > 0) std::snprintf(errbuf, (size_t)errcap, "%s", m.c_str());
+        return VGX_ERR_ARG;
+    };
+    if (!io || !io->infectious || !grid || !variant_of || !values || !root || !records) return fail("vgx_test_lineages: null argument");
+    const int64_t P = io->popNum, H = io->hapNum;
+    if (T < 1 || T >= VGX_PREV_MAX_POINTS) return fail("vgx_test_lineages: T = " + std::to_string(T) + " must be at least 1 and below 2^24");
+    for (int64_t k = 0; k < T; k++) {
+        if (!std::isfinite(grid[k])) return fail("vgx_test_lineages: grid[" + std::to_string(k) + "] is not finite");
+        if (k > 0 && !(grid[k - 1] < grid[k])) return fail("vgx_test_lineages: grid must increase strictly (grid[" + std::to_string(k) + "])");
+    }
+    if (P < 1 || H < 1 || P > INT32_MAX || H > INT32_MAX) return fail("vgx_test_lineages: bad dimensions");
+    if (V < 1 || V > INT32_MAX) return fail("vgx_test_lineages: V = " + std::to_string(V) + " must be at least 1");
+    if (vgx_prev_lds_bytes(P, V) > VGX_PREV_LDS_MAX)
+        return fail("vgx_test_lineages: " + std::to_string(P) + " populations x " + std::to_string(V) + " classes need " +
+                    std::to_string(vgx_prev_lds_bytes(P, V)) + " bytes of cells, above the " + std::to_string((int64_t)VGX_PREV_LDS_MAX) +
+                    " bytes of LDS a counting workgroup may use");
+    for (int64_t h = 0; h < H; h++)
+        if (variant_of[h] < -1 || variant_of[h] >= V)
+            return fail("vgx_test_lineages: variant_of[" + std::to_string(h) + "] = " + std::to_string(variant_of[h]) + " is outside [-1, " +
+                        std::to_string(V) + ")");
+    if (tile < 0) return fail("vgx_test_lineages: tile must not be negative");
+    if (tile == 0) tile = VGX_LN_TILE_DEFAULT;
+    if (io->sCounter < 2) return fail(walk_message(VGX_GW_FEW_SAMPLES, 0));
+    const int64_t n = io->ev_ptr, PH = P * H;
+    if (n < 0 || n >= VGX_PREV_MAX_EVENTS) return fail("vgx_test_lineages: a chain of " + std::to_string(n) + " events (2^30 or more)");
+    if (2 * io->sCounter > ((int64_t)1 << 31)) return fail("vgx_test_lineages: sCounter = " + std::to_string(io->sCounter) + " is too large");
+    if (n > 0 && (!io->ev_times || !io->ev_types || !io->ev_haplotypes || !io->ev_populations || !io->ev_newHaplotypes || !io->ev_newPopulations))
+        return fail("vgx_test_lineages: null event column");
+    // the chain in the device log's record layout, and what the sizing kernel counts
+    std::vector<int32_t> log((size_t)n * 6);
+    int64_t n_mut = 0, n_mig = 0;
+    for (int64_t e = 0; e < n; e++) {
+        const int64_t v[5] = {io->ev_types[e], io->ev_haplotypes[e], io->ev_populations[e], io->ev_newHaplotypes[e], io->ev_newPopulations[e]};
+        for (int c = 0; c < 5; c++) {
+            if (v[c] < INT32_MIN || v[c] > INT32_MAX) return fail("vgx_test_lineages: log value outside 32 bits");
+            log[(size_t)(e * 6 + c)] = (int32_t)v[c];
+        }
+        n_mut += v[0] == VGX_GW_MUTATION;
+        n_mig += v[0] == VGX_GW_MIGRATION;
+    }
+    const int64_t nodes = 2 * io->sCounter - 1;
+    const int64_t tsize = vgx_gw_table_size(n, PH);
+    std::vector<int64_t> key((size_t)tsize, -1), cnt((size_t)tsize);
+    std::unique_ptr<int32_t[]> base(new int32_t[(size_t)tsize]), len(new int32_t[(size_t)tsize]), lcap(new int32_t[(size_t)tsize]);
+    std::vector<int32_t> arena((size_t)std::max<int64_t>(n, 1)), tree((size_t)nodes);
+    const int64_t rec_cap = vgx_ln_capacity(io->sCounter, n_mut, n_mig);
+    std::vector<int32_t> rec((size_t)rec_cap * 6);
+    VgxGwRep w{};
+    w.n_ev = n; w.sCounter = io->sCounter; w.H = H; w.tsize = tsize;
+    w.key = key.data(); w.cnt = cnt.data(); w.base = base.get(); w.len = len.get(); w.lcap = lcap.get();
+    w.arena = arena.data(); w.arena_cap = n;
+    w.tree = tree.data();   // (the observer keeps no records: the other outputs are never touched)
+    VgxGwFlatReader rd{log.data()};
+    VgxGwResult res{};
+    res.status = vgx_gw_prepass(w, rd);
+    if (res.status != VGX_GW_OK) return fail(walk_message(res.status, res.arg));
+    for (int64_t s = 0; s < tsize; s++)   // the counts of the touched compartments
+        if (key[(size_t)s] >= 0 && key[(size_t)s] < PH) cnt[(size_t)s] = io->infectious[key[(size_t)s]];
+    VgxPcg64 g{io->rng_state[0], io->rng_state[1], io->rng_state[2], io->rng_state[3]};
+    VgxLnLog lg{rec.data(), rec_cap, 0, 0};
+    vgx_gw_walk(w, rd, g, res, VgxLnObserver{&lg});
+    if (res.status == VGX_GW_OK && lg.dropped > 0) res.status = VGX_GW_WORKSPACE;
+    for (int64_t s = 0; s < tsize; s++)   // walked back in place, as the host pass does
+        if (key[(size_t)s] >= 0 && key[(size_t)s] < PH) io->infectious[key[(size_t)s]] = cnt[(size_t)s];
+    if (res.status != VGX_GW_OK) return fail(walk_message(res.status, res.arg));
+    io->nodes_used = res.nodes_used;
+    io->rng_state[0] = g.sh; io->rng_state[1] = g.sl; io->rng_state[2] = g.ih; io->rng_state[3] = g.il;
+    *records = lg.n;
+    // the bounds from the chain's times, the tile walk over the lineage log, the suffix sum
+    std::vector<int32_t> bound((size_t)(T + 2));
+    VgxPrevCutter ct{grid, T, bound.data()};
+    for (int64_t e = 0; e < n; e++) ct.event(e, io->ev_times[e]);
+    ct.finish(n);
+    const int64_t cells = P * V;
+    for (int64_t i = 0; i < T * cells; i++) values[i] = 0;
+    for (int64_t i = 0; i < cells; i++) root[i] = 0;
+    std::vector<int32_t> hist((size_t)cells, 0);
+    for (int64_t r0 = 0; r0 < lg.n; r0 += tile)
+        vgx_ln_tile_host(rec.data(), bound.data(), (int32_t)T, (int32_t)P, (int32_t)H, (int32_t)V, variant_of, r0, std::min<int64_t>(r0 + tile, lg.n),
+                         hist.data(), values, root);
+    for (int64_t i = 0; i < cells; i++) vgx_ln_scan_column(values + i, root + i, (int32_t)T, cells);
     return VGX_OK;
 }

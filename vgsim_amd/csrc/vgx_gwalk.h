@@ -133,11 +133,27 @@ VGX_HD int vgx_gw_prepass(VgxGwRep &w, Rd &rd) {
     return acc <= w.arena_cap ? VGX_GW_OK : VGX_GW_WORKSPACE;
 }
 
-struct VgxGwWalk {
+// The observer of a walk is told where the walk changes a lineage list: a SAMPLING that pushes a lineage (tip), a BIRTH or a
+// MIGRATION that coalesces two (split; the migration's with pop = the event's newPopulation, where the lineage it takes away
+// lay), a MUTATION that takes a lineage (mutation) and a MIGRATION that moves one without coalescing (move), which leaves no
+// record at its own event.  `records` says whether the walk keeps the tree's populations and event indices and the mutation and
+// migration records; without them it keeps the parents alone (the closing pass needs them) and counts what it would have
+// written.  The default observes nothing and keeps everything: a walk with it is the walk without an observer.
+struct VgxGwNoObserver {
+    static constexpr bool records = true;
+    VGX_HD void tip(int64_t, int64_t, int64_t) {}
+    VGX_HD void split(int64_t, int64_t, int64_t) {}
+    VGX_HD void mutation(int64_t, int64_t, int64_t, int64_t) {}
+    VGX_HD void move(int64_t, int64_t, int64_t, int64_t) {}
+};
+
+template <class Obs>
+struct VgxGwWalkT {
     VgxGwRep &w;
     VgxPcg64 &g;
     VgxGwResult &res;
     int64_t ptr, nodes;
+    Obs obs{};
 
     VGX_HD double uniform() { return vgx_pcg64_double(g); }
     VGX_HD int32_t &at(int64_t s, int64_t i) { return w.arena[w.base[s] + i]; }
@@ -150,10 +166,14 @@ struct VgxGwWalk {
     VGX_HD void swap_pop(int64_t s, int64_t i) { at(s, i) = at(s, w.len[s] - 1); w.len[s] -= 1; }
     VGX_HD void parent(int64_t id, int64_t par) { if (id >= 0 && id < nodes) w.tree[id] = (int32_t)par; }
     VGX_HD void node(int64_t pop, int64_t e) {
-        if (ptr < nodes) { w.tree[ptr] = -1; w.tree_pop[ptr] = (int32_t)pop; w.node_ev[ptr] = (int32_t)e; }
+        if (ptr < nodes) {
+            w.tree[ptr] = -1;
+            if (Obs::records) { w.tree_pop[ptr] = (int32_t)pop; w.node_ev[ptr] = (int32_t)e; }
+        }
         ptr += 1;
     }
     VGX_HD bool mutation(int64_t nodeId, int64_t hap, int64_t nh, int64_t e) {   // models.pxi:13-29
+        if (!Obs::records) { res.mut_n += 1; return true; }
         if (res.mut_n >= w.mut_cap) { res.status = VGX_GW_MUT_CAP; return false; }
         int64_t d = nh > hap ? nh - hap : hap - nh, site = 0, digit4 = 1;
         while (d >= 4) { d /= 4; site += 1; digit4 *= 4; }
@@ -163,6 +183,7 @@ struct VgxGwWalk {
         return true;
     }
     VGX_HD bool migration(int64_t nodeId, int64_t e, int64_t oldPop, int64_t newPop) {   // models.pxi:44-48
+        if (!Obs::records) { res.mig_n += 1; return true; }
         if (res.mig_n >= w.mig_cap) { res.status = VGX_GW_MIG_CAP; return false; }
         const int64_t k = res.mig_n++;
         w.mig_node[k] = (int32_t)nodeId; w.mig_ev[k] = (int32_t)e; w.mig_old[k] = (int32_t)oldPop; w.mig_new[k] = (int32_t)newPop;
@@ -187,6 +208,7 @@ struct VgxGwWalk {
                 swap_pop(s, n2);
                 parent(id1, id3); parent(id2, id3);
                 node(pop, e);
+                obs.split(e, hap, pop);
             }
             w.cnt[s] -= 1;
             return true;
@@ -197,6 +219,7 @@ struct VgxGwWalk {
             w.cnt[s] += 1;
             if (!push(s, ptr)) return false;
             node(pop, e);
+            obs.tip(e, hap, pop);
             return true;
         }
         case VGX_GW_MUTATION: {
@@ -209,6 +232,7 @@ struct VgxGwWalk {
                 swap_pop(sn, n1);
                 if (!push(sh, id1)) return false;
                 if (!mutation(id1, hap, nh, e)) return false;
+                obs.mutation(e, hap, pop, nh);
             }
             w.cnt[sn] -= 1;
             w.cnt[sh] += 1;
@@ -231,9 +255,11 @@ struct VgxGwWalk {
                     parent(idt, id3); parent(ids, id3);
                     node(pop, e);
                     if (!migration(idt, e, pop, np)) return false;
+                    obs.split(e, hap, np);
                 } else {
                     if (!push(ss, at(st, nt))) return false;
                     swap_pop(st, nt);
+                    obs.move(e, hap, pop, np);
                 }
             }
             w.cnt[st] -= 1;
@@ -246,16 +272,21 @@ struct VgxGwWalk {
         }
     }
 };
+using VgxGwWalk = VgxGwWalkT<VgxGwNoObserver>;
 
 // The walk over [0, n_ev) from the last event back, then the closing pass (pyx:998-1000).  The table must hold the
-// pre-pass's compartments with their final infectious counts.  `g` advances by the draws made.
-template <class Rd>
-VGX_HD void vgx_gw_walk(VgxGwRep &w, Rd &rd, VgxPcg64 &g, VgxGwResult &res) {
+// pre-pass's compartments with their final infectious counts.  `g` advances by the draws made.  The draws, their order and the
+// generator afterwards do not depend on the observer.
+template <class Rd, class Obs = VgxGwNoObserver>
+VGX_HD void vgx_gw_walk(VgxGwRep &w, Rd &rd, VgxPcg64 &g, VgxGwResult &res, Obs obs = Obs{}) {
     res.status = VGX_GW_OK; res.arg = 0; res.nodes_used = 0; res.mut_n = 0; res.mig_n = 0;
     if (w.sCounter < 2) { res.status = VGX_GW_FEW_SAMPLES; return; }
     const int64_t nodes = 2 * w.sCounter - 1;
-    for (int64_t i = 0; i < nodes; i++) { w.tree[i] = 0; w.tree_pop[i] = 0; w.node_ev[i] = -1; }
-    VgxGwWalk k{w, g, res, 0, nodes};
+    for (int64_t i = 0; i < nodes; i++) {
+        w.tree[i] = 0;
+        if (Obs::records) { w.tree_pop[i] = 0; w.node_ev[i] = -1; }
+    }
+    VgxGwWalkT<Obs> k{w, g, res, 0, nodes, obs};
     int32_t c[5];
     for (int64_t e = w.n_ev - 1; e >= 0; --e) {
         rd.at(e, c);
@@ -267,7 +298,8 @@ VGX_HD void vgx_gw_walk(VgxGwRep &w, Rd &rd, VgxPcg64 &g, VgxGwResult &res) {
     for (int64_t i = 0; i < 2 * w.sCounter - 2; i++) {
         const int64_t par = w.tree[i];
         if (par < 0 || par >= nodes) { res.status = VGX_GW_NOT_COALESCED; res.arg = i; return; }
-        if (w.tree_pop[par] != w.tree_pop[i] && !k.migration(i, w.node_ev[i], w.tree_pop[par], w.tree_pop[i])) return;
+        // (these migration records of the closing pass change no lineage list: the observer is not told)
+        if (Obs::records && w.tree_pop[par] != w.tree_pop[i] && !k.migration(i, w.node_ev[i], w.tree_pop[par], w.tree_pop[i])) return;
     }
 }
 

@@ -308,6 +308,41 @@ class Prevalence:
         return out
 
 
+class Lineages:
+    """What ``Ensemble.lineages`` returns: the ancestral lineages of the sampled cases per selected replicate, grid time, population
+    and variant class: the tree's counterpart of :class:`Prevalence`.
+
+    ``values`` [n, T, P, V] int32 (None when the call had ``values=False``): the lineages of the sample's tree alive at
+    ``times[j]`` in population p that carry a haplotype of class c, events at exactly that time applied; ``root`` [n, P, V] int32
+    the same before the first event (with every haplotype tracked it sums to 1: the root of the tree); ``times`` [T];
+    ``variant_of`` [H] the class of every haplotype (-1: not tracked); ``replicates`` [n]; ``status``, ``status_arg`` [n] 0 or
+    why the walk of row i stopped, as :class:`GenealogyBatch` (``message(i)``; such a row holds zeros), ``ok`` = ``status == 0``;
+    ``records`` [n] the lineage records of every walk; ``rng_raw`` [n, 6] the generator after the walk, that of
+    ``genealogies()``; ``summary`` a :class:`TrajectorySummary` over the [T, P, V] columns, or None; ``passes`` (walk passes),
+    ``kernel_ms`` (``stage_ms``: walk, binning and suffix sum apart), ``clock_ms``, ``wall_ms``."""
+
+    @property
+    def ok(self):
+        return self.status == 0
+
+    def message(self, i):
+        """Text of row i's status: what ``Ensemble.genealogy`` raises for that replicate ('' when its walk succeeded)."""
+        return _capi.genealogy_message(int(self.status[i]), int(self.status_arg[i]))
+
+    def total(self):
+        """Lineages alive at every grid time, [n, T] int64: ``values`` summed over populations and classes."""
+        return self.values.sum(axis=(-1, -2), dtype=np.int64)
+
+    def sampled_share(self, pv):
+        """The share of the infectious hosts that are ancestors of the sample, [n, T, P, V] float64: ``values / pv.values`` for the
+        :class:`Prevalence` ``pv`` of the same replicates, grid and variants; NaN where ``pv.values`` is not positive."""
+        if pv.values is None or self.values is None or pv.values.shape != self.values.shape:
+            raise ValueError("sampled_share needs the values of a prevalence() call on the same replicates, grid and variants")
+        out = np.full(self.values.shape, np.nan, dtype=np.float64)
+        np.divide(self.values, pv.values, out=out, where=pv.values > 0)
+        return out
+
+
 class Susceptibles:
     """What ``Ensemble.susceptibles`` returns: susceptible hosts per selected replicate, grid time, population and class of
     susceptibility groups.
@@ -662,19 +697,7 @@ class Ensemble:
             if c.ev_first_new != 0:
                 raise ValueError("replicate %d: its chain does not start in the last call's device log (the model held %d events "
                                  "when the ensemble started); use genealogy(r, seed)" % (r, c.ev_first_new))
-        if seed is not None and not np.isscalar(seed):
-            seeds = np.ascontiguousarray(seed, dtype=np.int64).ravel()
-            if len(seeds) != n:
-                raise ValueError("one seed per selected replicate: got %d for %d" % (len(seeds), n))
-        rng = np.zeros((max(n, 1), 4), dtype=np.uint64)
-        pos = (C.c_uint64 * 4)()
-        for i, (r, c) in enumerate(zip(reps, counters)):   # the start of every walk, as genealogy(r, seed) finds it
-            if seed is None:
-                att, draws = (int(c.reserved[1]), 2 * int(c.reserved[2])) if c.reserved[1] >= 0 else (0, 0)
-                lib.vgx_rng_position(int(self.seeds[r]), att, draws, C.byref(pos))
-            else:
-                lib.vgx_rng_position(int(seed) if np.isscalar(seed) else int(seeds[i]), 0, 0, C.byref(pos))
-            rng[i] = list(pos)
+        rng = self._walk_starts(reps, counters, seed)
         b = GenealogyBatch(reps)
         io = _capi.VgxGenealogiesIO()
         io.n = n
@@ -957,10 +980,10 @@ class Ensemble:
             raise ValueError("replicates must be distinct")
         return reps
 
-    def _block_summary(self, summary, reps, cols, scenario_of, n_scenarios):
+    def _block_summary(self, summary, reps, cols, scenario_of, n_scenarios, leave_out=None):
         """The ``summary=`` dict of ``incidence()``, ``tau_incidence()``, ``prevalence()`` and ``tau_prevalence()`` checked and turned into the
         (io, finish) of ``_summary_request`` over the selected replicates' block with columns of the shape ``cols``;
-        (None, None) without one."""
+        (None, None) without one.  ``leave_out`` [R] bool: replicates that are in no group, whatever ``by`` says."""
         if summary is None:
             return None, None
         unknown = set(summary) - {"quantiles", "by", "method"}
@@ -969,6 +992,8 @@ class Ensemble:
         method = summary.get("method", 'linear')
         q = _summary_quantiles(summary.get("quantiles", (0.025, 0.5, 0.975)), method)
         group_of, G = _summary_groups(summary.get("by", 'auto'), None, self.R, scenario_of, n_scenarios)
+        if leave_out is not None:
+            group_of[leave_out] = -1
         return _summary_request(np.ascontiguousarray(group_of[reps]), G, q, method, cols)
 
     def _incidence_request(self, io, e, replicates, haplotypes, summary, counts, dtype, scenario_of, n_scenarios):
@@ -1201,6 +1226,91 @@ class Ensemble:
         pv.passes, pv.kernel_ms, pv.clock_ms, pv.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
         return pv
 
+    def _walk_starts(self, reps, counters, seed):
+        """The generator start of every selected replicate's backward walk, [n, 4] uint64, as ``genealogy(r, seed)`` finds it:
+        ``seed`` None (the replicate continues its own simulation stream), an int, or one seed per selected replicate."""
+        lib, n = self.engine.lib, len(reps)
+        if seed is not None and not np.isscalar(seed):
+            seeds = np.ascontiguousarray(seed, dtype=np.int64).ravel()
+            if len(seeds) != n:
+                raise ValueError("one seed per selected replicate: got %d for %d" % (len(seeds), n))
+        rng = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        pos = (C.c_uint64 * 4)()
+        for i, (r, c) in enumerate(zip(reps, counters)):
+            if seed is None:
+                att, draws = (int(c.reserved[1]), 2 * int(c.reserved[2])) if c.reserved[1] >= 0 else (0, 0)
+                lib.vgx_rng_position(int(self.seeds[r]), att, draws, C.byref(pos))
+            else:
+                lib.vgx_rng_position(int(seed) if np.isscalar(seed) else int(seeds[i]), 0, 0, C.byref(pos))
+            rng[i] = list(pos)
+        return rng
+
+    def lineages(self, times=None, points=None, window=None, variants=None, seed=None, replicates=None, summary=None, values=True):
+        """Ancestral lineages of the sampled cases per grid time, population and variant class of every selected replicate of the
+        last direct ``simulate(record_events=True)`` call, on ONE grid for all replicates and on the device
+        (``vgx_get_lineages``): the lineages-through-time curve of every replicate's tree, structured by population and variant.
+        The walk is that of ``genealogies(seed, replicates)``, with the same draws, status and generator afterwards, and logs
+        where it changes a lineage list (also where a migration moves a lineage without coalescing, and the haplotype a lineage
+        carries, neither of which ``genealogies()`` returns); a tile-parallel pass bins the logs on the grid and a scan sums the
+        intervals up.  Returns a :class:`Lineages`.
+
+        The grid (``times``, or ``points`` and ``window``) and ``variants`` as ``prevalence()`` takes them; ``seed`` and
+        ``replicates`` as ``genealogies()``.  A replicate whose walk fails (fewer than two samples, lineages that never coalesce,
+        ...) gets its status and zeros and does not fail the call.  ``summary``: a dict of ``quantiles``, ``by`` and ``method`` as
+        ``trajectory_summary`` takes them; replicates with fewer than two samples are left out of its groups, any other failed
+        walk inside a group refuses the summary (after the values are there: the exception carries them as ``.lineages``); with
+        ``values=False`` the block itself is not copied to the host.  Direct chains only."""
+        g = _prevalence_grid(times, points, window)
+        if self._last_call is None:
+            raise ValueError("lineages() needs a direct simulate(record_events=True) call first")
+        if self._last_call[0] != 'direct':
+            raise ValueError("lineages() walks direct chains only: the last call was simulate_tau")
+        if not self._last_call[1]:
+            raise ValueError("lineages() needs the event log: the last call had record_events=False")
+        eng = self.engine
+        reps = self._selected_replicates(replicates)
+        counters = [eng.counters(int(r)) for r in reps]
+        for r, c in zip(reps, counters):
+            if c.ev_first_new != 0:
+                raise ValueError("replicate %d: its chain does not start in the last call's device log (the model held %d events "
+                                 "when the ensemble started)" % (r, c.ev_first_new))
+        rng = self._walk_starts(reps, counters, seed)
+        # replicates with fewer than two samples are known from the counters before any walk: they are in no group of the summary
+        few = np.zeros(self.R, dtype=bool)
+        few[reps] = [c.reserved[4] < 2 for c in counters]
+        reps, n, vo, V, T, P, sio, done = self._prevalence_request(g, variants, reps, summary, values, 4, self.scenario_of,
+                                                                   len(self.scenarios) if self.scenarios is not None else 1, leave_out=few)
+        block = np.zeros((n, T, P, V), dtype=np.int32) if values else None
+        root = np.zeros((max(n, 1), P, V), dtype=np.int32)
+        per = {k: np.zeros(max(n, 1), dtype=np.int64) for k in ("status", "status_arg", "records")}
+        rng_out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        i32, u64 = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+        io = _capi.VgxLineagesIO()
+        io.n, io.replicates, io.rng_state = n, _capi._p(reps), rng.ctypes.data_as(u64)
+        io.T, io.grid, io.V, io.variant_of = T, _capi._p(g), V, vo.ctypes.data_as(i32)
+        io.values = block.ctypes.data_as(i32) if values and n else None
+        io.root = root.ctypes.data_as(i32)
+        io.status, io.status_arg, io.records = _capi._p(per["status"]), _capi._p(per["status_arg"]), _capi._p(per["records"])
+        io.rng_out = rng_out.ctypes.data_as(u64)
+        io.summary = C.pointer(sio) if sio is not None and n else None
+        rc = eng.lib.vgx_get_lineages(eng.handle, C.byref(io))
+        ln = Lineages()
+        ln.values, ln.root, ln.times, ln.variant_of, ln.replicates = block, root[:n], g, vo, reps
+        ln.status, ln.status_arg, ln.records = per["status"][:n], per["status_arg"][:n], per["records"][:n]
+        ln.rng_raw = np.zeros((n, 6), dtype=np.uint64)
+        ln.rng_raw[:, :4] = rng_out[:n]
+        ln.summary = None
+        ln.passes, ln.kernel_ms, ln.clock_ms, ln.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
+        ln.stage_ms = tuple(io.kernel_ms)
+        try:
+            eng._check(rc)
+        except _capi.VgxError as err:
+            if sio is not None and ": summary: " in str(err):   # refused after values, root and status were delivered
+                err.lineages = ln
+            raise
+        ln.summary = done() if done is not None else None
+        return ln
+
     def milestones(self, variants=None, thresholds=(), replicates=None):
         """Peaks, first passages and extinctions of every selected replicate of the last direct ``simulate(record_events=True)``
         call, per population, over all populations and per variant class, exact over every event and on the device
@@ -1297,14 +1407,15 @@ class Ensemble:
         ms.passes, ms.kernel_ms, ms.clock_ms, ms.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
         return ms
 
-    def _prevalence_request(self, g, variants, replicates, summary, values, cell_bytes, scenario_of, n_scenarios):
+    def _prevalence_request(self, g, variants, replicates, summary, values, cell_bytes, scenario_of, n_scenarios, leave_out=None):
         """What ``prevalence()`` and ``tau_prevalence()`` share: the checks on ``replicates``, ``variants``, the LDS limit (cells of
         ``cell_bytes`` bytes), ``summary`` and ``values`` (ValueError before the library is called).  Returns (replicates, n,
         variant_of, V, T, P, the summary's io, its finish)."""
         return self._class_block_request(g, _capi.variant_map, variants, self.model.hapNum, replicates, summary, values, cell_bytes,
-                                         scenario_of, n_scenarios)
+                                         scenario_of, n_scenarios, leave_out)
 
-    def _class_block_request(self, g, class_map, classes, members, replicates, summary, values, cell_bytes, scenario_of, n_scenarios):
+    def _class_block_request(self, g, class_map, classes, members, replicates, summary, values, cell_bytes, scenario_of, n_scenarios,
+                             leave_out=None):
         """The request checks of the calls that return a [n, T, P, classes] block (``prevalence``, ``susceptibles`` and their tau
         forms): ``class_map(classes, members)`` is ``_capi.variant_map`` over the haplotypes or ``_capi.group_map`` over the
         susceptibility groups."""
@@ -1314,7 +1425,7 @@ class Ensemble:
         if cell_bytes * P * V > 65536:
             raise ValueError("%d populations x %d classes need %d bytes of cells, above the 65536 bytes of LDS a counting workgroup may use"
                              % (P, V, cell_bytes * P * V))
-        sio, done = self._block_summary(summary, reps, (T, P, V), scenario_of, n_scenarios)
+        sio, done = self._block_summary(summary, reps, (T, P, V), scenario_of, n_scenarios, leave_out)
         if summary is None and not values:
             raise ValueError("values=False needs summary=: the call would return nothing")
         return reps, len(reps), vo, V, T, P, sio, done
