@@ -163,8 +163,8 @@ typedef struct vgx_counters {
     int64_t error;                 /* VGX_* code raised inside the kernel for this replicate */
     int64_t multievent_rows;       /* tau: rows appended to the multievent log by this call */
     int64_t reserved[5];           /* [0] tau: events drawn; direct: [1] index of the last attempt that drew random
-                                      numbers (-1 none), [2] its loop iterations (2 uniforms each), [4] sCounter (the
-                                      cases sampled); [3] tau: tries of the halving loop left out as certain rejections */
+                                      numbers (-1 none), [2] its loop iterations (2 uniforms each); both: [4] sCounter
+                                      (the cases sampled); [3] tau: tries of the halving loop left out as certain rejections */
 } vgx_counters;
 
 /* ---- lifecycle ------------------------------------------------------------------------------ */
@@ -757,6 +757,51 @@ int vgx_get_lineages(vgx_engine *e, vgx_lineages_io *io);
  * the message vgx_get_genealogy reports; a bad grid, V or variant_of and the LDS budget are refused as vgx_get_lineages does. */
 int vgx_test_lineages(vgx_genealogy_io *io, const double *grid, int64_t T, const int32_t *variant_of, int64_t V, int64_t tile,
                       int32_t *values, int32_t *root, int64_t *records, char *errbuf, int64_t errcap);
+
+/* The same lineages for many replicates of the last vgx_simulate_tau call (with the event log), on the device.
+ * The walk is that of vgx_get_tau_genealogies over the same chain (`prefix` as that call takes it: the model's chain before the
+ * tau call, shared by every replicate that did not restart, then the replicate's own steps as canonical rows): the same draws in
+ * the same order from rng_state, the same status and status_arg and the same six generator words afterwards (rng_out).  Where the
+ * row rule changes a lineage list it appends a lineage record with the meanings above: a BIRTH row a SPLIT per coalescence, a
+ * SAMPLING row a TIP per tip, a MUTATION row a MUTATION per lineage taken, a MIGRATION row a SPLIT (pop = the row's newPopulation)
+ * per coalescence and a MOVE per lineage moved without coalescing; prefix events of direct type as vgx_get_lineages.  `ev` is the
+ * chain's EVENT index: prefix events 0 .. prefix->ev_ptr - 1, the replicate's own step k is prefix->ev_ptr + k (k alone for a
+ * replicate that restarted), so all records of a step carry the same ev.  A log holds at most (2 sCounter - 1) records plus, per
+ * MUTATION and MIGRATION row, min(num, sCounter), summed over the replicate's raw rows on the device, plus the same over the prefix's
+ * rows (a direct event counts 1); a full log sets status 9.
+ * The grid's cuts are formed in event-index space: cut[j] = first event index i with grid[j] < t_i (strict; the position never
+ * goes back) over the prefix's event times, then the replicate's own step times, so a grid time exactly at a step's time has the
+ * whole step applied, as vgx_get_tau_prevalence has it.  The prefix part of the loop runs once per call.  values, root, summary,
+ * `values == NULL`, VGX_LINEAGES_TILE_RECORDS and VGX_GENEALOGY_CHUNK_BYTES as vgx_get_lineages; the binning and suffix-sum kernels
+ * are that call's.  kernel_ms: the canonicalise, walk, binning and suffix-sum kernels of ms[0] apart; ms[1] is the host's cuts.
+ * Preconditions and their refusals as vgx_get_tau_genealogies (the last call was vgx_simulate_tau, it recorded rows, the prefix
+ * length, prefix rows inside the model); the grid, class and LDS refusals of vgx_get_lineages; replicates out of range or given
+ * twice; a chain of 2^30 events or more.  All worded behind "vgx_get_tau_lineages: ". */
+typedef struct vgx_tau_lineages_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    const uint64_t *rng_state;                   /* [n][6] start of every walk: PCG64 state hi, lo, increment hi, lo, has_uint32, uinteger */
+    int64_t T; const double *grid;               /* [T] strictly increasing, finite */
+    int64_t V; const int32_t *variant_of;        /* [hapNum], values in [-1, V) */
+    int32_t *values;                             /* NULL or host [n][T][P][V] */
+    int32_t *root;                               /* host [n][P][V] */
+    int64_t *status, *status_arg;                /* [n] 0 or why the walk stopped, as vgx_tau_genealogies_io */
+    int64_t *records;                            /* [n] lineage records of the walk (0 for a walk that failed) */
+    uint64_t *rng_out;                           /* [n][6] generator state after the walk */
+    vgx_traj_summary_io *summary;                /* NULL or the summary of [n][T*P*V]; group_of has n entries */
+    int64_t passes;                              /* out: walk passes */
+    double ms[3];                                /* out: kernels (device time), host cuts, whole call */
+    double kernel_ms[4];                         /* out: the canonicalise, walk, binning and suffix-sum kernels of ms[0] apart */
+} vgx_tau_lineages_io;
+int vgx_get_tau_lineages(vgx_engine *e, vgx_tau_lineages_io *io, const vgx_tau_genealogy_prefix *prefix);
+/* Test hook: the walk of vgx_get_tau_lineages with its observer, the tile walk and the suffix sum compiled for the host, on the
+ * chain, state and generator of a vgx_genealogy_io, with the chain handling of vgx_test_tau_genealogy_walk (the trailing MULTITYPE
+ * events play the own steps, their rows in any order and granularity; `sites` as there).  The cuts come from the chain's event
+ * times.  infectious is walked back in place and the generator (all six words) advanced as vgx_test_tau_genealogy_walk does; the
+ * tree, mutation and migration outputs are not read or written.  values [T][P][V] and root [P][V] are overwritten, *records gets
+ * the number of lineage records.  A walk that fails is refused with the message vgx_test_tau_genealogy_walk reports; a bad grid, V
+ * or variant_of and the LDS budget are refused as vgx_get_tau_lineages does. */
+int vgx_test_tau_lineages(vgx_genealogy_io *io, int64_t sites, const double *grid, int64_t T, const int32_t *variant_of, int64_t V, int64_t tile,
+                          int32_t *values, int32_t *root, int64_t *records, char *errbuf, int64_t errcap);
 
 /* The same counts for many replicates of the last vgx_simulate_tau call (with the event log), on the device.
  * A tau replicate's chain is a list of weighted rows (num, type, haplotype, population, newHaplotype, newPopulation), six int64:

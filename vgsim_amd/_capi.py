@@ -149,6 +149,10 @@ class VgxLineagesIO(C.Structure):
                 ("summary", C.POINTER(VgxTrajSummaryIO)), ("passes", C.c_int64), ("ms", C.c_double * 3), ("kernel_ms", C.c_double * 3)]
 
 
+class VgxTauLineagesIO(C.Structure):   # VgxLineagesIO with six generator words per walk and four kernel stages
+    _fields_ = VgxLineagesIO._fields_[:-1] + [("kernel_ms", C.c_double * 4)]
+
+
 class VgxFlowsIO(C.Structure):
     _fields_ = [("n", C.c_int64), ("replicates", _I), ("T", C.c_int64), ("edges", _F), ("V", C.c_int64), ("variant_of", C.POINTER(C.c_int32)),
                 ("within", C.c_int32), ("counts", C.POINTER(C.c_int32)), ("outside", _I), ("summary", C.POINTER(VgxTrajSummaryIO)),
@@ -340,6 +344,9 @@ SIGNATURES = {
     "vgx_get_lineages": (C.c_int, [_H, C.POINTER(VgxLineagesIO)]),
     "vgx_test_lineages": (C.c_int, [C.POINTER(VgxGenealogyIO), _F, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int64, C.POINTER(C.c_int32),
                                     C.POINTER(C.c_int32), _I, C.c_char_p, C.c_int64]),
+    "vgx_get_tau_lineages": (C.c_int, [_H, C.POINTER(VgxTauLineagesIO), C.POINTER(VgxTauGenealogyPrefix)]),
+    "vgx_test_tau_lineages": (C.c_int, [C.POINTER(VgxGenealogyIO), C.c_int64, _F, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int64,
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, C.c_char_p, C.c_int64]),
     "vgx_get_flows": (C.c_int, [_H, C.POINTER(VgxFlowsIO)]),
     "vgx_test_flows": (C.c_int, [_F, _I, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, _F, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int32,
                                  C.c_int64, C.c_int64, C.POINTER(C.c_int32), _I, _I, C.c_char_p, C.c_int64]),
@@ -1042,6 +1049,33 @@ def replay_lineages(m, seed, grid, variant_of, V, tile=0, rng_raw=None):
         raise ValueError(err.value.decode() or "vgx_test_lineages failed")
     return {"values": values, "root": root, "records": int(records[0]), "nodes_used": int(io.nodes_used),
             "rng_raw": tuple(int(io.rng_state[i]) for i in range(4)) + (0, 0)}
+
+
+def replay_tau_lineages(m, seed, grid, variant_of, V, tile=0, rng_position=None, rng_raw=None):
+    """The values of ``Ensemble.tau_lineages`` for the chain and state of one host model through ``vgx_test_tau_lineages``: the tau
+    walk of the device pass with its observer, the tile walk and the suffix sum (vgx_gwalk_tau.h, vgx_lineages.h) compiled for
+    the host, tile after tile of ``tile`` lineage records (0: the default); no GPU.  The chain as ``tau_genealogy_walk`` takes it
+    (its trailing MULTITYPE events play a replicate's own steps, rows in any order and granularity); ``seed``, ``rng_position``
+    and ``rng_raw`` as ``get_genealogy``; ``variant_of`` [hapNum] with values in [-1, V).  Walks ``m.infectious`` back in place.
+    Returns the dict of ``replay_lineages`` with all six words in ``rng_raw``; a refusal or a walk that fails raises
+    ``ValueError`` with the library's message (a failed walk: the text ``tau_genealogy_walk`` raises)."""
+    grid = np.ascontiguousarray(grid, dtype=np.float64)
+    T, P, V = len(grid), int(m.popNum), int(V)
+    vo = np.ascontiguousarray(variant_of, dtype=np.int32)
+    if len(vo) != int(m.hapNum):
+        raise ValueError("variant_of must hold hapNum values")
+    io, _, _ = _genealogy_chain(m, seed, rng_position, rng_raw)
+    values = np.zeros((max(T, 1), max(P, 1), max(V, 1)), dtype=np.int32)
+    root = np.zeros((max(P, 1), max(V, 1)), dtype=np.int32)
+    records = np.zeros(1, dtype=np.int64)
+    err = C.create_string_buffer(512)
+    i32 = C.POINTER(C.c_int32)
+    rc = load_library().vgx_test_tau_lineages(C.byref(io), int(m.sites), _p(grid), T, vo.ctypes.data_as(i32), V, int(tile),
+                                              values.ctypes.data_as(i32), root.ctypes.data_as(i32), _p(records), err, 512)
+    if rc != VGX_OK:
+        raise ValueError(err.value.decode() or "vgx_test_tau_lineages failed")
+    return {"values": values, "root": root, "records": int(records[0]), "nodes_used": int(io.nodes_used),
+            "rng_raw": tuple(int(io.rng_state[i]) for i in range(4)) + (int(io.rng_has_uint32), int(io.rng_uinteger))}
 
 
 FLOW_FORMS = {None: 0, 'auto': 0, 'dense': 1, 'split': 2}   # VGX_FLOW_AUTO, VGX_FLOW_DENSE, VGX_FLOW_SPLIT

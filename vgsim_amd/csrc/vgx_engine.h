@@ -1,6 +1,6 @@
 // vgx_engine.h — the engine behind the C ABI of include/vgx.h, as the host drivers of libvgx.so share it: the engine structure,
 // its device buffers and error helpers, the launchers defined next to their kernels.  Host-only; included by the host drivers
-// (vgx_api.hip, vgx_direct_run.hip, vgx_tau_run.hip, vgx_tau_timelines.hip, vgx_tau_genealogies.hip) alone. Helpers that several of them use are `inline` here; direct_core and the
+// (vgx_api.hip, vgx_direct_run.hip, vgx_tau_run.hip, vgx_tau_timelines.hip, vgx_tau_genealogies.hip, vgx_tau_lineages.hip) alone. Helpers that several of them use are `inline` here; direct_core and the
 // choice of its kernel have their one definition in vgx_direct_run.hip, host_clock in vgx_api.hip.
 #pragma once
 #include <hip/hip_runtime.h>

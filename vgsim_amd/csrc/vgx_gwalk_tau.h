@@ -213,8 +213,13 @@ VGX_HD int vgx_gt_prepass(VgxGwRep &w, const VgxGtChain &c) {
     return acc <= w.arena_cap ? VGX_GW_OK : VGX_GW_WORKSPACE;
 }
 
-// one multievent row (pyx:873-994) of chain event e; `fresh`: scratch of 2 sCounter - 1 entries; false = the walk stops
-VGX_HD bool vgx_gt_row(VgxGwWalk &k, VgxGtGen &gen, int32_t *fresh, const VgxGtRow &row, int64_t e) {
+// one multievent row (pyx:873-994) of chain event e; `fresh`: scratch of 2 sCounter - 1 entries; false = the walk stops.  The
+// observer (vgx_gwalk.h) is told where the row changes a lineage list, with the meanings of VgxGwWalkT::single: split at every
+// coalescence of a BIRTH row and of a MIGRATION row (there with pop = the row's newPopulation, where the lineage it takes away
+// lay), tip at every tip of a SAMPLING row, mutation at every lineage a MUTATION row takes, move at every lineage a MIGRATION row
+// moves without coalescing.  All records of a step carry the same e.
+template <class Obs>
+VGX_HD bool vgx_gt_row(VgxGwWalkT<Obs> &k, VgxGtGen &gen, int32_t *fresh, const VgxGtRow &row, int64_t e) {
     VgxGwRep &w = k.w;
     const int64_t num = row.num, type = row.type, hap = row.hap, pop = row.pop, nh = row.nh, np = row.np, H = w.H;
     int64_t nf = 0, sa = -1;                       // arrivals of this row and their compartment
@@ -252,6 +257,7 @@ VGX_HD bool vgx_gt_row(VgxGwWalk &k, VgxGtGen &gen, int32_t *fresh, const VgxGtR
             w.len[s] -= 2;
             k.parent(id1, id3); k.parent(id2, id3);
             k.node(pop, e);
+            k.obs.split(e, hap, pop);
             lbs -= 2;
         }
         ds0 = s; dv0 = -num;
@@ -265,6 +271,7 @@ VGX_HD bool vgx_gt_row(VgxGwWalk &k, VgxGtGen &gen, int32_t *fresh, const VgxGtR
             if (k.ptr >= k.nodes) { k.res.status = VGX_GW_TREE_OVERFLOW; return false; }
             if (!arrive(k.ptr)) return false;
             k.node(pop, e);
+            k.obs.tip(e, hap, pop);
         }
         break;
     case VGX_GW_MUTATION: {
@@ -279,6 +286,7 @@ VGX_HD bool vgx_gt_row(VgxGwWalk &k, VgxGtGen &gen, int32_t *fresh, const VgxGtR
             w.len[s] -= 1;
             if (!arrive(id1)) return false;
             if (!k.mutation(id1, hap, nh, e)) return false;
+            k.obs.mutation(e, hap, pop, nh);
             lbs -= 1;
         }
         ds0 = s; dv0 = -num;
@@ -306,6 +314,7 @@ VGX_HD bool vgx_gt_row(VgxGwWalk &k, VgxGtGen &gen, int32_t *fresh, const VgxGtR
                 k.parent(idt, id3); k.parent(ids, id3);
                 k.node(pop, e);
                 if (!k.migration(idt, e, pop, np)) return false;
+                k.obs.split(e, hap, np);
                 lbss -= 1;
                 lbs -= 1;
             }
@@ -314,6 +323,7 @@ VGX_HD bool vgx_gt_row(VgxGwWalk &k, VgxGtGen &gen, int32_t *fresh, const VgxGtR
                 if (!arrive(k.at(st, nt))) return false;
                 k.at(st, nt) = k.at(st, lbs - 1);
                 w.len[st] -= 1;
+                k.obs.move(e, hap, pop, np);
                 lbs -= 1;
             }
         }
@@ -331,13 +341,19 @@ VGX_HD bool vgx_gt_row(VgxGwWalk &k, VgxGtGen &gen, int32_t *fresh, const VgxGtR
 }
 
 // The walk over the chain from the last event back, then the closing pass (pyx:998-1000).  The table holds the pre-pass's
-// compartments with their final infectious counts.  `gen` advances by the draws made.
-VGX_HD void vgx_gt_walk(VgxGwRep &w, const VgxGtChain &c, int32_t *fresh, VgxGtGen &gen, VgxGwResult &res) {
+// compartments with their final infectious counts.  `gen` advances by the draws made.  The draws, their order and the generator
+// afterwards do not depend on the observer; prefix events of direct type reach it through VgxGwWalkT::single, the closing pass
+// tells it nothing, and an observer without records leaves tree_pop, node_ev and the mutation and migration tables untouched.
+template <class Obs = VgxGwNoObserver>
+VGX_HD void vgx_gt_walk(VgxGwRep &w, const VgxGtChain &c, int32_t *fresh, VgxGtGen &gen, VgxGwResult &res, Obs obs = Obs{}) {
     res.status = VGX_GW_OK; res.arg = 0; res.nodes_used = 0; res.mut_n = 0; res.mig_n = 0;
     if (w.sCounter < 2) { res.status = VGX_GW_FEW_SAMPLES; return; }
     const int64_t nodes = 2 * w.sCounter - 1;
-    for (int64_t i = 0; i < nodes; i++) { w.tree[i] = 0; w.tree_pop[i] = 0; w.node_ev[i] = -1; }
-    VgxGwWalk k{w, gen.g, res, 0, nodes};
+    for (int64_t i = 0; i < nodes; i++) {
+        w.tree[i] = 0;
+        if (Obs::records) { w.tree_pop[i] = 0; w.node_ev[i] = -1; }
+    }
+    VgxGwWalkT<Obs> k{w, gen.g, res, 0, nodes, obs};
     for (int64_t e = w.n_ev - 1; e >= 0; --e) {
         const VgxGtRow *r;
         int64_t n;
@@ -356,7 +372,7 @@ VGX_HD void vgx_gt_walk(VgxGwRep &w, const VgxGtChain &c, int32_t *fresh, VgxGtG
     for (int64_t i = 0; i < 2 * w.sCounter - 2; i++) {
         const int64_t par = w.tree[i];
         if (par < 0 || par >= nodes) { res.status = VGX_GW_NOT_COALESCED; res.arg = i; return; }
-        if (w.tree_pop[par] != w.tree_pop[i] && !k.migration(i, w.node_ev[i], w.tree_pop[par], w.tree_pop[i])) return;
+        if (Obs::records && w.tree_pop[par] != w.tree_pop[i] && !k.migration(i, w.node_ev[i], w.tree_pop[par], w.tree_pop[i])) return;
     }
 }
 

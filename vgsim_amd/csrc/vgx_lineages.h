@@ -31,6 +31,13 @@ VGX_HD int64_t vgx_ln_capacity(int64_t sCounter, int64_t n_mut, int64_t n_mig) {
     return sCounter >= 2 ? 2 * sCounter - 1 + n_mut + n_mig : 0;
 }
 
+// lineage records a TAU chain can write (vgx_tau_lineages.h): its nodes and, for every MUTATION or MIGRATION row, the lineages the
+// row can take, min(num, sCounter), where a prefix event of direct type counts 1.  own_*: those sums over the replicate's raw rows
+// (merging rows can only lower them), pre_*: over the prefix's rows, 0 for a replicate that restarted.  None below two samples.
+VGX_HD int64_t vgx_ln_tau_capacity(int64_t sCounter, int64_t own_mut, int64_t own_mig, int64_t pre_mut, int64_t pre_mig) {
+    return sCounter >= 2 ? 2 * sCounter - 1 + own_mut + pre_mut + own_mig + pre_mig : 0;
+}
+
 // one replicate's lineage log: `n` records written, `dropped` that found it full (a walk that ends with status 0 drops none)
 struct VgxLnLog {
     int32_t *rec;   // [cap][6], 8-byte aligned

@@ -319,7 +319,9 @@ class Lineages:
     why the walk of row i stopped, as :class:`GenealogyBatch` (``message(i)``; such a row holds zeros), ``ok`` = ``status == 0``;
     ``records`` [n] the lineage records of every walk; ``rng_raw`` [n, 6] the generator after the walk, that of
     ``genealogies()``; ``summary`` a :class:`TrajectorySummary` over the [T, P, V] columns, or None; ``passes`` (walk passes),
-    ``kernel_ms`` (``stage_ms``: walk, binning and suffix sum apart), ``clock_ms``, ``wall_ms``."""
+    ``kernel_ms`` (``stage_ms``: walk, binning and suffix sum apart), ``clock_ms``, ``wall_ms``.  ``Ensemble.tau_lineages`` returns
+    the same class for tau replicates: ``rng_raw`` is then that of ``tau_genealogies()`` (all six words used), ``stage_ms`` has
+    four entries (canonicalise, walk, binning, suffix sum) and ``clock_ms`` is the host's cuts."""
 
     @property
     def ok(self):
@@ -740,8 +742,27 @@ class Ensemble:
         tau call.  Returns the dict of ``_capi.get_genealogy``; a chain with a row the reference's pass cannot take (numpy's
         hypergeometric would raise on it) raises the text of the device pass's status 12 instead."""
         import copy
-        from ._model import Events, MultiEvents
         self._check_tau_genealogy_call("tau_genealogy()")
+        m = self._tau_chain_model(replicate)
+        # vgx_get_genealogy trusts its rows as the reference does: where numpy's hypergeometric would raise (more migrants than the
+        # source compartment holds, ...) or a transmission row draws more pairs than there are lineages, it reads and writes outside
+        # its lists.  Tau steps at very small counts write such rows.  The guarded walk of the device pass (its host instance) goes
+        # first on a copy of the counts: what it refuses is raised here with the device's text, and never reaches the host pass.
+        probe = copy.copy(m)
+        probe.infectious = m.infectious.copy()
+        try:
+            _capi.tau_genealogy_walk(probe, seed, rng_position=(0, 0))
+        except RuntimeError as e:
+            if str(e).startswith("vgx_get_tau_genealogies:"):
+                raise
+        return _capi.get_genealogy(m, seed, rng_position=(0, 0))
+
+    def _tau_chain_model(self, replicate):
+        """A host model with the final state and the WHOLE chain of one replicate of the last ``simulate_tau(record_events=True)``
+        call, as ``tau_genealogy`` walks it: the model's events and rows before the call (none for a replicate that restarted),
+        then the replicate's own steps with their rows in the reference's order.  A step of more rows than the device pass sorts
+        raises its status-10 text."""
+        from ._model import Events, MultiEvents
         eng = self.engine
         r = int(replicate)
         m = self.replicate_state(r)
@@ -775,18 +796,19 @@ class Ensemble:
                   **{name: np.concatenate((mv0[j][:k_pre], rows[name])) for j, name in enumerate(mv.COLUMNS)})
         m.events, m.multievents = ev, mv
         m.user_seed = int(self.seeds[r])
-        # vgx_get_genealogy trusts its rows as the reference does: where numpy's hypergeometric would raise (more migrants than the
-        # source compartment holds, ...) or a transmission row draws more pairs than there are lineages, it reads and writes outside
-        # its lists.  Tau steps at very small counts write such rows.  The guarded walk of the device pass (its host instance) goes
-        # first on a copy of the counts: what it refuses is raised here with the device's text, and never reaches the host pass.
-        probe = copy.copy(m)
-        probe.infectious = m.infectious.copy()
-        try:
-            _capi.tau_genealogy_walk(probe, seed, rng_position=(0, 0))
-        except RuntimeError as e:
-            if str(e).startswith("vgx_get_tau_genealogies:"):
-                raise
-        return _capi.get_genealogy(m, seed, rng_position=(0, 0))
+        return m
+
+    def _tau_genealogy_prefix_struct(self):
+        """The model's chain before the last tau call as ``vgx_get_tau_genealogies`` and ``vgx_get_tau_lineages`` take it."""
+        pre = _capi.VgxTauGenealogyPrefix()
+        ev, mv, _ = self._tau_prefix
+        pre.ev_ptr, pre.ev_times = len(ev[0]), _capi._p(ev[0])
+        for name, col in zip(("types", "haplotypes", "populations", "newHaplotypes", "newPopulations"), ev[1:]):
+            setattr(pre, "ev_" + name, _capi._p(col))
+        pre.mev_rows, pre.mev_times = len(mv[0]), _capi._p(self._tau_prefix_mev_times)
+        for name, col in zip(_capi.MEV_COLUMNS, mv):
+            setattr(pre, "mev_" + name, _capi._p(col))
+        return pre
 
     def tau_genealogies(self, seed=None, replicates=None):
         """The backward pass of every selected replicate of the last ``simulate_tau(record_events=True)`` call at once, on the
@@ -817,14 +839,7 @@ class Ensemble:
         for i, r in enumerate(reps):
             lib.vgx_rng_position(int(self.seeds[r]) if seed is None else int(seed) if np.isscalar(seed) else int(seeds[i]), 0, 0, C.byref(pos))
             rng[i, :4] = list(pos)
-        pre = _capi.VgxTauGenealogyPrefix()
-        ev, mv, _ = self._tau_prefix
-        pre.ev_ptr, pre.ev_times = len(ev[0]), _capi._p(ev[0])
-        for name, col in zip(("types", "haplotypes", "populations", "newHaplotypes", "newPopulations"), ev[1:]):
-            setattr(pre, "ev_" + name, _capi._p(col))
-        pre.mev_rows, pre.mev_times = len(mv[0]), _capi._p(self._tau_prefix_mev_times)
-        for name, col in zip(_capi.MEV_COLUMNS, mv):
-            setattr(pre, "mev_" + name, _capi._p(col))
+        pre = self._tau_genealogy_prefix_struct()
         b = GenealogyBatch(reps)
         io = _capi.VgxTauGenealogiesIO()
         io.n = n
@@ -1299,6 +1314,73 @@ class Ensemble:
         ln.status, ln.status_arg, ln.records = per["status"][:n], per["status_arg"][:n], per["records"][:n]
         ln.rng_raw = np.zeros((n, 6), dtype=np.uint64)
         ln.rng_raw[:, :4] = rng_out[:n]
+        ln.summary = None
+        ln.passes, ln.kernel_ms, ln.clock_ms, ln.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
+        ln.stage_ms = tuple(io.kernel_ms)
+        try:
+            eng._check(rc)
+        except _capi.VgxError as err:
+            if sio is not None and ": summary: " in str(err):   # refused after values, root and status were delivered
+                err.lineages = ln
+            raise
+        ln.summary = done() if done is not None else None
+        return ln
+
+    def tau_lineages(self, times=None, points=None, window=None, variants=None, seed=None, replicates=None, summary=None, values=True):
+        """``lineages()`` for the replicates of the last ``simulate_tau(record_events=True)`` call (``vgx_get_tau_lineages``): the
+        lineages-through-time curve of every tau replicate's tree, structured by population and variant, on ONE grid and on the
+        device.  The walk is that of ``tau_genealogies(seed, replicates)`` over the same chain (the model's chain before the
+        call, none for a replicate that restarted, then the replicate's own steps in the reference's row order), with the same
+        draws, status and six generator words afterwards; it logs where a row changes a lineage list, and the binning and
+        suffix-sum passes of ``lineages()`` turn the logs into the block.  All rows of a step share the step's time: a grid time
+        exactly at a step's time has the whole step applied, as ``tau_prevalence()`` has it.  Returns a :class:`Lineages`
+        (``stage_ms``: the canonicalise, walk, binning and suffix-sum kernels apart), so ``sampled_share(tau_prevalence(...))`` on
+        the same grid, replicates and variants works.
+
+        The grid, ``variants``, ``summary`` and ``values`` as ``lineages()``; ``seed`` and ``replicates`` as
+        ``tau_genealogies()`` (``seed=None`` starts every walk at ``(seeds[r], attempt 0, 0 draws)``).  A replicate whose walk
+        fails (fewer than two samples, a step of more than 8192 raw rows, ...) gets its status and zeros and does not fail the
+        call; replicates with fewer than two samples are left out of the summary's groups, any other failed walk inside a group
+        refuses the summary after the values are there (the exception carries them as ``.lineages``)."""
+        g = _prevalence_grid(times, points, window)
+        self._check_tau_genealogy_call("tau_lineages()")
+        eng, lib = self.engine, self.engine.lib
+        reps = self._selected_replicates(replicates)
+        n = len(reps)
+        if seed is not None and not np.isscalar(seed):
+            seeds = np.ascontiguousarray(seed, dtype=np.int64).ravel()
+            if len(seeds) != n:
+                raise ValueError("one seed per selected replicate: got %d for %d" % (len(seeds), n))
+        rng = np.zeros((max(n, 1), 6), dtype=np.uint64)
+        pos = (C.c_uint64 * 4)()
+        for i, r in enumerate(reps):
+            lib.vgx_rng_position(int(self.seeds[r]) if seed is None else int(seed) if np.isscalar(seed) else int(seeds[i]), 0, 0, C.byref(pos))
+            rng[i, :4] = list(pos)
+        few = None
+        if summary is not None:   # replicates with fewer than two samples are known from the counters before any walk: they are in no group
+            few = np.zeros(self.R, dtype=bool)
+            few[reps] = [eng.counters(int(r)).reserved[4] < 2 for r in reps]
+        reps, n, vo, V, T, P, sio, done = self._prevalence_request(g, variants, reps, summary, values, 4, self.scenario_of,
+                                                                   len(self.scenarios) if self.scenarios is not None else 1, leave_out=few)
+        pre = self._tau_genealogy_prefix_struct()
+        block = np.zeros((n, T, P, V), dtype=np.int32) if values else None
+        root = np.zeros((max(n, 1), P, V), dtype=np.int32)
+        per = {k: np.zeros(max(n, 1), dtype=np.int64) for k in ("status", "status_arg", "records")}
+        rng_out = np.zeros((max(n, 1), 6), dtype=np.uint64)
+        i32, u64 = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+        io = _capi.VgxTauLineagesIO()
+        io.n, io.replicates, io.rng_state = n, _capi._p(reps), rng.ctypes.data_as(u64)
+        io.T, io.grid, io.V, io.variant_of = T, _capi._p(g), V, vo.ctypes.data_as(i32)
+        io.values = block.ctypes.data_as(i32) if values and n else None
+        io.root = root.ctypes.data_as(i32)
+        io.status, io.status_arg, io.records = _capi._p(per["status"]), _capi._p(per["status_arg"]), _capi._p(per["records"])
+        io.rng_out = rng_out.ctypes.data_as(u64)
+        io.summary = C.pointer(sio) if sio is not None and n else None
+        rc = lib.vgx_get_tau_lineages(eng.handle, C.byref(io), C.byref(pre))
+        ln = Lineages()
+        ln.values, ln.root, ln.times, ln.variant_of, ln.replicates = block, root[:n], g, vo, reps
+        ln.status, ln.status_arg, ln.records = per["status"][:n], per["status_arg"][:n], per["records"][:n]
+        ln.rng_raw = rng_out[:n]
         ln.summary = None
         ln.passes, ln.kernel_ms, ln.clock_ms, ln.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
         ln.stage_ms = tuple(io.kernel_ms)
