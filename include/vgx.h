@@ -803,6 +803,73 @@ int vgx_get_tau_lineages(vgx_engine *e, vgx_tau_lineages_io *io, const vgx_tau_g
 int vgx_test_tau_lineages(vgx_genealogy_io *io, int64_t sites, const double *grid, int64_t T, const int32_t *variant_of, int64_t V, int64_t tile,
                           int32_t *values, int32_t *root, int64_t *records, char *errbuf, int64_t errcap);
 
+/* ---- tree events: samples, coalescences, mutations and moves of the sampled trees per interval of a common grid --- */
+/* The tree's counterpart of vgx_get_incidence and vgx_get_flows: the lineage log of vgx_get_lineages, written by the
+ * same walk, binned with the kinds kept apart.  With c(h) = variant_of[h], read forward in time, a lineage record counts +1 at the
+ * cells (pop, class, channel)
+ *   0 samples           TIP                                                      (pop, c(hap))
+ *   1 coalescences      SPLIT (pop of a coalescing MIGRATION: its newPopulation) (pop, c(hap))
+ *   2 mutations_within  MUTATION with c(hap) == c(newHap) >= 0                   (pop, c(hap))
+ *   3 mutations_out     MUTATION with c(hap) >= 0 and c(newHap) != c(hap)        (pop, c(hap))
+ *   4 mutations_in      MUTATION with c(newHap) >= 0 and c(newHap) != c(hap)     (pop, c(newHap))
+ *   5 departures        MOVE with c(hap) >= 0                                    (pop, c(hap))
+ *   6 arrivals          MOVE with c(hap) >= 0 and newPop inside [0, popNum)      (newPop, c(hap))
+ * and nowhere for a class of -1, a population or haplotype outside the model or another kind, so that for every interval and cell
+ *   coalescences - samples + mutations_in - mutations_out + arrivals - departures == the net change vgx_get_lineages sums up:
+ * lineages' root = -(net of all intervals), values[j] = root + net of the intervals 0 .. j.
+ * The grid, its cuts and the intervals are vgx_get_lineages': interval i = 0 .. T holds the records with cut[i-1] <= ev < cut[i],
+ * interval T being the tail after the last grid time, an ordinary row of
+ *   counts[r][i][p][c][k]   int32 [n][T + 1][popNum][V][7]
+ * (int32: no cell counts more than a log holds, and the calls bound a log below 2^31 records).  A replicate whose walk fails gets
+ * its status and a row of zeros.  On the device a pass is the walk kernel of vgx_get_lineages and one binning kernel in its tile
+ * scheme (VGX_LINEAGES_TILE_RECORDS; 7 popNum V int32 cells in LDS); no scan follows.  All work after the cuts is integer addition:
+ * no value depends on the tile size, the launch geometry or the number of passes (VGX_GENEALOGY_CHUNK_BYTES).  `summary` is the
+ * column summary over `counts` as a matrix [n][(T + 1) * popNum * V * 7] where it lies, refused as vgx_get_lineages refuses it;
+ * `counts` may be NULL.  Preconditions, checks and refusals are those of vgx_get_lineages, worded behind "vgx_get_tree_events: ",
+ * and 7 * popNum * V * 4 bytes of cells above the 65536 bytes of LDS a binning workgroup may use. */
+typedef struct vgx_tree_events_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    const uint64_t *rng_state;                   /* [n][4] PCG64 start of every walk */
+    int64_t T; const double *grid;               /* [T] strictly increasing, finite */
+    int64_t V; const int32_t *variant_of;        /* [hapNum], values in [-1, V) */
+    int32_t *counts;                             /* NULL or host [n][T + 1][P][V][7] */
+    int64_t *status, *status_arg;                /* [n] 0 or why the walk stopped, as vgx_genealogies_io */
+    int64_t *records;                            /* [n] lineage records of the walk (0 for a walk that failed) */
+    uint64_t *rng_out;                           /* [n][4] generator state after the walk */
+    vgx_traj_summary_io *summary;                /* NULL or the summary of [n][(T+1)*P*V*7]; group_of has n entries */
+    int64_t passes;                              /* out: walk passes */
+    double ms[3];                                /* out: kernels (device time), host clock, whole call */
+    double kernel_ms[2];                         /* out: the walk and binning kernels of ms[0] apart */
+} vgx_tree_events_io;
+int vgx_get_tree_events(vgx_engine *e, vgx_tree_events_io *io);
+/* Test hook: vgx_test_lineages with the binning of vgx_get_tree_events (the same walk and observer, the host tile walk of
+ * vgx_tree_events.h, tile after tile of `tile` records, 0: the default).  counts [T + 1][P][V][7] is overwritten. */
+int vgx_test_tree_events(vgx_genealogy_io *io, const double *grid, int64_t T, const int32_t *variant_of, int64_t V, int64_t tile,
+                         int32_t *counts, int64_t *records, char *errbuf, int64_t errcap);
+
+/* The same counts for many replicates of the last vgx_simulate_tau call: the walk, chain, event indices, cuts, checks and refusals of
+ * vgx_get_tau_lineages (worded behind "vgx_get_tau_tree_events: ") with the binning kernel and the LDS limit of vgx_get_tree_events.
+ * All records of a step carry the step's event index, so a grid time exactly at a step's time has the whole step in the intervals
+ * up to it.  kernel_ms: the canonicalise, walk and binning kernels of ms[0] apart; ms[1] is the host's cuts. */
+typedef struct vgx_tau_tree_events_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    const uint64_t *rng_state;                   /* [n][6] start of every walk, as vgx_tau_lineages_io */
+    int64_t T; const double *grid;               /* [T] strictly increasing, finite */
+    int64_t V; const int32_t *variant_of;        /* [hapNum], values in [-1, V) */
+    int32_t *counts;                             /* NULL or host [n][T + 1][P][V][7] */
+    int64_t *status, *status_arg;                /* [n] 0 or why the walk stopped, as vgx_tau_genealogies_io */
+    int64_t *records;                            /* [n] lineage records of the walk (0 for a walk that failed) */
+    uint64_t *rng_out;                           /* [n][6] generator state after the walk */
+    vgx_traj_summary_io *summary;                /* NULL or the summary of [n][(T+1)*P*V*7]; group_of has n entries */
+    int64_t passes;                              /* out: walk passes */
+    double ms[3];                                /* out: kernels (device time), host cuts, whole call */
+    double kernel_ms[3];                         /* out: the canonicalise, walk and binning kernels of ms[0] apart */
+} vgx_tau_tree_events_io;
+int vgx_get_tau_tree_events(vgx_engine *e, vgx_tau_tree_events_io *io, const vgx_tau_genealogy_prefix *prefix);
+/* Test hook: vgx_test_tau_lineages with the binning of vgx_get_tau_tree_events.  counts [T + 1][P][V][7] is overwritten. */
+int vgx_test_tau_tree_events(vgx_genealogy_io *io, int64_t sites, const double *grid, int64_t T, const int32_t *variant_of, int64_t V, int64_t tile,
+                             int32_t *counts, int64_t *records, char *errbuf, int64_t errcap);
+
 /* The same counts for many replicates of the last vgx_simulate_tau call (with the event log), on the device.
  * A tau replicate's chain is a list of weighted rows (num, type, haplotype, population, newHaplotype, newPopulation), six int64:
  * the events the model held when the call started (`prefix`, as vgx_get_tau_timelines takes it; its lockdown columns are not

@@ -153,6 +153,18 @@ class VgxTauLineagesIO(C.Structure):   # VgxLineagesIO with six generator words 
     _fields_ = VgxLineagesIO._fields_[:-1] + [("kernel_ms", C.c_double * 4)]
 
 
+class VgxTreeEventsIO(C.Structure):   # VgxLineagesIO with `counts` for `values`, no root and two kernel stages
+    _fields_ = ([("counts", t) if f == "values" else (f, t) for f, t in VgxLineagesIO._fields_[:-1] if f != "root"]
+                + [("kernel_ms", C.c_double * 2)])
+
+
+class VgxTauTreeEventsIO(C.Structure):   # VgxTreeEventsIO with six generator words per walk and three kernel stages
+    _fields_ = VgxTreeEventsIO._fields_[:-1] + [("kernel_ms", C.c_double * 3)]
+
+
+TREE_EVENT_CHANNELS = ("samples", "coalescences", "mutations_within", "mutations_out", "mutations_in", "departures", "arrivals")
+
+
 class VgxFlowsIO(C.Structure):
     _fields_ = [("n", C.c_int64), ("replicates", _I), ("T", C.c_int64), ("edges", _F), ("V", C.c_int64), ("variant_of", C.POINTER(C.c_int32)),
                 ("within", C.c_int32), ("counts", C.POINTER(C.c_int32)), ("outside", _I), ("summary", C.POINTER(VgxTrajSummaryIO)),
@@ -347,6 +359,12 @@ SIGNATURES = {
     "vgx_get_tau_lineages": (C.c_int, [_H, C.POINTER(VgxTauLineagesIO), C.POINTER(VgxTauGenealogyPrefix)]),
     "vgx_test_tau_lineages": (C.c_int, [C.POINTER(VgxGenealogyIO), C.c_int64, _F, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int64,
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32), _I, C.c_char_p, C.c_int64]),
+    "vgx_get_tree_events": (C.c_int, [_H, C.POINTER(VgxTreeEventsIO)]),
+    "vgx_test_tree_events": (C.c_int, [C.POINTER(VgxGenealogyIO), _F, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int64, C.POINTER(C.c_int32),
+                                       _I, C.c_char_p, C.c_int64]),
+    "vgx_get_tau_tree_events": (C.c_int, [_H, C.POINTER(VgxTauTreeEventsIO), C.POINTER(VgxTauGenealogyPrefix)]),
+    "vgx_test_tau_tree_events": (C.c_int, [C.POINTER(VgxGenealogyIO), C.c_int64, _F, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int64,
+                                           C.POINTER(C.c_int32), _I, C.c_char_p, C.c_int64]),
     "vgx_get_flows": (C.c_int, [_H, C.POINTER(VgxFlowsIO)]),
     "vgx_test_flows": (C.c_int, [_F, _I, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, _F, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int32,
                                  C.c_int64, C.c_int64, C.POINTER(C.c_int32), _I, _I, C.c_char_p, C.c_int64]),
@@ -1076,6 +1094,33 @@ def replay_tau_lineages(m, seed, grid, variant_of, V, tile=0, rng_position=None,
         raise ValueError(err.value.decode() or "vgx_test_tau_lineages failed")
     return {"values": values, "root": root, "records": int(records[0]), "nodes_used": int(io.nodes_used),
             "rng_raw": tuple(int(io.rng_state[i]) for i in range(4)) + (int(io.rng_has_uint32), int(io.rng_uinteger))}
+
+
+def replay_tree_events(m, seed, grid, variant_of, V, tile=0, rng_position=None, rng_raw=None, tau=False):
+    """The block of ``Ensemble.tree_events`` (``tau=True``: ``Ensemble.tau_tree_events``) for the chain and state of one host model
+    through ``vgx_test_tree_events`` (``vgx_test_tau_tree_events``): the walk of ``replay_lineages`` (``replay_tau_lineages``) with
+    the host tile walk of vgx_tree_events.h, tile after tile of ``tile`` lineage records (0: the default); no GPU.  Arguments as
+    those take them.  Walks ``m.infectious`` back in place.  Returns a dict: counts [T + 1, P, V, 7] int32, records, nodes_used,
+    rng_raw; a refusal or a walk that fails raises ``ValueError`` with the library's message."""
+    grid = np.ascontiguousarray(grid, dtype=np.float64)
+    T, P, V = len(grid), int(m.popNum), int(V)
+    vo = np.ascontiguousarray(variant_of, dtype=np.int32)
+    if len(vo) != int(m.hapNum):
+        raise ValueError("variant_of must hold hapNum values")
+    io, _, _ = _genealogy_chain(m, seed, rng_position if tau else None, rng_raw)
+    counts = np.zeros((T + 1, max(P, 1), max(V, 1), len(TREE_EVENT_CHANNELS)), dtype=np.int32)
+    records = np.zeros(1, dtype=np.int64)
+    err = C.create_string_buffer(512)
+    i32 = C.POINTER(C.c_int32)
+    tail = (_p(grid), T, vo.ctypes.data_as(i32), V, int(tile), counts.ctypes.data_as(i32), _p(records), err, 512)
+    if tau:
+        rc = load_library().vgx_test_tau_tree_events(C.byref(io), int(m.sites), *tail)
+    else:
+        rc = load_library().vgx_test_tree_events(C.byref(io), *tail)
+    if rc != VGX_OK:
+        raise ValueError(err.value.decode() or "vgx_test_tree_events failed")
+    return {"counts": counts, "records": int(records[0]), "nodes_used": int(io.nodes_used),
+            "rng_raw": tuple(int(io.rng_state[i]) for i in range(4)) + ((int(io.rng_has_uint32), int(io.rng_uinteger)) if tau else (0, 0))}
 
 
 FLOW_FORMS = {None: 0, 'auto': 0, 'dense': 1, 'split': 2}   # VGX_FLOW_AUTO, VGX_FLOW_DENSE, VGX_FLOW_SPLIT

@@ -2122,52 +2122,58 @@ extern "C" int vgx_get_prevalence(vgx_engine *e, vgx_prevalence_io *io) {
 // vgx_get_genealogies' walk and vgx_get_prevalence's grid in one call: the sizing kernel counts every chain's MUTATION and
 // MIGRATION events, the host clock turns every replicate's times into T + 2 bounds, and pass by pass the device walks the selected
 // replicates with the logging observer, bins their lineage logs into the block of net changes and sums the intervals up where
-// they lie; the column summary reads the values there.
-extern "C" int vgx_get_lineages(vgx_engine *e, vgx_lineages_io *io) {
-    if (!e || !io || io->n < 0 ||
-        (io->n > 0 && (!io->replicates || !io->rng_state || !io->root || !io->status || !io->status_arg || !io->records || !io->rng_out)))
+// they lie; the column summary reads the values there.  With `events` it is vgx_get_tree_events: the block is
+// counts [n][T + 1][P][V][VGX_TE_K] behind io->values, binned by vgxi_te_bin, with no scan and no root.
+static int lineages_call(vgx_engine *e, vgx_lineages_io *io, const bool events, const char *name) {
+    if (io->n < 0 || (io->n > 0 && (!io->replicates || !io->rng_state || !io->status || !io->status_arg || !io->records || !io->rng_out)))
         return VGX_ERR_ARG;
+    const std::string me = std::string(name) + ": ";
     const auto t_call = std::chrono::steady_clock::now();
     auto wall = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(); };
     io->passes = 0;
     io->ms[0] = io->ms[1] = io->ms[2] = 0.0;
     io->kernel_ms[0] = io->kernel_ms[1] = io->kernel_ms[2] = 0.0;
-    if (!e->sc_host_valid || !e->dev_state_valid) return fail(e, VGX_ERR_ARG, "vgx_get_lineages: no direct simulate call yet");
-    if (e->last_was_tau) return fail(e, VGX_ERR_ARG, "vgx_get_lineages: the last call was vgx_simulate_tau (direct chains only)");
-    if (!e->call_recorded) return fail(e, VGX_ERR_ARG, "vgx_get_lineages: the last call did not record events");
+    if (!e->sc_host_valid || !e->dev_state_valid) return fail(e, VGX_ERR_ARG, me + "no direct simulate call yet");
+    if (e->last_was_tau) return fail(e, VGX_ERR_ARG, me + "the last call was vgx_simulate_tau (direct chains only)");
+    if (!e->call_recorded) return fail(e, VGX_ERR_ARG, me + "the last call did not record events");
     const int64_t n = io->n, P = e->d.popNum, H = e->d.hapNum, T = io->T, V = io->V;
-    if (T < 1 || T >= VGX_PREV_MAX_POINTS || !io->grid) return fail(e, VGX_ERR_ARG, "vgx_get_lineages: T = " + std::to_string(T) + " grid points: at least 1, below 2^24, with grid");
+    if (T < 1 || T >= VGX_PREV_MAX_POINTS || !io->grid) return fail(e, VGX_ERR_ARG, me + "T = " + std::to_string(T) + " grid points: at least 1, below 2^24, with grid");
     for (int64_t k = 0; k < T; k++) {
-        if (!std::isfinite(io->grid[k])) return fail(e, VGX_ERR_ARG, "vgx_get_lineages: grid[" + std::to_string(k) + "] is not finite");
+        if (!std::isfinite(io->grid[k])) return fail(e, VGX_ERR_ARG, me + "grid[" + std::to_string(k) + "] is not finite");
         if (k > 0 && !(io->grid[k - 1] < io->grid[k]))
-            return fail(e, VGX_ERR_ARG, "vgx_get_lineages: grid must increase strictly (grid[" + std::to_string(k) + "])");
+            return fail(e, VGX_ERR_ARG, me + "grid must increase strictly (grid[" + std::to_string(k) + "])");
     }
-    if (V < 1 || V > INT32_MAX || !io->variant_of) return fail(e, VGX_ERR_ARG, "vgx_get_lineages: V = " + std::to_string(V) + " classes: at least 1, with variant_of");
+    if (V < 1 || V > INT32_MAX || !io->variant_of) return fail(e, VGX_ERR_ARG, me + "V = " + std::to_string(V) + " classes: at least 1, with variant_of");
     for (int64_t h = 0; h < H; h++)
         if (io->variant_of[h] < -1 || io->variant_of[h] >= V)
-            return fail(e, VGX_ERR_ARG, "vgx_get_lineages: variant_of[" + std::to_string(h) + "] = " + std::to_string(io->variant_of[h]) + " is outside [-1, " + std::to_string(V) + ")");
+            return fail(e, VGX_ERR_ARG, me + "variant_of[" + std::to_string(h) + "] = " + std::to_string(io->variant_of[h]) + " is outside [-1, " + std::to_string(V) + ")");
     if (vgx_prev_lds_bytes(P, V) > VGX_PREV_LDS_MAX)
-        return fail(e, VGX_ERR_ARG, "vgx_get_lineages: " + std::to_string(P) + " populations x " + std::to_string(V) + " classes need " + std::to_string(vgx_prev_lds_bytes(P, V)) +
+        return fail(e, VGX_ERR_ARG, me + "" + std::to_string(P) + " populations x " + std::to_string(V) + " classes need " + std::to_string(vgx_prev_lds_bytes(P, V)) +
                                         " bytes of cells, above the " + std::to_string((int64_t)VGX_PREV_LDS_MAX) + " bytes of LDS a counting workgroup may use");
-    const int64_t cells = P * V;
+    if (events && vgx_te_lds_bytes(P, V) > VGX_PREV_LDS_MAX)
+        return fail(e, VGX_ERR_ARG, me + std::to_string(P) + " populations x " + std::to_string(V) + " classes x " + std::to_string(VGX_TE_K) + " channels need " +
+                                        std::to_string(vgx_te_lds_bytes(P, V)) + " bytes of cells, above the " + std::to_string((int64_t)VGX_PREV_LDS_MAX) +
+                                        " bytes of LDS a counting workgroup may use");
+    // the block: lineages' [n][T][cells] values and [n][cells] root, or the events' [n][T + 1][cells] counts with no root
+    const int64_t cells = events ? P * V * VGX_TE_K : P * V, rows = events ? T + 1 : T;
     std::vector<int32_t> n_ev((size_t)n);
     std::vector<int64_t> n_ev64((size_t)n), sC((size_t)n);
     {
         std::vector<char> seen((size_t)e->R, 0);
         for (int64_t i = 0; i < n; i++) {
             const int64_t r = io->replicates[i];
-            if (r < 0 || r >= e->R) return fail(e, VGX_ERR_ARG, "vgx_get_lineages: replicate index out of range");
-            if (seen[(size_t)r]) return fail(e, VGX_ERR_ARG, "vgx_get_lineages: replicates must be distinct");
+            if (r < 0 || r >= e->R) return fail(e, VGX_ERR_ARG, me + "replicate index out of range");
+            if (seen[(size_t)r]) return fail(e, VGX_ERR_ARG, me + "replicates must be distinct");
             seen[(size_t)r] = 1;
             const VgxRepScalars &s = e->sc_host[(size_t)r];
             const int64_t first = s.restarts > 0 ? 0 : ((size_t)r < e->call_ev0.size() ? e->call_ev0[(size_t)r] : e->ev_ptr0);
             if (first != 0 || e->ev_base != 0)
-                return fail(e, VGX_ERR_ARG, "vgx_get_lineages: the chain of replicate " + std::to_string(r) +
+                return fail(e, VGX_ERR_ARG, me + "the chain of replicate " + std::to_string(r) +
                                                 " does not start in the last call's device log (events.ptr was not 0 at its start)");
             if (s.ev_ptr >= VGX_PREV_MAX_EVENTS)
-                return fail(e, VGX_ERR_ARG, "vgx_get_lineages: replicate " + std::to_string(r) + " holds a chain of " + std::to_string(s.ev_ptr) + " events (2^30 or more)");
+                return fail(e, VGX_ERR_ARG, me + "replicate " + std::to_string(r) + " holds a chain of " + std::to_string(s.ev_ptr) + " events (2^30 or more)");
             if (s.ev_ptr < 0 || s.ev_ptr > e->evcap)
-                return fail(e, VGX_ERR_ARG, "vgx_get_lineages: event range of replicate " + std::to_string(r) + " outside the device log");
+                return fail(e, VGX_ERR_ARG, me + "event range of replicate " + std::to_string(r) + " outside the device log");
             n_ev[(size_t)i] = (int32_t)s.ev_ptr;
             n_ev64[(size_t)i] = s.ev_ptr;
             sC[(size_t)i] = s.sCounter;
@@ -2192,17 +2198,17 @@ extern "C" int vgx_get_lineages(vgx_engine *e, vgx_lineages_io *io) {
     auto up8 = [](int64_t b) { return (b + 255) / 256 * 256; };
     auto dev_free = [](char *p) { (void)hipFree(p); };
     // what stays for the whole call: [rep | n_ev | n_ev (8 bytes) | event counts | bound | variant_of | val | fin | min, max]
-    const int64_t val_bytes = n * T * cells * 4, fin_bytes = n * cells * 4;
+    const int64_t val_bytes = n * rows * cells * 4, fin_bytes = events ? 0 : n * cells * 4;
     const int64_t o_rep = 0, o_nev = o_rep + up8(n * 8), o_nev64 = o_nev + up8(n * 4), o_cnt = o_nev64 + up8(n * 8), o_bnd = o_cnt + up8(n * 16),
                   o_map = o_bnd + up8(n * (T + 2) * 4), o_val = o_map + up8(H * 4), o_fin = o_val + up8(val_bytes), o_mm = o_fin + up8(fin_bytes),
                   keep_total = o_mm + 256;
     if (keep_total > (int64_t)(free_b / 2))
-        return fail(e, VGX_ERR_ARG, "vgx_get_lineages: the block of " + std::to_string(n) + " x " + std::to_string(T + 1) + " x " + std::to_string(P) + " x " + std::to_string(V) +
+        return fail(e, VGX_ERR_ARG, me + "the block of " + std::to_string(n) + " x " + std::to_string(T + 1) + " x " + std::to_string(P) + " x " + std::to_string(V) +
                                         " values (" + std::to_string(val_bytes + fin_bytes) + " bytes) and its cuts take " + std::to_string(keep_total) +
                                         " bytes, above half of the " + std::to_string((int64_t)free_b) + " bytes of free device memory: select fewer replicates per call");
     char *kws = nullptr;
     hipError_t er = hipMalloc((void **)&kws, (size_t)keep_total);
-    if (er != hipSuccess) return fail(e, VGX_ERR_HIP, "vgx_get_lineages: hipMalloc of " + std::to_string(keep_total) + " bytes: " + hipGetErrorString(er));
+    if (er != hipSuccess) return fail(e, VGX_ERR_HIP, me + "hipMalloc of " + std::to_string(keep_total) + " bytes: " + hipGetErrorString(er));
     std::unique_ptr<char, void (*)(char *)> khold(kws, dev_free);
     std::vector<int64_t> reps_all(io->replicates, io->replicates + n);
     HIPCHECK(e, hipMemcpyAsync(kws + o_rep, reps_all.data(), (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
@@ -2215,7 +2221,7 @@ extern "C" int vgx_get_lineages(vgx_engine *e, vgx_lineages_io *io) {
     HIPCHECK(e, vgxi_gw_count(log, e->evcap, (const int64_t *)(kws + o_rep), (const int64_t *)(kws + o_nev64), n, (int64_t *)(kws + o_cnt), e->stream));
     HIPCHECK(e, hipMemcpyAsync(cnt.data(), kws + o_cnt, (size_t)n * 16, hipMemcpyDeviceToHost, e->stream));
     if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)
-        return fail(e, VGX_ERR_HIP, std::string("vgx_get_lineages: counting pass: ") + hipGetErrorString(er));
+        return fail(e, VGX_ERR_HIP, std::string(me + "counting pass: ") + hipGetErrorString(er));
 
     // host: every replicate's event times -> its T + 2 bounds (the device work of a clock chunk comes later, pass by pass)
     const int64_t share_clock = (int64_t)(free_b / 2) - keep_total + 4096;
@@ -2273,7 +2279,7 @@ extern "C" int vgx_get_lineages(vgx_engine *e, vgx_lineages_io *io) {
         char *ws = nullptr;
         er = hipMalloc((void **)&ws, (size_t)total);
         if (er != hipSuccess)
-            return fail(e, VGX_ERR_HIP, "vgx_get_lineages: hipMalloc of " + std::to_string(total) + " bytes: " + hipGetErrorString(er));
+            return fail(e, VGX_ERR_HIP, me + "hipMalloc of " + std::to_string(total) + " bytes: " + hipGetErrorString(er));
         std::unique_ptr<char, void (*)(char *)> hold(ws, dev_free);
         VgxLnLaunch a{};
         a.m = m;
@@ -2293,23 +2299,28 @@ extern "C" int vgx_get_lineages(vgx_engine *e, vgx_lineages_io *io) {
         a.T = (int32_t)T; a.V = (int32_t)V;
         a.variant_of = (const int32_t *)(kws + o_map);
         a.tile = (int32_t)tile; a.max_rec = max_rec;
-        a.val = (int32_t *)(kws + o_val) + i0 * T * cells;
+        a.val = (int32_t *)(kws + o_val) + i0 * rows * cells;
         a.fin = (int32_t *)(kws + o_fin) + i0 * cells;
         HIPCHECK(e, hipMemcpyAsync(ws + o_desc, dp.data(), (size_t)m * sizeof(VgxLnDesc), hipMemcpyHostToDevice, e->stream));
         if (TB > 0) HIPCHECK(e, hipMemsetAsync(a.key, 0xFF, (size_t)TB * 8, e->stream));   // every slot empty (-1)
         HIPCHECK(e, hipEventRecord(tm.ev[0], e->stream));
         HIPCHECK(e, vgxi_ln_walk(&a, e->stream));
         HIPCHECK(e, hipEventRecord(tm.ev[1], e->stream));
-        HIPCHECK(e, vgxi_ln_bin(&a, e->stream));
+        if (events) {
+            const VgxTeLaunch b{m, a.desc, a.rec, a.n_rec, a.bound, a.T, (int32_t)P, (int32_t)H, a.V, a.variant_of, a.tile, max_rec, a.val};
+            HIPCHECK(e, vgxi_te_bin(&b, e->stream));
+        } else {
+            HIPCHECK(e, vgxi_ln_bin(&a, e->stream));
+        }
         HIPCHECK(e, hipEventRecord(tm.ev[2], e->stream));
-        HIPCHECK(e, vgxi_ln_scan(&a, e->stream));
+        if (!events) HIPCHECK(e, vgxi_ln_scan(&a, e->stream));
         HIPCHECK(e, hipEventRecord(tm.ev[3], e->stream));
         std::vector<int64_t> res((size_t)m * 5), nrec((size_t)m);
         HIPCHECK(e, hipMemcpyAsync(res.data(), a.res, (size_t)m * 40, hipMemcpyDeviceToHost, e->stream));
         HIPCHECK(e, hipMemcpyAsync(io->rng_out + i0 * 4, a.rng_out, (size_t)m * 32, hipMemcpyDeviceToHost, e->stream));
         HIPCHECK(e, hipMemcpyAsync(nrec.data(), a.n_rec, (size_t)m * 8, hipMemcpyDeviceToHost, e->stream));
         if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)   // before anything reads the outputs
-            return fail(e, VGX_ERR_HIP, std::string("vgx_get_lineages: walk, binning or scan kernel failed: ") + hipGetErrorString(er));
+            return fail(e, VGX_ERR_HIP, std::string(me + "walk, binning or scan kernel failed: ") + hipGetErrorString(er));
         for (int k = 0; k < 3; k++) {
             float kms = 0.f;
             HIPCHECK(e, hipEventElapsedTime(&kms, tm.ev[k], tm.ev[k + 1]));
@@ -2325,27 +2336,50 @@ extern "C" int vgx_get_lineages(vgx_engine *e, vgx_lineages_io *io) {
         i0 = i1;
     }
     if (io->values) HIPCHECK(e, hipMemcpy(io->values, kws + o_val, (size_t)val_bytes, hipMemcpyDeviceToHost));
-    HIPCHECK(e, hipMemcpy(io->root, kws + o_fin, (size_t)fin_bytes, hipMemcpyDeviceToHost));
+    if (!events) HIPCHECK(e, hipMemcpy(io->root, kws + o_fin, (size_t)fin_bytes, hipMemcpyDeviceToHost));
     if (io->summary) {
-        if (!io->summary->group_of) return fail(e, VGX_ERR_ARG, "vgx_get_lineages: summary: null group_of");
+        if (!io->summary->group_of) return fail(e, VGX_ERR_ARG, me + "summary: null group_of");
         int64_t failed = 0;
         for (int64_t i = 0; i < n; i++) failed += io->summary->group_of[i] >= 0 && io->status[i] != VGX_GW_OK;
         if (failed > 0)
-            return fail(e, VGX_ERR_ARG, "vgx_get_lineages: summary: " + std::to_string(failed) + " replicate(s) of a group have a walk that failed (status is not 0): leave them out of the groups");
+            return fail(e, VGX_ERR_ARG, me + "summary: " + std::to_string(failed) + " replicate(s) of a group have a walk that failed (status is not 0): leave them out of the groups");
         // the column summary sorts 32-bit keys of whole numbers in [0, 2^31)
         int32_t mm[2] = {0, 0};
-        HIPCHECK(e, vgxi_prev_minmax((const int32_t *)(kws + o_val), n * T * cells, (int32_t *)(kws + o_mm), e->stream));
+        HIPCHECK(e, vgxi_prev_minmax((const int32_t *)(kws + o_val), n * rows * cells, (int32_t *)(kws + o_mm), e->stream));
         HIPCHECK(e, hipMemcpyAsync(mm, kws + o_mm, sizeof mm, hipMemcpyDeviceToHost, e->stream));
         if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)
-            return fail(e, VGX_ERR_HIP, std::string("vgx_get_lineages: min/max kernel failed: ") + hipGetErrorString(er));
+            return fail(e, VGX_ERR_HIP, std::string(me + "min/max kernel failed: ") + hipGetErrorString(er));
         if (mm[0] < 0)
-            return fail(e, VGX_ERR_ARG, "vgx_get_lineages: summary: a value of " + std::to_string(mm[0]) + " is not a whole number in [0, 2^31)");
+            return fail(e, VGX_ERR_ARG, me + "summary: a value of " + std::to_string(mm[0]) + " is not a whole number in [0, 2^31)");
         char msg[512] = "";
-        const int rc = vgxi_column_summary_i32("vgx_get_lineages: summary", (const int32_t *)(kws + o_val), n, T * cells, io->summary, e->stream, msg, sizeof msg);
+        const int rc = vgxi_column_summary_i32((me + "summary").c_str(), (const int32_t *)(kws + o_val), n, rows * cells, io->summary, e->stream, msg, sizeof msg);
         if (rc) return fail(e, rc, msg);
     }
     io->ms[2] = wall();
     return VGX_OK;
+}
+
+extern "C" int vgx_get_lineages(vgx_engine *e, vgx_lineages_io *io) {
+    if (!e || !io || (io->n > 0 && !io->root)) return VGX_ERR_ARG;
+    return lineages_call(e, io, false, "vgx_get_lineages");
+}
+
+// ---- coalescences, samples, mutations and moves of the trees per interval (vgx_tree_events.hip, vgx_tree_events.h) ----
+// vgx_get_lineages with the kinds kept apart: the same checks, sizing, cuts, passes and walk; the binning kernel of
+// vgx_tree_events.hip counts every pass's logs into the block [n][T + 1][P][V][VGX_TE_K] and no scan follows.
+extern "C" int vgx_get_tree_events(vgx_engine *e, vgx_tree_events_io *io) {
+    if (!e || !io) return VGX_ERR_ARG;
+    vgx_lineages_io l{};
+    l.n = io->n; l.replicates = io->replicates; l.rng_state = io->rng_state;
+    l.T = io->T; l.grid = io->grid; l.V = io->V; l.variant_of = io->variant_of;
+    l.values = io->counts;
+    l.status = io->status; l.status_arg = io->status_arg; l.records = io->records; l.rng_out = io->rng_out;
+    l.summary = io->summary;
+    const int rc = lineages_call(e, &l, true, "vgx_get_tree_events");
+    io->passes = l.passes;
+    for (int k = 0; k < 3; k++) io->ms[k] = l.ms[k];
+    io->kernel_ms[0] = l.kernel_ms[0]; io->kernel_ms[1] = l.kernel_ms[1];
+    return rc;
 }
 
 // ---- peaks, first passages and last positive events of many replicates (vgx_milestones.hip, vgx_milestones.h) -----

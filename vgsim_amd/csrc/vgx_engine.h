@@ -28,6 +28,7 @@
 #include "vgx_milestones.h"
 #include "vgx_flows.h"
 #include "vgx_lineages.h"
+#include "vgx_tree_events.h"   // (declares its launcher, vgxi_te_bin, itself)
 
 #pragma GCC visibility push(hidden)   // nothing here is part of the exported C ABI
 

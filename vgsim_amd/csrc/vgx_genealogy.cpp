@@ -23,6 +23,7 @@
 #include "vgx_gwalk.h"
 #include "vgx_gwalk_tau.h"
 #include "vgx_lineages.h"
+#include "vgx_tree_events.h"
 #include "vgx_logfact.h"
 #include "vgx_rng.h"
 
@@ -480,44 +481,51 @@ extern "C" int vgx_test_genealogy_walk(vgx_genealogy_io *io, char *errbuf, int64
 }
 
 // ---- lineages on a grid (vgx_lineages.h): the walk with the logging observer, the tile walk and the suffix sum on one chain ------
-extern "C" int vgx_test_lineages(vgx_genealogy_io *io, const double *grid, int64_t T, const int32_t *variant_of, int64_t V, int64_t tile,
-                                 int32_t *values, int32_t *root, int64_t *records, char *errbuf, int64_t errcap) {
+// With `events` it is vgx_test_tree_events (vgx_tree_events.h): `values` is counts [T + 1][P][V][VGX_TE_K] by vgx_te_tile_host, with no
+// root and no suffix sum.
+static int lineages_hook(vgx_genealogy_io *io, const double *grid, int64_t T, const int32_t *variant_of, int64_t V, int64_t tile, int32_t *values,
+                         int32_t *root, int64_t *records, char *errbuf, int64_t errcap, const bool events, const char *name) {
+    const std::string me = std::string(name) + ": ";
     auto fail = [&](const std::string &m) {
         if (errbuf && errcap > 0) std::snprintf(errbuf, (size_t)errcap, "%s", m.c_str());
         return VGX_ERR_ARG;
     };
-    if (!io || !io->infectious || !grid || !variant_of || !values || !root || !records) return fail("vgx_test_lineages: null argument");
+    if (!io || !io->infectious || !grid || !variant_of || !values || (!events && !root) || !records) return fail(me + "null argument");
     const int64_t P = io->popNum, H = io->hapNum;
-    if (T < 1 || T >= VGX_PREV_MAX_POINTS) return fail("vgx_test_lineages: T = " + std::to_string(T) + " must be at least 1 and below 2^24");
+    if (T < 1 || T >= VGX_PREV_MAX_POINTS) return fail(me + "T = " + std::to_string(T) + " must be at least 1 and below 2^24");
     for (int64_t k = 0; k < T; k++) {
-        if (!std::isfinite(grid[k])) return fail("vgx_test_lineages: grid[" + std::to_string(k) + "] is not finite");
-        if (k > 0 && !(grid[k - 1] < grid[k])) return fail("vgx_test_lineages: grid must increase strictly (grid[" + std::to_string(k) + "])");
+        if (!std::isfinite(grid[k])) return fail(me + "grid[" + std::to_string(k) + "] is not finite");
+        if (k > 0 && !(grid[k - 1] < grid[k])) return fail(me + "grid must increase strictly (grid[" + std::to_string(k) + "])");
     }
-    if (P < 1 || H < 1 || P > INT32_MAX || H > INT32_MAX) return fail("vgx_test_lineages: bad dimensions");
-    if (V < 1 || V > INT32_MAX) return fail("vgx_test_lineages: V = " + std::to_string(V) + " must be at least 1");
+    if (P < 1 || H < 1 || P > INT32_MAX || H > INT32_MAX) return fail(me + "bad dimensions");
+    if (V < 1 || V > INT32_MAX) return fail(me + "V = " + std::to_string(V) + " must be at least 1");
     if (vgx_prev_lds_bytes(P, V) > VGX_PREV_LDS_MAX)
-        return fail("vgx_test_lineages: " + std::to_string(P) + " populations x " + std::to_string(V) + " classes need " +
+        return fail(me + "" + std::to_string(P) + " populations x " + std::to_string(V) + " classes need " +
                     std::to_string(vgx_prev_lds_bytes(P, V)) + " bytes of cells, above the " + std::to_string((int64_t)VGX_PREV_LDS_MAX) +
+                    " bytes of LDS a counting workgroup may use");
+    if (events && vgx_te_lds_bytes(P, V) > VGX_PREV_LDS_MAX)
+        return fail(me + std::to_string(P) + " populations x " + std::to_string(V) + " classes x " + std::to_string(VGX_TE_K) + " channels need " +
+                    std::to_string(vgx_te_lds_bytes(P, V)) + " bytes of cells, above the " + std::to_string((int64_t)VGX_PREV_LDS_MAX) +
                     " bytes of LDS a counting workgroup may use");
     for (int64_t h = 0; h < H; h++)
         if (variant_of[h] < -1 || variant_of[h] >= V)
-            return fail("vgx_test_lineages: variant_of[" + std::to_string(h) + "] = " + std::to_string(variant_of[h]) + " is outside [-1, " +
+            return fail(me + "variant_of[" + std::to_string(h) + "] = " + std::to_string(variant_of[h]) + " is outside [-1, " +
                         std::to_string(V) + ")");
-    if (tile < 0) return fail("vgx_test_lineages: tile must not be negative");
+    if (tile < 0) return fail(me + "tile must not be negative");
     if (tile == 0) tile = VGX_LN_TILE_DEFAULT;
     if (io->sCounter < 2) return fail(walk_message(VGX_GW_FEW_SAMPLES, 0));
     const int64_t n = io->ev_ptr, PH = P * H;
-    if (n < 0 || n >= VGX_PREV_MAX_EVENTS) return fail("vgx_test_lineages: a chain of " + std::to_string(n) + " events (2^30 or more)");
-    if (2 * io->sCounter > ((int64_t)1 << 31)) return fail("vgx_test_lineages: sCounter = " + std::to_string(io->sCounter) + " is too large");
+    if (n < 0 || n >= VGX_PREV_MAX_EVENTS) return fail(me + "a chain of " + std::to_string(n) + " events (2^30 or more)");
+    if (2 * io->sCounter > ((int64_t)1 << 31)) return fail(me + "sCounter = " + std::to_string(io->sCounter) + " is too large");
     if (n > 0 && (!io->ev_times || !io->ev_types || !io->ev_haplotypes || !io->ev_populations || !io->ev_newHaplotypes || !io->ev_newPopulations))
-        return fail("vgx_test_lineages: null event column");
+        return fail(me + "null event column");
     // the chain in the device log's record layout, and what the sizing kernel counts
     std::vector<int32_t> log((size_t)n * 6);
     int64_t n_mut = 0, n_mig = 0;
     for (int64_t e = 0; e < n; e++) {
         const int64_t v[5] = {io->ev_types[e], io->ev_haplotypes[e], io->ev_populations[e], io->ev_newHaplotypes[e], io->ev_newPopulations[e]};
         for (int c = 0; c < 5; c++) {
-            if (v[c] < INT32_MIN || v[c] > INT32_MAX) return fail("vgx_test_lineages: log value outside 32 bits");
+            if (v[c] < INT32_MIN || v[c] > INT32_MAX) return fail(me + "log value outside 32 bits");
             log[(size_t)(e * 6 + c)] = (int32_t)v[c];
         }
         n_mut += v[0] == VGX_GW_MUTATION;
@@ -556,6 +564,15 @@ extern "C" int vgx_test_lineages(vgx_genealogy_io *io, const double *grid, int64
     VgxPrevCutter ct{grid, T, bound.data()};
     for (int64_t e = 0; e < n; e++) ct.event(e, io->ev_times[e]);
     ct.finish(n);
+    if (events) {
+        const int64_t cells = P * V * VGX_TE_K;
+        for (int64_t i = 0; i < (T + 1) * cells; i++) values[i] = 0;
+        std::vector<int32_t> hist((size_t)cells, 0);
+        for (int64_t r0 = 0; r0 < lg.n; r0 += tile)
+            vgx_te_tile_host(rec.data(), bound.data(), (int32_t)T, (int32_t)P, (int32_t)H, (int32_t)V, variant_of, r0, std::min<int64_t>(r0 + tile, lg.n),
+                             hist.data(), values);
+        return VGX_OK;
+    }
     const int64_t cells = P * V;
     for (int64_t i = 0; i < T * cells; i++) values[i] = 0;
     for (int64_t i = 0; i < cells; i++) root[i] = 0;
@@ -565,4 +582,14 @@ extern "C" int vgx_test_lineages(vgx_genealogy_io *io, const double *grid, int64
                          hist.data(), values, root);
     for (int64_t i = 0; i < cells; i++) vgx_ln_scan_column(values + i, root + i, (int32_t)T, cells);
     return VGX_OK;
+}
+
+extern "C" int vgx_test_lineages(vgx_genealogy_io *io, const double *grid, int64_t T, const int32_t *variant_of, int64_t V, int64_t tile,
+                                 int32_t *values, int32_t *root, int64_t *records, char *errbuf, int64_t errcap) {
+    return lineages_hook(io, grid, T, variant_of, V, tile, values, root, records, errbuf, errcap, false, "vgx_test_lineages");
+}
+
+extern "C" int vgx_test_tree_events(vgx_genealogy_io *io, const double *grid, int64_t T, const int32_t *variant_of, int64_t V, int64_t tile,
+                                    int32_t *counts, int64_t *records, char *errbuf, int64_t errcap) {
+    return lineages_hook(io, grid, T, variant_of, V, tile, counts, nullptr, records, errbuf, errcap, true, "vgx_test_tree_events");
 }

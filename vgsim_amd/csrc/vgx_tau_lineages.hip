@@ -56,7 +56,7 @@ __global__ void __launch_bounds__(64) vgxtl_walk_kernel(VgxTauLnLaunch a) {
 using namespace vgxtc;
 
 // "" or why the grid, the classes or the LDS budget are refused (the wording of vgx_get_lineages)
-std::string check_request(const double *grid, int64_t T, int64_t V, const int32_t *variant_of, int64_t P, int64_t H) {
+std::string check_request(const double *grid, int64_t T, int64_t V, const int32_t *variant_of, int64_t P, int64_t H, bool events = false) {
     if (T < 1 || T >= VGX_PREV_MAX_POINTS || !grid) return "T = " + std::to_string(T) + " grid points: at least 1, below 2^24, with grid";
     for (int64_t k = 0; k < T; k++) {
         if (!std::isfinite(grid[k])) return "grid[" + std::to_string(k) + "] is not finite";
@@ -69,6 +69,10 @@ std::string check_request(const double *grid, int64_t T, int64_t V, const int32_
     if (vgx_prev_lds_bytes(P, V) > VGX_PREV_LDS_MAX)
         return std::to_string(P) + " populations x " + std::to_string(V) + " classes need " + std::to_string(vgx_prev_lds_bytes(P, V)) +
                " bytes of cells, above the " + std::to_string((int64_t)VGX_PREV_LDS_MAX) + " bytes of LDS a counting workgroup may use";
+    if (events && vgx_te_lds_bytes(P, V) > VGX_PREV_LDS_MAX)   // (the tree events' cells: vgx_get_tree_events' wording)
+        return std::to_string(P) + " populations x " + std::to_string(V) + " classes x " + std::to_string(VGX_TE_K) + " channels need " +
+               std::to_string(vgx_te_lds_bytes(P, V)) + " bytes of cells, above the " + std::to_string((int64_t)VGX_PREV_LDS_MAX) +
+               " bytes of LDS a counting workgroup may use";
     return "";
 }
 
@@ -80,13 +84,14 @@ extern "C" __attribute__((visibility("hidden"))) hipError_t vgxi_tau_ln_walk(con
     return hipGetLastError();
 }
 
-extern "C" int vgx_get_tau_lineages(vgx_engine *e, vgx_tau_lineages_io *io, const vgx_tau_genealogy_prefix *prefix) {
-    if (!e || !io || io->n < 0 ||
-        (io->n > 0 && (!io->replicates || !io->rng_state || !io->root || !io->status || !io->status_arg || !io->records || !io->rng_out)))
+// vgx_get_tau_lineages, and with `events` vgx_get_tau_tree_events: the block is then counts
+// [n][T + 1][P][V][VGX_TE_K] behind io->values, binned by vgxi_te_bin, with no scan and no root.
+static int tau_lineages_call(vgx_engine *e, vgx_tau_lineages_io *io, const vgx_tau_genealogy_prefix *prefix, const bool events, const char *name) {
+    if (io->n < 0 || (io->n > 0 && (!io->replicates || !io->rng_state || !io->status || !io->status_arg || !io->records || !io->rng_out)))
         return VGX_ERR_ARG;
     const auto t_call = std::chrono::steady_clock::now();
     auto since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-    const std::string me = "vgx_get_tau_lineages: ";
+    const std::string me = std::string(name) + ": ";
     io->passes = 0;
     io->ms[0] = io->ms[1] = io->ms[2] = 0.0;
     io->kernel_ms[0] = io->kernel_ms[1] = io->kernel_ms[2] = io->kernel_ms[3] = 0.0;
@@ -95,10 +100,11 @@ extern "C" int vgx_get_tau_lineages(vgx_engine *e, vgx_tau_lineages_io *io, cons
     if (e->tau_mev_cap <= 0) return fail(e, VGX_ERR_ARG, me + "the last call recorded no multievent rows (record_events = 0)");
     const int64_t n = io->n, P = e->d.popNum, H = e->d.hapNum, PH = P * H, T = io->T, V = io->V, mev_cap = e->tau_mev_cap;
     {
-        const std::string why = check_request(io->grid, T, V, io->variant_of, P, H);
+        const std::string why = check_request(io->grid, T, V, io->variant_of, P, H, events);
         if (!why.empty()) return fail(e, VGX_ERR_ARG, me + why);
     }
-    const int64_t cells = P * V;
+    // the block: lineages' [n][T][cells] values and [n][cells] root, or the events' [n][T + 1][cells] counts with no root
+    const int64_t cells = events ? P * V * VGX_TE_K : P * V, rows_out = events ? T + 1 : T;
     const int64_t pre_ev = prefix ? prefix->ev_ptr : 0;
     if (pre_ev >= VGX_PREV_MAX_EVENTS) return fail(e, VGX_ERR_ARG, me + "the prefix holds a chain of " + std::to_string(pre_ev) + " events (2^30 or more)");
     if (pre_ev < 0 ||
@@ -164,7 +170,7 @@ extern "C" int vgx_get_tau_lineages(vgx_engine *e, vgx_tau_lineages_io *io, cons
     auto dev_free = [](char *p) { (void)hipFree(p); };
     typedef std::unique_ptr<char, void (*)(char *)> Hold;
     // what stays for the whole call: [rep | raw rows | sCounter | row sums | bound | variant_of | prefix rows | prefix offsets | val | fin | min, max]
-    const int64_t val_bytes = n * T * cells * 4, fin_bytes = n * cells * 4;
+    const int64_t val_bytes = n * rows_out * cells * 4, fin_bytes = events ? 0 : n * cells * 4;
     const int64_t o_rep = 0, o_raw = o_rep + up8(n * 8), o_sc = o_raw + up8(n * 8), o_cnt = o_sc + up8(n * 8), o_bnd = o_cnt + up8(n * 24),
                   o_map = o_bnd + up8(n * (T + 2) * 4), o_prow = o_map + up8(H * 4), o_poff = o_prow + up8(pre_rows * 32 + 32),
                   o_val = o_poff + up8((int64_t)pre.off.size() * 4), o_fin = o_val + up8(val_bytes), o_mm = o_fin + up8(fin_bytes), keep_total = o_mm + 256;
@@ -356,7 +362,7 @@ extern "C" int vgx_get_tau_lineages(vgx_engine *e, vgx_tau_lineages_io *io, cons
         b.T = (int32_t)T; b.V = (int32_t)V;
         b.variant_of = (const int32_t *)(kws + o_map);
         b.tile = (int32_t)tile; b.max_rec = max_rec;
-        b.val = (int32_t *)(kws + o_val) + i0 * T * cells;
+        b.val = (int32_t *)(kws + o_val) + i0 * rows_out * cells;
         b.fin = (int32_t *)(kws + o_fin) + i0 * cells;
         HIPCHECK(e, hipMemcpyAsync(ws + o_desc, dp.data(), (size_t)m * sizeof(VgxTauLnDesc), hipMemcpyHostToDevice, e->stream));
         HIPCHECK(e, hipMemcpyAsync(ws + o_bdesc, bd.data(), (size_t)m * sizeof(VgxLnDesc), hipMemcpyHostToDevice, e->stream));
@@ -364,9 +370,14 @@ extern "C" int vgx_get_tau_lineages(vgx_engine *e, vgx_tau_lineages_io *io, cons
         HIPCHECK(e, hipEventRecord(tm.ev[0], e->stream));
         HIPCHECK(e, vgxi_tau_ln_walk(&a, e->stream));
         HIPCHECK(e, hipEventRecord(tm.ev[1], e->stream));
-        HIPCHECK(e, vgxi_ln_bin(&b, e->stream));
+        if (events) {
+            const VgxTeLaunch te{m, b.desc, b.rec, b.n_rec, b.bound, b.T, (int32_t)P, (int32_t)H, b.V, b.variant_of, b.tile, max_rec, b.val};
+            HIPCHECK(e, vgxi_te_bin(&te, e->stream));
+        } else {
+            HIPCHECK(e, vgxi_ln_bin(&b, e->stream));
+        }
         HIPCHECK(e, hipEventRecord(tm.ev[2], e->stream));
-        HIPCHECK(e, vgxi_ln_scan(&b, e->stream));
+        if (!events) HIPCHECK(e, vgxi_ln_scan(&b, e->stream));
         HIPCHECK(e, hipEventRecord(tm.ev[3], e->stream));
         std::vector<int64_t> res((size_t)m * 5), nrec((size_t)m);
         HIPCHECK(e, hipMemcpyAsync(res.data(), a.res, (size_t)m * 40, hipMemcpyDeviceToHost, e->stream));
@@ -388,7 +399,7 @@ extern "C" int vgx_get_tau_lineages(vgx_engine *e, vgx_tau_lineages_io *io, cons
         i0 = i1;
     }
     if (io->values) HIPCHECK(e, hipMemcpy(io->values, kws + o_val, (size_t)val_bytes, hipMemcpyDeviceToHost));
-    HIPCHECK(e, hipMemcpy(io->root, kws + o_fin, (size_t)fin_bytes, hipMemcpyDeviceToHost));
+    if (!events) HIPCHECK(e, hipMemcpy(io->root, kws + o_fin, (size_t)fin_bytes, hipMemcpyDeviceToHost));
     if (io->summary) {
         if (!io->summary->group_of) return fail(e, VGX_ERR_ARG, me + "summary: null group_of");
         int64_t failed = 0;
@@ -397,22 +408,42 @@ extern "C" int vgx_get_tau_lineages(vgx_engine *e, vgx_tau_lineages_io *io, cons
             return fail(e, VGX_ERR_ARG, me + "summary: " + std::to_string(failed) + " replicate(s) of a group have a walk that failed (status is not 0): leave them out of the groups");
         // the column summary sorts 32-bit keys of whole numbers in [0, 2^31)
         int32_t mm[2] = {0, 0};
-        HIPCHECK(e, vgxi_prev_minmax((const int32_t *)(kws + o_val), n * T * cells, (int32_t *)(kws + o_mm), e->stream));
+        HIPCHECK(e, vgxi_prev_minmax((const int32_t *)(kws + o_val), n * rows_out * cells, (int32_t *)(kws + o_mm), e->stream));
         HIPCHECK(e, hipMemcpyAsync(mm, kws + o_mm, sizeof mm, hipMemcpyDeviceToHost, e->stream));
         if ((er = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(e, VGX_ERR_HIP, me + "min/max kernel failed: " + hipGetErrorString(er));
         if (mm[0] < 0) return fail(e, VGX_ERR_ARG, me + "summary: a value of " + std::to_string(mm[0]) + " is not a whole number in [0, 2^31)");
         char msg[512] = "";
-        const int rc = vgxi_column_summary_i32("vgx_get_tau_lineages: summary", (const int32_t *)(kws + o_val), n, T * cells, io->summary, e->stream, msg, sizeof msg);
+        const int rc = vgxi_column_summary_i32((me + "summary").c_str(), (const int32_t *)(kws + o_val), n, rows_out * cells, io->summary, e->stream, msg, sizeof msg);
         if (rc) return fail(e, rc, msg);
     }
     io->ms[2] = since(t_call);
     return VGX_OK;
 }
 
+extern "C" int vgx_get_tau_lineages(vgx_engine *e, vgx_tau_lineages_io *io, const vgx_tau_genealogy_prefix *prefix) {
+    if (!e || !io || (io->n > 0 && !io->root)) return VGX_ERR_ARG;
+    return tau_lineages_call(e, io, prefix, false, "vgx_get_tau_lineages");
+}
+
+extern "C" int vgx_get_tau_tree_events(vgx_engine *e, vgx_tau_tree_events_io *io, const vgx_tau_genealogy_prefix *prefix) {
+    if (!e || !io) return VGX_ERR_ARG;
+    vgx_tau_lineages_io l{};
+    l.n = io->n; l.replicates = io->replicates; l.rng_state = io->rng_state;
+    l.T = io->T; l.grid = io->grid; l.V = io->V; l.variant_of = io->variant_of;
+    l.values = io->counts;
+    l.status = io->status; l.status_arg = io->status_arg; l.records = io->records; l.rng_out = io->rng_out;
+    l.summary = io->summary;
+    const int rc = tau_lineages_call(e, &l, prefix, true, "vgx_get_tau_tree_events");
+    io->passes = l.passes;
+    for (int k = 0; k < 3; k++) { io->ms[k] = l.ms[k]; io->kernel_ms[k] = l.kernel_ms[k]; }
+    return rc;
+}
+
 // ---- the host instance: the chain handling of vgx_test_tau_genealogy_walk, the walk with the logging observer, the tile walk and the
 // suffix sum on a chain given as arrays (no device, no engine)
-extern "C" int vgx_test_tau_lineages(vgx_genealogy_io *io, int64_t sites, const double *grid, int64_t T, const int32_t *variant_of, int64_t V, int64_t tile,
-                                     int32_t *values, int32_t *root, int64_t *records, char *errbuf, int64_t errcap) {
+// (with `events`, vgx_test_tau_tree_events: `values` is counts [T + 1][P][V][VGX_TE_K] by vgx_te_tile_host, no root, no suffix sum)
+static int tau_lineages_hook(vgx_genealogy_io *io, int64_t sites, const double *grid, int64_t T, const int32_t *variant_of, int64_t V, int64_t tile,
+                             int32_t *values, int32_t *root, int64_t *records, char *errbuf, int64_t errcap, const bool events, const char *name) {
     auto fail_ = [&](const std::string &m) {
         if (errbuf && errcap > 0) snprintf(errbuf, (size_t)errcap, "%s", m.c_str());
         return VGX_ERR_ARG;
@@ -422,14 +453,14 @@ extern "C" int vgx_test_tau_lineages(vgx_genealogy_io *io, int64_t sites, const 
         vgx_genealogy_message(status, arg, buf, 512);
         return std::string(buf);
     };
-    const std::string me = "vgx_test_tau_lineages: ";
-    if (!io || !io->infectious || !grid || !variant_of || !values || !root || !records) return fail_(me + "null argument");
+    const std::string me = std::string(name) + ": ";
+    if (!io || !io->infectious || !grid || !variant_of || !values || (!events && !root) || !records) return fail_(me + "null argument");
     const int64_t P = io->popNum, H = io->hapNum, PH = P * H, sC = io->sCounter, n = io->ev_ptr;
     if (P < 1 || H < 1 || P > INT32_MAX || H > INT32_MAX) return fail_(me + "bad dimensions");
     if (T < 1 || T >= VGX_PREV_MAX_POINTS) return fail_(me + "T = " + std::to_string(T) + " must be at least 1 and below 2^24");   // (vgx_test_lineages' words)
     if (V < 1 || V > INT32_MAX) return fail_(me + "V = " + std::to_string(V) + " must be at least 1");
     {
-        const std::string why = check_request(grid, T, V, variant_of, P, H);
+        const std::string why = check_request(grid, T, V, variant_of, P, H, events);
         if (!why.empty()) return fail_(me + why);
     }
     if (tile < 0) return fail_(me + "tile must not be negative");
@@ -483,6 +514,15 @@ extern "C" int vgx_test_tau_lineages(vgx_genealogy_io *io, int64_t sites, const 
     VgxPrevCutter ct{grid, T, bound.data()};
     for (int64_t e = 0; e < n; e++) ct.event(e, io->ev_times[e]);
     ct.finish(n);
+    if (events) {
+        const int64_t cells = P * V * VGX_TE_K;
+        for (int64_t i = 0; i < (T + 1) * cells; i++) values[i] = 0;
+        std::vector<int32_t> hist((size_t)cells, 0);
+        for (int64_t r0 = 0; r0 < lg.n; r0 += tile)
+            vgx_te_tile_host(rec.data(), bound.data(), (int32_t)T, (int32_t)P, (int32_t)H, (int32_t)V, variant_of, r0, std::min<int64_t>(r0 + tile, lg.n),
+                             hist.data(), values);
+        return VGX_OK;
+    }
     const int64_t cells = P * V;
     for (int64_t i = 0; i < T * cells; i++) values[i] = 0;
     for (int64_t i = 0; i < cells; i++) root[i] = 0;
@@ -492,4 +532,14 @@ extern "C" int vgx_test_tau_lineages(vgx_genealogy_io *io, int64_t sites, const 
                          hist.data(), values, root);
     for (int64_t i = 0; i < cells; i++) vgx_ln_scan_column(values + i, root + i, (int32_t)T, cells);
     return VGX_OK;
+}
+
+extern "C" int vgx_test_tau_lineages(vgx_genealogy_io *io, int64_t sites, const double *grid, int64_t T, const int32_t *variant_of, int64_t V, int64_t tile,
+                                     int32_t *values, int32_t *root, int64_t *records, char *errbuf, int64_t errcap) {
+    return tau_lineages_hook(io, sites, grid, T, variant_of, V, tile, values, root, records, errbuf, errcap, false, "vgx_test_tau_lineages");
+}
+
+extern "C" int vgx_test_tau_tree_events(vgx_genealogy_io *io, int64_t sites, const double *grid, int64_t T, const int32_t *variant_of, int64_t V, int64_t tile,
+                                        int32_t *counts, int64_t *records, char *errbuf, int64_t errcap) {
+    return tau_lineages_hook(io, sites, grid, T, variant_of, V, tile, counts, nullptr, records, errbuf, errcap, true, "vgx_test_tau_tree_events");
 }

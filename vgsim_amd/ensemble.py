@@ -345,6 +345,76 @@ class Lineages:
         return out
 
 
+class TreeEvents:
+    """What ``Ensemble.tree_events`` and ``Ensemble.tau_tree_events`` return: the events of every selected replicate's sampled tree
+    per interval of the grid, population, variant class and kind: the tree's counterpart of :class:`Incidence` and
+    :class:`Flows`, from the walk and the lineage log of :class:`Lineages`.
+
+    ``counts`` [n, T + 1, P, V, 7] int32 (None when the call had ``values=False``): interval i = 0 .. T holds the events after
+    ``times[i - 1]`` up to and including ``times[i]`` (interval 0 from the start, interval T the tail after the last grid time),
+    the last axis the channels ``CHANNELS``, each with an accessor of its name that gives [n, T + 1, P, V]: ``samples`` (a tip),
+    ``coalescences`` (an internal node; in the population of the lineages it joins), ``mutations_within`` (a lineage's mutation
+    inside one class), ``mutations_out`` and ``mutations_in`` (between classes, at the class left and the class entered),
+    ``departures`` and ``arrivals`` (a lineage moved by a migration without coalescing, at its source and its destination).
+    ``net()`` is their signed sum, the net change of the lineages of a cell, and ``lineages()`` the :class:`Lineages` that
+    follows from it.  ``times`` [T]; ``variant_of`` [H]; ``replicates`` [n]; ``status``, ``status_arg``, ``ok``, ``message(i)``,
+    ``records``, ``rng_raw`` as :class:`Lineages` (a failed walk's row holds zeros); ``summary`` a :class:`TrajectorySummary`
+    over the [T + 1, P, V, 7] columns, or None; ``passes``, ``kernel_ms`` (``stage_ms``: walk and binning apart; for tau
+    replicates canonicalise, walk and binning), ``clock_ms``, ``wall_ms``."""
+
+    CHANNELS = _capi.TREE_EVENT_CHANNELS
+
+    @property
+    def ok(self):
+        return self.status == 0
+
+    def message(self, i):
+        """Text of row i's status: what ``Ensemble.genealogy`` raises for that replicate ('' when its walk succeeded)."""
+        return _capi.genealogy_message(int(self.status[i]), int(self.status_arg[i]))
+
+    def net(self):
+        """The net change of the lineages per interval and cell, [n, T + 1, P, V] int64: coalescences - samples + mutations_in -
+        mutations_out + arrivals - departures."""
+        c = self.counts.astype(np.int64)
+        return c[..., 1] - c[..., 0] + c[..., 4] - c[..., 3] + c[..., 6] - c[..., 5]
+
+    def lineages(self):
+        """The :class:`Lineages` of the same walk, computed on the host from ``counts``: no lineage is alive after the last event,
+        so ``root`` is minus the net change of all intervals and ``values[:, j]`` the root plus that of the intervals 0 .. j."""
+        net = self.net()
+        ln = Lineages()
+        root = -net.sum(axis=1)
+        ln.root = root.astype(np.int32)
+        ln.values = (root[:, None] + np.cumsum(net[:, :-1], axis=1)).astype(np.int32)
+        ln.times, ln.variant_of, ln.replicates = self.times, self.variant_of, self.replicates
+        ln.status, ln.status_arg, ln.records, ln.rng_raw = self.status, self.status_arg, self.records, self.rng_raw
+        ln.summary = None
+        ln.passes, ln.kernel_ms, ln.clock_ms, ln.wall_ms, ln.stage_ms = self.passes, self.kernel_ms, self.clock_ms, self.wall_ms, self.stage_ms
+        return ln
+
+    # one accessor per channel, [n, T + 1, P, V]
+    def samples(self):
+        return self.counts[..., 0]
+
+    def coalescences(self):
+        return self.counts[..., 1]
+
+    def mutations_within(self):
+        return self.counts[..., 2]
+
+    def mutations_out(self):
+        return self.counts[..., 3]
+
+    def mutations_in(self):
+        return self.counts[..., 4]
+
+    def departures(self):
+        return self.counts[..., 5]
+
+    def arrivals(self):
+        return self.counts[..., 6]
+
+
 class Susceptibles:
     """What ``Ensemble.susceptibles`` returns: susceptible hosts per selected replicate, grid time, population and class of
     susceptibility groups.
@@ -1392,6 +1462,107 @@ class Ensemble:
             raise
         ln.summary = done() if done is not None else None
         return ln
+
+    def tree_events(self, times=None, points=None, window=None, variants=None, seed=None, replicates=None, summary=None, values=True):
+        """The events of every selected replicate's sampled tree per interval of ONE grid, population, variant class and kind, for
+        the last direct ``simulate(record_events=True)`` call and on the device (``vgx_get_tree_events``): samples, coalescences
+        (the skyline's numerator), lineage mutations within and between classes, and lineage moves out of and into every
+        population.  The walk and its lineage log are those of ``lineages()``; one binning pass keeps the kinds apart.  Returns a
+        :class:`TreeEvents`, whose ``lineages()`` gives what ``lineages()`` returns for the same arguments without a second walk.
+
+        All arguments as ``lineages()`` takes them, with its refusals; interval i = 0 .. T of the block lies between
+        ``times[i - 1]`` and ``times[i]`` (the last one after ``times[-1]``).  ``summary`` is taken over the [T + 1, P, V, 7] columns;
+        a summary refused after the block is there carries it as ``.tree_events``.  Direct chains only."""
+        g = _prevalence_grid(times, points, window)
+        if self._last_call is None:
+            raise ValueError("tree_events() needs a direct simulate(record_events=True) call first")
+        if self._last_call[0] != 'direct':
+            raise ValueError("tree_events() walks direct chains only: the last call was simulate_tau")
+        if not self._last_call[1]:
+            raise ValueError("tree_events() needs the event log: the last call had record_events=False")
+        reps = self._selected_replicates(replicates)
+        counters = [self.engine.counters(int(r)) for r in reps]
+        for r, c in zip(reps, counters):
+            if c.ev_first_new != 0:
+                raise ValueError("replicate %d: its chain does not start in the last call's device log (the model held %d events "
+                                 "when the ensemble started)" % (r, c.ev_first_new))
+        rng = self._walk_starts(reps, counters, seed)
+        return self._tree_events(False, g, variants, reps, rng, [c.reserved[4] < 2 for c in counters], summary, values)
+
+    def tau_tree_events(self, times=None, points=None, window=None, variants=None, seed=None, replicates=None, summary=None, values=True):
+        """``tree_events()`` for the replicates of the last ``simulate_tau(record_events=True)`` call
+        (``vgx_get_tau_tree_events``): the walk, chain and cuts of ``tau_lineages()`` with the binning of ``tree_events()``.  All
+        records of a step share the step's time: a grid time exactly at a step's time has the whole step in the intervals up to
+        it.  Arguments and refusals as ``tau_lineages()``; returns a :class:`TreeEvents` (``stage_ms``: canonicalise, walk,
+        binning)."""
+        g = _prevalence_grid(times, points, window)
+        self._check_tau_genealogy_call("tau_tree_events()")
+        lib = self.engine.lib
+        reps = self._selected_replicates(replicates)
+        n = len(reps)
+        if seed is not None and not np.isscalar(seed):
+            seeds = np.ascontiguousarray(seed, dtype=np.int64).ravel()
+            if len(seeds) != n:
+                raise ValueError("one seed per selected replicate: got %d for %d" % (len(seeds), n))
+        rng = np.zeros((max(n, 1), 6), dtype=np.uint64)
+        pos = (C.c_uint64 * 4)()
+        for i, r in enumerate(reps):
+            lib.vgx_rng_position(int(self.seeds[r]) if seed is None else int(seed) if np.isscalar(seed) else int(seeds[i]), 0, 0, C.byref(pos))
+            rng[i, :4] = list(pos)
+        few = [self.engine.counters(int(r)).reserved[4] < 2 for r in reps] if summary is not None else None
+        return self._tree_events(True, g, variants, reps, rng, few, summary, values)
+
+    def _tree_events(self, tau, g, variants, reps, rng, few, summary, values):
+        """What ``tree_events()`` and ``tau_tree_events()`` share once the walks' starts ``rng`` are known: the checks on
+        ``variants``, the LDS limit, ``summary`` and ``values``, the library call and the :class:`TreeEvents`.  ``few``: per selected
+        replicate, fewer than two samples (known from the counters before any walk: such a replicate is in no group)."""
+        eng = self.engine
+        vo, V = _capi.variant_map(variants, self.model.hapNum)
+        n, T, P, K = len(reps), len(g), self.model.popNum, len(TreeEvents.CHANNELS)
+        if 4 * K * P * V > 65536:
+            raise ValueError("%d populations x %d classes x %d channels need %d bytes of cells, above the 65536 bytes of LDS a counting "
+                             "workgroup may use" % (P, V, K, 4 * K * P * V))
+        leave_out = None
+        if few is not None:
+            leave_out = np.zeros(self.R, dtype=bool)
+            leave_out[reps] = few
+        sio, done = self._block_summary(summary, reps, (T + 1, P, V, K), self.scenario_of,
+                                        len(self.scenarios) if self.scenarios is not None else 1, leave_out)
+        if summary is None and not values:
+            raise ValueError("values=False needs summary=: the call would return nothing")
+        words = 6 if tau else 4
+        block = np.zeros((n, T + 1, P, V, K), dtype=np.int32) if values else None
+        per = {k: np.zeros(max(n, 1), dtype=np.int64) for k in ("status", "status_arg", "records")}
+        rng_out = np.zeros((max(n, 1), words), dtype=np.uint64)
+        i32, u64 = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+        io = _capi.VgxTauTreeEventsIO() if tau else _capi.VgxTreeEventsIO()
+        io.n, io.replicates, io.rng_state = n, _capi._p(reps), rng.ctypes.data_as(u64)
+        io.T, io.grid, io.V, io.variant_of = T, _capi._p(g), V, vo.ctypes.data_as(i32)
+        io.counts = block.ctypes.data_as(i32) if values and n else None
+        io.status, io.status_arg, io.records = _capi._p(per["status"]), _capi._p(per["status_arg"]), _capi._p(per["records"])
+        io.rng_out = rng_out.ctypes.data_as(u64)
+        io.summary = C.pointer(sio) if sio is not None and n else None
+        if tau:
+            pre = self._tau_genealogy_prefix_struct()
+            rc = eng.lib.vgx_get_tau_tree_events(eng.handle, C.byref(io), C.byref(pre))
+        else:
+            rc = eng.lib.vgx_get_tree_events(eng.handle, C.byref(io))
+        te = TreeEvents()
+        te.counts, te.times, te.variant_of, te.replicates = block, g, vo, reps
+        te.status, te.status_arg, te.records = per["status"][:n], per["status_arg"][:n], per["records"][:n]
+        te.rng_raw = np.zeros((n, 6), dtype=np.uint64)
+        te.rng_raw[:, :words] = rng_out[:n]
+        te.summary = None
+        te.passes, te.kernel_ms, te.clock_ms, te.wall_ms = int(io.passes), io.ms[0], io.ms[1], io.ms[2]
+        te.stage_ms = tuple(io.kernel_ms)
+        try:
+            eng._check(rc)
+        except _capi.VgxError as err:
+            if sio is not None and ": summary: " in str(err):   # refused after counts and status were delivered
+                err.tree_events = te
+            raise
+        te.summary = done() if done is not None else None
+        return te
 
     def milestones(self, variants=None, thresholds=(), replicates=None):
         """Peaks, first passages and extinctions of every selected replicate of the last direct ``simulate(record_events=True)``
