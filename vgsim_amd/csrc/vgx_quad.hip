@@ -504,6 +504,14 @@ static __device__ __forceinline__ void quad_body() {
     // drops the tag (register path, below); UpdateRates of another population leaves this one's tE alone (no lockdown switches).
     double tc = 0.0;
     int tc_pi = -1;
+    // Short-list kernel: the population choice reads no LDS.  Lane l of the row keeps infectPopRate of its populations l, l + 16,
+    // l + 32, l + 48 (the copy of s_inf[]: patched wherever that is written) and, row-uniform, the serial prefix sums at the end
+    // of the four slots (what s_cc[] holds in the long-list kernel).
+    double inf4[4] = {0.0, 0.0, 0.0, 0.0}, cc4[4] = {0.0, 0.0, 0.0, 0.0};
+    // iterations for which the integer loop conditions (log space, sample count, loop guard) certainly hold: each of the three
+    // margins falls by at most one per iteration, so while the countdown runs only the time limit is looked at; at zero it is
+    // formed again from the conditions themselves (a Restart only widens the margins)
+    int safe = 0;
 
 #ifdef VGX_PROFILE
     unsigned long long prof_acc[VGX_PROF_SLOTS], prof_t0 = __builtin_readcyclecounter();
@@ -539,12 +547,36 @@ static __device__ __forceinline__ void quad_body() {
                     if (!(totalRate + totalMig != 0.0 && gI != 0.0)) end_attempt = true;   // pyx:404
                 }
             }
-            if (st == ST_RUN && !end_attempt &&
-                !(ev_ptr < a.ev_size && (a.sample_size == -1 || cS <= a.sample_size) && (!has_tl || t_now < tlimit)))
-                end_attempt = true;
-            if (st == ST_RUN && !end_attempt) {
-                if (loops >= a.max_loop) { err = Q_ERR_LOOP_GUARD; st = ST_DONE; }
-                else ev = true;
+            if (QT >= 4) {
+                if (st == ST_RUN && !end_attempt &&
+                    !(ev_ptr < a.ev_size && (a.sample_size == -1 || cS <= a.sample_size) && (!has_tl || t_now < tlimit)))
+                    end_attempt = true;
+                if (st == ST_RUN && !end_attempt) {
+                    if (loops >= a.max_loop) { err = Q_ERR_LOOP_GUARD; st = ST_DONE; }
+                    else ev = true;
+                }
+            }
+        }
+        if (QT < 4) {       // the short-list kernel: the same conditions behind the countdown
+            const bool chk = st == ST_RUN && !end_attempt;
+            bool slow = false;
+            if (__builtin_expect(__ballot(chk && safe <= 0) != 0, 0)) {
+                if (chk && safe <= 0) {
+                    int64_t m = min(a.ev_size - ev_ptr, a.max_loop - loops);
+                    if (a.sample_size != -1) m = min(m, a.sample_size - cS + 1);
+                    safe = (int)max(min(m, (int64_t)0x7fffffff), (int64_t)0);
+                    if (safe == 0) {       // one of them fails now: the conditions themselves, in the reference's order
+                        slow = true;
+                        if (!(ev_ptr < a.ev_size && (a.sample_size == -1 || cS <= a.sample_size) && (!has_tl || t_now < tlimit)))
+                            end_attempt = true;
+                        else if (loops >= a.max_loop) { err = Q_ERR_LOOP_GUARD; st = ST_DONE; }
+                        else ev = true;
+                    }
+                }
+            }
+            if (chk && !slow) {
+                safe -= 1;
+                if (has_tl && !(t_now < tlimit)) end_attempt = true; else ev = true;
             }
         }
 
@@ -610,29 +642,52 @@ static __device__ __forceinline__ void quad_body() {
             // every 16-population slot are cached (they are partial sums of the totalRate loop, pyx:537-539): the first slot
             // whose end reaches r holds the pick, and the prefix sums inside it are formed again — same additions, same order.
             int pi = 0;
+            double infect_pi = 0.0;
             {
                 rn = choose / totalRate;
                 const double rr_ = totalRate * rn;
-                const double c0 = s_cc[0], c1 = s_cc[1], c2 = s_cc[2], c3 = s_cc[3];   // slots beyond P repeat the total
-                const int slot = !(c0 < rr_) ? 0 : !(c1 < rr_) ? 1 : !(c2 < rr_) ? 2 : 3;
-                const bool any = !(c3 < rr_);
-                const double cin = slot == 0 ? 0.0 : slot == 1 ? c0 : slot == 2 ? c1 : c2;
-                const double w = s_inf[slot * 16 + rl];
-                double tot_;
-                const double pre = row_scan16(w, cin, tot_);
-                const int q = row_min(any && slot * 16 + rl < P && !(pre < rr_) ? rl : 16);
                 double total, wi;
-                if (q < 16) { pi = slot * 16 + q; total = rowget_f64(pre, q); wi = rowget_f64(w, q); }
-                else { pi = P - 1; total = c3; wi = s_inf[P - 1]; }       // clamp at n-1 (fc:26)
+                if (QT < 4) {
+                    // slots beyond P repeat the total.  Nothing reaches r: clamp at n-1 (fc:26), whose weight is in the last slot in use
+                    const double c0 = cc4[0], c1 = cc4[1], c2 = cc4[2], c3 = cc4[3];
+                    const bool any = !(c3 < rr_);
+                    const int slot = !any ? nslot - 1 : !(c0 < rr_) ? 0 : !(c1 < rr_) ? 1 : !(c2 < rr_) ? 2 : 3;
+                    const double cin = slot == 0 ? 0.0 : slot == 1 ? c0 : slot == 2 ? c1 : c2;
+                    const double w = slot == 0 ? inf4[0] : slot == 1 ? inf4[1] : slot == 2 ? inf4[2] : inf4[3];
+                    double tot_;
+                    const double pre = row_scan16(w, cin, tot_);
+                    // (the slot's end is the prefix at its last population, by the same additions: with `any` some lane has the hit)
+                    const int q = row_min(any && slot * 16 + rl < P && !(pre < rr_) ? rl : 16);
+                    const int qq = q < 16 ? q : (P - 1) & 15;
+                    pi = q < 16 ? slot * 16 + q : P - 1;
+                    const double tq = rowget_f64(pre, qq);
+                    wi = rowget_f64(w, qq);
+                    total = q < 16 ? tq : c3;
+                } else {
+                    const double c0 = s_cc[0], c1 = s_cc[1], c2 = s_cc[2], c3 = s_cc[3];   // slots beyond P repeat the total
+                    const int slot = !(c0 < rr_) ? 0 : !(c1 < rr_) ? 1 : !(c2 < rr_) ? 2 : 3;
+                    const bool any = !(c3 < rr_);
+                    const double cin = slot == 0 ? 0.0 : slot == 1 ? c0 : slot == 2 ? c1 : c2;
+                    const double w = s_inf[slot * 16 + rl];
+                    double tot_;
+                    const double pre = row_scan16(w, cin, tot_);
+                    const int q = row_min(any && slot * 16 + rl < P && !(pre < rr_) ? rl : 16);
+                    if (q < 16) { pi = slot * 16 + q; total = rowget_f64(pre, q); wi = rowget_f64(w, q); }
+                    else { pi = P - 1; total = c3; wi = s_inf[P - 1]; }       // clamp at n-1 (fc:26)
+                }
                 if (evn && wi == 0.0) err = Q_ERR_ZERO_WEIGHT + 256 * 1;
                 rn = (rr_ - (total - wi)) / wi;
                 choose = rn * wi;                    // pyx:493: rn * popRate[pi]
+                infect_pi = wi;
             }
-            // immunePopRate[pi] = +0.0 is never > choose: the infect branch (pyx:499-500)
-            const double infect_pi = s_inf[pi];
+            // immunePopRate[pi] = +0.0 is never > choose: the infect branch (pyx:499-500).  infectPopRate[pi] is the weight of the pick.
+            if (QT >= 4) infect_pi = s_inf[pi];
             rn = (choose - 0.0) / infect_pi;
+            // what the event needs of its population, behind one wait (the long-list kernel reads the totals where it applies the event)
             const double bC = s_bc[pi];
             const double smul = k_smul[pi];
+            double ts_pi = 0.0, ti_pi = 0.0;
+            if (QT < 4) { ts_pi = s_ts[pi]; ti_pi = s_ti[pi]; }
             const double tE = ((bC + c_d) + smul) + c_tm;          // tEventHapPopRate (pyx:522-526)
             const int n_sel = evn ? s_nocc[pi] : 0;
             const int32_t *lh = lhap + (int64_t)pi * cap;
@@ -757,7 +812,7 @@ static __device__ __forceinline__ void quad_body() {
                 rn = (r3 - (total - wi)) / wi;
             }
             const bool go = evn && err == 0;
-            const double ts_pi = s_ts[pi], ti_pi = s_ti[pi];
+            if (QT >= 4) { ts_pi = s_ts[pi]; ti_pi = s_ti[pi]; }
             const bool isB = go && ei == 0, isD = go && (ei == 1 || ei == 2), isM = go && ei == 3;
             if (isB) {
                 // ---- Birth (pyx:568-605; one susceptibility group: si = 0, its weight susceptHapPopRate = S * sigma) ----
@@ -1198,21 +1253,28 @@ static __device__ __forceinline__ void quad_body() {
                     acc = q_long_sum<QT>(l3, L8(pi), n, maxn, tE, (double *)(ltsum + (int64_t)pi * capT + R * P * capT), act, pi, tc, tc_pi);   // (the long-list kernel's running sums lie behind the tile sums, vgx_dev.h)
                 }
                 if (act && rl == 0) { s_bc[pi] = bC; s_inf[pi] = acc; }
-                WSYNC();
+                if (QT < 4) {       // the lane that owns pi takes the row's sum as it stands: the LDS copy is for the indexed readers
+#pragma unroll
+                    for (int s = 0; s < 4; ++s)
+                        if (act && pi == s * 16 + rl) inf4[s] = acc;
+                } else WSYNC();
                 QPROF(12);
             }
             // totalRate and the serial prefix sums of popRate (pyx:537-539)
             {
                 double w4[4], carry = 0.0, cend[4];
 #pragma unroll
-                for (int s = 0; s < 4; ++s) w4[s] = s_inf[s * 16 + rl];      // lanes beyond P hold +0.0
+                for (int s = 0; s < 4; ++s) w4[s] = QT < 4 ? inf4[s] : s_inf[s * 16 + rl];      // lanes beyond P hold +0.0
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
                     if (s < nslot) carry = row_sum16(w4[s], carry);
                     cend[s] = carry;
                 }
                 if (u_hi > u_lo) {
-                    if (rl < 4) s_cc[rl] = rl == 0 ? cend[0] : rl == 1 ? cend[1] : rl == 2 ? cend[2] : cend[3];
+                    if (QT < 4) {
+#pragma unroll
+                        for (int s = 0; s < 4; ++s) cc4[s] = cend[s];
+                    } else if (rl < 4) s_cc[rl] = rl == 0 ? cend[0] : rl == 1 ? cend[1] : rl == 2 ? cend[2] : cend[3];
                     totalRate = carry;       // = the prefix sum at P-1: the lanes beyond P add +0.0
                 }
                 WSYNC();
@@ -1255,6 +1317,7 @@ static __device__ __forceinline__ void quad_body() {
                 restarts += 1; att += 1;
                 st = ST_REBUILD;
                 tc_pi = -1;
+                safe = 0;
             } else {
                 good_attempt = (int64_t)att + 1;
                 st = ST_DONE;
