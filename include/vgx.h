@@ -870,6 +870,48 @@ int vgx_get_tau_tree_events(vgx_engine *e, vgx_tau_tree_events_io *io, const vgx
 int vgx_test_tau_tree_events(vgx_genealogy_io *io, int64_t sites, const double *grid, int64_t T, const int32_t *variant_of, int64_t V, int64_t tile,
                              int32_t *counts, int64_t *records, char *errbuf, int64_t errcap);
 
+/* ---- tree shapes: balance, depth and branch statistics of every replicate's sampled tree ---------------------------------- */
+/* One row of scalars per selected replicate of the last vgx_simulate_direct call: the walk of vgx_get_genealogies
+ * (same draws, status and generator afterwards), then one kernel that reduces every tree where the walk left it.  A tree of a walk
+ * with status 0 has N = 2 sCounter - 1 nodes in creation order: tree[N - 1] == -1 is the root, i < tree[i] < N otherwise, every node
+ * has no children (a tip) or two, and node times do not increase with the id.  With n_v the tips below node v, minkid_v the smaller
+ * of its two children's n, tipkids_v its tip children, and lad_v = 1 + max over children of lad_c where tipkids_v == 1, else 0:
+ *   stats[r][k]  int64 [n][12]: 0 tips, 1 internal, 2 cherries (tipkids == 2), 3 pitchforks (n_v == 3), 4 sackin (sum of the tips'
+ *                depths), 5 colless (sum over internal nodes of n_v - 2 minkid_v), 6 max_depth (edges), 7 depth_sumsq (sum of the
+ *                tips' squared depths: wraps beyond about 2 * 10^6 tips of a caterpillar tree), 8 ladder_nodes (tipkids == 1),
+ *                9 max_ladder (max lad_v), 10 root_event, 11 last_tip_event (the event indices of node N - 1 and node 0)
+ *   lengths[r][k] f64 [n][7]: with b_i = times[i] - times[tree[i]] >= 0: 0 root_time, 1 last_tip_time (times of node N - 1 and node
+ *                0), 2 length (sum b_i), 3 external_length (sum over tips), 4 length_sumsq (sum b_i^2), 5 tip_height_sum (sum over
+ *                tips of times[i] - root_time), 6 max_branch.  0, 1 and 6 are exact; the four sums are taken in the kernel's order,
+ *                within 2 (N + 2) 2^-53 of their value of any other order.
+ * A replicate whose walk fails gets its status (as vgx_genealogies_io), zeros and NaN lengths and does not fail the call; a tree
+ * that breaks the structure above gets status 13 (status_arg = the first offending node; vgx_genealogy_message has its text).  There
+ * is no sizing call: the walk's record capacities are counted inside.  Per pass (sized as vgx_get_genealogies sizes its passes, the
+ * node times and 44 bytes of accumulators per node added; VGX_GENEALOGY_CHUNK_BYTES) only the 4-byte node event indices come to the
+ * host and the 8-byte node times of the host clock go back.  Preconditions and refusals are those of vgx_get_genealogies, worded
+ * behind "vgx_get_tree_shapes: "; replicates must be distinct. */
+typedef struct vgx_tree_shapes_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    const uint64_t *rng_state;                   /* [n][4] PCG64 start of every walk */
+    int64_t *stats;                              /* [n][12] */
+    double *lengths;                             /* [n][7] */
+    int64_t *status, *status_arg;                /* [n] */
+    uint64_t *rng_out;                           /* [n][4] generator state after the walk */
+    int64_t passes;                              /* out: device passes */
+    double ms[4];                                /* out: walk kernel, shape kernel (device time), host clock with the two node copies, whole call */
+} vgx_tree_shapes_io;
+int vgx_get_tree_shapes(vgx_engine *e, vgx_tree_shapes_io *io);
+/* Test hook: the sequential sweep of vgx_tree_shape.h on one tree of `nodes` nodes on the host.  Refuses (message in errbuf, naming
+ * the first offending node) a tree that breaks the structure above. */
+int vgx_test_tree_shape(const int32_t *tree, const int32_t *node_ev, const double *times, int64_t nodes, int64_t *stats, double *lengths,
+                        char *errbuf, int64_t errcap);
+/* Test hook: n given trees (tree t: nodes node_off[t] .. node_off[t + 1] of the three arrays) through the kernel of
+ * vgx_get_tree_shapes on the current device's default stream; no engine.  stats [n][12], lengths [n][7], status [n][2] (status and
+ * its argument: 0, or 13 and the node; that tree's row holds zeros and NaN).  Parents outside i < tree[i] < N (-1 at the last node)
+ * and node counts that are even or below 3 are refused before anything is uploaded. */
+int vgx_test_tree_shape_device(int64_t n, const int64_t *node_off, const int32_t *tree, const int32_t *node_ev, const double *times,
+                               int64_t *stats, double *lengths, int64_t *status, char *errbuf, int64_t errcap);
+
 /* The same counts for many replicates of the last vgx_simulate_tau call (with the event log), on the device.
  * A tau replicate's chain is a list of weighted rows (num, type, haplotype, population, newHaplotype, newPopulation), six int64:
  * the events the model held when the call started (`prefix`, as vgx_get_tau_timelines takes it; its lockdown columns are not

@@ -165,6 +165,18 @@ class VgxTauTreeEventsIO(C.Structure):   # VgxTreeEventsIO with six generator wo
 TREE_EVENT_CHANNELS = ("samples", "coalescences", "mutations_within", "mutations_out", "mutations_in", "departures", "arrivals")
 
 
+class VgxTreeShapesIO(C.Structure):
+    _fields_ = [("n", C.c_int64), ("replicates", _I), ("rng_state", C.POINTER(C.c_uint64)), ("stats", _I), ("lengths", _F),
+                ("status", _I), ("status_arg", _I), ("rng_out", C.POINTER(C.c_uint64)), ("passes", C.c_int64), ("ms", C.c_double * 4)]
+
+
+# the columns of vgx_tree_shapes_io.stats and .lengths (vgx_tree_shape.h)
+TREE_SHAPE_STATS = ("tips", "internal", "cherries", "pitchforks", "sackin", "colless", "max_depth", "depth_sumsq", "ladder_nodes", "max_ladder",
+                    "root_event", "last_tip_event")
+TREE_SHAPE_LENGTHS = ("root_time", "last_tip_time", "length", "external_length", "length_sumsq", "tip_height_sum", "max_branch")
+GW_BAD_TREE = 13   # the status of a replicate whose tree breaks the structure the shape sweep needs (status_arg: the node)
+
+
 class VgxFlowsIO(C.Structure):
     _fields_ = [("n", C.c_int64), ("replicates", _I), ("T", C.c_int64), ("edges", _F), ("V", C.c_int64), ("variant_of", C.POINTER(C.c_int32)),
                 ("within", C.c_int32), ("counts", C.POINTER(C.c_int32)), ("outside", _I), ("summary", C.POINTER(VgxTrajSummaryIO)),
@@ -365,6 +377,9 @@ SIGNATURES = {
     "vgx_get_tau_tree_events": (C.c_int, [_H, C.POINTER(VgxTauTreeEventsIO), C.POINTER(VgxTauGenealogyPrefix)]),
     "vgx_test_tau_tree_events": (C.c_int, [C.POINTER(VgxGenealogyIO), C.c_int64, _F, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int64,
                                            C.POINTER(C.c_int32), _I, C.c_char_p, C.c_int64]),
+    "vgx_get_tree_shapes": (C.c_int, [_H, C.POINTER(VgxTreeShapesIO)]),
+    "vgx_test_tree_shape": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F, C.c_int64, _I, _F, C.c_char_p, C.c_int64]),
+    "vgx_test_tree_shape_device": (C.c_int, [C.c_int64, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F, _I, _F, _I, C.c_char_p, C.c_int64]),
     "vgx_get_flows": (C.c_int, [_H, C.POINTER(VgxFlowsIO)]),
     "vgx_test_flows": (C.c_int, [_F, _I, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, _F, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int32,
                                  C.c_int64, C.c_int64, C.POINTER(C.c_int32), _I, _I, C.c_char_p, C.c_int64]),
@@ -1125,6 +1140,60 @@ def replay_tree_events(m, seed, grid, variant_of, V, tile=0, rng_position=None, 
 
 FLOW_FORMS = {None: 0, 'auto': 0, 'dense': 1, 'split': 2}   # VGX_FLOW_AUTO, VGX_FLOW_DENSE, VGX_FLOW_SPLIT
 FLOW_FORM_NAMES = {0: None, 1: 'dense', 2: 'split'}
+
+
+def _tree_arrays(tree, node_ev, times):
+    i32 = C.POINTER(C.c_int32)
+    t = np.ascontiguousarray(tree, dtype=np.int64).ravel()
+    ev = np.ascontiguousarray(node_ev, dtype=np.int64).ravel()
+    tm = np.ascontiguousarray(times, dtype=np.float64).ravel()
+    if not (len(t) == len(ev) == len(tm)):
+        raise ValueError("tree, node_ev and times must have one entry per node")
+    for name, a in (("tree", t), ("node_ev", ev)):
+        if len(a) and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise ValueError("%s does not fit 32 bits" % name)
+    t, ev = t.astype(np.int32), ev.astype(np.int32)
+    return t, ev, tm, i32
+
+
+def tree_shape(tree, node_ev, times):
+    """The row of ``Ensemble.tree_shapes`` for one tree through ``vgx_test_tree_shape``: the sequential sweep of vgx_tree_shape.h on
+    the host; no GPU.  ``tree`` parents (-1 at the last node, the root), ``node_ev`` event indices, ``times`` node times, one entry per
+    node.  Returns (stats int64 [12], lengths float64 [7]) in the order of ``TREE_SHAPE_STATS`` and ``TREE_SHAPE_LENGTHS``; raises
+    ``ValueError`` naming the first offending node for a tree that is not binary in creation order."""
+    t, ev, tm, i32 = _tree_arrays(tree, node_ev, times)
+    stats, lengths = np.zeros(len(TREE_SHAPE_STATS), dtype=np.int64), np.zeros(len(TREE_SHAPE_LENGTHS), dtype=np.float64)
+    err = C.create_string_buffer(512)
+    rc = load_library().vgx_test_tree_shape(t.ctypes.data_as(i32), ev.ctypes.data_as(i32), _p(tm), len(t), _p(stats), _p(lengths), err, 512)
+    if rc != VGX_OK:
+        raise ValueError(err.value.decode() or "vgx_test_tree_shape failed")
+    return stats, lengths
+
+
+def tree_shape_device(trees):
+    """The rows of given trees through the kernel of ``Ensemble.tree_shapes`` (``vgx_test_tree_shape_device``, one launch, no engine).
+    ``trees``: a sequence of (tree, node_ev, times) as ``tree_shape`` takes them.  Returns (stats [n, 12], lengths [n, 7], status
+    [n, 2]: status and its argument, ``GW_BAD_TREE`` and the node for a tree with a node of one child or more than two; its row holds
+    zeros and NaN).  Parents outside the tree are refused with ``ValueError`` before anything is uploaded."""
+    parts = [_tree_arrays(*tr)[:3] for tr in trees]
+    n = len(parts)
+    off = np.zeros(n + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(p[0]) for p in parts])
+    i32 = C.POINTER(C.c_int32)
+    t = np.ascontiguousarray(np.concatenate([p[0] for p in parts]) if n else np.zeros(0, np.int32), dtype=np.int32)
+    ev = np.ascontiguousarray(np.concatenate([p[1] for p in parts]) if n else np.zeros(0, np.int32), dtype=np.int32)
+    tm = np.ascontiguousarray(np.concatenate([p[2] for p in parts]) if n else np.zeros(0), dtype=np.float64)
+    stats = np.zeros((max(n, 1), len(TREE_SHAPE_STATS)), dtype=np.int64)
+    lengths = np.zeros((max(n, 1), len(TREE_SHAPE_LENGTHS)), dtype=np.float64)
+    status = np.zeros((max(n, 1), 2), dtype=np.int64)
+    err = C.create_string_buffer(512)
+    rc = load_library().vgx_test_tree_shape_device(n, _p(off), t.ctypes.data_as(i32), ev.ctypes.data_as(i32), _p(tm), _p(stats), _p(lengths),
+                                                   _p(status), err, 512)
+    if rc == 1:
+        raise ValueError(err.value.decode())
+    if rc != VGX_OK:
+        raise VgxError(rc, err.value.decode() or "vgx_test_tree_shape_device failed")
+    return stats[:n], lengths[:n], status[:n]
 
 
 def replay_flows(times, types, haplotypes, populations, newHaplotypes, newPopulations, popNum, hapNum, edges, variant_of, V, within=True,

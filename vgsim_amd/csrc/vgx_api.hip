@@ -2382,6 +2382,218 @@ extern "C" int vgx_get_tree_events(vgx_engine *e, vgx_tree_events_io *io) {
     return rc;
 }
 
+// ---- balance, depth and branch statistics of every tree (vgx_tree_shapes.hip, vgx_tree_shape.h) ----------------------
+// The walk pass of vgx_get_genealogies with the conversion left out: of the walk's outputs only the node event indices come to the
+// host, the host clock turns them into node times (the lookup of vgx_get_genealogies), the times go back and the shape kernel reduces
+// every tree where the walk left it.
+extern "C" int vgx_get_tree_shapes(vgx_engine *e, vgx_tree_shapes_io *io) {
+    if (!e || !io || io->n < 0 ||
+        (io->n > 0 && (!io->replicates || !io->rng_state || !io->stats || !io->lengths || !io->status || !io->status_arg || !io->rng_out)))
+        return VGX_ERR_ARG;
+    const std::string me = "vgx_get_tree_shapes: ";
+    const auto t_call = std::chrono::steady_clock::now();
+    auto since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
+    io->passes = 0;
+    io->ms[0] = io->ms[1] = io->ms[2] = io->ms[3] = 0.0;
+    if (!e->sc_host_valid || !e->dev_state_valid) return fail(e, VGX_ERR_ARG, me + "no direct simulate call yet");
+    if (e->last_was_tau) return fail(e, VGX_ERR_ARG, me + "the last call was vgx_simulate_tau (direct chains only)");
+    if (!e->call_recorded) return fail(e, VGX_ERR_ARG, me + "the last call did not record events");
+    const int64_t n = io->n, P = e->d.popNum, H = e->d.hapNum;
+    std::vector<int64_t> n_ev((size_t)n), sC((size_t)n);
+    {
+        std::vector<char> seen((size_t)e->R, 0);
+        for (int64_t i = 0; i < n; i++) {
+            const int64_t r = io->replicates[i];
+            if (r < 0 || r >= e->R) return fail(e, VGX_ERR_ARG, me + "replicate index out of range");
+            if (seen[(size_t)r]) return fail(e, VGX_ERR_ARG, me + "replicates must be distinct");
+            seen[(size_t)r] = 1;
+            const VgxRepScalars &s = e->sc_host[(size_t)r];
+            const int64_t first = s.restarts > 0 ? 0 : ((size_t)r < e->call_ev0.size() ? e->call_ev0[(size_t)r] : e->ev_ptr0);
+            if (first != 0 || e->ev_base != 0)
+                return fail(e, VGX_ERR_ARG, me + "the chain of replicate " + std::to_string(r) +
+                                                " does not start in the last call's device log (events.ptr was not 0 at its start)");
+            if (s.ev_ptr < 0 || s.ev_ptr > e->evcap || s.ev_ptr >= ((int64_t)1 << 30))
+                return fail(e, VGX_ERR_ARG, me + "event range of replicate " + std::to_string(r) + " outside the device log");
+            n_ev[(size_t)i] = s.ev_ptr;
+            sC[(size_t)i] = s.sCounter;
+        }
+    }
+    if (n == 0) {
+        io->ms[3] = since(t_call);
+        return VGX_OK;
+    }
+    HIPCHECK(e, hipSetDevice(e->device));
+    const int32_t *log = (const int32_t *)e->r_evcols.p;
+    auto up8 = [](int64_t b) { return (b + 255) / 256 * 256; };
+    hipError_t er;
+    // the MUTATION and MIGRATION events of every chain: the record capacities the walk needs (what the sizing call of vgx_get_genealogies counts)
+    std::vector<int64_t> cnt((size_t)n * 2);
+    {
+        char *cws = nullptr;
+        const int64_t o_n = up8(n * 8), o_out = o_n + up8(n * 8);
+        if ((er = hipMalloc((void **)&cws, (size_t)(o_out + up8(n * 16)))) != hipSuccess) return fail(e, VGX_ERR_HIP, me + "hipMalloc: " + hipGetErrorString(er));
+        std::unique_ptr<char, void (*)(char *)> chold(cws, [](char *p) { (void)hipFree(p); });
+        HIPCHECK(e, hipMemcpyAsync(cws, io->replicates, (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(cws + o_n, n_ev.data(), (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, vgxi_gw_count(log, e->evcap, (const int64_t *)cws, (const int64_t *)(cws + o_n), n, (int64_t *)(cws + o_out), e->stream));
+        HIPCHECK(e, hipMemcpyAsync(cnt.data(), cws + o_out, (size_t)n * 16, hipMemcpyDeviceToHost, e->stream));
+        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(e, VGX_ERR_HIP, me + "counting pass: " + hipGetErrorString(er));
+    }
+    // the walk reads the 8-byte counts of the final occupancy lists
+    if (!e->counts64_valid) {
+        HIPCHECK(e, vgxi_launch_counts64(e->dr.lcnt32, e->dr.lcnt, e->R * P * e->cap, e->stream));
+        HIPCHECK(e, hipStreamSynchronize(e->stream));
+        e->counts64_valid = true;
+    }
+    // per-replicate workspace and outputs (elements), and the passes: every pass holds at most `share` bytes
+    std::vector<VgxGwDesc> desc((size_t)n);
+    std::vector<int64_t> bytes((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        VgxGwDesc &d = desc[(size_t)i];
+        const int64_t nodes = sC[(size_t)i] >= 2 ? 2 * sC[(size_t)i] - 1 : 0;
+        d.rep = io->replicates[i];
+        d.n_ev = n_ev[(size_t)i];
+        d.sCounter = sC[(size_t)i];
+        d.tsize = d.sCounter >= 2 ? vgx_gw_table_size(d.n_ev, P * H) : 0;
+        d.arena_cap = d.sCounter >= 2 ? d.n_ev : 0;
+        d.mut_cap = cnt[(size_t)(2 * i)];
+        d.mig_cap = cnt[(size_t)(2 * i + 1)] + nodes;
+        for (int k = 0; k < 4; k++) d.rng[k] = io->rng_state[i * 4 + k];
+        bytes[(size_t)i] = d.tsize * 28 + d.arena_cap * 4 + nodes * (12 + 8 + VGX_TS_NODE_BYTES) + d.mut_cap * 20 + d.mig_cap * 16 +
+                           (int64_t)(sizeof(VgxGwDesc) + sizeof(VgxTsDesc)) + 72 + 8 * (VGX_TS_K + VGX_TS_L + 2);
+    }
+    size_t free_b = 0, total_b = 0;
+    HIPCHECK(e, hipMemGetInfo(&free_b, &total_b));
+    int64_t share = (int64_t)(free_b / 2);
+    if (const char *cb = getenv("VGX_GENEALOGY_CHUNK_BYTES")) share = std::min<int64_t>(share, std::max<int64_t>(atoll(cb), 1));
+    std::vector<int64_t> mism((size_t)n, 0);
+    int64_t i0 = 0;
+    while (i0 < n) {
+        int64_t i1 = i0, sum = 0;
+        while (i1 < n && (i1 == i0 || sum + bytes[(size_t)i1] <= share)) sum += bytes[(size_t)i1++];
+        const int64_t m = i1 - i0;
+        int64_t T = 0, A = 0, N = 0, M = 0, G = 0;
+        std::vector<VgxGwDesc> dp(desc.begin() + i0, desc.begin() + i1);
+        std::vector<VgxTsDesc> ts((size_t)m);
+        for (int64_t j = 0; j < m; j++) {
+            VgxGwDesc &d = dp[(size_t)j];
+            const int64_t nodes = d.sCounter >= 2 ? 2 * d.sCounter - 1 : 0;
+            d.tab_off = T; d.arena_off = A; d.node_off = N; d.mut_off = M; d.mig_off = G;
+            ts[(size_t)j] = VgxTsDesc{N, nodes};
+            T += d.tsize; A += d.arena_cap; N += nodes; M += d.mut_cap; G += d.mig_cap;
+        }
+        // one allocation: the walk's of vgx_get_genealogies [desc | res | rng | key | cnt | base | len | lcap | arena | node x3 | mut x5 | mig x4],
+        // then [tree descs | node times | A, B | seven int32 accumulators | stats | lengths | status]
+        const int64_t o_desc = 0, o_res = o_desc + up8(m * (int64_t)sizeof(VgxGwDesc)), o_rng = o_res + up8(m * 40),
+                      o_key = o_rng + up8(m * 32), o_cnt = o_key + up8(T * 8), o_base = o_cnt + up8(T * 8), o_len = o_base + up8(T * 4),
+                      o_lcap = o_len + up8(T * 4), o_arena = o_lcap + up8(T * 4), o_out = o_arena + up8(A * 4),
+                      o_ts = o_out + up8((3 * N + 5 * M + 4 * G) * 4), o_times = o_ts + up8(m * (int64_t)sizeof(VgxTsDesc)), o_w64 = o_times + up8(N * 8),
+                      o_w32 = o_w64 + up8(2 * N * 8), o_stats = o_w32 + up8(7 * N * 4), o_lens = o_stats + up8(m * VGX_TS_K * 8),
+                      o_status = o_lens + up8(m * VGX_TS_L * 8), total = o_status + up8(m * 16);
+        char *ws = nullptr;
+        if ((er = hipMalloc((void **)&ws, (size_t)total)) != hipSuccess)
+            return fail(e, VGX_ERR_HIP, me + "hipMalloc of " + std::to_string(total) + " bytes: " + hipGetErrorString(er));
+        std::unique_ptr<char, void (*)(char *)> hold(ws, [](char *p) { (void)hipFree(p); });
+        VgxGwLaunch a{};
+        a.n = m;
+        a.desc = (const VgxGwDesc *)(ws + o_desc);
+        a.log = log; a.evcap = e->evcap;
+        a.nocc = e->dr.nocc; a.lhap = e->dr.lhap; a.lcnt = e->dr.lcnt;
+        a.P = P; a.H = H; a.cap = e->cap;
+        a.key = (int64_t *)(ws + o_key); a.cnt = (int64_t *)(ws + o_cnt);
+        a.base = (int32_t *)(ws + o_base); a.len = (int32_t *)(ws + o_len); a.lcap = (int32_t *)(ws + o_lcap);
+        a.arena = (int32_t *)(ws + o_arena);
+        int32_t *o32 = (int32_t *)(ws + o_out);
+        a.tree = o32; a.tree_pop = o32 + N; a.node_ev = o32 + 2 * N;
+        int32_t *mu = o32 + 3 * N;
+        a.mut_node = mu; a.mut_AS = mu + M; a.mut_DS = mu + 2 * M; a.mut_site = mu + 3 * M; a.mut_ev = mu + 4 * M;
+        int32_t *mg = mu + 5 * M;
+        a.mig_node = mg; a.mig_old = mg + G; a.mig_new = mg + 2 * G; a.mig_ev = mg + 3 * G;
+        a.res = (int64_t *)(ws + o_res);
+        a.rng_out = (uint64_t *)(ws + o_rng);
+        // 1. the walk, in wave layout
+        HIPCHECK(e, hipMemcpyAsync(ws + o_desc, dp.data(), (size_t)m * sizeof(VgxGwDesc), hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(ws + o_ts, ts.data(), (size_t)m * sizeof(VgxTsDesc), hipMemcpyHostToDevice, e->stream));
+        if (T > 0) HIPCHECK(e, hipMemsetAsync(a.key, 0xFF, (size_t)T * 8, e->stream));   // every slot empty (-1)
+        HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
+        HIPCHECK(e, vgxi_gw_walk(&a, 1, e->stream));
+        HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
+        // 2. before anything reads the walk's outputs
+        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(e, VGX_ERR_HIP, me + "walk kernel failed: " + hipGetErrorString(er));
+        float kms = 0.f;
+        HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
+        io->ms[0] += kms;
+        std::vector<int64_t> res((size_t)m * 5);
+        HIPCHECK(e, hipMemcpy(res.data(), a.res, (size_t)m * 40, hipMemcpyDeviceToHost));
+        HIPCHECK(e, hipMemcpy(io->rng_out + i0 * 4, a.rng_out, (size_t)m * 32, hipMemcpyDeviceToHost));
+        // 3. the node event indices alone  4. every replicate's host clock  5. the node times, back to the device
+        const auto t_clock = std::chrono::steady_clock::now();
+        std::vector<int32_t> h_nev((size_t)N);
+        std::vector<double> h_times((size_t)N, 0.0);
+        if (N > 0) HIPCHECK(e, hipMemcpy(h_nev.data(), a.node_ev, (size_t)N * 4, hipMemcpyDeviceToHost));
+        std::vector<std::string> errs((size_t)m);
+        std::vector<int> rcs((size_t)m, 0);
+        int64_t work = 0;
+        for (int64_t j = 0; j < m; j++) work += dp[(size_t)j].n_ev;
+        for_parts(m, [&](int64_t j0, int64_t j1, unsigned) {
+            if (hipSetDevice(e->device) != hipSuccess) { for (int64_t j = j0; j < j1; j++) { rcs[(size_t)j] = VGX_ERR_HIP; errs[(size_t)j] = "hipSetDevice"; } return; }
+            vgx_engine::HostClock hc;
+            for (int64_t j = j0; j < j1; j++) {
+                const VgxGwDesc &d = dp[(size_t)j];
+                int rc = clock_build(e, d.rep, hc, errs[(size_t)j]);
+                if (rc) { rcs[(size_t)j] = rc; continue; }
+                mism[(size_t)(i0 + j)] = hc.limit_mismatch ? 1 : 0;
+                if (res[(size_t)(j * 5)] != VGX_GW_OK) continue;
+                bool ok = true;
+                const int64_t nodes = 2 * d.sCounter - 1;
+                for (int64_t k = 0; k < nodes; k++) {   // (the lookup of vgx_get_genealogies: -1 = 0.0)
+                    const int32_t ev = h_nev[(size_t)(d.node_off + k)];
+                    const int64_t q = (int64_t)ev - hc.e0;
+                    if (ev < 0) h_times[(size_t)(d.node_off + k)] = 0.0;
+                    else if (q < 0 || q >= (int64_t)hc.times.size()) ok = false;
+                    else h_times[(size_t)(d.node_off + k)] = hc.times[(size_t)q];
+                }
+                if (!ok) { rcs[(size_t)j] = VGX_ERR_ARG; errs[(size_t)j] = me + "an event index outside the host clock's range"; }
+            }
+        }, std::max<int64_t>(work / std::max<int64_t>(m, 1), 1) * 64);
+        for (int64_t j = 0; j < m; j++)
+            if (rcs[(size_t)j]) return fail(e, rcs[(size_t)j], errs[(size_t)j]);
+        if (N > 0) HIPCHECK(e, hipMemcpy(ws + o_times, h_times.data(), (size_t)N * 8, hipMemcpyHostToDevice));
+        io->ms[2] += since(t_clock);
+        // 6. the shape kernel
+        VgxTsLaunch b{};
+        b.n = m;
+        b.desc = (const VgxTsDesc *)(ws + o_ts);
+        b.res = a.res;
+        b.tree = a.tree; b.node_ev = a.node_ev; b.times = (const double *)(ws + o_times);
+        int32_t *w32 = (int32_t *)(ws + o_w32);
+        int64_t *w64 = (int64_t *)(ws + o_w64);
+        b.w = VgxTsWork{w32, w32 + N, w32 + 2 * N, w32 + 3 * N, w32 + 4 * N, w32 + 5 * N, w32 + 6 * N, w64, w64 + N};
+        b.stats = (int64_t *)(ws + o_stats); b.lengths = (double *)(ws + o_lens); b.status = (int64_t *)(ws + o_status);
+        HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
+        HIPCHECK(e, vgxi_ts_shape(&b, e->stream));
+        HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
+        // 7. before anything reads the rows
+        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(e, VGX_ERR_HIP, me + "shape kernel failed: " + hipGetErrorString(er));
+        HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
+        io->ms[1] += kms;
+        std::vector<int64_t> st2((size_t)m * 2);
+        HIPCHECK(e, hipMemcpy(io->stats + i0 * VGX_TS_K, b.stats, (size_t)m * VGX_TS_K * 8, hipMemcpyDeviceToHost));
+        HIPCHECK(e, hipMemcpy(io->lengths + i0 * VGX_TS_L, b.lengths, (size_t)m * VGX_TS_L * 8, hipMemcpyDeviceToHost));
+        HIPCHECK(e, hipMemcpy(st2.data(), b.status, (size_t)m * 16, hipMemcpyDeviceToHost));
+        for (int64_t j = 0; j < m; j++) {
+            io->status[i0 + j] = st2[(size_t)(2 * j)];
+            io->status_arg[i0 + j] = st2[(size_t)(2 * j + 1)];
+        }
+        io->passes += 1;
+        i0 = i1;
+    }
+    // every replicate's clock was built once, as when the replicates are fetched one by one
+    for (int64_t i = 0; i < n; i++) e->clock_mismatches += mism[(size_t)i];
+    io->ms[3] = since(t_call);
+    return VGX_OK;
+}
+
 // ---- peaks, first passages and last positive events of many replicates (vgx_milestones.hip, vgx_milestones.h) -----
 // vgx_get_prevalence's host side with the tile edges in place of a grid: per chunk, pass A (its counting and scan kernels) gives
 // every tile its base, the ordered walk merges every tile's records into the block the host initialised from the start state, and

@@ -29,6 +29,7 @@
 #include "vgx_flows.h"
 #include "vgx_lineages.h"
 #include "vgx_tree_events.h"   // (declares its launcher, vgxi_te_bin, itself)
+#include "vgx_tree_shape.h"    // (likewise: vgxi_ts_shape)
 
 #pragma GCC visibility push(hidden)   // nothing here is part of the exported C ABI
 

@@ -24,6 +24,7 @@
 #include "vgx_gwalk_tau.h"
 #include "vgx_lineages.h"
 #include "vgx_tree_events.h"
+#include "vgx_tree_shape.h"
 #include "vgx_logfact.h"
 #include "vgx_rng.h"
 
@@ -404,6 +405,9 @@ static std::string walk_message(int64_t status, int64_t arg) {
     case VGX_GW_UNKNOWN_ROW_TYPE: return "vgx_get_genealogy: unknown multievent type " + std::to_string(arg);
     case VGX_GW_BAD_ROW:
         return "vgx_get_tau_genealogies: a multievent row of event " + std::to_string(arg) + " does not fit the model or the compartment counts";
+    case VGX_GW_BAD_TREE:
+        return "vgx_get_tree_shapes: node " + std::to_string(arg) + " breaks the tree's structure (every node but the last has a parent of a higher id, " +
+               "every node none or two children)";
     default: return "vgx_get_genealogy: walk status " + std::to_string(status);
     }
 }
@@ -592,4 +596,27 @@ extern "C" int vgx_test_lineages(vgx_genealogy_io *io, const double *grid, int64
 extern "C" int vgx_test_tree_events(vgx_genealogy_io *io, const double *grid, int64_t T, const int32_t *variant_of, int64_t V, int64_t tile,
                                     int32_t *counts, int64_t *records, char *errbuf, int64_t errcap) {
     return lineages_hook(io, grid, T, variant_of, V, tile, counts, nullptr, records, errbuf, errcap, true, "vgx_test_tree_events");
+}
+
+// ---- the shape of one tree (vgx_tree_shape.h) -------------------------------------------------------------------
+extern "C" int vgx_test_tree_shape(const int32_t *tree, const int32_t *node_ev, const double *times, int64_t nodes, int64_t *stats, double *lengths,
+                                   char *errbuf, int64_t errcap) {
+    auto fail = [&](const std::string &m) {
+        if (errbuf && errcap > 0) std::snprintf(errbuf, (size_t)errcap, "%s", m.c_str());
+        return VGX_ERR_ARG;
+    };
+    if (!tree || !node_ev || !times || !stats || !lengths) return fail("vgx_test_tree_shape: null argument");
+    int64_t bad = vgx_ts_check_parents(tree, nodes);
+    if (bad == nodes) return fail("vgx_test_tree_shape: " + std::to_string(nodes) + " nodes: an odd number, at least 3 (node " + std::to_string(nodes) + ")");
+    if (bad >= 0)
+        return fail("vgx_test_tree_shape: the parent of node " + std::to_string(bad) + " is " + std::to_string(tree[bad]) +
+                    " (a higher id inside the tree, -1 at the last node)");
+    const size_t N = (size_t)nodes;
+    std::vector<int32_t> w32(7 * N);
+    std::vector<int64_t> w64(2 * N);
+    const VgxTsWork w{w32.data(), w32.data() + N, w32.data() + 2 * N, w32.data() + 3 * N, w32.data() + 4 * N, w32.data() + 5 * N, w32.data() + 6 * N,
+                      w64.data(), w64.data() + N};
+    bad = vgx_ts_sweep(tree, node_ev, times, nodes, w, stats, lengths);
+    if (bad >= 0) return fail("vgx_test_tree_shape: node " + std::to_string(bad) + " has " + std::to_string(w.kids[bad]) + " children (none or two)");
+    return VGX_OK;
 }

@@ -415,6 +415,72 @@ class TreeEvents:
         return self.counts[..., 6]
 
 
+class TreeShapes:
+    """What ``Ensemble.tree_shapes`` returns: one row of scalars per selected replicate's sampled tree: its balance, depth and
+    branch statistics, the summaries simulated trees are compared by.
+
+    ``stats`` [n, 12] int64 in the order of ``STATS`` and ``lengths`` [n, 7] float64 in the order of ``LENGTHS``, each column also
+    an attribute of its name ([n]).  A tip is a node without children; ``n_v`` the tips below node v.  ``tips``; ``internal``
+    (= tips - 1); ``cherries`` (nodes with two tip children); ``pitchforks`` (``n_v == 3``); ``sackin`` (sum of the tips' depths in
+    edges); ``colless`` (sum over internal nodes of the difference of their two children's ``n``); ``max_depth``; ``depth_sumsq``
+    (sum of the tips' squared depths); ``ladder_nodes`` (nodes with exactly one tip child); ``max_ladder`` (the longest chain of
+    them); ``root_event`` and ``last_tip_event`` (the event indices of the root and of node 0, the latest sample).  With
+    ``b_i`` the branch above node i in time: ``root_time``, ``last_tip_time``, ``length`` (sum of ``b_i``), ``external_length``
+    (over the tips), ``length_sumsq``, ``tip_height_sum`` (sum over the tips of their time above the root), ``max_branch``.
+    ``replicates`` [n]; ``status``, ``status_arg``, ``ok``, ``message(i)``, ``rng_raw`` as :class:`GenealogyBatch`: the row of a
+    replicate whose walk failed holds zeros and NaN lengths, and the derived values are NaN there.  ``passes``, ``kernel_ms``
+    (walk, shape), ``clock_ms`` (the host clock with the two node copies), ``wall_ms``."""
+
+    STATS = _capi.TREE_SHAPE_STATS
+    LENGTHS = _capi.TREE_SHAPE_LENGTHS
+
+    def __getattr__(self, name):   # one attribute per column
+        if name in TreeShapes.STATS:
+            return self.stats[:, TreeShapes.STATS.index(name)]
+        if name in TreeShapes.LENGTHS:
+            return self.lengths[:, TreeShapes.LENGTHS.index(name)]
+        raise AttributeError(name)
+
+    @property
+    def ok(self):
+        return self.status == 0
+
+    def message(self, i):
+        """Text of row i's status: what ``Ensemble.genealogy`` raises for that replicate ('' when its walk succeeded)."""
+        return _capi.genealogy_message(int(self.status[i]), int(self.status_arg[i]))
+
+    def _ratio(self, num, den, where=None):
+        out = np.full(len(self.status), np.nan, dtype=np.float64)
+        ok = self.ok & (den != 0) if where is None else self.ok & where
+        np.divide(num, den, out=out, where=ok)
+        return out
+
+    def height(self):
+        """The tree's height in time: ``last_tip_time - root_time``."""
+        return np.where(self.ok, self.last_tip_time - self.root_time, np.nan)
+
+    def mean_depth(self):
+        """Mean depth of a tip in edges: ``sackin / tips``."""
+        return self._ratio(self.sackin.astype(np.float64), self.tips.astype(np.float64))
+
+    def depth_variance(self):
+        """Variance of the tips' depths: ``depth_sumsq / tips - mean_depth() ** 2``."""
+        return self._ratio(self.depth_sumsq.astype(np.float64), self.tips.astype(np.float64)) - self.mean_depth() ** 2
+
+    def colless_normalized(self):
+        """``colless`` over its maximum ``(tips - 1)(tips - 2) / 2``, the caterpillar tree's; NaN at two tips."""
+        t = self.tips.astype(np.float64)
+        return self._ratio(self.colless.astype(np.float64), (t - 1) * (t - 2) / 2, where=self.tips > 2)
+
+    def mean_branch(self):
+        """Mean branch length: ``length / (2 tips - 2)``."""
+        return self._ratio(self.length, 2.0 * self.tips - 2)
+
+    def external_share(self):
+        """The share of the tree's length on branches that end in a tip: ``external_length / length``."""
+        return self._ratio(self.external_length, self.length)
+
+
 class Susceptibles:
     """What ``Ensemble.susceptibles`` returns: susceptible hosts per selected replicate, grid time, population and class of
     susceptibility groups.
@@ -1563,6 +1629,53 @@ class Ensemble:
             raise
         te.summary = done() if done is not None else None
         return te
+
+    def tree_shapes(self, seed=None, replicates=None):
+        """Balance, depth and branch statistics of the sampled tree of every selected replicate of the last direct
+        ``simulate(record_events=True)`` call, on the device (``vgx_get_tree_shapes``): the walk of ``genealogies(seed, replicates)``
+        with the same draws, status and generator afterwards, then one kernel that reduces every tree where the walk left it to a
+        row of 12 integers and 7 lengths; only the node event indices and the node times cross to the host and back.  Returns a
+        :class:`TreeShapes`, whose rows are what the tree of ``genealogies(seed).replicate(r)`` gives.
+
+        ``seed`` and ``replicates`` as ``genealogies()``.  A replicate whose walk fails (fewer than two samples, lineages that never
+        coalesce, ...) gets its status, zeros and NaN and does not fail the call.  Direct chains only."""
+        if self._last_call is None:
+            raise ValueError("tree_shapes() needs a direct simulate(record_events=True) call first")
+        if self._last_call[0] != 'direct':
+            raise ValueError("tree_shapes() walks direct chains only: the last call was simulate_tau")
+        if not self._last_call[1]:
+            raise ValueError("tree_shapes() needs the event log: the last call had record_events=False")
+        eng = self.engine
+        reps = np.arange(self.R, dtype=np.int64) if replicates is None else np.ascontiguousarray(replicates, dtype=np.int64).ravel()
+        n = len(reps)
+        if n and (reps.min() < 0 or reps.max() >= self.R):
+            raise ValueError("replicate index out of range")
+        if len(np.unique(reps)) != n:
+            raise ValueError("replicates must be distinct")
+        counters = [eng.counters(int(r)) for r in reps]
+        for r, c in zip(reps, counters):
+            if c.ev_first_new != 0:
+                raise ValueError("replicate %d: its chain does not start in the last call's device log (the model held %d events "
+                                 "when the ensemble started)" % (r, c.ev_first_new))
+        rng = self._walk_starts(reps, counters, seed)
+        ts = TreeShapes()
+        ts.replicates = reps.copy()
+        ts.stats = np.zeros((max(n, 1), len(TreeShapes.STATS)), dtype=np.int64)
+        ts.lengths = np.zeros((max(n, 1), len(TreeShapes.LENGTHS)), dtype=np.float64)
+        per = {k: np.zeros(max(n, 1), dtype=np.int64) for k in ("status", "status_arg")}
+        rng_out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+        u64 = C.POINTER(C.c_uint64)
+        io = _capi.VgxTreeShapesIO()
+        io.n, io.replicates, io.rng_state = n, _capi._p(reps), rng.ctypes.data_as(u64)
+        io.stats, io.lengths = _capi._p(ts.stats), _capi._p(ts.lengths)
+        io.status, io.status_arg, io.rng_out = _capi._p(per["status"]), _capi._p(per["status_arg"]), rng_out.ctypes.data_as(u64)
+        eng._check(eng.lib.vgx_get_tree_shapes(eng.handle, C.byref(io)))
+        ts.stats, ts.lengths = ts.stats[:n], ts.lengths[:n]
+        ts.status, ts.status_arg = per["status"][:n], per["status_arg"][:n]
+        ts.rng_raw = np.zeros((n, 6), dtype=np.uint64)
+        ts.rng_raw[:, :4] = rng_out[:n]
+        ts.passes, ts.kernel_ms, ts.clock_ms, ts.wall_ms = int(io.passes), (io.ms[0], io.ms[1]), io.ms[2], io.ms[3]
+        return ts
 
     def milestones(self, variants=None, thresholds=(), replicates=None):
         """Peaks, first passages and extinctions of every selected replicate of the last direct ``simulate(record_events=True)``
