@@ -1,6 +1,6 @@
 // vgx_engine.h — the engine behind the C ABI of include/vgx.h, as the host drivers of libvgx.so share it: the engine structure,
 // its device buffers and error helpers, the launchers defined next to their kernels.  Host-only; included by the host drivers
-// (vgx_api.hip, vgx_direct_run.hip, vgx_tau_run.hip, vgx_tau_timelines.hip, vgx_tau_genealogies.hip, vgx_tau_lineages.hip) alone. Helpers that several of them use are `inline` here; direct_core and the
+// (vgx_api.hip, vgx_direct_run.hip, vgx_tau_run.hip, vgx_tau_timelines.hip, vgx_tau_genealogies.hip, vgx_tau_lineages.hip; the tau replays through their frame, vgx_tau_replay.h) alone. Helpers that several of them use are `inline` here; direct_core and the
 // choice of its kernel have their one definition in vgx_direct_run.hip, host_clock in vgx_api.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -70,19 +70,15 @@ extern "C" hipError_t vgxi_ln_walk(const VgxLnLaunch *a, hipStream_t s);
 extern "C" hipError_t vgxi_ln_bin(const VgxLnLaunch *a, hipStream_t s);
 extern "C" hipError_t vgxi_ln_scan(const VgxLnLaunch *a, hipStream_t s);
 extern "C" hipError_t vgxi_flow_count(const VgxFlowLaunch *a, hipStream_t s);   // vgx_flows.hip: a->form is the form that runs (dense or split)
-// the launchers of vgx_tau_prevalence.hip that vgx_tau_susceptible.hip shares (net blocks from the prefix's, the 64-bit running
-// sums, the narrowing min/max pass)
+// the launchers of vgx_tau_prevalence.hip that vgx_tau_susceptible.hip and the frame of the tau replays (vgx_tau_replay.h) share
+// (the 64-bit running sums, the narrowing min/max pass)
 struct VgxTauPrevLaunch;
-extern "C" hipError_t vgxi_tau_prev_init(int64_t m, int64_t tc, int64_t cells, const int32_t *with, const int64_t *pre_val, const int64_t *pre_fin,
-                                         const int64_t *pre_out, int64_t *val, int64_t *fin, int64_t *outside, hipStream_t s);
 extern "C" hipError_t vgxi_tau_prev_count(const VgxTauPrevLaunch *a, hipStream_t s);   // (vgx_tau_milestones.hip: pass A over tile edges)
 extern "C" hipError_t vgxi_tau_prev_scan(const VgxTauPrevLaunch *a, hipStream_t s);
 extern "C" hipError_t vgxi_tau_prev_minmax(int64_t total, const int64_t *src, int32_t *dst, uint64_t *mm, hipStream_t s);
-// vgx_tau_flows.hip: the weighted-row count (a->form is the form that runs) and the start of m blocks of tc cells from the prefix's
+// vgx_tau_flows.hip: the weighted-row count (a->form is the form that runs)
 struct VgxTauFlowLaunch;
 extern "C" hipError_t vgxi_tau_flow_count(const VgxTauFlowLaunch *a, hipStream_t s);
-extern "C" hipError_t vgxi_tau_flow_init(int64_t m, int64_t tc, const int32_t *with, const int64_t *pre, const int64_t *pre_out, int64_t *counts,
-                                         int64_t *outside, hipStream_t s);
 // the column summary of vgx_colsummary.hip on a device int32 matrix x[R][N] of values in [0, 2^31) (a refusal's message goes to errbuf)
 extern "C" int vgxi_column_summary_i32(const char *what, const int32_t *x, int64_t R, int64_t N, vgx_traj_summary_io *io, hipStream_t stream,
                                        char *errbuf, int64_t errcap);

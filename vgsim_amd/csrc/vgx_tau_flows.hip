@@ -19,21 +19,10 @@
 #include <string.h>
 #include <string>
 #include <vector>
-#include "vgx_engine.h"
 #include "vgx_tau_flows.h"
-#include "vgx_tau_rows.h"   // EventCols, RowCols, FlatChain, flatten
+#include "vgx_tau_replay.h"   // the frame: selection, cuts, workspace, prefix pass, chunks, summary, the hook's chain split
 
 namespace {
-
-__device__ __forceinline__ long long wave_sum(long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-__device__ __forceinline__ void add64(long long *p, long long v) {
-    atomicAdd((unsigned long long *)p, (unsigned long long)v);   // two's complement: the sum is the signed one
-}
 
 template <int FORM>
 __global__ void __launch_bounds__(256) vgxtf_count_kernel(VgxTauFlowLaunch a, int stage) {
@@ -104,19 +93,6 @@ __global__ void __launch_bounds__(256) vgxtf_count_kernel(VgxTauFlowLaunch a, in
     }
 }
 
-// the blocks and `outside` counters of m chains start from the prefix's (with[i] != 0) or from zero
-__global__ void __launch_bounds__(256) vgxtf_init_kernel(int64_t m, int64_t tc, const int32_t *with, const long long *pre, const long long *pre_out,
-                                                         long long *counts, long long *outside) {
-    const int64_t total = m * tc, stride = (int64_t)gridDim.x * 256;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-        const int64_t c = i / tc;
-        counts[i] = with[c] ? pre[i - c * tc] : 0;
-    }
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < 2 * m; i += stride) outside[i] = with[i >> 1] ? pre_out[i & 1] : 0;
-}
-
-unsigned flat_grid(int64_t total) { return (unsigned)std::min<int64_t>(std::max<int64_t>((total + 255) / 256, 1), 1 << 16); }
-
 template <int FORM>
 hipError_t launch(const VgxTauFlowLaunch *a, hipStream_t s) {
     const bool stage = vgx_tau_flow_stage_map(FORM, a->P, a->V, a->hapNum);
@@ -149,26 +125,6 @@ std::string check_request(const double *edges, int64_t T, int64_t V, const int32
     return "";
 }
 
-// The prefix as a chain of its own: its cuts (the literal loop over its events, then its row count) and where the loop stands
-// after it.  cut: [T + 1].
-int64_t prefix_cuts(const FlatChain &f, int64_t n_ev, const double *times, const double *edges, int64_t T, int32_t *cut) {
-    VgxIncCutter ct{edges, T, cut};
-    for (int64_t i = 0; i < n_ev; i++) ct.event(f.ev_row[(size_t)i], times[i]);
-    const int64_t point0 = ct.point;
-    ct.finish(f.ev_row[(size_t)n_ev]);
-    return point0;
-}
-
-// A chain's own events after a prefix that left the loop at point0: cuts relative to the chain's first own row
-template <class OwnTime, class OwnRow>
-void own_cuts(const double *edges, int64_t T, int64_t point0, int64_t n_own, OwnTime own_time, OwnRow own_m0, int64_t n_rows, int32_t *cut) {
-    for (int64_t k = 0; k < point0; k++) cut[k] = 0;   // these cuts lie inside the prefix: before the first own row
-    VgxIncCutter ct{edges, T, cut};
-    ct.point = point0;
-    for (int64_t k = 0; k < n_own; k++) ct.event(own_m0(k), own_time(k));
-    ct.finish(n_rows);
-}
-
 }  // namespace
 
 extern "C" hipError_t vgxi_tau_flow_count(const VgxTauFlowLaunch *a, hipStream_t s) {
@@ -178,15 +134,7 @@ extern "C" hipError_t vgxi_tau_flow_count(const VgxTauFlowLaunch *a, hipStream_t
     return a->form == VGX_FLOW_DENSE ? launch<VGX_FLOW_DENSE>(a, s) : launch<VGX_FLOW_SPLIT>(a, s);
 }
 
-extern "C" hipError_t vgxi_tau_flow_init(int64_t m, int64_t tc, const int32_t *with, const int64_t *pre, const int64_t *pre_out, int64_t *counts,
-                                         int64_t *outside, hipStream_t s) {
-    hipLaunchKernelGGL(vgxtf_init_kernel, dim3(flat_grid(m * tc)), dim3(256), 0, s, m, tc, with, (const long long *)pre, (const long long *)pre_out,
-                       (long long *)counts, (long long *)outside);
-    return hipGetLastError();
-}
-
-// vgx_get_tau_incidence step for step, with the block [n][T][P][P][V], vgx_get_flows's variant_of, `within` and form in place of
-// the mask.
+// The frame of vgx_tau_replay.h around the block [n][T][P][P][V], with vgx_get_flows's variant_of, `within` and form.
 extern "C" int vgx_get_tau_flows(vgx_engine *e, vgx_tau_flows_io *io, const vgx_timelines_prefix *prefix) {
     if (!e || !io || io->n < 0 || (io->n > 0 && (!io->replicates || !io->outside))) return VGX_ERR_ARG;
     const auto t_call = std::chrono::steady_clock::now();
@@ -195,68 +143,22 @@ extern "C" int vgx_get_tau_flows(vgx_engine *e, vgx_tau_flows_io *io, const vgx_
     io->passes = 0;
     io->form = 0;
     io->ms[0] = io->ms[1] = io->ms[2] = 0.0;
-    if (!e->sc_host_valid || !e->last_was_tau || (int64_t)e->tau_log.size() < e->R)
-        return fail(e, VGX_ERR_ARG, me + "the last call was not vgx_simulate_tau (counts tau chains only)");
-    if (e->tau_mev_cap <= 0) return fail(e, VGX_ERR_ARG, me + "the last call recorded no multievent rows (record_events = 0)");
     const int64_t n = io->n, P = e->d.popNum, H = e->d.hapNum, T = io->T, V = io->V, mev_cap = e->tau_mev_cap;
-    int asked = VGX_FLOW_AUTO, form = 0;
-    if (const char *fm = getenv("VGX_FLOWS_FORM")) {
-        if (!strcmp(fm, "dense")) asked = VGX_FLOW_DENSE;
-        else if (!strcmp(fm, "split")) asked = VGX_FLOW_SPLIT;
-        else if (*fm) return fail(e, VGX_ERR_ARG, me + "VGX_FLOWS_FORM=" + fm + " is neither dense nor split");
-    }
-    {
-        const std::string why = check_request(io->edges, T, V, io->variant_of, P, H, asked, form);
-        if (!why.empty()) return fail(e, VGX_ERR_ARG, me + why);
-    }
-    io->form = form;
-    const int64_t cells = P * P * V, tc = T * cells;   // (P * V <= 2^13 and P <= 2^13: cells below 2^26)
-    // the prefix: what the model held when the call started
-    const int64_t pre_ev = prefix ? prefix->ev_ptr : 0;
-    if (pre_ev < 0 || (pre_ev > 0 && (!prefix->ev_times || !prefix->ev_types || !prefix->ev_haplotypes || !prefix->ev_populations ||
-                                      !prefix->ev_newHaplotypes || !prefix->ev_newPopulations)))
-        return fail(e, VGX_ERR_ARG, me + "null prefix column");
-    std::vector<int32_t> n_own((size_t)n), with_prefix((size_t)n, 0);
-    bool any_prefix = false;
-    {
-        std::vector<char> seen((size_t)e->R, 0);
-        for (int64_t i = 0; i < n; i++) {
-            const int64_t r = io->replicates[i];
-            if (r < 0 || r >= e->R) return fail(e, VGX_ERR_ARG, me + "replicate index out of range");
-            if (seen[(size_t)r]) return fail(e, VGX_ERR_ARG, me + "replicates must be distinct");
-            seen[(size_t)r] = 1;
-            const VgxRepScalars &s = e->sc_host[(size_t)r];
-            const int64_t first = s.restarts > 0 ? 0 : e->ev_ptr0;   // vgx_counters.ev_first_new
-            if (s.restarts == 0 && first != pre_ev)
-                return fail(e, VGX_ERR_ARG, me + "replicate " + std::to_string(r) + ": its chain continues a log of " + std::to_string(first) +
-                                                " events, the prefix holds " + std::to_string(pre_ev));
-            with_prefix[(size_t)i] = s.restarts == 0 && pre_ev > 0;
-            any_prefix = any_prefix || with_prefix[(size_t)i];
-            const auto &lg = e->tau_log[(size_t)r];
-            for (size_t k = 0; k < lg.size(); k++)   // the steps' row ranges tile the replicate's block
-                if (lg[k].m0 != (k ? lg[k - 1].m1 : 0) || lg[k].m1 < lg[k].m0)
-                    return fail(e, VGX_ERR_ARG, me + "replicate " + std::to_string(r) + ": row ranges of its steps are not contiguous");
-            if (!lg.empty() && lg.back().m1 > mev_cap) return fail(e, VGX_ERR_ARG, me + "replicate " + std::to_string(r) + " logged more rows than its block holds");
+    int form = 0;
+    TauSel sel;
+    auto request = [&]() -> std::string {
+        int asked = VGX_FLOW_AUTO;
+        if (const char *fm = getenv("VGX_FLOWS_FORM")) {
+            if (!strcmp(fm, "dense")) asked = VGX_FLOW_DENSE;
+            else if (!strcmp(fm, "split")) asked = VGX_FLOW_SPLIT;
+            else if (*fm) return std::string("VGX_FLOWS_FORM=") + fm + " is neither dense nor split";
         }
-    }
-    FlatChain pre;
-    pre.ev_row.assign(1, 0);
-    if (any_prefix) {
-        const EventCols ev{pre_ev, prefix->ev_times, prefix->ev_types, prefix->ev_haplotypes, prefix->ev_populations, prefix->ev_newHaplotypes, prefix->ev_newPopulations};
-        const RowCols mv{prefix->mev_rows, prefix->mev_num, prefix->mev_types, prefix->mev_haplotypes, prefix->mev_populations, prefix->mev_newHaplotypes,
-                         prefix->mev_newPopulations};
-        if (mv.n > 0 && (!mv.num || !mv.types || !mv.hap || !mv.pop || !mv.nh || !mv.np)) return fail(e, VGX_ERR_ARG, me + "null prefix multievent column");
-        const std::string why = flatten(ev, pre_ev, mv, pre);
-        if (!why.empty()) return fail(e, VGX_ERR_ARG, me + "prefix: " + why);
-    }
-    const int64_t pre_rows = pre.n_rows();
-    for (int64_t i = 0; i < n; i++) {
-        const auto &lg = e->tau_log[(size_t)io->replicates[i]];
-        const int64_t own = lg.empty() ? 0 : lg.back().m1, total = (with_prefix[(size_t)i] ? pre_rows : 0) + own;
-        if (total >= ((int64_t)1 << 31))
-            return fail(e, VGX_ERR_ARG, me + "replicate " + std::to_string(io->replicates[i]) + ": prefix and own rows reach 2^31 (" + std::to_string(total) + ")");
-        n_own[(size_t)i] = (int32_t)own;
-    }
+        const std::string why = check_request(io->edges, T, V, io->variant_of, P, H, asked, form);
+        if (why.empty()) io->form = form;
+        return why;
+    };
+    if (const int rc = tau_select(e, me, "counts", request, n, io->replicates, prefix, false, tau_every, sel)) return rc;
+    const int64_t cells = P * P * V, tc = T * cells, pre_rows = sel.pre_rows;   // (P * V <= 2^13 and P <= 2^13: cells below 2^26)
     if (n == 0) {
         io->ms[2] = since(t_call);
         return VGX_OK;
@@ -269,48 +171,34 @@ extern "C" int vgx_get_tau_flows(vgx_engine *e, vgx_tau_flows_io *io, const vgx_
     HIPCHECK(e, hipSetDevice(e->device));
     size_t free_b = 0, total_b = 0;
     HIPCHECK(e, hipMemGetInfo(&free_b, &total_b));
-    auto up8 = [](int64_t b) { return (b + 255) / 256 * 256; };
-    auto dev_free = [](char *p) { (void)hipFree(p); };
-    // what stays for the whole call: [rep | n_own | with | variant_of | prefix: rows, cut, n_rows, block, outside | counts | outside | narrow | min/max]
+    // what stays for the whole call: [rep | n_own | with | variant_of | prefix: rows, cut, n_rows, block, outside | counts | outside | narrow | min, max]
     const int64_t block_bytes = n * tc * 8, narrow_bytes = io->summary ? n * tc * 4 : 0;
-    const int64_t o_rep = 0, o_nown = o_rep + up8(n * 8), o_with = o_nown + up8(n * 4), o_map = o_with + up8(n * 4),
-                  o_prow = o_map + up8(H * 4), o_pcut = o_prow + up8(pre_rows * 48 + 8), o_pn = o_pcut + up8((T + 1) * 4),
-                  o_pcnt = o_pn + up8(4), o_pout = o_pcnt + up8(tc * 8), o_cnt = o_pout + up8(16), o_out = o_cnt + up8(block_bytes),
-                  o_nar = o_out + up8(n * 16), o_mm = o_nar + up8(narrow_bytes + 8), keep_total = o_mm + up8(16);
+    DevLayout lay;
+    const int64_t o_rep = lay.take(n * 8), o_nown = lay.take(n * 4), o_with = lay.take(n * 4), o_map = lay.take(H * 4), o_prow = lay.take(pre_rows * 48 + 8),
+                  o_pcut = lay.take((T + 1) * 4), o_pn = lay.take(4), o_pcnt = lay.take(tc * 8), o_pout = lay.take(16), o_cnt = lay.take(block_bytes),
+                  o_out = lay.take(n * 16), o_nar = lay.take(narrow_bytes + 8), o_mm = lay.take(16), keep_total = lay.total;
     if (keep_total > (int64_t)(free_b / 2))
         return fail(e, VGX_ERR_ARG, me + "the block of " + dims + " counts of 8 bytes, the prefix block, the prefix rows and " +
                                         (io->summary ? "the summary's 4-byte copy take " : "their counters take ") + std::to_string(keep_total) + " bytes, above half of the " +
                                         std::to_string((int64_t)free_b) + " bytes of free device memory: select fewer replicates per call");
-    char *kws = nullptr;
-    hipError_t er = hipMalloc((void **)&kws, (size_t)keep_total);
-    if (er != hipSuccess) return fail(e, VGX_ERR_HIP, me + "hipMalloc of " + std::to_string(keep_total) + " bytes: " + hipGetErrorString(er));
-    std::unique_ptr<char, void (*)(char *)> khold(kws, dev_free);
+    DevHold khold;
+    if (const int rc = dev_alloc(e, me, keep_total, khold)) return rc;
+    char *const kws = khold.get();
     std::vector<int64_t> reps_all(io->replicates, io->replicates + n);
     HIPCHECK(e, hipMemcpyAsync(kws + o_rep, reps_all.data(), (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
-    HIPCHECK(e, hipMemcpyAsync(kws + o_nown, n_own.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
-    HIPCHECK(e, hipMemcpyAsync(kws + o_with, with_prefix.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_nown, sel.n_own.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    HIPCHECK(e, hipMemcpyAsync(kws + o_with, sel.with_prefix.data(), (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
     HIPCHECK(e, hipMemcpyAsync(kws + o_map, io->variant_of, (size_t)H * 4, hipMemcpyHostToDevice, e->stream));
     HIPCHECK(e, hipMemsetAsync(kws + o_pcnt, 0, (size_t)(o_cnt - o_pcnt), e->stream));   // the prefix block and its outside counters
-    auto fill = [&](VgxTauFlowLaunch &a) {
-        a.T = (int32_t)T; a.P = (int32_t)P; a.hapNum = (int32_t)H; a.V = (int32_t)V;
-        a.variant_of = (const int32_t *)(kws + o_map);
-        a.within = io->within ? 1 : 0; a.form = form; a.tile = (int32_t)tile;
-    };
+    VgxTauFlowLaunch base{};   // what every launch of the call shares
+    base.T = (int32_t)T; base.P = (int32_t)P; base.hapNum = (int32_t)H; base.V = (int32_t)V;
+    base.variant_of = (const int32_t *)(kws + o_map);
+    base.within = io->within ? 1 : 0; base.form = form; base.tile = (int32_t)tile;
 
     // the prefix, once: flattened rows uploaded, its cuts, counted as a chain of its own
     int64_t point0 = 0;
-    std::vector<int32_t> pcut((size_t)(T + 1), 0);
-    const int32_t pn = (int32_t)pre_rows;
-    if (any_prefix) {
-        const auto t_cuts = std::chrono::steady_clock::now();
-        point0 = prefix_cuts(pre, pre_ev, prefix->ev_times, io->edges, T, pcut.data());
-        io->ms[1] += since(t_cuts);
-        if (pre_rows > 0) HIPCHECK(e, hipMemcpyAsync(kws + o_prow, pre.rows.data(), (size_t)pre_rows * 48, hipMemcpyHostToDevice, e->stream));
-        HIPCHECK(e, hipMemcpyAsync(kws + o_pcut, pcut.data(), (size_t)(T + 1) * 4, hipMemcpyHostToDevice, e->stream));
-        HIPCHECK(e, hipMemcpyAsync(kws + o_pn, &pn, 4, hipMemcpyHostToDevice, e->stream));
-        HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
-        VgxTauFlowLaunch a{};
-        fill(a);
+    int rc = tau_prefix_pass<VgxIncCutter, 0>(e, me, io->ms, sel, prefix ? prefix->ev_times : nullptr, io->edges, T, kws + o_prow, kws + o_pcut, kws + o_pn, point0, [&]() -> int {
+        VgxTauFlowLaunch a = base;
         a.m = 1;
         a.rows = (const int64_t *)(kws + o_prow); a.stride = 0; a.rep = nullptr;
         a.n_rows = (const int32_t *)(kws + o_pn); a.cut = (const int32_t *)(kws + o_pcut);
@@ -318,169 +206,63 @@ extern "C" int vgx_get_tau_flows(vgx_engine *e, vgx_tau_flows_io *io, const vgx_
         a.counts = (int64_t *)(kws + o_pcnt); a.outside = (int64_t *)(kws + o_pout);
         HIPCHECK(e, vgxi_tau_flow_count(&a, e->stream));
         if (pre_rows > 0) io->passes += 1;
-        HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
-        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(e, VGX_ERR_HIP, me + "counting kernel failed on the prefix: " + hipGetErrorString(er));
-        float kms = 0.f;
-        HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
-        io->ms[0] += kms;
-    }
-
-    // chunks of replicates: the cuts of a chunk fit `share` bytes of device memory
-    int64_t share = std::min<int64_t>((int64_t)(free_b / 2) - keep_total + 4096, (int64_t)1 << 30);
-    if (const char *cb = getenv("VGX_TIMELINES_CHUNK_BYTES")) share = std::min<int64_t>(share, std::max<int64_t>(atoll(cb), 1));
-    const int64_t per_rep = (T + 1) * 4 + 64;
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(share / per_rep, (int64_t)1 << 20));
-    for (int64_t i0 = 0; i0 < n; i0 += chunk) {
-        const int64_t i1 = std::min(n, i0 + chunk), m = i1 - i0;
-        char *ws = nullptr;
-        const int64_t total = up8(m * (T + 1) * 4);
-        er = hipMalloc((void **)&ws, (size_t)total);
-        if (er != hipSuccess) return fail(e, VGX_ERR_HIP, me + "hipMalloc of " + std::to_string(total) + " bytes: " + hipGetErrorString(er));
-        std::unique_ptr<char, void (*)(char *)> hold(ws, dev_free);
-        // host: every replicate's cuts in the row index space of its own block (the loop continued where the prefix left it)
-        const auto t_cuts = std::chrono::steady_clock::now();
-        std::vector<int32_t> cuts((size_t)(m * (T + 1)));
-        int64_t steps_all = 0, max_n = 0;
-        for (int64_t j = 0; j < m; j++) {
-            steps_all += (int64_t)e->tau_log[(size_t)io->replicates[i0 + j]].size();
-            max_n = std::max<int64_t>(max_n, n_own[(size_t)(i0 + j)]);
-        }
-        for_parts(m, [&](int64_t j0, int64_t j1, unsigned) {
-            for (int64_t j = j0; j < j1; j++) {
-                const int64_t gi = i0 + j;
-                const auto &lg = e->tau_log[(size_t)io->replicates[gi]];
-                own_cuts(io->edges, T, with_prefix[(size_t)gi] ? point0 : 0, (int64_t)lg.size(), [&](int64_t k) { return lg[(size_t)k].time; },
-                         [&](int64_t k) { return lg[(size_t)k].m0; }, n_own[(size_t)gi], cuts.data() + j * (T + 1));
-            }
-        }, std::max<int64_t>(steps_all / std::max<int64_t>(m, 1), 1) + T);
-        io->ms[1] += since(t_cuts);
-        HIPCHECK(e, hipMemcpyAsync(ws, cuts.data(), (size_t)(m * (T + 1)) * 4, hipMemcpyHostToDevice, e->stream));
-        HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
-        HIPCHECK(e, vgxi_tau_flow_init(m, tc, (const int32_t *)(kws + o_with) + i0, (const int64_t *)(kws + o_pcnt), (const int64_t *)(kws + o_pout),
-                                       (int64_t *)(kws + o_cnt) + i0 * tc, (int64_t *)(kws + o_out) + 2 * i0, e->stream));
-        VgxTauFlowLaunch a{};
-        fill(a);
+        return VGX_OK;
+    });
+    if (rc) return rc;
+    // chunks of replicates: their blocks start from the prefix's or from zero, their own rows are counted on top
+    rc = tau_chunks<VgxIncCutter, 0>(e, me, me + "counting kernel failed: ", io->ms, sel, n, io->replicates, io->edges, T, point0, (int64_t)(free_b / 2) - keep_total,
+                                     [&](int64_t i0, int64_t m, int64_t max_n, const int32_t *cuts) -> int {
+        VgxTauFlowLaunch a = base;
         a.m = m;
         a.rows = (const int64_t *)e->t_mev.p; a.stride = mev_cap;
         a.rep = (const int64_t *)(kws + o_rep) + i0; a.n_rows = (const int32_t *)(kws + o_nown) + i0;
-        a.cut = (const int32_t *)ws;
+        a.cut = cuts;
         a.max_n = max_n;
         a.counts = (int64_t *)(kws + o_cnt) + i0 * tc; a.outside = (int64_t *)(kws + o_out) + 2 * i0;
+        HIPCHECK(e, vgxi_tau_block_init(m, tc, 0, (const int32_t *)(kws + o_with) + i0, (const int64_t *)(kws + o_pcnt), nullptr, (const int64_t *)(kws + o_pout),
+                                        a.counts, nullptr, a.outside, e->stream));
         HIPCHECK(e, vgxi_tau_flow_count(&a, e->stream));
         if (max_n > 0) io->passes += 1;
-        HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
-        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(e, VGX_ERR_HIP, me + "counting kernel failed: " + hipGetErrorString(er));
-        float kms = 0.f;
-        HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
-        io->ms[0] += kms;
-    }
+        return VGX_OK;
+    });
+    if (rc) return rc;
     HIPCHECK(e, hipMemcpy(io->outside, kws + o_out, (size_t)n * 16, hipMemcpyDeviceToHost));
     if (io->counts) HIPCHECK(e, hipMemcpy(io->counts, kws + o_cnt, (size_t)block_bytes, hipMemcpyDeviceToHost));
-    if (io->summary) {
-        // the column summary takes whole numbers below 2^31: narrow the block, and find its largest count on the way
-        const uint64_t init[2] = {~(uint64_t)0, 0};
-        uint64_t mm[2] = {0, 0};
-        HIPCHECK(e, hipMemcpyAsync(kws + o_mm, init, sizeof init, hipMemcpyHostToDevice, e->stream));
-        HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
-        HIPCHECK(e, vgxi_tau_prev_minmax(n * tc, (const int64_t *)(kws + o_cnt), (int32_t *)(kws + o_nar), (uint64_t *)(kws + o_mm), e->stream));
-        HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
-        HIPCHECK(e, hipMemcpyAsync(mm, kws + o_mm, sizeof mm, hipMemcpyDeviceToHost, e->stream));
-        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(e, VGX_ERR_HIP, me + "narrowing kernel failed: " + hipGetErrorString(er));
-        float kms = 0.f;
-        HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
-        io->ms[0] += kms;
-        const int64_t lo = (int64_t)(mm[0] ^ 0x8000000000000000ull), hi = (int64_t)(mm[1] ^ 0x8000000000000000ull);
-        if (lo <= hi && hi >= ((int64_t)1 << 31))
-            return fail(e, VGX_ERR_ARG, me + "summary: the largest count is " + std::to_string(hi) + ", the column summary takes whole numbers below 2^31 (use narrower bins, or summarise the int64 counts on the host)");
-        char msg[512] = "";
-        const int rc = vgxi_column_summary_i32("vgx_get_tau_flows: summary", (const int32_t *)(kws + o_nar), n, tc, io->summary, e->stream, msg, sizeof msg);
-        if (rc) return fail(e, rc, msg);
-    }
+    if (io->summary)
+        if ((rc = tau_summary(e, me, true, (const int64_t *)(kws + o_cnt), n, tc, (int32_t *)(kws + o_nar), (uint64_t *)(kws + o_mm), io->summary, io->ms))) return rc;
     io->ms[2] = since(t_call);
     return VGX_OK;
 }
 
 // ---- the host instance: the same flattening, cuts, cell and tile walk on a chain given as arrays (no device, no engine).  The
-// last n_own_events events play the replicate's own steps (their rows are taken as they are, as the device reads t_mev), everything
-// before them the prefix, which is flattened, counted once as a chain of its own and added, as on the device.
+// last n_own_events events play the replicate's own steps, everything before them the prefix, which is counted once as a chain
+// of its own and added, as on the device (tau_hook_split, tau_hook_count).
 extern "C" int vgx_test_tau_flows(vgx_tau_flows_chain *io, char *errbuf, int64_t errcap) {
     auto fail_ = [&](const std::string &m) {
         if (errbuf && errcap > 0) snprintf(errbuf, (size_t)errcap, "vgx_test_tau_flows: %s", m.c_str());
         return VGX_ERR_ARG;
     };
     if (!io || !io->counts || !io->outside) return fail_("null argument");
-    const int64_t n = io->ev_ptr, T = io->T, P = io->popNum, H = io->hapNum, V = io->V;
+    const int64_t T = io->T, P = io->popNum, H = io->hapNum, V = io->V;
     if (P < 1 || H < 1 || P > INT32_MAX || H > INT32_MAX) return fail_("bad dimensions");
     if (io->form != VGX_FLOW_AUTO && io->form != VGX_FLOW_DENSE && io->form != VGX_FLOW_SPLIT)
         return fail_("form = " + std::to_string(io->form) + " is none of 0 (automatic), 1 (dense), 2 (split)");
     int ran = 0;
-    {
-        const std::string why = check_request(io->edges, T, V, io->variant_of, P, H, (int)io->form, ran);
-        if (!why.empty()) return fail_(why);
-    }
+    std::string why = check_request(io->edges, T, V, io->variant_of, P, H, (int)io->form, ran);
+    if (!why.empty()) return fail_(why);
     io->form_ran = ran;
-    if (n < 0 || n >= ((int64_t)1 << 31)) return fail_("chain too long");
-    if (n > 0 && (!io->ev_times || !io->ev_types || !io->ev_haplotypes || !io->ev_populations || !io->ev_newHaplotypes || !io->ev_newPopulations))
-        return fail_("null event column");
-    if (io->mev_rows < 0 || (io->mev_rows > 0 && (!io->mev_num || !io->mev_types || !io->mev_haplotypes || !io->mev_populations ||
-                                                  !io->mev_newHaplotypes || !io->mev_newPopulations)))
-        return fail_("null multievent column");
-    int64_t tile = io->tile;
-    if (tile < 0) return fail_("tile must not be negative");
-    if (tile == 0) tile = VGX_FLOW_TILE_DEFAULT;
     const int64_t cells = P * P * V;
-    if (T * cells >= ((int64_t)1 << 40)) return fail_("block too large");
-    int64_t n_own_ev = io->n_own_events;
-    if (n_own_ev < -1 || n_own_ev > n) return fail_("n_own_events must be -1 or lie in [0, ev_ptr]");
-    if (n_own_ev < 0) {   // the chain's trailing MULTITYPE events
-        n_own_ev = 0;
-        while (n_own_ev < n && io->ev_types[n - 1 - n_own_ev] == VGX_TL_MULTITYPE) n_own_ev++;
-    }
-    const int64_t n_pre_ev = n - n_own_ev;
-    const EventCols ev{n, io->ev_times, io->ev_types, io->ev_haplotypes, io->ev_populations, io->ev_newHaplotypes, io->ev_newPopulations};
-    const RowCols mv{io->mev_rows, io->mev_num, io->mev_types, io->mev_haplotypes, io->mev_populations, io->mev_newHaplotypes, io->mev_newPopulations};
-    FlatChain pre;
-    {
-        const std::string why = flatten(ev, n_pre_ev, mv, pre);
-        if (!why.empty()) return fail_(why);
-    }
-    // the own rows as a block of their own, unjudged, with every own event's first row
-    std::vector<int64_t> own, own_m0((size_t)n_own_ev);
-    for (int64_t k = 0; k < n_own_ev; k++) {
-        const int64_t i = n_pre_ev + k, t = ev.types[i];
-        own_m0[(size_t)k] = (int64_t)own.size() / 6;
-        if (t == VGX_TL_MULTITYPE) {
-            const int64_t j0 = ev.hap[i], j1 = ev.pop[i];
-            if (j1 <= j0) continue;
-            if (j0 < 0 || j1 > mv.n) return fail_("event " + std::to_string(i) + ": MULTITYPE row range outside the multievent log");
-            for (int64_t j = j0; j < j1; j++) {
-                const int64_t v[6] = {mv.num[j], mv.types[j], mv.hap[j], mv.pop[j], mv.nh[j], mv.np[j]};
-                own.insert(own.end(), v, v + 6);
-            }
-        } else {
-            const int64_t v[6] = {1, t, ev.hap[i], ev.pop[i], ev.nh[i], ev.np[i]};
-            own.insert(own.end(), v, v + 6);
-        }
-        if (pre.n_rows() + (int64_t)own.size() / 6 >= ((int64_t)1 << 31)) return fail_("the chain has 2^31 rows or more");
-    }
-    const int64_t pre_rows = pre.n_rows(), own_rows = (int64_t)own.size() / 6;
-    std::vector<int32_t> pcut((size_t)(T + 1)), ocut((size_t)(T + 1));
-    const int64_t point0 = prefix_cuts(pre, n_pre_ev, io->ev_times, io->edges, T, pcut.data());
-    own_cuts(io->edges, T, point0, n_own_ev, [&](int64_t k) { return io->ev_times[n_pre_ev + k]; }, [&](int64_t k) { return own_m0[(size_t)k]; }, own_rows,
-             ocut.data());
+    TauHookChain c;
+    why = tau_hook_split(io, VGX_FLOW_TILE_DEFAULT, T * cells, c);
+    if (!why.empty()) return fail_(why);
+    std::vector<int32_t> pcut, ocut;
+    tau_hook_marks<VgxIncCutter, 0>(c, io->ev_times, io->edges, T, pcut, ocut);
     const int32_t within = io->within ? 1 : 0;
-    // the prefix block, counted once ...
-    std::vector<int64_t> pblock((size_t)(T * cells), 0), hist((size_t)(vgx_tau_flow_lds_bytes(ran, P, V) / 8), 0);
-    int64_t pout[2] = {0, 0};
-    for (int64_t t0 = 0; t0 < pre_rows; t0 += tile)
-        vgx_tau_flow_tile_host(ran, pre.rows.data(), pcut.data(), (int32_t)T, (int32_t)P, (int32_t)H, (int32_t)V, io->variant_of, within, (int32_t)t0,
-                               (int32_t)std::min<int64_t>(t0 + tile, pre_rows), hist.data(), pblock.data(), pout);
-    // ... is what the chain's block starts from; its own rows are added on top
-    for (int64_t i = 0; i < T * cells; i++) io->counts[i] = pblock[(size_t)i];
-    io->outside[0] = pout[0];
-    io->outside[1] = pout[1];
-    for (int64_t t0 = 0; t0 < own_rows; t0 += tile)
-        vgx_tau_flow_tile_host(ran, own.data(), ocut.data(), (int32_t)T, (int32_t)P, (int32_t)H, (int32_t)V, io->variant_of, within, (int32_t)t0,
-                               (int32_t)std::min<int64_t>(t0 + tile, own_rows), hist.data(), io->counts, io->outside);
+    std::vector<int64_t> hist((size_t)(vgx_tau_flow_lds_bytes(ran, P, V) / 8), 0);
+    int64_t *const dst[2] = {io->counts, io->outside};
+    const int64_t len[2] = {T * cells, 2};
+    tau_hook_count(c, pcut.data(), ocut.data(), dst, len, [&](const int64_t *rows, const int32_t *cut, int32_t t0, int32_t t1, int64_t *const *b) {
+        vgx_tau_flow_tile_host(ran, rows, cut, (int32_t)T, (int32_t)P, (int32_t)H, (int32_t)V, io->variant_of, within, t0, t1, hist.data(), b[0], b[1]);
+    });
     return VGX_OK;
 }

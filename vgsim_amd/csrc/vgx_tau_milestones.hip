@@ -18,9 +18,8 @@
 #include <stdio.h>
 #include <string>
 #include <vector>
-#include "vgx_engine.h"
 #include "vgx_tau_milestones.h"
-#include "vgx_tau_rows.h"   // EventCols, RowCols, FlatChain, flatten
+#include "vgx_tau_replay.h"   // the frame: selection, workspace, timed sections, the hook's chain split
 
 namespace {
 
@@ -203,15 +202,6 @@ void fill_tables(ChainTables &ct, int64_t m, const std::vector<int32_t> *const *
     }
 }
 
-// a state [P][H] folded through variant_of: [P][V]
-std::vector<int64_t> fold_state(const std::vector<int64_t> &src, int64_t P, int64_t H, int64_t V, const int32_t *variant_of) {
-    std::vector<int64_t> out((size_t)(P * V), 0);
-    for (int64_t pn = 0; pn < P; pn++)
-        for (int64_t h = 0; h < H; h++)
-            if (variant_of[h] >= 0) out[(size_t)(pn * V + variant_of[h])] += src[(size_t)(pn * H + h)];
-    return out;
-}
-
 // host blocks of n chains
 struct HostBlocks {
     int64_t cells, K;
@@ -247,64 +237,19 @@ extern "C" int vgx_get_tau_milestones(vgx_engine *e, vgx_tau_milestones_io *io, 
     const std::string me = "vgx_get_tau_milestones: ";
     io->passes = 0;
     io->ms[0] = io->ms[1] = io->ms[2] = 0.0;
-    if (!e->sc_host_valid || !e->last_was_tau || (int64_t)e->tau_log.size() < e->R)
-        return fail(e, VGX_ERR_ARG, me + "the last call was not vgx_simulate_tau (walks tau chains only)");
-    if (e->tau_mev_cap <= 0) return fail(e, VGX_ERR_ARG, me + "the last call recorded no multievent rows (record_events = 0)");
     const int64_t n = io->n, P = e->d.popNum, H = e->d.hapNum, V = io->V, K = io->K, mev_cap = e->tau_mev_cap;
-    {
-        const std::string why = check_request(V, io->variant_of, K, io->thresholds, P, H);
-        if (!why.empty()) return fail(e, VGX_ERR_ARG, me + why);
-    }
-    const int64_t pv = P * V, cells = pv + V;
-    // the prefix: what the model held when the call started
-    const int64_t pre_ev = prefix ? prefix->ev_ptr : 0;
-    if (pre_ev < 0 || (pre_ev > 0 && (!prefix->ev_times || !prefix->ev_types || !prefix->ev_haplotypes || !prefix->ev_populations ||
-                                      !prefix->ev_newHaplotypes || !prefix->ev_newPopulations)))
-        return fail(e, VGX_ERR_ARG, me + "null prefix column");
-    std::vector<int32_t> n_own((size_t)n), with_prefix((size_t)n, 0);
-    bool any_prefix = false;
-    {
-        std::vector<char> seen((size_t)e->R, 0);
-        for (int64_t i = 0; i < n; i++) {
-            const int64_t r = io->replicates[i];
-            if (r < 0 || r >= e->R) return fail(e, VGX_ERR_ARG, me + "replicate index out of range");
-            if (seen[(size_t)r]) return fail(e, VGX_ERR_ARG, me + "replicates must be distinct");
-            seen[(size_t)r] = 1;
-            const VgxRepScalars &s = e->sc_host[(size_t)r];
-            const int64_t first = s.restarts > 0 ? 0 : e->ev_ptr0;   // vgx_counters.ev_first_new
-            if (s.restarts == 0 && first != pre_ev)
-                return fail(e, VGX_ERR_ARG, me + "replicate " + std::to_string(r) + ": its chain continues a log of " + std::to_string(first) +
-                                                " events, the prefix holds " + std::to_string(pre_ev));
-            with_prefix[(size_t)i] = s.restarts == 0 && pre_ev > 0;
-            any_prefix = any_prefix || with_prefix[(size_t)i];
-            const auto &lg = e->tau_log[(size_t)r];
-            for (size_t k = 0; k < lg.size(); k++)   // the steps' row ranges tile the replicate's block
-                if (lg[k].m0 != (k ? lg[k - 1].m1 : 0) || lg[k].m1 < lg[k].m0)
-                    return fail(e, VGX_ERR_ARG, me + "replicate " + std::to_string(r) + ": row ranges of its steps are not contiguous");
-            if (!lg.empty() && lg.back().m1 > mev_cap) return fail(e, VGX_ERR_ARG, me + "replicate " + std::to_string(r) + " logged more rows than its block holds");
-            const int64_t events = (with_prefix[(size_t)i] ? pre_ev : 0) + (int64_t)lg.size();
-            if (events >= VGX_MS_MAX_EVENTS)
-                return fail(e, VGX_ERR_ARG, me + "replicate " + std::to_string(r) + " holds a chain of " + std::to_string(events) + " events (2^30 or more)");
-        }
-    }
-    FlatChain pre;
-    pre.ev_row.assign(1, 0);
-    if (any_prefix) {
-        const EventCols ev{pre_ev, prefix->ev_times, prefix->ev_types, prefix->ev_haplotypes, prefix->ev_populations, prefix->ev_newHaplotypes, prefix->ev_newPopulations};
-        const RowCols mv{prefix->mev_rows, prefix->mev_num, prefix->mev_types, prefix->mev_haplotypes, prefix->mev_populations, prefix->mev_newHaplotypes,
-                         prefix->mev_newPopulations};
-        if (mv.n > 0 && (!mv.num || !mv.types || !mv.hap || !mv.pop || !mv.nh || !mv.np)) return fail(e, VGX_ERR_ARG, me + "null prefix multievent column");
-        const std::string why = flatten(ev, pre_ev, mv, pre);
-        if (!why.empty()) return fail(e, VGX_ERR_ARG, me + "prefix: " + why);
-    }
-    const int64_t pre_rows = pre.n_rows();
-    for (int64_t i = 0; i < n; i++) {
-        const auto &lg = e->tau_log[(size_t)io->replicates[i]];
-        const int64_t own = lg.empty() ? 0 : lg.back().m1, total = (with_prefix[(size_t)i] ? pre_rows : 0) + own;
-        if (total >= ((int64_t)1 << 31))
-            return fail(e, VGX_ERR_ARG, me + "replicate " + std::to_string(io->replicates[i]) + ": prefix and own rows reach 2^31 (" + std::to_string(total) + ")");
-        n_own[(size_t)i] = (int32_t)own;
-    }
+    TauSel sel;
+    if (const int rc = tau_select(e, me, "walks", [&]() { return check_request(V, io->variant_of, K, io->thresholds, P, H); }, n, io->replicates, prefix, false,
+                                  [&](int64_t, int64_t r, bool with) -> std::string {
+                                      const int64_t events = (with ? sel.pre_ev : 0) + (int64_t)e->tau_log[(size_t)r].size();
+                                      if (events < VGX_MS_MAX_EVENTS) return "";
+                                      return "replicate " + std::to_string(r) + " holds a chain of " + std::to_string(events) + " events (2^30 or more)";
+                                  }, sel))
+        return rc;
+    const FlatChain &pre = sel.pre;
+    const std::vector<int32_t> &n_own = sel.n_own, &with_prefix = sel.with_prefix;
+    const bool any_prefix = sel.any_prefix;
+    const int64_t pv = P * V, cells = pv + V, pre_ev = sel.pre_ev, pre_rows = sel.pre_rows;
     if (n == 0) {
         io->ms[2] = since(t_call);
         return VGX_OK;
@@ -332,18 +277,16 @@ extern "C" int vgx_get_tau_milestones(vgx_engine *e, vgx_tau_milestones_io *io, 
     HIPCHECK(e, hipSetDevice(e->device));
     size_t free_b = 0, total_b = 0;
     HIPCHECK(e, hipMemGetInfo(&free_b, &total_b));
-    auto up8 = [](int64_t b) { return (b + 255) / 256 * 256; };
-    auto dev_free = [](char *p) { (void)hipFree(p); };
     // what stays for the whole call: [rep | n_own | ev0 | variant_of | prefix rows | start | peak | peak_event | last_pos | first]
-    const int64_t o_rep = 0, o_nown = o_rep + up8(n * 8), o_ev0 = o_nown + up8(n * 4), o_map = o_ev0 + up8(n * 4), o_prow = o_map + up8(H * 4),
-                  o_start = o_prow + up8(pre_rows * 48 + 8), o_peak = o_start + up8(n * pv * 8), o_pev = o_peak + up8(n * cells * 8),
-                  o_last = o_pev + up8(n * cells * 4), o_first = o_last + up8(n * cells * 4), keep_total = o_first + up8(n * K * cells * 4) + 256;
+    DevLayout lay;
+    const int64_t o_rep = lay.take(n * 8), o_nown = lay.take(n * 4), o_ev0 = lay.take(n * 4), o_map = lay.take(H * 4), o_prow = lay.take(pre_rows * 48 + 8),
+                  o_start = lay.take(n * pv * 8), o_peak = lay.take(n * cells * 8), o_pev = lay.take(n * cells * 4), o_last = lay.take(n * cells * 4),
+                  o_first = lay.take(n * K * cells * 4), keep_total = lay.total + 256;
     if (keep_total > (int64_t)(free_b / 2))
         return fail(e, VGX_ERR_ARG, me + "the block of " + std::to_string(n) + " x " + std::to_string(P + 1) + " x " + std::to_string(V) + " records of " +
                                         std::to_string(K) + " thresholds, the prefix rows and the start take " + std::to_string(keep_total) +
                                         " bytes, above half of the " + std::to_string((int64_t)free_b) + " bytes of free device memory: select fewer replicates per call");
-    int64_t share = std::min<int64_t>((int64_t)(free_b / 2) - keep_total + 4096, (int64_t)1 << 30);
-    if (const char *cb = getenv("VGX_TIMELINES_CHUNK_BYTES")) share = std::min<int64_t>(share, std::max<int64_t>(atoll(cb), 1));
+    const int64_t share = tau_chunk_share((int64_t)(free_b / 2) - keep_total + 4096);
     // device bytes of m chains of at most T tiles with `events` events in all: the first row of every event, pass A's bounds, the
     // tile edges, the tile bases (val, fin), the peak slots
     const int64_t tile_bytes = pv * 8 + cells * 12 + 8;
@@ -356,10 +299,9 @@ extern "C" int vgx_get_tau_milestones(vgx_engine *e, vgx_tau_milestones_io *io, 
                                             std::to_string(need) + " bytes, above the " + std::to_string(share) +
                                             " bytes of device memory the call may use: raise VGX_TAU_MILESTONES_TILE_ROWS");
     }
-    char *kws = nullptr;
-    hipError_t er = hipMalloc((void **)&kws, (size_t)keep_total);
-    if (er != hipSuccess) return fail(e, VGX_ERR_HIP, me + "hipMalloc of " + std::to_string(keep_total) + " bytes: " + hipGetErrorString(er));
-    std::unique_ptr<char, void (*)(char *)> khold(kws, dev_free);
+    DevHold khold;
+    if (const int rc = dev_alloc(e, me, keep_total, khold)) return rc;
+    char *const kws = khold.get();
     const int32_t *d_map = (const int32_t *)(kws + o_map);
     HIPCHECK(e, hipMemcpyAsync(kws + o_map, io->variant_of, (size_t)H * 4, hipMemcpyHostToDevice, e->stream));
 
@@ -369,20 +311,19 @@ extern "C" int vgx_get_tau_milestones(vgx_engine *e, vgx_tau_milestones_io *io, 
                    const int32_t *d_ev0, const int64_t *d_start, char *d_peak, char *d_pev, char *d_last, char *d_first, HostBlocks &blocks, int64_t b0,
                    int64_t *fin) -> int {
         const int64_t T = ct.T;
-        const int64_t c_evrow = 0, c_evoff = c_evrow + up8((int64_t)ct.ev_row.size() * 4), c_tev = c_evoff + up8(m * 8), c_nt = c_tev + up8(m * (T + 1) * 4),
-                      c_bnd = c_nt + up8(m * 4), c_val = c_bnd + up8(m * (T + 2) * 4), c_fin = c_val + up8(m * T * pv * 8), c_out = c_fin + up8(m * pv * 8),
-                      c_speak = c_out + up8(m * 16), c_sev = c_speak + up8(m * T * cells * 8), c_total = c_sev + up8(m * T * cells * 4);
-        char *cws = nullptr;
-        hipError_t er2 = hipMalloc((void **)&cws, (size_t)c_total);
-        if (er2 != hipSuccess) return fail(e, VGX_ERR_HIP, me + "hipMalloc of " + std::to_string(c_total) + " bytes: " + hipGetErrorString(er2));
-        std::unique_ptr<char, void (*)(char *)> chold(cws, dev_free);
+        DevLayout cl;
+        const int64_t c_evrow = cl.take((int64_t)ct.ev_row.size() * 4), c_evoff = cl.take(m * 8), c_tev = cl.take(m * (T + 1) * 4), c_nt = cl.take(m * 4),
+                      c_bnd = cl.take(m * (T + 2) * 4), c_val = cl.take(m * T * pv * 8), c_fin = cl.take(m * pv * 8), c_out = cl.take(m * 16),
+                      c_speak = cl.take(m * T * cells * 8), c_sev = cl.take(m * T * cells * 4);
+        DevHold chold;
+        if (const int rc = dev_alloc(e, me, cl.total, chold)) return rc;
+        char *const cws = chold.get();
         HIPCHECK(e, hipMemcpyAsync(cws + c_evrow, ct.ev_row.data(), ct.ev_row.size() * 4, hipMemcpyHostToDevice, e->stream));
         HIPCHECK(e, hipMemcpyAsync(cws + c_evoff, ct.ev_off.data(), (size_t)m * 8, hipMemcpyHostToDevice, e->stream));
         HIPCHECK(e, hipMemcpyAsync(cws + c_tev, ct.tile_ev.data(), ct.tile_ev.size() * 4, hipMemcpyHostToDevice, e->stream));
         HIPCHECK(e, hipMemcpyAsync(cws + c_nt, ct.n_tiles.data(), (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
         HIPCHECK(e, hipMemcpyAsync(cws + c_bnd, ct.bound.data(), ct.bound.size() * 4, hipMemcpyHostToDevice, e->stream));
         HIPCHECK(e, hipMemsetAsync(cws + c_val, 0, (size_t)(c_speak - c_val), e->stream));   // val, fin and pass A's outside counters
-        HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
         VgxTauMsLaunch g{};
         VgxTauPrevLaunch &a = g.a;
         a.m = m;
@@ -399,22 +340,20 @@ extern "C" int vgx_get_tau_milestones(vgx_engine *e, vgx_tau_milestones_io *io, 
         g.max_tiles = ct.max_tiles;
         g.peak = (int64_t *)d_peak; g.peak_event = (int32_t *)d_pev; g.last_pos = (int32_t *)d_last; g.first = (int32_t *)d_first;
         g.slot_peak = (int64_t *)(cws + c_speak); g.slot_event = (int32_t *)(cws + c_sev);
-        HIPCHECK(e, vgxi_tau_prev_count(&a, e->stream));
-        HIPCHECK(e, vgxi_tau_prev_scan(&a, e->stream));
-        HIPCHECK(e, launch_walk(&g, waves, e->stream));
-        if (ct.max_tiles > 0) io->passes += 1;
-        HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
-        HIPCHECK(e, hipMemcpyAsync(fin, cws + c_fin, (size_t)(m * pv) * 8, hipMemcpyDeviceToHost, e->stream));
-        HIPCHECK(e, hipMemcpyAsync(blocks.peak.data() + b0 * cells, d_peak, (size_t)(m * cells) * 8, hipMemcpyDeviceToHost, e->stream));
-        HIPCHECK(e, hipMemcpyAsync(blocks.peak_event.data() + b0 * cells, d_pev, (size_t)(m * cells) * 4, hipMemcpyDeviceToHost, e->stream));
-        HIPCHECK(e, hipMemcpyAsync(blocks.last_pos.data() + b0 * cells, d_last, (size_t)(m * cells) * 4, hipMemcpyDeviceToHost, e->stream));
-        if (K > 0) HIPCHECK(e, hipMemcpyAsync(blocks.first.data() + b0 * K * cells, d_first, (size_t)(m * K * cells) * 4, hipMemcpyDeviceToHost, e->stream));
-        if ((er2 = hipStreamSynchronize(e->stream)) != hipSuccess)
-            return fail(e, VGX_ERR_HIP, me + "counting, scan, walk or reduce kernel failed: " + hipGetErrorString(er2));
-        float kms = 0.f;
-        HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
-        io->ms[0] += kms;
-        return VGX_OK;
+        return tau_timed(e, io->ms, me + "counting, scan, walk or reduce kernel failed: ", [&]() -> int {
+            HIPCHECK(e, vgxi_tau_prev_count(&a, e->stream));
+            HIPCHECK(e, vgxi_tau_prev_scan(&a, e->stream));
+            HIPCHECK(e, launch_walk(&g, waves, e->stream));
+            if (ct.max_tiles > 0) io->passes += 1;
+            return VGX_OK;
+        }, [&]() -> int {
+            HIPCHECK(e, hipMemcpyAsync(fin, cws + c_fin, (size_t)(m * pv) * 8, hipMemcpyDeviceToHost, e->stream));
+            HIPCHECK(e, hipMemcpyAsync(blocks.peak.data() + b0 * cells, d_peak, (size_t)(m * cells) * 8, hipMemcpyDeviceToHost, e->stream));
+            HIPCHECK(e, hipMemcpyAsync(blocks.peak_event.data() + b0 * cells, d_pev, (size_t)(m * cells) * 4, hipMemcpyDeviceToHost, e->stream));
+            HIPCHECK(e, hipMemcpyAsync(blocks.last_pos.data() + b0 * cells, d_last, (size_t)(m * cells) * 4, hipMemcpyDeviceToHost, e->stream));
+            if (K > 0) HIPCHECK(e, hipMemcpyAsync(blocks.first.data() + b0 * K * cells, d_first, (size_t)(m * K * cells) * 4, hipMemcpyDeviceToHost, e->stream));
+            return VGX_OK;
+        });
     };
     auto up_blocks = [&](HostBlocks &b, int64_t m, char *d_peak, char *d_pev, char *d_last, char *d_first) -> int {
         HIPCHECK(e, hipMemcpyAsync(d_peak, b.peak.data(), (size_t)(m * cells) * 8, hipMemcpyHostToDevice, e->stream));
@@ -426,7 +365,7 @@ extern "C" int vgx_get_tau_milestones(vgx_engine *e, vgx_tau_milestones_io *io, 
 
     // the state every chain starts from, folded through variant_of: the initial state for a chain that starts at the beginning of
     // the model's history (a restarted replicate, or one that carries a prefix), else the state the call started from
-    const std::vector<int64_t> fold[2] = {fold_state(e->hs.infectious, P, H, V, io->variant_of), fold_state(e->hs.initial_infectious, P, H, V, io->variant_of)};
+    const std::vector<int64_t> fold[2] = {tau_fold_state(e->hs.infectious, P, H, V, io->variant_of), tau_fold_state(e->hs.initial_infectious, P, H, V, io->variant_of)};
 
     // the prefix, once: a chain of its own from the initial state.  Its block and its final row use the places of chain 0, which
     // are written again below.
@@ -532,48 +471,14 @@ extern "C" int vgx_test_tau_milestones(vgx_tau_milestones_chain *io, char *errbu
         if (!why.empty()) return fail_(why);
     }
     if (n < 0 || n >= VGX_MS_MAX_EVENTS) return fail_("a chain of " + std::to_string(n) + " events (2^30 or more)");
-    if (n > 0 && (!io->ev_times || !io->ev_types || !io->ev_haplotypes || !io->ev_populations || !io->ev_newHaplotypes || !io->ev_newPopulations))
-        return fail_("null event column");
-    if (io->mev_rows < 0 || (io->mev_rows > 0 && (!io->mev_num || !io->mev_types || !io->mev_haplotypes || !io->mev_populations ||
-                                                  !io->mev_newHaplotypes || !io->mev_newPopulations)))
-        return fail_("null multievent column");
-    int64_t tile = io->tile;
-    if (tile < 0) return fail_("tile must not be negative");
-    if (tile == 0) tile = VGX_TAU_MS_TILE_DEFAULT;
-    int64_t n_own_ev = io->n_own_events;
-    if (n_own_ev < -1 || n_own_ev > n) return fail_("n_own_events must be -1 or lie in [0, ev_ptr]");
-    if (n_own_ev < 0) {   // the chain's trailing MULTITYPE events
-        n_own_ev = 0;
-        while (n_own_ev < n && io->ev_types[n - 1 - n_own_ev] == VGX_TL_MULTITYPE) n_own_ev++;
-    }
-    const int64_t n_pre_ev = n - n_own_ev, pv = P * V, cells = pv + V;
-    const EventCols ev{n, io->ev_times, io->ev_types, io->ev_haplotypes, io->ev_populations, io->ev_newHaplotypes, io->ev_newPopulations};
-    const RowCols mv{io->mev_rows, io->mev_num, io->mev_types, io->mev_haplotypes, io->mev_populations, io->mev_newHaplotypes, io->mev_newPopulations};
-    FlatChain pre;
+    TauHookChain c;
     {
-        const std::string why = flatten(ev, n_pre_ev, mv, pre);
+        const std::string why = tau_hook_split(io, VGX_TAU_MS_TILE_DEFAULT, 0, c);
         if (!why.empty()) return fail_(why);
     }
-    // the own rows as a block of their own, unjudged, with every own event's first row
-    std::vector<int64_t> own, own_row((size_t)n_own_ev + 1);
-    for (int64_t k = 0; k < n_own_ev; k++) {
-        const int64_t i = n_pre_ev + k, t = ev.types[i];
-        own_row[(size_t)k] = (int64_t)own.size() / 6;
-        if (t == VGX_TL_MULTITYPE) {
-            const int64_t j0 = ev.hap[i], j1 = ev.pop[i];
-            if (j1 <= j0) continue;
-            if (j0 < 0 || j1 > mv.n) return fail_("event " + std::to_string(i) + ": MULTITYPE row range outside the multievent log");
-            for (int64_t j = j0; j < j1; j++) {
-                const int64_t v[6] = {mv.num[j], mv.types[j], mv.hap[j], mv.pop[j], mv.nh[j], mv.np[j]};
-                own.insert(own.end(), v, v + 6);
-            }
-        } else {
-            const int64_t v[6] = {1, t, ev.hap[i], ev.pop[i], ev.nh[i], ev.np[i]};
-            own.insert(own.end(), v, v + 6);
-        }
-        if (pre.n_rows() + (int64_t)own.size() / 6 >= ((int64_t)1 << 31)) return fail_("the chain has 2^31 rows or more");
-    }
-    own_row[(size_t)n_own_ev] = (int64_t)own.size() / 6;
+    const int64_t tile = c.tile, n_pre_ev = c.n_pre_ev, n_own_ev = c.n_own_ev, pv = P * V, cells = pv + V;
+    const FlatChain &pre = c.pre;
+    const std::vector<int64_t> &own = c.own, &own_row = c.own_m0;
     const int32_t Pi = (int32_t)P, Hi = (int32_t)H, Vi = (int32_t)V, Ki = (int32_t)K;
     HostBlocks block(1, cells, K);
     const VgxTauMsBlock blk = block.at(0);

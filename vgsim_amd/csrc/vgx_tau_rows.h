@@ -1,6 +1,8 @@
 // vgx_tau_rows.h — host: the flattened list of a chain's events as weighted rows in the 48-byte layout of the multievent log (the
-// prefix of a tau call, or a whole chain in a test hook).  Shared by the units that read tau chains as rows
-// (vgx_tau_timelines.hip, vgx_tau_incidence.hip); every unit gets its own copy (anonymous namespace).
+// prefix of a tau call, or a whole chain in a test hook).  Host-only; the frame of the tau replays (vgx_tau_replay.h) builds on
+// it, and through the frame the six units that read tau chains as rows: vgx_tau_timelines.hip, vgx_tau_incidence.hip,
+// vgx_tau_flows.hip, vgx_tau_prevalence.hip, vgx_tau_susceptible.hip and vgx_tau_milestones.hip.  `flatten` is inline: one
+// definition for all of them.
 #pragma once
 #include <stdint.h>
 #include <algorithm>
@@ -8,7 +10,7 @@
 #include <vector>
 #include "vgx_tline.h"
 
-namespace {
+#pragma GCC visibility push(hidden)   // nothing here is part of the exported C ABI
 
 // ---- host: the flattened list of a chain's events (the prefix of a call, or a whole chain in the test hook)
 struct EventCols {
@@ -28,7 +30,7 @@ struct FlatChain {
 };
 
 // events [0, n_ev) of `ev` as rows; "" or why not
-std::string flatten(const EventCols &ev, int64_t n_ev, const RowCols &mv, FlatChain &f) {
+inline std::string flatten(const EventCols &ev, int64_t n_ev, const RowCols &mv, FlatChain &f) {
     f.rows.clear();
     f.ev_row.assign((size_t)n_ev + 1, 0);
     f.ev_max.resize((size_t)n_ev);
@@ -61,4 +63,4 @@ std::string flatten(const EventCols &ev, int64_t n_ev, const RowCols &mv, FlatCh
     return "";
 }
 
-}  // namespace
+#pragma GCC visibility pop

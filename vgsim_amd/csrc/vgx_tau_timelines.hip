@@ -22,8 +22,7 @@
 #include <stdio.h>
 #include <string>
 #include <vector>
-#include "vgx_engine.h"
-#include "vgx_tau_rows.h"   // EventCols, RowCols, FlatChain, flatten
+#include "vgx_tau_replay.h"   // the frame: selection, workspace, timed sections, wave_sum; FlatChain and flatten of vgx_tau_rows.h
 
 namespace {
 
@@ -51,12 +50,6 @@ struct Row { longlong2 a, b, c; };   // num, type | haplotype, population | newH
 
 // a field of a row as a 32-bit index: anything that is not one (never written by the tau kernels) matches no query
 __device__ __forceinline__ int32_t idx32(long long v) { return (unsigned long long)v < 0x80000000ull ? (int32_t)v : -1; }
-
-__device__ __forceinline__ long long wave_sum(long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
 
 __device__ __forceinline__ void lds_add(long long *p, long long v) {
     atomicAdd((unsigned long long *)p, (unsigned long long)v);   // two's complement: the sum is the signed one
@@ -192,82 +185,43 @@ extern "C" int vgx_get_tau_timelines(vgx_engine *e, vgx_timelines_io *io, const 
     const std::string me = "vgx_get_tau_timelines: ";
     io->passes = 0;
     io->ms[0] = io->ms[1] = io->ms[2] = 0.0;
-    if (!e->sc_host_valid || !e->last_was_tau || (int64_t)e->tau_log.size() < e->R)
-        return fail(e, VGX_ERR_ARG, me + "the last call was not vgx_simulate_tau (replays tau chains only)");
-    if (e->tau_mev_cap <= 0) return fail(e, VGX_ERR_ARG, me + "the last call recorded no multievent rows (record_events = 0)");
     const int64_t n = io->n, P = e->d.popNum, H = e->d.hapNum, S = e->d.susNum, step = io->step_num, T = step + 1;
     const int64_t n_inf = io->n_inf, n_sus = io->n_sus, mev_cap = e->tau_mev_cap;
-    if (step < 1) return fail(e, VGX_ERR_ARG, me + "step_num must be at least 1");
-    if (io->semantics != VGX_TL_REFERENCE && io->semantics != VGX_TL_COMPARTMENT)
-        return fail(e, VGX_ERR_ARG, me + "semantics must be 0 (reference) or 1 (compartment)");
-    if ((n_inf > 0 && (!io->inf_pop || !io->inf_hap)) || (n_sus > 0 && (!io->sus_pop || !io->sus_grp)) || n_inf + n_sus >= ((int64_t)1 << 20))
-        return fail(e, VGX_ERR_ARG, me + "bad query list");
-    {
+    auto request = [&]() -> std::string {
+        if (step < 1) return "step_num must be at least 1";
+        if (io->semantics != VGX_TL_REFERENCE && io->semantics != VGX_TL_COMPARTMENT) return "semantics must be 0 (reference) or 1 (compartment)";
+        if ((n_inf > 0 && (!io->inf_pop || !io->inf_hap)) || (n_sus > 0 && (!io->sus_pop || !io->sus_grp)) || n_inf + n_sus >= ((int64_t)1 << 20))
+            return "bad query list";
         std::vector<std::pair<int64_t, int64_t>> qi, qs;
         for (int64_t k = 0; k < n_inf; k++) {
-            if (io->inf_pop[k] < 0 || io->inf_pop[k] >= P) return fail(e, VGX_ERR_ARG, me + "population index out of range");
-            if (io->inf_hap[k] < 0 || io->inf_hap[k] >= H) return fail(e, VGX_ERR_ARG, me + "haplotype index out of range");
+            if (io->inf_pop[k] < 0 || io->inf_pop[k] >= P) return "population index out of range";
+            if (io->inf_hap[k] < 0 || io->inf_hap[k] >= H) return "haplotype index out of range";
             qi.emplace_back(io->inf_pop[k], io->inf_hap[k]);
         }
         for (int64_t k = 0; k < n_sus; k++) {
-            if (io->sus_pop[k] < 0 || io->sus_pop[k] >= P) return fail(e, VGX_ERR_ARG, me + "population index out of range");
-            if (io->sus_grp[k] < 0 || io->sus_grp[k] >= S) return fail(e, VGX_ERR_ARG, me + "susceptibility group index out of range");
+            if (io->sus_pop[k] < 0 || io->sus_pop[k] >= P) return "population index out of range";
+            if (io->sus_grp[k] < 0 || io->sus_grp[k] >= S) return "susceptibility group index out of range";
             qs.emplace_back(io->sus_pop[k], io->sus_grp[k]);
         }
         std::sort(qi.begin(), qi.end());
         std::sort(qs.begin(), qs.end());
-        if (std::adjacent_find(qi.begin(), qi.end()) != qi.end() || std::adjacent_find(qs.begin(), qs.end()) != qs.end())
-            return fail(e, VGX_ERR_ARG, me + "a query is given twice");
-    }
-    // the prefix: what the model held when the call started
-    const int64_t pre_ev = prefix ? prefix->ev_ptr : 0, pre_loc = prefix ? std::max<int64_t>(prefix->loc_n, 0) : 0;
-    if (pre_ev < 0 || (pre_ev > 0 && (!prefix->ev_times || !prefix->ev_types || !prefix->ev_haplotypes || !prefix->ev_populations ||
-                                      !prefix->ev_newHaplotypes || !prefix->ev_newPopulations)))
-        return fail(e, VGX_ERR_ARG, me + "null prefix column");
-    if (pre_loc > 0 && (!prefix->loc_state || !prefix->loc_pop || !prefix->loc_time)) return fail(e, VGX_ERR_ARG, me + "null prefix lockdown column");
-    std::vector<int32_t> n_pre((size_t)n), n_rows((size_t)n);
-    std::vector<char> with_prefix((size_t)n, 0);
-    bool any_prefix = false;
+        if (std::adjacent_find(qi.begin(), qi.end()) != qi.end() || std::adjacent_find(qs.begin(), qs.end()) != qs.end()) return "a query is given twice";
+        return "";
+    };
+    TauSel sel;
     int64_t loc_need = 1;
-    {
-        std::vector<char> seen((size_t)e->R, 0);
-        for (int64_t i = 0; i < n; i++) {
-            const int64_t r = io->replicates[i];
-            if (r < 0 || r >= e->R) return fail(e, VGX_ERR_ARG, me + "replicate index out of range");
-            if (seen[(size_t)r]) return fail(e, VGX_ERR_ARG, me + "replicates must be distinct");
-            seen[(size_t)r] = 1;
-            const VgxRepScalars &s = e->sc_host[(size_t)r];
-            const int64_t first = s.restarts > 0 ? 0 : e->ev_ptr0;   // vgx_counters.ev_first_new
-            if (s.restarts == 0 && first != pre_ev)
-                return fail(e, VGX_ERR_ARG, me + "replicate " + std::to_string(r) + ": its chain continues a log of " + std::to_string(first) +
-                                                " events, the prefix holds " + std::to_string(pre_ev));
-            with_prefix[(size_t)i] = s.restarts == 0 && pre_ev > 0;
-            any_prefix = any_prefix || with_prefix[(size_t)i];
-            const auto &lg = e->tau_log[(size_t)r];
-            for (size_t k = 0; k < lg.size(); k++)   // the steps' row ranges tile the replicate's block
-                if (lg[k].m0 != (k ? lg[k - 1].m1 : 0) || lg[k].m1 < lg[k].m0)
-                    return fail(e, VGX_ERR_ARG, me + "replicate " + std::to_string(r) + ": row ranges of its steps are not contiguous");
-            if (!lg.empty() && lg.back().m1 > mev_cap) return fail(e, VGX_ERR_ARG, me + "replicate " + std::to_string(r) + " logged more rows than its block holds");
-            loc_need = std::max<int64_t>(loc_need, (s.restarts == 0 ? pre_loc : 0) + (int64_t)e->tau_loc_time[(size_t)r].size());
-        }
-    }
-    FlatChain pre;
-    pre.ev_row.assign(1, 0);
-    if (any_prefix) {
-        const EventCols ev{pre_ev, prefix->ev_times, prefix->ev_types, prefix->ev_haplotypes, prefix->ev_populations, prefix->ev_newHaplotypes, prefix->ev_newPopulations};
-        const RowCols mv{prefix->mev_rows, prefix->mev_num, prefix->mev_types, prefix->mev_haplotypes, prefix->mev_populations, prefix->mev_newHaplotypes,
-                         prefix->mev_newPopulations};
-        if (mv.n > 0 && (!mv.num || !mv.types || !mv.hap || !mv.pop || !mv.nh || !mv.np)) return fail(e, VGX_ERR_ARG, me + "null prefix multievent column");
-        const std::string why = flatten(ev, pre_ev, mv, pre);
-        if (!why.empty()) return fail(e, VGX_ERR_ARG, me + "prefix: " + why);
-    }
+    if (const int rc = tau_select(e, me, "replays", request, n, io->replicates, prefix, true, [&](int64_t, int64_t r, bool) -> std::string {
+            loc_need = std::max<int64_t>(loc_need, (e->sc_host[(size_t)r].restarts == 0 ? sel.pre_loc : 0) + (int64_t)e->tau_loc_time[(size_t)r].size());
+            return "";
+        }, sel))
+        return rc;
+    const FlatChain &pre = sel.pre;
+    const std::vector<int32_t> &with_prefix = sel.with_prefix;
+    const int64_t pre_ev = sel.pre_ev, pre_loc = sel.pre_loc;
+    std::vector<int32_t> n_pre((size_t)n), n_rows((size_t)n);   // prefix rows of a chain; prefix + own rows
     for (int64_t i = 0; i < n; i++) {
-        const auto &lg = e->tau_log[(size_t)io->replicates[i]];
-        const int64_t np = with_prefix[(size_t)i] ? pre.n_rows() : 0, total = np + (lg.empty() ? 0 : lg.back().m1);
-        if (total >= ((int64_t)1 << 31))
-            return fail(e, VGX_ERR_ARG, me + "replicate " + std::to_string(io->replicates[i]) + ": prefix and own rows reach 2^31 (" + std::to_string(total) + ")");
-        n_pre[(size_t)i] = (int32_t)np;
-        n_rows[(size_t)i] = (int32_t)total;
+        n_pre[(size_t)i] = with_prefix[(size_t)i] ? (int32_t)sel.pre_rows : 0;
+        n_rows[(size_t)i] = n_pre[(size_t)i] + sel.n_own[(size_t)i];
     }
     if (!io->time_points) {   // sizing
         io->loc_cap = loc_need;
@@ -313,15 +267,12 @@ extern "C" int vgx_get_tau_timelines(vgx_engine *e, vgx_timelines_io *io, const 
         s += g.ns;
     }
     HIPCHECK(e, hipSetDevice(e->device));
-    auto up8 = [](int64_t b) { return (b + 255) / 256 * 256; };
-    auto dev_free = [](char *p) { (void)hipFree(p); };
     // one allocation for what every chunk shares: [table | start | prefix rows], uploaded ONCE per call
-    char *qws = nullptr;
-    const int64_t q_tab = 0, q_start = up8((int64_t)h_tab.size() * 4 + 8), q_pre = q_start + up8((int64_t)h_start.size() * 8 + 8),
-                  q_total = q_pre + up8((int64_t)pre.rows.size() * 8 + 8);
-    hipError_t er = hipMalloc((void **)&qws, (size_t)q_total);
-    if (er != hipSuccess) return fail(e, VGX_ERR_HIP, me + "hipMalloc of " + std::to_string(q_total) + " bytes: " + hipGetErrorString(er));
-    std::unique_ptr<char, void (*)(char *)> qhold(qws, dev_free);
+    DevLayout ql;
+    const int64_t q_tab = ql.take((int64_t)h_tab.size() * 4 + 8), q_start = ql.take((int64_t)h_start.size() * 8 + 8), q_pre = ql.take((int64_t)pre.rows.size() * 8 + 8);
+    DevHold qhold;
+    if (const int rc = dev_alloc(e, me, ql.total, qhold)) return rc;
+    char *const qws = qhold.get();
     if (!h_tab.empty()) HIPCHECK(e, hipMemcpy(qws + q_tab, h_tab.data(), h_tab.size() * 4, hipMemcpyHostToDevice));
     if (!h_start.empty()) HIPCHECK(e, hipMemcpy(qws + q_start, h_start.data(), h_start.size() * 8, hipMemcpyHostToDevice));
     if (!pre.rows.empty()) HIPCHECK(e, hipMemcpy(qws + q_pre, pre.rows.data(), pre.rows.size() * 8, hipMemcpyHostToDevice));
@@ -329,20 +280,18 @@ extern "C" int vgx_get_tau_timelines(vgx_engine *e, vgx_timelines_io *io, const 
     // chunks of replicates: cuts and outputs of a chunk fit `share` bytes of device memory
     size_t free_b = 0, total_b = 0;
     HIPCHECK(e, hipMemGetInfo(&free_b, &total_b));
-    int64_t share = std::min<int64_t>((int64_t)(free_b / 2), (int64_t)1 << 30);
-    if (const char *cb = getenv("VGX_TIMELINES_CHUNK_BYTES")) share = std::min<int64_t>(share, std::max<int64_t>(atoll(cb), 1));
+    const int64_t share = tau_chunk_share((int64_t)(free_b / 2));
     const int64_t per_rep = step * 4 + (2 * n_inf + n_sus) * T * 8 + 64;
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(share / per_rep, (int64_t)1 << 20));
     for (int64_t i0 = 0; i0 < n; i0 += chunk) {
         const int64_t i1 = std::min(n, i0 + chunk), m = i1 - i0;
         // one allocation: [rep | n_pre | n_rows | last | cut | inf | smp | sus]
-        const int64_t o_rep = 0, o_npre = o_rep + up8(m * 8), o_nrows = o_npre + up8(m * 4), o_last = o_nrows + up8(m * 4), o_cut = o_last + up8(m * 4),
-                      o_inf = o_cut + up8(m * step * 4), o_smp = o_inf + up8(m * n_inf * T * 8), o_sus = o_smp + up8(m * n_inf * T * 8),
-                      total = o_sus + up8(m * n_sus * T * 8);
-        char *ws = nullptr;
-        er = hipMalloc((void **)&ws, (size_t)total);
-        if (er != hipSuccess) return fail(e, VGX_ERR_HIP, me + "hipMalloc of " + std::to_string(total) + " bytes: " + hipGetErrorString(er));
-        std::unique_ptr<char, void (*)(char *)> hold(ws, dev_free);
+        DevLayout lay;
+        const int64_t o_rep = lay.take(m * 8), o_npre = lay.take(m * 4), o_nrows = lay.take(m * 4), o_last = lay.take(m * 4), o_cut = lay.take(m * step * 4),
+                      o_inf = lay.take(m * n_inf * T * 8), o_smp = lay.take(m * n_inf * T * 8), o_sus = lay.take(m * n_sus * T * 8);
+        DevHold hold;
+        if (const int rc = dev_alloc(e, me, lay.total, hold)) return rc;
+        char *const ws = hold.get();
         // host: time_points, cuts in row index space, last_point, lockdown records
         const auto t_cuts = std::chrono::steady_clock::now();
         std::vector<int32_t> cuts((size_t)(m * step)), last((size_t)m);
@@ -379,28 +328,26 @@ extern "C" int vgx_get_tau_timelines(vgx_engine *e, vgx_timelines_io *io, const 
         HIPCHECK(e, hipMemcpyAsync(ws + o_nrows, n_rows.data() + i0, (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
         HIPCHECK(e, hipMemcpyAsync(ws + o_cut, cuts.data(), (size_t)(m * step) * 4, hipMemcpyHostToDevice, e->stream));
         HIPCHECK(e, hipMemcpyAsync(ws + o_last, last.data(), (size_t)m * 4, hipMemcpyHostToDevice, e->stream));
-        HIPCHECK(e, hipEventRecord(e->ev0, e->stream));
-        for (const Group &g : groups) {
-            VgxTtlLaunch a{};
-            a.m = m;
-            a.pre = (const int64_t *)(qws + q_pre);
-            a.mev = (const int64_t *)e->t_mev.p; a.mev_cap = mev_cap;
-            a.rep = (const int64_t *)(ws + o_rep); a.n_pre = (const int32_t *)(ws + o_npre); a.n_rows = (const int32_t *)(ws + o_nrows);
-            a.last = (const int32_t *)(ws + o_last); a.cut = (const int32_t *)(ws + o_cut);
-            a.step = (int)step; a.semantics = (int)io->semantics;
-            a.ni = (int)g.ni; a.ns = (int)g.ns; a.i0 = (int)g.i0; a.s0 = (int)g.s0; a.n_inf = (int)n_inf; a.n_sus = (int)n_sus;
-            a.tsize = vgx_tl_table_size((int)(g.ni + g.ns));
-            a.tab = (const int32_t *)(qws + q_tab) + g.tab_off;
-            a.start = (const int64_t *)(qws + q_start) + g.start_off;
-            a.inf = (double *)(ws + o_inf); a.smp = (double *)(ws + o_smp); a.sus = (double *)(ws + o_sus);
-            HIPCHECK(e, launch_replay(&a, e->stream));
-            io->passes += 1;
-        }
-        HIPCHECK(e, hipEventRecord(e->ev1, e->stream));
-        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(e, VGX_ERR_HIP, me + "replay kernel failed: " + hipGetErrorString(er));
-        float kms = 0.f;
-        HIPCHECK(e, hipEventElapsedTime(&kms, e->ev0, e->ev1));
-        io->ms[0] += kms;
+        const int rc = tau_timed(e, io->ms, me + "replay kernel failed: ", [&]() -> int {
+            for (const Group &g : groups) {
+                VgxTtlLaunch a{};
+                a.m = m;
+                a.pre = (const int64_t *)(qws + q_pre);
+                a.mev = (const int64_t *)e->t_mev.p; a.mev_cap = mev_cap;
+                a.rep = (const int64_t *)(ws + o_rep); a.n_pre = (const int32_t *)(ws + o_npre); a.n_rows = (const int32_t *)(ws + o_nrows);
+                a.last = (const int32_t *)(ws + o_last); a.cut = (const int32_t *)(ws + o_cut);
+                a.step = (int)step; a.semantics = (int)io->semantics;
+                a.ni = (int)g.ni; a.ns = (int)g.ns; a.i0 = (int)g.i0; a.s0 = (int)g.s0; a.n_inf = (int)n_inf; a.n_sus = (int)n_sus;
+                a.tsize = vgx_tl_table_size((int)(g.ni + g.ns));
+                a.tab = (const int32_t *)(qws + q_tab) + g.tab_off;
+                a.start = (const int64_t *)(qws + q_start) + g.start_off;
+                a.inf = (double *)(ws + o_inf); a.smp = (double *)(ws + o_smp); a.sus = (double *)(ws + o_sus);
+                HIPCHECK(e, launch_replay(&a, e->stream));
+                io->passes += 1;
+            }
+            return VGX_OK;
+        });
+        if (rc) return rc;
         if (n_inf > 0) {
             HIPCHECK(e, hipMemcpy(io->inf_data + i0 * n_inf * T, ws + o_inf, (size_t)(m * n_inf * T) * 8, hipMemcpyDeviceToHost));
             HIPCHECK(e, hipMemcpy(io->inf_sample + i0 * n_inf * T, ws + o_smp, (size_t)(m * n_inf * T) * 8, hipMemcpyDeviceToHost));
