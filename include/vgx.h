@@ -912,6 +912,52 @@ int vgx_test_tree_shape(const int32_t *tree, const int32_t *node_ev, const doubl
 int vgx_test_tree_shape_device(int64_t n, const int64_t *node_off, const int32_t *tree, const int32_t *node_ev, const double *times,
                                int64_t *stats, double *lengths, int64_t *status, char *errbuf, int64_t errcap);
 
+/* The same rows for many replicates of the last vgx_simulate_tau call (with the event log), with nothing of a tree crossing to the
+ * host.  The walk is that of vgx_get_tau_genealogies over the same chain (`prefix` as that call takes it): the same
+ * draws in the same order from rng_state, the same status and status_arg and the same six generator words afterwards (rng_out).  A
+ * tau chain needs no clock.  A node carries the chain's EVENT index: prefix events 0 .. prefix->ev_ptr - 1, the replicate's own step
+ * k is prefix->ev_ptr + k (k alone for a replicate that restarted), -1 for a node no event made.  Its time is
+ *   0.0 for -1;  the prefix event's time (a MULTITYPE event of an earlier tau call: the time of its first row);  the time of the
+ *   step's MULTITYPE record otherwise,
+ * the lookup of vgx_get_tau_genealogies with its branches in its order, so every time has the bits that call delivers.  All rows of
+ * a step share the step's time: coalescences inside one step give branches of length 0 (they count in the integer statistics as
+ * any other branch and add 0 to the sums; max_branch stays >= 0).  Per pass (sized as vgx_get_tau_genealogies sizes its passes, 8
+ * bytes of node time and 44 bytes of accumulators per node and the step times added; VGX_GENEALOGY_CHUNK_BYTES): the canonicalise
+ * kernel, the one synchronisation that sizes the walk's workspace from its report, then the walk kernel, the node-time kernel
+ * (vgx_tau_tree_shapes.hip) and the shape kernel of vgx_get_tree_shapes on one stream with no host step between them.  stats,
+ * lengths, status 13 and a failed walk's row as vgx_tree_shapes_io; statuses 10 .. 12 as vgx_tau_genealogies_io.  There is no
+ * sizing call: the record capacities are those the sizing call of vgx_get_tau_genealogies gives, counted inside.  An event index
+ * outside a chain (no healthy walk leaves one) fails the call with "vgx_get_tau_tree_shapes: an event index outside the chain".
+ * Preconditions and refusals as vgx_get_tau_genealogies (the last call was vgx_simulate_tau, it recorded rows, the prefix length,
+ * replicates distinct and in range, contiguous row ranges, the chain's length, prefix rows inside the model), worded behind
+ * "vgx_get_tau_tree_shapes: ". */
+typedef struct vgx_tau_tree_shapes_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    const uint64_t *rng_state;                   /* [n][6] start of every walk: PCG64 state hi, lo, increment hi, lo, has_uint32, uinteger */
+    int64_t *stats;                              /* [n][12] */
+    double *lengths;                             /* [n][7] */
+    int64_t *status, *status_arg;                /* [n] */
+    uint64_t *rng_out;                           /* [n][6] generator state after the walk */
+    int64_t passes;                              /* out: device passes */
+    double ms[3];                                /* out: kernels (device time), host part (descriptors and step-time tables), whole call */
+    double kernel_ms[4];                         /* out: the canonicalise, walk, node-time and shape kernels of ms[0] apart */
+} vgx_tau_tree_shapes_io;
+int vgx_get_tau_tree_shapes(vgx_engine *e, vgx_tau_tree_shapes_io *io, const vgx_tau_genealogy_prefix *prefix);
+/* Test hook: the node-time rule (vgx_tau_tree_shape.h) over one tree's node event indices on the host: times[k] for node_ev[k] in a
+ * chain of n_pre prefix events (times pre_times[n_pre]) and n_steps own steps (step_times[n_steps]).  An index below 0 gives 0.0; an
+ * index of n_pre + n_steps or more is refused (message in errbuf, naming the node). */
+int vgx_test_tau_node_times(const int32_t *node_ev, int64_t nodes, int64_t n_pre, const double *pre_times, int64_t n_steps,
+                            const double *step_times, double *times, char *errbuf, int64_t errcap);
+/* Test hook: n given trees (tree t: nodes node_off[t] .. node_off[t + 1] of node_ev and times, n_pre[t] prefix events out of the
+ * shared table pre_times[n_pre_times], own step times step_times[step_off[t] .. step_off[t + 1]]) through the node-time kernel of
+ * vgx_get_tau_tree_shapes on the current device's default stream; no engine.  bad [n]: the lowest node of tree t whose index lies
+ * outside its chain (its time is 0.0), INT32_MAX for none.  Unlike vgx_test_tree_shape_device such an index does reach the device:
+ * the kernel compares every index with the lengths of its two tables before it loads.  Offsets that decrease and an n_pre outside
+ * the shared table are refused before anything is uploaded. */
+int vgx_test_tau_node_times_device(int64_t n, const int64_t *node_off, const int32_t *node_ev, const int64_t *n_pre, int64_t n_pre_times,
+                                   const double *pre_times, const int64_t *step_off, const double *step_times, double *times, int32_t *bad,
+                                   char *errbuf, int64_t errcap);
+
 /* The same counts for many replicates of the last vgx_simulate_tau call (with the event log), on the device.
  * A tau replicate's chain is a list of weighted rows (num, type, haplotype, population, newHaplotype, newPopulation), six int64:
  * the events the model held when the call started (`prefix`, as vgx_get_tau_timelines takes it; its lockdown columns are not

@@ -170,6 +170,10 @@ class VgxTreeShapesIO(C.Structure):
                 ("status", _I), ("status_arg", _I), ("rng_out", C.POINTER(C.c_uint64)), ("passes", C.c_int64), ("ms", C.c_double * 4)]
 
 
+class VgxTauTreeShapesIO(C.Structure):   # VgxTreeShapesIO with six generator words per walk, three times and four kernel stages
+    _fields_ = VgxTreeShapesIO._fields_[:-1] + [("ms", C.c_double * 3), ("kernel_ms", C.c_double * 4)]
+
+
 # the columns of vgx_tree_shapes_io.stats and .lengths (vgx_tree_shape.h)
 TREE_SHAPE_STATS = ("tips", "internal", "cherries", "pitchforks", "sackin", "colless", "max_depth", "depth_sumsq", "ladder_nodes", "max_ladder",
                     "root_event", "last_tip_event")
@@ -380,6 +384,10 @@ SIGNATURES = {
     "vgx_get_tree_shapes": (C.c_int, [_H, C.POINTER(VgxTreeShapesIO)]),
     "vgx_test_tree_shape": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F, C.c_int64, _I, _F, C.c_char_p, C.c_int64]),
     "vgx_test_tree_shape_device": (C.c_int, [C.c_int64, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F, _I, _F, _I, C.c_char_p, C.c_int64]),
+    "vgx_get_tau_tree_shapes": (C.c_int, [_H, C.POINTER(VgxTauTreeShapesIO), C.POINTER(VgxTauGenealogyPrefix)]),
+    "vgx_test_tau_node_times": (C.c_int, [C.POINTER(C.c_int32), C.c_int64, C.c_int64, _F, C.c_int64, _F, _F, C.c_char_p, C.c_int64]),
+    "vgx_test_tau_node_times_device": (C.c_int, [C.c_int64, _I, C.POINTER(C.c_int32), _I, C.c_int64, _F, _I, _F, _F, C.POINTER(C.c_int32),
+                                                 C.c_char_p, C.c_int64]),
     "vgx_get_flows": (C.c_int, [_H, C.POINTER(VgxFlowsIO)]),
     "vgx_test_flows": (C.c_int, [_F, _I, _I, _I, _I, _I, C.c_int64, C.c_int64, C.c_int64, _F, C.c_int64, C.POINTER(C.c_int32), C.c_int64, C.c_int32,
                                  C.c_int64, C.c_int64, C.POINTER(C.c_int32), _I, _I, C.c_char_p, C.c_int64]),
@@ -1194,6 +1202,58 @@ def tree_shape_device(trees):
     if rc != VGX_OK:
         raise VgxError(rc, err.value.decode() or "vgx_test_tree_shape_device failed")
     return stats[:n], lengths[:n], status[:n]
+
+
+def _event_indices(node_ev):
+    ev = np.ascontiguousarray(node_ev, dtype=np.int64).ravel()
+    if len(ev) and (ev.min() < -2 ** 31 or ev.max() >= 2 ** 31):
+        raise ValueError("node_ev does not fit 32 bits")
+    return ev.astype(np.int32)
+
+
+def tau_node_times(node_ev, pre_times, step_times):
+    """The node times of one tree of a tau chain through ``vgx_test_tau_node_times``: the rule of vgx_tau_tree_shape.h on the host; no
+    GPU.  ``node_ev`` the nodes' event indices in a chain of ``len(pre_times)`` prefix events followed by ``len(step_times)`` own
+    steps.  Returns float64 [nodes]: 0.0 for a negative index, the prefix event's or the step's time otherwise; raises ``ValueError``
+    naming the node for an index beyond the chain."""
+    ev = _event_indices(node_ev)
+    pre = np.ascontiguousarray(pre_times, dtype=np.float64).ravel()
+    st = np.ascontiguousarray(step_times, dtype=np.float64).ravel()
+    times = np.zeros(len(ev), dtype=np.float64)
+    err = C.create_string_buffer(512)
+    rc = load_library().vgx_test_tau_node_times(ev.ctypes.data_as(C.POINTER(C.c_int32)), len(ev), len(pre), _p(pre), len(st), _p(st), _p(times),
+                                                err, 512)
+    if rc != VGX_OK:
+        raise ValueError(err.value.decode() or "vgx_test_tau_node_times failed")
+    return times
+
+
+def tau_node_times_device(trees, pre_times):
+    """The node times of given trees through the node-time kernel of ``Ensemble.tau_tree_shapes`` (``vgx_test_tau_node_times_device``,
+    one launch, no engine).  ``trees``: a sequence of (node_ev, n_pre, step_times): the tree's event indices, how many events of the
+    shared table ``pre_times`` its chain starts with (0: a replicate that restarted) and its own step times.  Returns (a list of
+    float64 arrays, one per tree, and bad int32 [n]: the lowest node whose index lies beyond its chain, whose time is 0.0, or
+    ``INT32_MAX``).  An index beyond the chain does reach the device: the kernel checks every index before it loads."""
+    pre = np.ascontiguousarray(pre_times, dtype=np.float64).ravel()
+    evs = [_event_indices(t[0]) for t in trees]
+    sts = [np.ascontiguousarray(t[2], dtype=np.float64).ravel() for t in trees]
+    n = len(evs)
+    node_off, step_off = np.zeros(n + 1, dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
+    node_off[1:], step_off[1:] = np.cumsum([len(x) for x in evs]), np.cumsum([len(x) for x in sts])
+    n_pre = np.ascontiguousarray([int(t[1]) for t in trees] + [0], dtype=np.int64)
+    ev = np.ascontiguousarray(np.concatenate(evs + [np.zeros(1, np.int32)]), dtype=np.int32)
+    st = np.ascontiguousarray(np.concatenate(sts + [np.zeros(1)]), dtype=np.float64)
+    times = np.zeros(len(ev), dtype=np.float64)
+    bad = np.zeros(n + 1, dtype=np.int32)
+    i32 = C.POINTER(C.c_int32)
+    err = C.create_string_buffer(512)
+    rc = load_library().vgx_test_tau_node_times_device(n, _p(node_off), ev.ctypes.data_as(i32), _p(n_pre), len(pre), _p(pre), _p(step_off), _p(st),
+                                                       _p(times), bad.ctypes.data_as(i32), err, 512)
+    if rc == 1:
+        raise ValueError(err.value.decode())
+    if rc != VGX_OK:
+        raise VgxError(rc, err.value.decode() or "vgx_test_tau_node_times_device failed")
+    return [times[node_off[t]:node_off[t + 1]].copy() for t in range(n)], bad[:n]
 
 
 def replay_flows(times, types, haplotypes, populations, newHaplotypes, newPopulations, popNum, hapNum, edges, variant_of, V, within=True,

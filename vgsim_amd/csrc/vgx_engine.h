@@ -30,6 +30,7 @@
 #include "vgx_lineages.h"
 #include "vgx_tree_events.h"   // (declares its launcher, vgxi_te_bin, itself)
 #include "vgx_tree_shape.h"    // (likewise: vgxi_ts_shape)
+#include "vgx_tau_tree_shape.h"   // (likewise: vgxi_tts_times)
 
 #pragma GCC visibility push(hidden)   // nothing here is part of the exported C ABI
 

@@ -226,6 +226,13 @@ hipError_t launch_canon(const VgxGtCanonLaunch *a, hipStream_t s) {
 // the canonicalise and counting launches as vgx_tau_lineages.hip shares them (declared in vgx_tau_lineages.h)
 extern "C" __attribute__((visibility("hidden"))) hipError_t vgxi_tg_canon(const VgxGtCanonLaunch *a, hipStream_t s) { return launch_canon(a, s); }
 
+// the walk launch as vgx_tau_tree_shapes.hip shares it
+extern "C" __attribute__((visibility("hidden"))) hipError_t vgxi_tg_walk(const VgxGtLaunch *a, hipStream_t s) {
+    if (a->n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(vgxtg_walk_kernel, dim3((unsigned)a->n), dim3(64), 0, s, *a);
+    return hipGetLastError();
+}
+
 extern "C" __attribute__((visibility("hidden"))) hipError_t vgxi_tg_count(const int64_t *mev, int64_t mev_cap, const int64_t *reps, const int64_t *n_rows,
                                                                           const int64_t *sC, int64_t n, int64_t *out, hipStream_t s) {
     if (n <= 0) return hipSuccess;

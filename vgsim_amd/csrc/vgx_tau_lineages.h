@@ -42,6 +42,8 @@ extern "C" hipError_t vgxi_tau_ln_walk(const VgxTauLnLaunch *a, hipStream_t s);
 // vgx_tau_genealogies.hip: the canonicalise launch and the counting launch (out[3 i ..]: sums of min(num, sCounter) over replicate
 // i's raw MUTATION rows, MIGRATION rows, rows that can push a lineage)
 extern "C" hipError_t vgxi_tg_canon(const VgxGtCanonLaunch *a, hipStream_t s);
+// (and its walk launch, for vgx_tau_tree_shapes.hip)
+extern "C" hipError_t vgxi_tg_walk(const VgxGtLaunch *a, hipStream_t s);
 extern "C" hipError_t vgxi_tg_count(const int64_t *mev, int64_t mev_cap, const int64_t *reps, const int64_t *n_rows, const int64_t *sC, int64_t n,
                                     int64_t *out, hipStream_t s);
 #pragma GCC visibility pop

@@ -1677,6 +1677,52 @@ class Ensemble:
         ts.passes, ts.kernel_ms, ts.clock_ms, ts.wall_ms = int(io.passes), (io.ms[0], io.ms[1]), io.ms[2], io.ms[3]
         return ts
 
+    def tau_tree_shapes(self, seed=None, replicates=None):
+        """``tree_shapes()`` for the replicates of the last ``simulate_tau(record_events=True)`` call (``vgx_get_tau_tree_shapes``):
+        the walk of ``tau_genealogies(seed, replicates)`` over the same chain with the same draws, status and six generator words
+        afterwards, then a kernel that turns every node's event index into its time and the shape kernel of ``tree_shapes()``, all on
+        the device: a tau chain needs no host clock, and nothing of a tree crosses to the host.  Returns a :class:`TreeShapes` whose
+        rows are what the tree of ``tau_genealogies(seed).replicate(r)`` gives.  A node's time is its prefix event's time or its
+        step's: all rows of a step share the step's time, so coalescences inside one step give branches of length 0.
+
+        ``seed`` and ``replicates`` as ``tau_genealogies()`` (``seed=None`` starts every walk at ``(seeds[r], attempt 0, 0 draws)``).
+        A replicate whose walk fails (fewer than two samples, a step of more than 8192 raw rows, ...) gets its status, zeros and NaN
+        and does not fail the call.  ``kernel_ms``: (canonicalise + walk, node times + shape); ``stage_ms``: the four kernels apart;
+        ``clock_ms``: the host's descriptors and step-time tables."""
+        self._check_tau_genealogy_call("tau_tree_shapes()")
+        eng, lib = self.engine, self.engine.lib
+        reps = self._selected_replicates(replicates)
+        n = len(reps)
+        if seed is not None and not np.isscalar(seed):
+            seeds = np.ascontiguousarray(seed, dtype=np.int64).ravel()
+            if len(seeds) != n:
+                raise ValueError("one seed per selected replicate: got %d for %d" % (len(seeds), n))
+        rng = np.zeros((max(n, 1), 6), dtype=np.uint64)
+        pos = (C.c_uint64 * 4)()
+        for i, r in enumerate(reps):
+            lib.vgx_rng_position(int(self.seeds[r]) if seed is None else int(seed) if np.isscalar(seed) else int(seeds[i]), 0, 0, C.byref(pos))
+            rng[i, :4] = list(pos)
+        pre = self._tau_genealogy_prefix_struct()
+        ts = TreeShapes()
+        ts.replicates = reps.copy()
+        ts.stats = np.zeros((max(n, 1), len(TreeShapes.STATS)), dtype=np.int64)
+        ts.lengths = np.zeros((max(n, 1), len(TreeShapes.LENGTHS)), dtype=np.float64)
+        per = {k: np.zeros(max(n, 1), dtype=np.int64) for k in ("status", "status_arg")}
+        rng_out = np.zeros((max(n, 1), 6), dtype=np.uint64)
+        u64 = C.POINTER(C.c_uint64)
+        io = _capi.VgxTauTreeShapesIO()
+        io.n, io.replicates, io.rng_state = n, _capi._p(reps), rng.ctypes.data_as(u64)
+        io.stats, io.lengths = _capi._p(ts.stats), _capi._p(ts.lengths)
+        io.status, io.status_arg, io.rng_out = _capi._p(per["status"]), _capi._p(per["status_arg"]), rng_out.ctypes.data_as(u64)
+        eng._check(lib.vgx_get_tau_tree_shapes(eng.handle, C.byref(io), C.byref(pre)))
+        ts.stats, ts.lengths = ts.stats[:n], ts.lengths[:n]
+        ts.status, ts.status_arg = per["status"][:n], per["status_arg"][:n]
+        ts.rng_raw = rng_out[:n]
+        ts.stage_ms = tuple(io.kernel_ms)
+        ts.passes, ts.kernel_ms = int(io.passes), (io.kernel_ms[0] + io.kernel_ms[1], io.kernel_ms[2] + io.kernel_ms[3])
+        ts.clock_ms, ts.wall_ms = io.ms[1], io.ms[2]
+        return ts
+
     def milestones(self, variants=None, thresholds=(), replicates=None):
         """Peaks, first passages and extinctions of every selected replicate of the last direct ``simulate(record_events=True)``
         call, per population, over all populations and per variant class, exact over every event and on the device
