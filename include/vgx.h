@@ -958,6 +958,84 @@ int vgx_test_tau_node_times_device(int64_t n, const int64_t *node_off, const int
                                    const double *pre_times, const int64_t *step_off, const double *step_times, double *times, int32_t *bad,
                                    char *errbuf, int64_t errcap);
 
+/* ---- mutation spectrum: clade sizes of every replicate's mutation records ------------------------------------------------- */
+/* One row of integers per selected replicate of the last vgx_simulate_direct call: the walk of vgx_get_genealogies
+ * (same draws, status and generator afterwards), then one kernel that reduces the walk's mutation records (mut_node, mut_AS, mut_DS,
+ * mut_site) over the tree where the walk left both.  The tree is that of vgx_tree_shapes_io (N = 2 sCounter - 1 nodes, parents of a
+ * higher id, none or two children).  clade[i] is the number of tips below node i; record k sits on the branch above mut_node[k], so
+ * its frequency in the sample is c_k = clade[mut_node[k]]; a record on the root has c = tips.  Every record is one mutation event
+ * (the infinite-sites reading of a model with recurrent mutation).  With S = the model's sites (0 .. 15; a model without sites has empty per-site blocks):
+ *   spectrum[r][s][b]        int64 [n][S][32]: records of site s with floor(log2 c) == b (bin 0: the singletons; bin 31 stays 0)
+ *   substitutions[r][s][a][d] int64 [n][S][4][4]: records by site, AS and DS
+ *   sums[r][s][k]            int64 [n][S][3]: 0 clade_sum (sum c), 1 clade_sumsq (sum c^2), 2 pair_sum (sum c (tips - c)); wrapping:
+ *                            clade_sumsq is below mutations * tips^2 and wraps only beyond 2^63 / tips^2 records (8 * 10^6 records
+ *                            on the root at 10^6 tips)
+ *   stats[r][k]              int64 [n][4]: 0 tips, 1 mutations, 2 fixed (records with c == tips), 3 max_clade (0 without records)
+ * Sums, counts and one maximum of integers: every path gives the same bits.  No node time is read and no host clock runs: only the
+ * rows, the status pairs and the generator words come to the host (vgx_clock_mismatches is not touched).  A replicate whose walk
+ * fails gets its status (as vgx_genealogies_io) and zeros and does not fail the call; a tree that breaks the structure gets status
+ * 13 (status_arg = the first offending node); a record with mut_node outside [0, N), mut_site outside [0, S) or mut_AS / mut_DS
+ * outside 0 .. 3 (no healthy walk leaves one) gives status 14 (status_arg = the lowest such record index) and zeros;
+ * vgx_genealogy_message has both texts.  There is no sizing call: the walk's record capacities are counted inside.  Passes are sized
+ * as vgx_get_genealogies sizes its passes, 16 bytes of workspace per node and the rows added (VGX_GENEALOGY_CHUNK_BYTES).
+ * Preconditions and refusals are those of vgx_get_tree_shapes, worded behind "vgx_get_mutation_spectrum: "; replicates must be
+ * distinct. */
+typedef struct vgx_mutation_spectrum_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    const uint64_t *rng_state;                   /* [n][4] PCG64 start of every walk */
+    int64_t *spectrum;                           /* [n][sites][32] */
+    int64_t *substitutions;                      /* [n][sites][4][4] */
+    int64_t *sums;                               /* [n][sites][3] */
+    int64_t *stats;                              /* [n][4] */
+    int64_t *status, *status_arg;                /* [n] */
+    uint64_t *rng_out;                           /* [n][4] generator state after the walk */
+    int64_t sites;                               /* out: the model's sites (the caller sizes the blocks with vgx_dims.sites) */
+    int64_t passes;                              /* out: device passes */
+    double ms[3];                                /* out: walk kernel, spectrum kernel (device time), whole call */
+} vgx_mutation_spectrum_io;
+int vgx_get_mutation_spectrum(vgx_engine *e, vgx_mutation_spectrum_io *io);
+/* The same rows for many replicates of the last vgx_simulate_tau call (with the event log).  The walk is that of
+ * vgx_get_tau_genealogies over the same chain (`prefix` as that call takes it): the same draws from rng_state, the same status and
+ * status_arg and the same six generator words afterwards.  Per pass (sized as vgx_get_tau_genealogies sizes its passes, 16 bytes of
+ * workspace per node and the rows added; VGX_GENEALOGY_CHUNK_BYTES): the canonicalise kernel, the one synchronisation that sizes the
+ * walk's workspace from its report, then the walk kernel and the spectrum kernel on one stream with no host step between them; no
+ * node-time kernel and no step times.  Rows, statuses 13 and 14 and a failed walk's row as vgx_mutation_spectrum_io; statuses
+ * 10 .. 12 as vgx_tau_genealogies_io.  Preconditions and refusals as vgx_get_tau_tree_shapes, worded behind
+ * "vgx_get_tau_mutation_spectrum: ". */
+typedef struct vgx_tau_mutation_spectrum_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    const uint64_t *rng_state;                   /* [n][6] start of every walk: PCG64 state hi, lo, increment hi, lo, has_uint32, uinteger */
+    int64_t *spectrum;                           /* [n][sites][32] */
+    int64_t *substitutions;                      /* [n][sites][4][4] */
+    int64_t *sums;                               /* [n][sites][3] */
+    int64_t *stats;                              /* [n][4] */
+    int64_t *status, *status_arg;                /* [n] */
+    uint64_t *rng_out;                           /* [n][6] generator state after the walk */
+    int64_t sites;                               /* out: the model's sites */
+    int64_t passes;                              /* out: device passes */
+    double ms[3];                                /* out: kernels (device time), host part (descriptors), whole call */
+    double kernel_ms[3];                         /* out: the canonicalise, walk and spectrum kernels of ms[0] apart */
+} vgx_tau_mutation_spectrum_io;
+int vgx_get_tau_mutation_spectrum(vgx_engine *e, vgx_tau_mutation_spectrum_io *io, const vgx_tau_genealogy_prefix *prefix);
+/* Test hook: the sequential sweep of vgx_mutation_spectrum.h (the definition) on one tree of `nodes` nodes and `muts` records on the
+ * host.  spectrum [sites][32], substitutions [sites][4][4], sums [sites][3], stats [4]; clade NULL or [nodes].  Refuses (message in
+ * errbuf) a tree that breaks the structure, naming the node, and a record outside the tree or the model, naming the record. */
+int vgx_test_mutation_spectrum(const int32_t *tree, int64_t nodes, const int32_t *mut_node, const int32_t *mut_AS, const int32_t *mut_DS,
+                               const int32_t *mut_site, int64_t muts, int64_t sites, int64_t *spectrum, int64_t *substitutions, int64_t *sums,
+                               int64_t *stats, int32_t *clade, char *errbuf, int64_t errcap);
+/* Test hook: n given trees (tree t: nodes node_off[t] .. node_off[t + 1] of `tree`, records mut_off[t] .. mut_off[t + 1] of the four
+ * record arrays) through the kernel of vgx_get_mutation_spectrum on the current device's default stream; no engine.  walk_status NULL,
+ * or [n][2] a walk status and its argument per tree: a tree whose status is not 0 is skipped as the calls skip a failed walk.
+ * spectrum [n][sites][32], substitutions [n][sites][4][4], sums [n][sites][3], stats [n][4], status [n][2] (0; the given walk status;
+ * 13 and the node; 14 and the record: the last three with an all-zero row); clade NULL or [node_off[n]] (zeros for a tree that was
+ * skipped, unspecified for one that got 13).  Offsets that decrease, node counts that are even or below 3 and parents outside i < tree[i] < N (-1 at the
+ * last node) are refused before anything is uploaded.  A bad RECORD does reach the device: the kernel compares every record with
+ * N, sites and 0 .. 3 before it uses it. */
+int vgx_test_mutation_spectrum_device(int64_t n, const int64_t *node_off, const int32_t *tree, const int64_t *mut_off, const int32_t *mut_node,
+                                      const int32_t *mut_AS, const int32_t *mut_DS, const int32_t *mut_site, int64_t sites,
+                                      const int64_t *walk_status, int64_t *spectrum, int64_t *substitutions, int64_t *sums, int64_t *stats,
+                                      int64_t *status, int32_t *clade, char *errbuf, int64_t errcap);
+
 /* The same counts for many replicates of the last vgx_simulate_tau call (with the event log), on the device.
  * A tau replicate's chain is a list of weighted rows (num, type, haplotype, population, newHaplotype, newPopulation), six int64:
  * the events the model held when the call started (`prefix`, as vgx_get_tau_timelines takes it; its lockdown columns are not

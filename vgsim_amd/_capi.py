@@ -181,6 +181,23 @@ TREE_SHAPE_LENGTHS = ("root_time", "last_tip_time", "length", "external_length",
 GW_BAD_TREE = 13   # the status of a replicate whose tree breaks the structure the shape sweep needs (status_arg: the node)
 
 
+class VgxMutationSpectrumIO(C.Structure):
+    _fields_ = [("n", C.c_int64), ("replicates", _I), ("rng_state", C.POINTER(C.c_uint64)), ("spectrum", _I), ("substitutions", _I),
+                ("sums", _I), ("stats", _I), ("status", _I), ("status_arg", _I), ("rng_out", C.POINTER(C.c_uint64)), ("sites", C.c_int64),
+                ("passes", C.c_int64), ("ms", C.c_double * 3)]
+
+
+class VgxTauMutationSpectrumIO(C.Structure):   # VgxMutationSpectrumIO with six generator words per walk and three kernel stages
+    _fields_ = VgxMutationSpectrumIO._fields_ + [("kernel_ms", C.c_double * 3)]
+
+
+# the columns of vgx_mutation_spectrum_io.sums and .stats (vgx_mutation_spectrum.h)
+MUTATION_SPECTRUM_BINS = 32
+MUTATION_SPECTRUM_SUMS = ("clade_sum", "clade_sumsq", "pair_sum")
+MUTATION_SPECTRUM_STATS = ("tips", "mutations", "fixed", "max_clade")
+GW_BAD_RECORD = 14   # the status of a replicate with a mutation record outside its tree or the model (status_arg: the record)
+
+
 class VgxFlowsIO(C.Structure):
     _fields_ = [("n", C.c_int64), ("replicates", _I), ("T", C.c_int64), ("edges", _F), ("V", C.c_int64), ("variant_of", C.POINTER(C.c_int32)),
                 ("within", C.c_int32), ("counts", C.POINTER(C.c_int32)), ("outside", _I), ("summary", C.POINTER(VgxTrajSummaryIO)),
@@ -385,6 +402,12 @@ SIGNATURES = {
     "vgx_test_tree_shape": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F, C.c_int64, _I, _F, C.c_char_p, C.c_int64]),
     "vgx_test_tree_shape_device": (C.c_int, [C.c_int64, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _F, _I, _F, _I, C.c_char_p, C.c_int64]),
     "vgx_get_tau_tree_shapes": (C.c_int, [_H, C.POINTER(VgxTauTreeShapesIO), C.POINTER(VgxTauGenealogyPrefix)]),
+    "vgx_get_mutation_spectrum": (C.c_int, [_H, C.POINTER(VgxMutationSpectrumIO)]),
+    "vgx_get_tau_mutation_spectrum": (C.c_int, [_H, C.POINTER(VgxTauMutationSpectrumIO), C.POINTER(VgxTauGenealogyPrefix)]),
+    "vgx_test_mutation_spectrum": (C.c_int, [C.POINTER(C.c_int32), C.c_int64] + [C.POINTER(C.c_int32)] * 4 + [C.c_int64, C.c_int64, _I, _I, _I, _I,
+                                             C.POINTER(C.c_int32), C.c_char_p, C.c_int64]),
+    "vgx_test_mutation_spectrum_device": (C.c_int, [C.c_int64, _I, C.POINTER(C.c_int32), _I] + [C.POINTER(C.c_int32)] * 4 +
+                                          [C.c_int64, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int32), C.c_char_p, C.c_int64]),
     "vgx_test_tau_node_times": (C.c_int, [C.POINTER(C.c_int32), C.c_int64, C.c_int64, _F, C.c_int64, _F, _F, C.c_char_p, C.c_int64]),
     "vgx_test_tau_node_times_device": (C.c_int, [C.c_int64, _I, C.POINTER(C.c_int32), _I, C.c_int64, _F, _I, _F, _F, C.POINTER(C.c_int32),
                                                  C.c_char_p, C.c_int64]),
@@ -1202,6 +1225,76 @@ def tree_shape_device(trees):
     if rc != VGX_OK:
         raise VgxError(rc, err.value.decode() or "vgx_test_tree_shape_device failed")
     return stats[:n], lengths[:n], status[:n]
+
+
+def _spectrum_arrays(tree, mut_node, mut_AS, mut_DS, mut_site):
+    t = np.ascontiguousarray(tree, dtype=np.int64).ravel()
+    cols = [np.ascontiguousarray(c, dtype=np.int64).ravel() for c in (mut_node, mut_AS, mut_DS, mut_site)]
+    if len({len(c) for c in cols}) != 1:
+        raise ValueError("mut_node, mut_AS, mut_DS and mut_site must have one entry per record")
+    for name, a in zip(("tree", "mut_node", "mut_AS", "mut_DS", "mut_site"), [t] + cols):
+        if len(a) and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise ValueError("%s does not fit 32 bits" % name)
+    return [t.astype(np.int32)] + [c.astype(np.int32) for c in cols]
+
+
+def mutation_spectrum(tree, mut_node, mut_AS, mut_DS, mut_site, sites, with_clade=False):
+    """The row of ``Ensemble.mutation_spectrum`` for one tree through ``vgx_test_mutation_spectrum``: the sequential sweep of
+    vgx_mutation_spectrum.h (the definition) on the host; no GPU.  ``tree`` parents (-1 at the last node, the root), one entry per
+    node; the four record columns, one entry per mutation record; ``sites`` the model's sites (0 .. 15).  Returns (spectrum int64
+    [sites, 32], substitutions [sites, 4, 4], sums [sites, 3], stats [4]) in the order of ``MUTATION_SPECTRUM_SUMS`` and
+    ``MUTATION_SPECTRUM_STATS``, with ``clade`` int32 [nodes] appended when ``with_clade``; raises ``ValueError`` naming the node of a
+    tree that is not binary in creation order, or the record that lies outside the tree or the model."""
+    t, mn, mA, mD, ms = _spectrum_arrays(tree, mut_node, mut_AS, mut_DS, mut_site)
+    S, i32 = int(sites), C.POINTER(C.c_int32)
+    if not 0 <= S <= 15:
+        raise ValueError("sites = %d (0 .. 15)" % S)
+    spectrum, subs = np.zeros((S, MUTATION_SPECTRUM_BINS), dtype=np.int64), np.zeros((S, 4, 4), dtype=np.int64)
+    sums, stats = np.zeros((S, len(MUTATION_SPECTRUM_SUMS)), dtype=np.int64), np.zeros(len(MUTATION_SPECTRUM_STATS), dtype=np.int64)
+    clade = np.zeros(max(len(t), 1), dtype=np.int32)
+    err = C.create_string_buffer(512)
+    rc = load_library().vgx_test_mutation_spectrum(t.ctypes.data_as(i32), len(t), mn.ctypes.data_as(i32), mA.ctypes.data_as(i32),
+                                                   mD.ctypes.data_as(i32), ms.ctypes.data_as(i32), len(mn), S, _p(spectrum), _p(subs), _p(sums),
+                                                   _p(stats), clade.ctypes.data_as(i32), err, 512)
+    if rc != VGX_OK:
+        raise ValueError(err.value.decode() or "vgx_test_mutation_spectrum failed")
+    return (spectrum, subs, sums, stats) + ((clade[:len(t)],) if with_clade else ())
+
+
+def mutation_spectrum_device(trees, sites, walk_status=None):
+    """The rows of given trees through the kernel of ``Ensemble.mutation_spectrum`` (``vgx_test_mutation_spectrum_device``, one launch,
+    no engine).  ``trees``: a sequence of (tree, mut_node, mut_AS, mut_DS, mut_site) as ``mutation_spectrum`` takes them; ``sites`` is
+    shared.  ``walk_status``: None, or [n, 2] a walk status and its argument per tree (a tree whose status is not 0 is skipped).
+    Returns (spectrum [n, sites, 32], substitutions [n, sites, 4, 4], sums [n, sites, 3], stats [n, 4], status [n, 2], clade: a list
+    of int32 arrays, one per tree).  ``status`` is 0, the given walk status, ``GW_BAD_TREE`` and the node, or ``GW_BAD_RECORD`` and the
+    lowest offending record; the last three come with an all-zero row.  Parents outside the tree are refused with ``ValueError``
+    before anything is uploaded; a bad record does reach the device."""
+    parts = [_spectrum_arrays(*tr) for tr in trees]
+    n, S, i32 = len(parts), int(sites), C.POINTER(C.c_int32)
+    if not 0 <= S <= 15:
+        raise ValueError("sites = %d (0 .. 15)" % S)
+    node_off, mut_off = np.zeros(n + 1, dtype=np.int64), np.zeros(n + 1, dtype=np.int64)
+    node_off[1:] = np.cumsum([len(p[0]) for p in parts])
+    mut_off[1:] = np.cumsum([len(p[1]) for p in parts])
+    cat = [np.ascontiguousarray(np.concatenate([p[k] for p in parts] + [np.zeros(1, np.int32)]), dtype=np.int32) for k in range(5)]
+    ws = None
+    if walk_status is not None:
+        ws = np.ascontiguousarray(walk_status, dtype=np.int64).reshape(n, 2)
+    spectrum, subs = np.zeros((max(n, 1), S, MUTATION_SPECTRUM_BINS), dtype=np.int64), np.zeros((max(n, 1), S, 4, 4), dtype=np.int64)
+    sums = np.zeros((max(n, 1), S, len(MUTATION_SPECTRUM_SUMS)), dtype=np.int64)
+    stats, status = np.zeros((max(n, 1), len(MUTATION_SPECTRUM_STATS)), dtype=np.int64), np.zeros((max(n, 1), 2), dtype=np.int64)
+    clade = np.zeros(int(node_off[n]) + 1, dtype=np.int32)
+    err = C.create_string_buffer(512)
+    rc = load_library().vgx_test_mutation_spectrum_device(n, _p(node_off), cat[0].ctypes.data_as(i32), _p(mut_off), cat[1].ctypes.data_as(i32),
+                                                          cat[2].ctypes.data_as(i32), cat[3].ctypes.data_as(i32), cat[4].ctypes.data_as(i32), S,
+                                                          _p(ws) if ws is not None else None, _p(spectrum), _p(subs), _p(sums), _p(stats),
+                                                          _p(status), clade.ctypes.data_as(i32), err, 512)
+    if rc == 1:
+        raise ValueError(err.value.decode())
+    if rc != VGX_OK:
+        raise VgxError(rc, err.value.decode() or "vgx_test_mutation_spectrum_device failed")
+    return (spectrum[:n], subs[:n], sums[:n], stats[:n], status[:n],
+            [clade[node_off[t]:node_off[t + 1]].copy() for t in range(n)])
 
 
 def _event_indices(node_ev):

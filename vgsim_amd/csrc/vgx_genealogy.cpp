@@ -25,6 +25,7 @@
 #include "vgx_lineages.h"
 #include "vgx_tree_events.h"
 #include "vgx_tree_shape.h"
+#include "vgx_mutation_spectrum.h"
 #include "vgx_logfact.h"
 #include "vgx_rng.h"
 
@@ -408,6 +409,9 @@ static std::string walk_message(int64_t status, int64_t arg) {
     case VGX_GW_BAD_TREE:
         return "vgx_get_tree_shapes: node " + std::to_string(arg) + " breaks the tree's structure (every node but the last has a parent of a higher id, " +
                "every node none or two children)";
+    case VGX_GW_BAD_RECORD:
+        return "vgx_get_mutation_spectrum: mutation record " + std::to_string(arg) + " lies outside the tree or the model (mut_node in [0, nodes), " +
+               "mut_site in [0, sites), mut_AS and mut_DS in 0 .. 3)";
     default: return "vgx_get_genealogy: walk status " + std::to_string(status);
     }
 }
@@ -618,5 +622,36 @@ extern "C" int vgx_test_tree_shape(const int32_t *tree, const int32_t *node_ev, 
                       w64.data(), w64.data() + N};
     bad = vgx_ts_sweep(tree, node_ev, times, nodes, w, stats, lengths);
     if (bad >= 0) return fail("vgx_test_tree_shape: node " + std::to_string(bad) + " has " + std::to_string(w.kids[bad]) + " children (none or two)");
+    return VGX_OK;
+}
+
+// ---- the mutation spectrum of one tree (vgx_mutation_spectrum.h) ---------------------------------------------------
+extern "C" int vgx_test_mutation_spectrum(const int32_t *tree, int64_t nodes, const int32_t *mut_node, const int32_t *mut_AS, const int32_t *mut_DS,
+                                          const int32_t *mut_site, int64_t muts, int64_t sites, int64_t *spectrum, int64_t *substitutions, int64_t *sums,
+                                          int64_t *stats, int32_t *clade, char *errbuf, int64_t errcap) {
+    auto fail = [&](const std::string &m) {
+        if (errbuf && errcap > 0) std::snprintf(errbuf, (size_t)errcap, "%s", m.c_str());
+        return VGX_ERR_ARG;
+    };
+    const std::string me = "vgx_test_mutation_spectrum: ";
+    if (!tree || !spectrum || !substitutions || !sums || !stats || muts < 0 || (muts > 0 && (!mut_node || !mut_AS || !mut_DS || !mut_site)))
+        return fail(me + "null argument");
+    if (sites < 0 || sites > VGX_MSP_SITES_MAX) return fail(me + "sites = " + std::to_string(sites) + " (0 .. 15)");
+    if (muts >= ((int64_t)1 << 30)) return fail(me + "too many records");
+    const int64_t bad = vgx_ts_check_parents(tree, nodes);
+    if (bad == nodes) return fail(me + std::to_string(nodes) + " nodes: an odd number, at least 3 (node " + std::to_string(nodes) + ")");
+    if (bad >= 0)
+        return fail(me + "the parent of node " + std::to_string(bad) + " is " + std::to_string(tree[bad]) + " (a higher id inside the tree, -1 at the last node)");
+    const size_t N = (size_t)nodes;
+    std::vector<int32_t> w32(4 * N);
+    const VgxMspWork w{w32.data(), w32.data() + N, w32.data() + 2 * N, w32.data() + 3 * N};
+    int64_t arg = 0;
+    const int st = vgx_ms_sweep(tree, nodes, w, mut_node, mut_AS, mut_DS, mut_site, muts, sites, spectrum, substitutions, sums, stats, &arg);
+    if (st == VGX_GW_BAD_TREE) return fail(me + "node " + std::to_string(arg) + " has " + std::to_string(w.kids[arg]) + " children (none or two)");
+    if (st == VGX_GW_BAD_RECORD)
+        return fail(me + "record " + std::to_string(arg) + " (node " + std::to_string(mut_node[arg]) + ", AS " + std::to_string(mut_AS[arg]) + ", DS " +
+                    std::to_string(mut_DS[arg]) + ", site " + std::to_string(mut_site[arg]) + ") lies outside the tree of " + std::to_string(nodes) +
+                    " nodes or the model of " + std::to_string(sites) + " sites");
+    if (clade) std::copy(w.clade, w.clade + N, clade);
     return VGX_OK;
 }

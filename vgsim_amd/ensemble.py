@@ -481,6 +481,116 @@ class TreeShapes:
         return self._ratio(self.external_length, self.length)
 
 
+class MutationSpectrum:
+    """What ``Ensemble.mutation_spectrum`` returns: the mutation records of every selected replicate's sampled tree reduced to their
+    clade sizes: the site-frequency spectrum in log2 bins, the substitution counts and the sums its scalar estimators are made of.
+
+    A record sits on the branch above its node; its frequency in the sample is ``c``, the number of tips below that node.  Every
+    record is one mutation event (the infinite-sites reading of a model with finitely many sites and recurrent mutation).  With
+    ``sites`` = S: ``spectrum`` [n, S, 32] int64, records of site s with ``floor(log2 c) == b``; ``substitutions`` [n, S, 4, 4],
+    records by site, ancestral and derived state; ``sums`` [n, S, 3] in the order of ``SUMS``: ``clade_sum`` (sum of c),
+    ``clade_sumsq`` (sum of c^2), ``pair_sum`` (sum of c (tips - c)); ``stats`` [n, 4] in the order of ``STATS``, each column also an
+    attribute: ``tips``, ``mutations``, ``fixed`` (records with c == tips: on the root), ``max_clade``.  All exact integers: the same
+    bits on every path.  ``replicates`` [n]; ``status``, ``status_arg``, ``ok``, ``message(i)``, ``rng_raw`` as
+    :class:`GenealogyBatch`: the row of a replicate whose walk failed holds zeros, and the derived values are NaN there and wherever
+    a denominator is 0.  ``passes``, ``kernel_ms`` (walk, spectrum), ``wall_ms``."""
+
+    SUMS = _capi.MUTATION_SPECTRUM_SUMS
+    STATS = _capi.MUTATION_SPECTRUM_STATS
+    BINS = _capi.MUTATION_SPECTRUM_BINS
+
+    def __getattr__(self, name):   # one attribute per column of stats
+        if name in MutationSpectrum.STATS:
+            return self.stats[:, MutationSpectrum.STATS.index(name)]
+        raise AttributeError(name)
+
+    @property
+    def ok(self):
+        return self.status == 0
+
+    def message(self, i):
+        """Text of row i's status: what ``Ensemble.genealogy`` raises for that replicate ('' when its walk succeeded)."""
+        return _capi.genealogy_message(int(self.status[i]), int(self.status_arg[i]))
+
+    def _ratio(self, num, den, where=None):
+        num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+        ok = self.ok & (den != 0) if where is None else self.ok & where
+        if num.ndim == 2:
+            den, ok = np.broadcast_to(den[:, None], num.shape), np.broadcast_to(ok[:, None], num.shape)
+        out = np.full(num.shape, np.nan, dtype=np.float64)
+        np.divide(num, den, out=out, where=ok)
+        return out
+
+    def _pairs(self):   # tips (tips - 1), as float64
+        t = self.tips.astype(np.float64)
+        return t * (t - 1.0)
+
+    @staticmethod
+    def bin_edges():
+        """The lower edges of the 32 bins, ``2 ** b``: bin b holds the clade sizes ``2 ** b <= c < 2 ** (b + 1)``."""
+        return 2 ** np.arange(MutationSpectrum.BINS, dtype=np.int64)
+
+    def per_site(self):
+        """Records per site, int64 [n, S]: ``spectrum.sum(-1)``."""
+        return self.spectrum.sum(axis=-1)
+
+    def singletons(self):
+        """Records below which lies one tip, int64 [n]: bin 0 over all sites."""
+        return self.spectrum[:, :, 0].sum(axis=-1)
+
+    def singleton_share(self):
+        """``singletons() / mutations``; NaN without records."""
+        return self._ratio(self.singletons(), self.mutations)
+
+    def substitution_matrix(self):
+        """Records by ancestral and derived state over all sites, int64 [n, 4, 4]."""
+        return self.substitutions.sum(axis=1)
+
+    def pi(self, per_site=False):
+        """Nucleotide diversity, the mean number of differences of two sampled tips: ``2 pair_sum / (tips (tips - 1))``, over all
+        sites [n], or per site [n, S] with ``per_site``."""
+        ps = self.sums[:, :, 2] if per_site else self.sums[:, :, 2].sum(axis=-1)   # (the integer sum first: exact)
+        return self._ratio(2.0 * ps.astype(np.float64), self._pairs())
+
+    def _harmonic(self):   # a1 = sum_{i < tips} 1 / i and a2 = sum_{i < tips} 1 / i^2 per row, each summed in ascending i
+        a1, a2 = np.zeros(len(self.status), dtype=np.float64), np.zeros(len(self.status), dtype=np.float64)
+        for k, t in enumerate(self.tips):
+            i = np.arange(1, max(int(t), 1), dtype=np.float64)
+            a1[k], a2[k] = np.cumsum(1.0 / i)[-1] if len(i) else 0.0, np.cumsum(1.0 / (i * i))[-1] if len(i) else 0.0
+        return a1, a2
+
+    def watterson(self):
+        """Watterson's theta: ``mutations / a1`` with ``a1 = sum_{i=1}^{tips-1} 1 / i``."""
+        return self._ratio(self.mutations, self._harmonic()[0])
+
+    def theta_h(self):
+        """Fay and Wu's theta_H: ``2 clade_sumsq / (tips (tips - 1))``."""
+        return self._ratio(2.0 * self.sums[:, :, 1].sum(axis=-1).astype(np.float64), self._pairs())
+
+    def fay_wu_h(self):
+        """Fay and Wu's H: ``pi() - theta_h()``."""
+        return self.pi() - self.theta_h()
+
+    def tajimas_d(self):
+        """Tajima's D: ``(pi - S / a1) / sqrt(e1 S + e2 S (S - 1))`` with S = ``mutations``, n = ``tips`` and
+        ``a1 = sum_{i<n} 1/i``, ``a2 = sum_{i<n} 1/i^2``, ``b1 = (n + 1) / (3 (n - 1))``, ``b2 = 2 (n^2 + n + 3) / (9 n (n - 1))``,
+        ``c1 = b1 - 1 / a1``, ``c2 = b2 - (n + 2) / (a1 n) + a2 / a1^2``, ``e1 = c1 / a1``, ``e2 = c2 / (a1^2 + a2)``.
+        NaN without records, below two tips and where the variance term is not positive."""
+        n, S = self.tips.astype(np.float64), self.mutations.astype(np.float64)
+        a1, a2 = self._harmonic()
+        with np.errstate(divide='ignore', invalid='ignore'):
+            b1 = (n + 1.0) / (3.0 * (n - 1.0))
+            b2 = 2.0 * (n * n + n + 3.0) / (9.0 * n * (n - 1.0))
+            c1 = b1 - 1.0 / a1
+            c2 = b2 - (n + 2.0) / (a1 * n) + a2 / (a1 * a1)
+            e1 = c1 / a1
+            e2 = c2 / (a1 * a1 + a2)
+            var = e1 * S + e2 * S * (S - 1.0)
+            good = np.isfinite(var) & (var > 0)
+            d = self.pi() - self.watterson()
+            return self._ratio(d, np.sqrt(np.where(good, var, 1.0)), where=good & np.isfinite(d))
+
+
 class Susceptibles:
     """What ``Ensemble.susceptibles`` returns: susceptible hosts per selected replicate, grid time, population and class of
     susceptibility groups.
@@ -1722,6 +1832,97 @@ class Ensemble:
         ts.passes, ts.kernel_ms = int(io.passes), (io.kernel_ms[0] + io.kernel_ms[1], io.kernel_ms[2] + io.kernel_ms[3])
         ts.clock_ms, ts.wall_ms = io.ms[1], io.ms[2]
         return ts
+
+    def _spectrum_blocks(self, io, n, reps, rng, words):
+        """The output blocks of a MutationSpectrum behind ``io`` (either of the two io structs); returns (ms, per, rng_out)."""
+        S = int(self.engine.dims.sites)
+        ms = MutationSpectrum()
+        ms.replicates, ms.sites = reps.copy(), S
+        ms.spectrum = np.zeros((max(n, 1), S, MutationSpectrum.BINS), dtype=np.int64)
+        ms.substitutions = np.zeros((max(n, 1), S, 4, 4), dtype=np.int64)
+        ms.sums = np.zeros((max(n, 1), S, len(MutationSpectrum.SUMS)), dtype=np.int64)
+        ms.stats = np.zeros((max(n, 1), len(MutationSpectrum.STATS)), dtype=np.int64)
+        per = {k: np.zeros(max(n, 1), dtype=np.int64) for k in ("status", "status_arg")}
+        rng_out = np.zeros((max(n, 1), words), dtype=np.uint64)
+        u64 = C.POINTER(C.c_uint64)
+        io.n, io.replicates, io.rng_state = n, _capi._p(reps), rng.ctypes.data_as(u64)
+        io.spectrum, io.substitutions, io.sums, io.stats = _capi._p(ms.spectrum), _capi._p(ms.substitutions), _capi._p(ms.sums), _capi._p(ms.stats)
+        io.status, io.status_arg, io.rng_out = _capi._p(per["status"]), _capi._p(per["status_arg"]), rng_out.ctypes.data_as(u64)
+        return ms, per, rng_out
+
+    def mutation_spectrum(self, seed=None, replicates=None):
+        """The site-frequency spectrum of the mutation records of every selected replicate of the last direct
+        ``simulate(record_events=True)`` call, on the device (``vgx_get_mutation_spectrum``): the walk of
+        ``genealogies(seed, replicates)`` with the same draws, status and generator afterwards, then one kernel that counts the tips
+        below every node and bins every mutation record by the clade below its branch.  No node time is needed, so no host clock
+        runs: only the rows cross to the host.  Returns a :class:`MutationSpectrum`, whose rows are what the ``tree`` and ``mut_*`` of
+        ``genealogies(seed).replicate(r)`` give.
+
+        ``seed`` and ``replicates`` as ``genealogies()``.  A replicate whose walk fails (fewer than two samples, lineages that never
+        coalesce, ...) gets its status and zeros and does not fail the call.  Direct chains only."""
+        if self._last_call is None:
+            raise ValueError("mutation_spectrum() needs a direct simulate(record_events=True) call first")
+        if self._last_call[0] != 'direct':
+            raise ValueError("mutation_spectrum() walks direct chains only: the last call was simulate_tau")
+        if not self._last_call[1]:
+            raise ValueError("mutation_spectrum() needs the event log: the last call had record_events=False")
+        eng = self.engine
+        reps = np.arange(self.R, dtype=np.int64) if replicates is None else np.ascontiguousarray(replicates, dtype=np.int64).ravel()
+        n = len(reps)
+        if n and (reps.min() < 0 or reps.max() >= self.R):
+            raise ValueError("replicate index out of range")
+        if len(np.unique(reps)) != n:
+            raise ValueError("replicates must be distinct")
+        counters = [eng.counters(int(r)) for r in reps]
+        for r, c in zip(reps, counters):
+            if c.ev_first_new != 0:
+                raise ValueError("replicate %d: its chain does not start in the last call's device log (the model held %d events "
+                                 "when the ensemble started)" % (r, c.ev_first_new))
+        rng = self._walk_starts(reps, counters, seed)
+        io = _capi.VgxMutationSpectrumIO()
+        ms, per, rng_out = self._spectrum_blocks(io, n, reps, rng, 4)
+        eng._check(eng.lib.vgx_get_mutation_spectrum(eng.handle, C.byref(io)))
+        ms.spectrum, ms.substitutions, ms.sums, ms.stats = ms.spectrum[:n], ms.substitutions[:n], ms.sums[:n], ms.stats[:n]
+        ms.status, ms.status_arg = per["status"][:n], per["status_arg"][:n]
+        ms.rng_raw = np.zeros((n, 6), dtype=np.uint64)
+        ms.rng_raw[:, :4] = rng_out[:n]
+        ms.passes, ms.kernel_ms, ms.wall_ms = int(io.passes), (io.ms[0], io.ms[1]), io.ms[2]
+        return ms
+
+    def tau_mutation_spectrum(self, seed=None, replicates=None):
+        """``mutation_spectrum()`` for the replicates of the last ``simulate_tau(record_events=True)`` call
+        (``vgx_get_tau_mutation_spectrum``): the walk of ``tau_genealogies(seed, replicates)`` over the same chain with the same
+        draws, status and six generator words afterwards, then the spectrum kernel of ``mutation_spectrum()``; nothing of a tree or
+        a record crosses to the host.  Returns a :class:`MutationSpectrum` whose rows are what the ``tree`` and ``mut_*`` of
+        ``tau_genealogies(seed).replicate(r)`` give.
+
+        ``seed`` and ``replicates`` as ``tau_genealogies()``.  A replicate whose walk fails gets its status and zeros and does not
+        fail the call.  ``kernel_ms``: (canonicalise + walk, spectrum); ``stage_ms``: the three kernels apart; ``host_ms``: the
+        host's descriptors."""
+        self._check_tau_genealogy_call("tau_mutation_spectrum()")
+        eng, lib = self.engine, self.engine.lib
+        reps = self._selected_replicates(replicates)
+        n = len(reps)
+        if seed is not None and not np.isscalar(seed):
+            seeds = np.ascontiguousarray(seed, dtype=np.int64).ravel()
+            if len(seeds) != n:
+                raise ValueError("one seed per selected replicate: got %d for %d" % (len(seeds), n))
+        rng = np.zeros((max(n, 1), 6), dtype=np.uint64)
+        pos = (C.c_uint64 * 4)()
+        for i, r in enumerate(reps):
+            lib.vgx_rng_position(int(self.seeds[r]) if seed is None else int(seed) if np.isscalar(seed) else int(seeds[i]), 0, 0, C.byref(pos))
+            rng[i, :4] = list(pos)
+        pre = self._tau_genealogy_prefix_struct()
+        io = _capi.VgxTauMutationSpectrumIO()
+        ms, per, rng_out = self._spectrum_blocks(io, n, reps, rng, 6)
+        eng._check(lib.vgx_get_tau_mutation_spectrum(eng.handle, C.byref(io), C.byref(pre)))
+        ms.spectrum, ms.substitutions, ms.sums, ms.stats = ms.spectrum[:n], ms.substitutions[:n], ms.sums[:n], ms.stats[:n]
+        ms.status, ms.status_arg = per["status"][:n], per["status_arg"][:n]
+        ms.rng_raw = rng_out[:n]
+        ms.stage_ms = tuple(io.kernel_ms)
+        ms.passes, ms.kernel_ms = int(io.passes), (io.kernel_ms[0] + io.kernel_ms[1], io.kernel_ms[2])
+        ms.host_ms, ms.wall_ms = io.ms[1], io.ms[2]
+        return ms
 
     def milestones(self, variants=None, thresholds=(), replicates=None):
         """Peaks, first passages and extinctions of every selected replicate of the last direct ``simulate(record_events=True)``
