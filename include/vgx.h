@@ -1036,6 +1036,88 @@ int vgx_test_mutation_spectrum_device(int64_t n, const int64_t *node_off, const 
                                       const int64_t *walk_status, int64_t *spectrum, int64_t *substitutions, int64_t *sums, int64_t *stats,
                                       int64_t *status, int32_t *clade, char *errbuf, int64_t errcap);
 
+/* ---- introductions: the transmission lineages of every replicate's tree ------------------------------------------------------- */
+/* One row of integers per selected replicate of the last vgx_simulate_direct call: the walk of vgx_get_genealogies
+ * (same draws, status and generator afterwards), then one kernel that reduces the walk's node labels (tree_pop) over the tree
+ * where the walk left both.  The tree is that of vgx_tree_shapes_io (N = 2 sCounter - 1 nodes, parents of a higher id, none or two
+ * children).  The branch above node i crosses when pop[tree[i]] != pop[i]: it is then one NET introduction from src = pop[tree[i]]
+ * into dst = pop[i] (moves along a branch that left no node are invisible: 0 -> 2 -> 1 counts as 0 -> 1, 0 -> 1 -> 0 not at all;
+ * the walk's migration records are not read).  clade[i] is the number of tips below node i, local[i] the number of those reached
+ * without passing a crossing branch.  The root and every node below a crossing branch head a transmission lineage of size
+ * local[i] (possibly 0) in population pop[i]; every tip lies in exactly one.  With P = the model's populations (1 .. 1024: a row
+ * holds P^2 + 39 P + 8 cells, 8.7 MB at 1024; more is refused with VGX_ERR_ARG):
+ *   tips_by_pop[r][p]       int64 [n][P]: tips by population
+ *   imports[r][src][dst]    int64 [n][P][P]: crossing branches by source and destination; the diagonal is 0
+ *   into[r][dst][k]         int64 [n][P][6] over the introductions into dst: 0 count, 1 clade_sum, 2 local_sum, 3 local_sumsq, 4 empty
+ *                           (local == 0), 5 max_local.  local_sumsq <= tips^2 <= 2^60 and clade_sum < 2 tips^2: nothing wraps on a
+ *                           tree the walk can make (tips <= 2^30); the sums are wrapping adds regardless
+ *   spectrum[r][dst][b]     int64 [n][P][32]: introductions into dst with floor(log2 local) == b, local >= 1 (bin 0: the singletons;
+ *                           the empty ones are counted in into alone; bin 31 stays 0)
+ *   stats[r][k]             int64 [n][8]: 0 tips, 1 introductions, 2 root_pop, 3 root_local, 4 max_local (the root's lineage
+ *                           included), 5 max_clade (over the introductions), 6 empty, 7 populations with at least one tip
+ * Counts, sums and maxima of integers: every path gives the same bits.  No node time is read and no host clock runs: only the
+ * rows, the status pairs, the walk's result and the generator words come to the host (vgx_clock_mismatches is not touched).  A
+ * replicate whose walk fails gets its status (as vgx_genealogies_io) and zeros and does not fail the call; a tree that breaks the
+ * structure gets status 13 (status_arg = the first offending node); a node label outside [0, P) (no healthy walk leaves one) gives
+ * status 15 (status_arg = the lowest such node) and zeros; the tree is judged before the labels; vgx_genealogy_message has both
+ * texts.  There is no sizing call: the walk's record capacities are counted inside.  Passes are sized as vgx_get_genealogies sizes
+ * its passes, 16 bytes of workspace per node and the rows added (VGX_GENEALOGY_CHUNK_BYTES).  Preconditions and refusals are those
+ * of vgx_get_mutation_spectrum, worded behind "vgx_get_introductions: "; replicates must be distinct. */
+typedef struct vgx_introductions_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    const uint64_t *rng_state;                   /* [n][4] PCG64 start of every walk */
+    int64_t *tips_by_pop;                        /* [n][pops] */
+    int64_t *imports;                            /* [n][pops][pops] */
+    int64_t *into;                               /* [n][pops][6] */
+    int64_t *spectrum;                           /* [n][pops][32] */
+    int64_t *stats;                              /* [n][8] */
+    int64_t *status, *status_arg;                /* [n] */
+    uint64_t *rng_out;                           /* [n][4] generator state after the walk */
+    int64_t pops;                                /* out: the model's populations (the caller sizes the blocks with vgx_dims.popNum) */
+    int64_t passes;                              /* out: device passes */
+    double ms[3];                                /* out: walk kernel, lineage kernel (device time), whole call */
+} vgx_introductions_io;
+int vgx_get_introductions(vgx_engine *e, vgx_introductions_io *io);
+/* The same rows for many replicates of the last vgx_simulate_tau call (with the event log).  The walk is that of
+ * vgx_get_tau_genealogies over the same chain (`prefix` as that call takes it): the same draws from rng_state, the same status and
+ * status_arg and the same six generator words afterwards.  Per pass (sized as vgx_get_tau_genealogies sizes its passes, 16 bytes of
+ * workspace per node and the rows added; VGX_GENEALOGY_CHUNK_BYTES): the canonicalise kernel, the one synchronisation that sizes the
+ * walk's workspace from its report, then the walk kernel and the lineage kernel on one stream with no host step between them; no
+ * node-time kernel and no step times.  Rows, statuses 13 and 15 and a failed walk's row as vgx_introductions_io; statuses
+ * 10 .. 12 as vgx_tau_genealogies_io.  Preconditions and refusals as vgx_get_tau_mutation_spectrum, worded behind
+ * "vgx_get_tau_introductions: ". */
+typedef struct vgx_tau_introductions_io {
+    int64_t n; const int64_t *replicates;        /* selected replicates, distinct */
+    const uint64_t *rng_state;                   /* [n][6] start of every walk: PCG64 state hi, lo, increment hi, lo, has_uint32, uinteger */
+    int64_t *tips_by_pop;                        /* [n][pops] */
+    int64_t *imports;                            /* [n][pops][pops] */
+    int64_t *into;                               /* [n][pops][6] */
+    int64_t *spectrum;                           /* [n][pops][32] */
+    int64_t *stats;                              /* [n][8] */
+    int64_t *status, *status_arg;                /* [n] */
+    uint64_t *rng_out;                           /* [n][6] generator state after the walk */
+    int64_t pops;                                /* out: the model's populations */
+    int64_t passes;                              /* out: device passes */
+    double ms[3];                                /* out: kernels (device time), host part (descriptors), whole call */
+    double kernel_ms[3];                         /* out: the canonicalise, walk and lineage kernels of ms[0] apart */
+} vgx_tau_introductions_io;
+int vgx_get_tau_introductions(vgx_engine *e, vgx_tau_introductions_io *io, const vgx_tau_genealogy_prefix *prefix);
+/* Test hook: the sequential sweep of vgx_introductions.h (the definition) on one tree of `nodes` nodes with labels `pop` on the
+ * host.  tips_by_pop [pops], imports [pops][pops], into [pops][6], spectrum [pops][32], stats [8]; clade and local NULL or [nodes].
+ * Refuses (message in errbuf) a tree that breaks the structure, naming the node, and a label outside [0, pops), naming the node. */
+int vgx_test_introductions(const int32_t *tree, const int32_t *pop, int64_t nodes, int64_t pops, int64_t *tips_by_pop, int64_t *imports,
+                           int64_t *into, int64_t *spectrum, int64_t *stats, int32_t *clade, int32_t *local, char *errbuf, int64_t errcap);
+/* Test hook: n given trees (tree t: nodes node_off[t] .. node_off[t + 1] of `tree` and `pop`) through the kernel of
+ * vgx_get_introductions on the current device's default stream; no engine.  walk_status NULL, or [n][2] a walk status and its
+ * argument per tree: a tree whose status is not 0 is skipped as the calls skip a failed walk.  tips_by_pop [n][pops], imports
+ * [n][pops][pops], into [n][pops][6], spectrum [n][pops][32], stats [n][8], status [n][2] (0; the given walk status; 13 and the
+ * node; 15 and the node: the last three with an all-zero row).  Offsets that decrease, node counts that are even or below 3 and
+ * parents outside i < tree[i] < N (-1 at the last node) are refused before anything is uploaded.  A bad LABEL does reach the device:
+ * the kernel compares every label with pops before anything indexes by it. */
+int vgx_test_introductions_device(int64_t n, const int64_t *node_off, const int32_t *tree, const int32_t *pop, int64_t pops,
+                                  const int64_t *walk_status, int64_t *tips_by_pop, int64_t *imports, int64_t *into, int64_t *spectrum,
+                                  int64_t *stats, int64_t *status, char *errbuf, int64_t errcap);
+
 /* The same counts for many replicates of the last vgx_simulate_tau call (with the event log), on the device.
  * A tau replicate's chain is a list of weighted rows (num, type, haplotype, population, newHaplotype, newPopulation), six int64:
  * the events the model held when the call started (`prefix`, as vgx_get_tau_timelines takes it; its lockdown columns are not

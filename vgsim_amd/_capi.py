@@ -198,6 +198,24 @@ MUTATION_SPECTRUM_STATS = ("tips", "mutations", "fixed", "max_clade")
 GW_BAD_RECORD = 14   # the status of a replicate with a mutation record outside its tree or the model (status_arg: the record)
 
 
+class VgxIntroductionsIO(C.Structure):
+    _fields_ = [("n", C.c_int64), ("replicates", _I), ("rng_state", C.POINTER(C.c_uint64)), ("tips_by_pop", _I), ("imports", _I), ("into", _I),
+                ("spectrum", _I), ("stats", _I), ("status", _I), ("status_arg", _I), ("rng_out", C.POINTER(C.c_uint64)), ("pops", C.c_int64),
+                ("passes", C.c_int64), ("ms", C.c_double * 3)]
+
+
+class VgxTauIntroductionsIO(C.Structure):   # VgxIntroductionsIO with six generator words per walk and three kernel stages
+    _fields_ = VgxIntroductionsIO._fields_ + [("kernel_ms", C.c_double * 3)]
+
+
+# the columns of vgx_introductions_io.into and .stats (vgx_introductions.h)
+INTRODUCTIONS_BINS = 32
+INTRODUCTIONS_INTO = ("count", "clade_sum", "local_sum", "local_sumsq", "empty", "max_local")
+INTRODUCTIONS_STATS = ("tips", "introductions", "root_pop", "root_local", "max_local", "max_clade", "empty", "pops_with_tips")
+INTRODUCTIONS_POPS_MAX = 1024
+GW_BAD_LABEL = 15   # the status of a replicate with a node label outside the model (status_arg: the node)
+
+
 class VgxFlowsIO(C.Structure):
     _fields_ = [("n", C.c_int64), ("replicates", _I), ("T", C.c_int64), ("edges", _F), ("V", C.c_int64), ("variant_of", C.POINTER(C.c_int32)),
                 ("within", C.c_int32), ("counts", C.POINTER(C.c_int32)), ("outside", _I), ("summary", C.POINTER(VgxTrajSummaryIO)),
@@ -408,6 +426,12 @@ SIGNATURES = {
                                              C.POINTER(C.c_int32), C.c_char_p, C.c_int64]),
     "vgx_test_mutation_spectrum_device": (C.c_int, [C.c_int64, _I, C.POINTER(C.c_int32), _I] + [C.POINTER(C.c_int32)] * 4 +
                                           [C.c_int64, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int32), C.c_char_p, C.c_int64]),
+    "vgx_get_introductions": (C.c_int, [_H, C.POINTER(VgxIntroductionsIO)]),
+    "vgx_get_tau_introductions": (C.c_int, [_H, C.POINTER(VgxTauIntroductionsIO), C.POINTER(VgxTauGenealogyPrefix)]),
+    "vgx_test_introductions": (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64, C.c_int64, _I, _I, _I, _I, _I,
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_char_p, C.c_int64]),
+    "vgx_test_introductions_device": (C.c_int, [C.c_int64, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64, _I, _I, _I, _I, _I, _I, _I,
+                                                C.c_char_p, C.c_int64]),
     "vgx_test_tau_node_times": (C.c_int, [C.POINTER(C.c_int32), C.c_int64, C.c_int64, _F, C.c_int64, _F, _F, C.c_char_p, C.c_int64]),
     "vgx_test_tau_node_times_device": (C.c_int, [C.c_int64, _I, C.POINTER(C.c_int32), _I, C.c_int64, _F, _I, _F, _F, C.POINTER(C.c_int32),
                                                  C.c_char_p, C.c_int64]),
@@ -1295,6 +1319,72 @@ def mutation_spectrum_device(trees, sites, walk_status=None):
         raise VgxError(rc, err.value.decode() or "vgx_test_mutation_spectrum_device failed")
     return (spectrum[:n], subs[:n], sums[:n], stats[:n], status[:n],
             [clade[node_off[t]:node_off[t + 1]].copy() for t in range(n)])
+
+
+def _labelled_tree(tree, pop):
+    t, p = np.ascontiguousarray(tree, dtype=np.int64).ravel(), np.ascontiguousarray(pop, dtype=np.int64).ravel()
+    if len(t) != len(p):
+        raise ValueError("tree and pop must have one entry per node")
+    for name, a in (("tree", t), ("pop", p)):
+        if len(a) and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise ValueError("%s does not fit 32 bits" % name)
+    return t.astype(np.int32), p.astype(np.int32)
+
+
+def _introductions_blocks(n, P):
+    return (np.zeros((n, P), dtype=np.int64), np.zeros((n, P, P), dtype=np.int64), np.zeros((n, P, len(INTRODUCTIONS_INTO)), dtype=np.int64),
+            np.zeros((n, P, INTRODUCTIONS_BINS), dtype=np.int64), np.zeros((n, len(INTRODUCTIONS_STATS)), dtype=np.int64))
+
+
+def introductions(tree, pop, pops, with_nodes=False):
+    """The row of ``Ensemble.introductions`` for one tree through ``vgx_test_introductions``: the sequential sweep of
+    vgx_introductions.h (the definition) on the host; no GPU.  ``tree`` parents (-1 at the last node, the root) and ``pop`` the
+    population label, one entry per node; ``pops`` the model's populations (1 .. 1024).  Returns (tips_by_pop int64 [pops], imports
+    [pops, pops] by (source, destination), into [pops, 6], spectrum [pops, 32], stats [8]) in the order of ``INTRODUCTIONS_INTO`` and
+    ``INTRODUCTIONS_STATS``, with ``clade`` and ``local`` int32 [nodes] appended when ``with_nodes``; raises ``ValueError`` naming the
+    node of a tree that is not binary in creation order, or the node whose label lies outside the model."""
+    t, p = _labelled_tree(tree, pop)
+    P, i32 = int(pops), C.POINTER(C.c_int32)
+    if not 1 <= P <= INTRODUCTIONS_POPS_MAX:
+        raise ValueError("populations = %d (1 .. %d)" % (P, INTRODUCTIONS_POPS_MAX))
+    blocks = [b[0] for b in _introductions_blocks(1, P)]
+    clade, local = np.zeros(max(len(t), 1), dtype=np.int32), np.zeros(max(len(t), 1), dtype=np.int32)
+    err = C.create_string_buffer(512)
+    rc = load_library().vgx_test_introductions(t.ctypes.data_as(i32), p.ctypes.data_as(i32), len(t), P, *[_p(b) for b in blocks],
+                                               clade.ctypes.data_as(i32), local.ctypes.data_as(i32), err, 512)
+    if rc != VGX_OK:
+        raise ValueError(err.value.decode() or "vgx_test_introductions failed")
+    return tuple(blocks) + ((clade[:len(t)], local[:len(t)]) if with_nodes else ())
+
+
+def introductions_device(trees, pops, walk_status=None):
+    """The rows of given trees through the kernel of ``Ensemble.introductions`` (``vgx_test_introductions_device``, one launch, no
+    engine).  ``trees``: a sequence of (tree, pop) as ``introductions`` takes them; ``pops`` is shared.  ``walk_status``: None, or
+    [n, 2] a walk status and its argument per tree (a tree whose status is not 0 is skipped).  Returns (tips_by_pop [n, pops],
+    imports [n, pops, pops], into [n, pops, 6], spectrum [n, pops, 32], stats [n, 8], status [n, 2]).  ``status`` is 0, the given
+    walk status, ``GW_BAD_TREE`` and the node, or ``GW_BAD_LABEL`` and the lowest offending node; the last three come with an
+    all-zero row.  Parents outside the tree are refused with ``ValueError`` before anything is uploaded; a bad label does reach the
+    device."""
+    parts = [_labelled_tree(*tr) for tr in trees]
+    n, P, i32 = len(parts), int(pops), C.POINTER(C.c_int32)
+    if not 1 <= P <= INTRODUCTIONS_POPS_MAX:
+        raise ValueError("populations = %d (1 .. %d)" % (P, INTRODUCTIONS_POPS_MAX))
+    node_off = np.zeros(n + 1, dtype=np.int64)
+    node_off[1:] = np.cumsum([len(p[0]) for p in parts])
+    cat = [np.ascontiguousarray(np.concatenate([p[k] for p in parts] + [np.zeros(1, np.int32)]), dtype=np.int32) for k in range(2)]
+    ws = None
+    if walk_status is not None:
+        ws = np.ascontiguousarray(walk_status, dtype=np.int64).reshape(n, 2)
+    blocks = _introductions_blocks(max(n, 1), P)
+    status = np.zeros((max(n, 1), 2), dtype=np.int64)
+    err = C.create_string_buffer(512)
+    rc = load_library().vgx_test_introductions_device(n, _p(node_off), cat[0].ctypes.data_as(i32), cat[1].ctypes.data_as(i32), P,
+                                                      _p(ws) if ws is not None else None, *[_p(b) for b in blocks], _p(status), err, 512)
+    if rc == 1:
+        raise ValueError(err.value.decode())
+    if rc != VGX_OK:
+        raise VgxError(rc, err.value.decode() or "vgx_test_introductions_device failed")
+    return tuple(b[:n] for b in blocks) + (status[:n],)
 
 
 def _event_indices(node_ev):

@@ -7,6 +7,7 @@
 // (this file is compiled with -ffp-contract=off as well); launches the kernels.
 #include "vgx_engine.h"
 #include "vgx_mutation_spectrum.h"   // (declares its launcher, vgxi_ms_spectrum, itself)
+#include "vgx_introductions.h"       // (and vgxi_in_lineages)
 #include "vgx_rng.h"
 
 static std::string g_create_error;
@@ -2771,6 +2772,196 @@ extern "C" int vgx_get_mutation_spectrum(vgx_engine *e, vgx_mutation_spectrum_io
             // (a walk that stopped keeps its status: the kernel copies it; a walk that used more records than it counted cannot be)
             if (res[(size_t)(j * 5)] == VGX_GW_OK && res[(size_t)(j * 5 + 3)] > dp[(size_t)j].mut_cap)
                 return fail(e, VGX_ERR_ARG, me + "replicate " + std::to_string(dp[(size_t)j].rep) + ": the walk reports more mutation records than its capacity");
+            io->status[i0 + j] = st2[(size_t)(2 * j)];
+            io->status_arg[i0 + j] = st2[(size_t)(2 * j + 1)];
+        }
+        io->passes += 1;
+        i0 = i1;
+    }
+    io->ms[2] = since(t_call);
+    return VGX_OK;
+}
+
+// ---- transmission lineages of every tree (vgx_introductions.hip, vgx_introductions.h) -------------------------------
+// The frame of vgx_get_mutation_spectrum: the lineage kernel needs the parents and the node labels alone, so walk and lineages run
+// on the stream with no host step between them and only the rows, the status pairs, the walk's result and the generator words
+// come to the host.
+extern "C" int vgx_get_introductions(vgx_engine *e, vgx_introductions_io *io) {
+    if (!e || !io || io->n < 0 ||
+        (io->n > 0 && (!io->replicates || !io->rng_state || !io->tips_by_pop || !io->imports || !io->into || !io->spectrum || !io->stats ||
+                       !io->status || !io->status_arg || !io->rng_out)))
+        return VGX_ERR_ARG;
+    const std::string me = "vgx_get_introductions: ";
+    const auto t_call = std::chrono::steady_clock::now();
+    auto since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
+    io->passes = 0;
+    io->pops = e->d.popNum;
+    io->ms[0] = io->ms[1] = io->ms[2] = 0.0;
+    if (!e->sc_host_valid || !e->dev_state_valid) return fail(e, VGX_ERR_ARG, me + "no direct simulate call yet");
+    if (e->last_was_tau) return fail(e, VGX_ERR_ARG, me + "the last call was vgx_simulate_tau (direct chains only)");
+    if (!e->call_recorded) return fail(e, VGX_ERR_ARG, me + "the last call did not record events");
+    const int64_t n = io->n, P = e->d.popNum, H = e->d.hapNum;
+    if (P < 1 || P > VGX_IN_POPS_MAX)
+        return fail(e, VGX_ERR_ARG, me + "the model has " + std::to_string(P) + " populations (1 .. " + std::to_string(VGX_IN_POPS_MAX) + ": a row holds popNum^2 cells)");
+    std::vector<int64_t> n_ev((size_t)n), sC((size_t)n);
+    {
+        std::vector<char> seen((size_t)e->R, 0);
+        for (int64_t i = 0; i < n; i++) {
+            const int64_t r = io->replicates[i];
+            if (r < 0 || r >= e->R) return fail(e, VGX_ERR_ARG, me + "replicate index out of range");
+            if (seen[(size_t)r]) return fail(e, VGX_ERR_ARG, me + "replicates must be distinct");
+            seen[(size_t)r] = 1;
+            const VgxRepScalars &s = e->sc_host[(size_t)r];
+            const int64_t first = s.restarts > 0 ? 0 : ((size_t)r < e->call_ev0.size() ? e->call_ev0[(size_t)r] : e->ev_ptr0);
+            if (first != 0 || e->ev_base != 0)
+                return fail(e, VGX_ERR_ARG, me + "the chain of replicate " + std::to_string(r) +
+                                                " does not start in the last call's device log (events.ptr was not 0 at its start)");
+            if (s.ev_ptr < 0 || s.ev_ptr > e->evcap || s.ev_ptr >= ((int64_t)1 << 30))
+                return fail(e, VGX_ERR_ARG, me + "event range of replicate " + std::to_string(r) + " outside the device log");
+            n_ev[(size_t)i] = s.ev_ptr;
+            sC[(size_t)i] = s.sCounter;
+        }
+    }
+    if (n == 0) {
+        io->ms[2] = since(t_call);
+        return VGX_OK;
+    }
+    HIPCHECK(e, hipSetDevice(e->device));
+    const int32_t *log = (const int32_t *)e->r_evcols.p;
+    auto up8 = [](int64_t b) { return (b + 255) / 256 * 256; };
+    hipError_t er;
+    // the MUTATION and MIGRATION events of every chain: the record capacities the walk needs (what the sizing call of vgx_get_genealogies counts)
+    std::vector<int64_t> cnt((size_t)n * 2);
+    {
+        char *cws = nullptr;
+        const int64_t o_n = up8(n * 8), o_out = o_n + up8(n * 8);
+        if ((er = hipMalloc((void **)&cws, (size_t)(o_out + up8(n * 16)))) != hipSuccess) return fail(e, VGX_ERR_HIP, me + "hipMalloc: " + hipGetErrorString(er));
+        std::unique_ptr<char, void (*)(char *)> chold(cws, [](char *p) { (void)hipFree(p); });
+        HIPCHECK(e, hipMemcpyAsync(cws, io->replicates, (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(cws + o_n, n_ev.data(), (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, vgxi_gw_count(log, e->evcap, (const int64_t *)cws, (const int64_t *)(cws + o_n), n, (int64_t *)(cws + o_out), e->stream));
+        HIPCHECK(e, hipMemcpyAsync(cnt.data(), cws + o_out, (size_t)n * 16, hipMemcpyDeviceToHost, e->stream));
+        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(e, VGX_ERR_HIP, me + "counting pass: " + hipGetErrorString(er));
+    }
+    // the walk reads the 8-byte counts of the final occupancy lists
+    if (!e->counts64_valid) {
+        HIPCHECK(e, vgxi_launch_counts64(e->dr.lcnt32, e->dr.lcnt, e->R * P * e->cap, e->stream));
+        HIPCHECK(e, hipStreamSynchronize(e->stream));
+        e->counts64_valid = true;
+    }
+    // per-replicate workspace and outputs (elements), and the passes: every pass holds at most `share` bytes
+    const int64_t row_cells = vgx_in_row_cells(P) + 2;
+    std::vector<VgxGwDesc> desc((size_t)n);
+    std::vector<int64_t> bytes((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        VgxGwDesc &d = desc[(size_t)i];
+        const int64_t nodes = sC[(size_t)i] >= 2 ? 2 * sC[(size_t)i] - 1 : 0;
+        d.rep = io->replicates[i];
+        d.n_ev = n_ev[(size_t)i];
+        d.sCounter = sC[(size_t)i];
+        d.tsize = d.sCounter >= 2 ? vgx_gw_table_size(d.n_ev, P * H) : 0;
+        d.arena_cap = d.sCounter >= 2 ? d.n_ev : 0;
+        d.mut_cap = cnt[(size_t)(2 * i)];
+        d.mig_cap = cnt[(size_t)(2 * i + 1)] + nodes;
+        for (int k = 0; k < 4; k++) d.rng[k] = io->rng_state[i * 4 + k];
+        bytes[(size_t)i] = d.tsize * 28 + d.arena_cap * 4 + nodes * (12 + VGX_IN_NODE_BYTES) + d.mut_cap * 20 + d.mig_cap * 16 +
+                           (int64_t)(sizeof(VgxGwDesc) + sizeof(VgxInDesc)) + 72 + 8 * row_cells;
+    }
+    size_t free_b = 0, total_b = 0;
+    HIPCHECK(e, hipMemGetInfo(&free_b, &total_b));
+    int64_t share = (int64_t)(free_b / 2);
+    if (const char *cb = getenv("VGX_GENEALOGY_CHUNK_BYTES")) share = std::min<int64_t>(share, std::max<int64_t>(atoll(cb), 1));
+    struct Events {   // walk and lineage kernel, timed apart
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+        ~Events() { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); }
+    } tm;
+    for (hipEvent_t &x : tm.ev) HIPCHECK(e, hipEventCreate(&x));
+    int64_t i0 = 0;
+    while (i0 < n) {
+        int64_t i1 = i0, sum = 0;
+        while (i1 < n && (i1 == i0 || sum + bytes[(size_t)i1] <= share)) sum += bytes[(size_t)i1++];
+        const int64_t m = i1 - i0;
+        int64_t T = 0, A = 0, N = 0, M = 0, G = 0;
+        std::vector<VgxGwDesc> dp(desc.begin() + i0, desc.begin() + i1);
+        std::vector<VgxInDesc> md((size_t)m);
+        for (int64_t j = 0; j < m; j++) {
+            VgxGwDesc &d = dp[(size_t)j];
+            const int64_t nodes = d.sCounter >= 2 ? 2 * d.sCounter - 1 : 0;
+            d.tab_off = T; d.arena_off = A; d.node_off = N; d.mut_off = M; d.mig_off = G;
+            md[(size_t)j] = VgxInDesc{N, nodes};
+            T += d.tsize; A += d.arena_cap; N += nodes; M += d.mut_cap; G += d.mig_cap;
+        }
+        // one allocation: the walk's of vgx_get_genealogies [desc | res | rng | key | cnt | base | len | lcap | arena | node x3 | mut x5 | mig x4],
+        // then [tree descs | kids, got, n, ln | tips_by_pop | imports | into | spectrum | stats | status]
+        const int64_t o_desc = 0, o_res = o_desc + up8(m * (int64_t)sizeof(VgxGwDesc)), o_rng = o_res + up8(m * 40),
+                      o_key = o_rng + up8(m * 32), o_cnt = o_key + up8(T * 8), o_base = o_cnt + up8(T * 8), o_len = o_base + up8(T * 4),
+                      o_lcap = o_len + up8(T * 4), o_arena = o_lcap + up8(T * 4), o_out = o_arena + up8(A * 4),
+                      o_md = o_out + up8((3 * N + 5 * M + 4 * G) * 4), o_w32 = o_md + up8(m * (int64_t)sizeof(VgxInDesc)),
+                      o_tp = o_w32 + up8(4 * N * 4), o_imp = o_tp + up8(m * P * 8), o_into = o_imp + up8(m * P * P * 8),
+                      o_sp = o_into + up8(m * P * VGX_IN_INTO * 8), o_stats = o_sp + up8(m * P * VGX_IN_BINS * 8),
+                      o_status = o_stats + up8(m * VGX_IN_STATS * 8), total = o_status + up8(m * 16);
+        char *ws = nullptr;
+        if ((er = hipMalloc((void **)&ws, (size_t)total)) != hipSuccess)
+            return fail(e, VGX_ERR_HIP, me + "hipMalloc of " + std::to_string(total) + " bytes: " + hipGetErrorString(er));
+        std::unique_ptr<char, void (*)(char *)> hold(ws, [](char *p) { (void)hipFree(p); });
+        VgxGwLaunch a{};
+        a.n = m;
+        a.desc = (const VgxGwDesc *)(ws + o_desc);
+        a.log = log; a.evcap = e->evcap;
+        a.nocc = e->dr.nocc; a.lhap = e->dr.lhap; a.lcnt = e->dr.lcnt;
+        a.P = P; a.H = H; a.cap = e->cap;
+        a.key = (int64_t *)(ws + o_key); a.cnt = (int64_t *)(ws + o_cnt);
+        a.base = (int32_t *)(ws + o_base); a.len = (int32_t *)(ws + o_len); a.lcap = (int32_t *)(ws + o_lcap);
+        a.arena = (int32_t *)(ws + o_arena);
+        int32_t *o32 = (int32_t *)(ws + o_out);
+        a.tree = o32; a.tree_pop = o32 + N; a.node_ev = o32 + 2 * N;
+        int32_t *mu = o32 + 3 * N;
+        a.mut_node = mu; a.mut_AS = mu + M; a.mut_DS = mu + 2 * M; a.mut_site = mu + 3 * M; a.mut_ev = mu + 4 * M;
+        int32_t *mg = mu + 5 * M;
+        a.mig_node = mg; a.mig_old = mg + G; a.mig_new = mg + 2 * G; a.mig_ev = mg + 3 * G;
+        a.res = (int64_t *)(ws + o_res);
+        a.rng_out = (uint64_t *)(ws + o_rng);
+        VgxInLaunch b{};
+        b.n = m;
+        b.desc = (const VgxInDesc *)(ws + o_md);
+        b.res = a.res;
+        b.tree = a.tree; b.pop = a.tree_pop;
+        b.P = P;
+        int32_t *w32 = (int32_t *)(ws + o_w32);
+        b.w = VgxInWork{w32, w32 + N, w32 + 2 * N, w32 + 3 * N};
+        b.tips_by_pop = (int64_t *)(ws + o_tp); b.imports = (int64_t *)(ws + o_imp); b.into = (int64_t *)(ws + o_into);
+        b.spectrum = (int64_t *)(ws + o_sp); b.stats = (int64_t *)(ws + o_stats); b.status = (int64_t *)(ws + o_status);
+        // descriptors up, the rows zeroed (they are counted in place), the walk in wave layout, the lineage kernel: no host step between them
+        HIPCHECK(e, hipMemcpyAsync(ws + o_desc, dp.data(), (size_t)m * sizeof(VgxGwDesc), hipMemcpyHostToDevice, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(ws + o_md, md.data(), (size_t)m * sizeof(VgxInDesc), hipMemcpyHostToDevice, e->stream));
+        if (T > 0) HIPCHECK(e, hipMemsetAsync(a.key, 0xFF, (size_t)T * 8, e->stream));   // every slot empty (-1)
+        HIPCHECK(e, hipMemsetAsync(ws + o_tp, 0, (size_t)(o_stats - o_tp), e->stream));
+        HIPCHECK(e, hipEventRecord(tm.ev[0], e->stream));
+        HIPCHECK(e, vgxi_gw_walk(&a, 1, e->stream));
+        HIPCHECK(e, hipEventRecord(tm.ev[1], e->stream));
+        HIPCHECK(e, vgxi_in_lineages(&b, e->stream));
+        HIPCHECK(e, hipEventRecord(tm.ev[2], e->stream));
+        std::vector<int64_t> st2((size_t)m * 2), res((size_t)m * 5);
+        HIPCHECK(e, hipMemcpyAsync(io->tips_by_pop + i0 * P, b.tips_by_pop, (size_t)(m * P) * 8, hipMemcpyDeviceToHost, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(io->imports + i0 * P * P, b.imports, (size_t)(m * P * P) * 8, hipMemcpyDeviceToHost, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(io->into + i0 * P * VGX_IN_INTO, b.into, (size_t)(m * P * VGX_IN_INTO) * 8, hipMemcpyDeviceToHost, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(io->spectrum + i0 * P * VGX_IN_BINS, b.spectrum, (size_t)(m * P * VGX_IN_BINS) * 8, hipMemcpyDeviceToHost, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(io->stats + i0 * VGX_IN_STATS, b.stats, (size_t)m * VGX_IN_STATS * 8, hipMemcpyDeviceToHost, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(st2.data(), b.status, (size_t)m * 16, hipMemcpyDeviceToHost, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(res.data(), a.res, (size_t)m * 40, hipMemcpyDeviceToHost, e->stream));
+        HIPCHECK(e, hipMemcpyAsync(io->rng_out + i0 * 4, a.rng_out, (size_t)m * 32, hipMemcpyDeviceToHost, e->stream));
+        // the one synchronisation of a pass: before anything reads the rows
+        if ((er = hipStreamSynchronize(e->stream)) != hipSuccess) return fail(e, VGX_ERR_HIP, me + "walk or lineage kernel failed: " + hipGetErrorString(er));
+        float kms = 0.f;
+        for (int k = 0; k < 2; k++) {
+            HIPCHECK(e, hipEventElapsedTime(&kms, tm.ev[k], tm.ev[k + 1]));
+            io->ms[k] += kms;
+        }
+        for (int64_t j = 0; j < m; j++) {
+            // (a walk that stopped keeps its status: the kernel copies it; a walk that used more nodes than its samples allow cannot be)
+            const int64_t nodes = dp[(size_t)j].sCounter >= 2 ? 2 * dp[(size_t)j].sCounter - 1 : 0;
+            if (res[(size_t)(j * 5)] == VGX_GW_OK && res[(size_t)(j * 5 + 2)] > nodes)
+                return fail(e, VGX_ERR_ARG, me + "replicate " + std::to_string(dp[(size_t)j].rep) + ": the walk reports more nodes than its samples give");
             io->status[i0 + j] = st2[(size_t)(2 * j)];
             io->status_arg[i0 + j] = st2[(size_t)(2 * j + 1)];
         }

@@ -26,6 +26,7 @@
 #include "vgx_tree_events.h"
 #include "vgx_tree_shape.h"
 #include "vgx_mutation_spectrum.h"
+#include "vgx_introductions.h"
 #include "vgx_logfact.h"
 #include "vgx_rng.h"
 
@@ -412,6 +413,8 @@ static std::string walk_message(int64_t status, int64_t arg) {
     case VGX_GW_BAD_RECORD:
         return "vgx_get_mutation_spectrum: mutation record " + std::to_string(arg) + " lies outside the tree or the model (mut_node in [0, nodes), " +
                "mut_site in [0, sites), mut_AS and mut_DS in 0 .. 3)";
+    case VGX_GW_BAD_LABEL:
+        return "vgx_get_introductions: the label of node " + std::to_string(arg) + " lies outside the model (tree_pop in [0, populations))";
     default: return "vgx_get_genealogy: walk status " + std::to_string(status);
     }
 }
@@ -653,5 +656,31 @@ extern "C" int vgx_test_mutation_spectrum(const int32_t *tree, int64_t nodes, co
                     std::to_string(mut_DS[arg]) + ", site " + std::to_string(mut_site[arg]) + ") lies outside the tree of " + std::to_string(nodes) +
                     " nodes or the model of " + std::to_string(sites) + " sites");
     if (clade) std::copy(w.clade, w.clade + N, clade);
+    return VGX_OK;
+}
+
+// ---- the introductions of one tree (vgx_introductions.h) -----------------------------------------------------------
+extern "C" int vgx_test_introductions(const int32_t *tree, const int32_t *pop, int64_t nodes, int64_t pops, int64_t *tips_by_pop, int64_t *imports,
+                                      int64_t *into, int64_t *spectrum, int64_t *stats, int32_t *clade, int32_t *local, char *errbuf, int64_t errcap) {
+    auto fail = [&](const std::string &m) {
+        if (errbuf && errcap > 0) std::snprintf(errbuf, (size_t)errcap, "%s", m.c_str());
+        return VGX_ERR_ARG;
+    };
+    const std::string me = "vgx_test_introductions: ";
+    if (!tree || !pop || !tips_by_pop || !imports || !into || !spectrum || !stats) return fail(me + "null argument");
+    if (pops < 1 || pops > VGX_IN_POPS_MAX) return fail(me + "populations = " + std::to_string(pops) + " (1 .. " + std::to_string(VGX_IN_POPS_MAX) + ")");
+    const int64_t bad = vgx_ts_check_parents(tree, nodes);
+    if (bad == nodes) return fail(me + std::to_string(nodes) + " nodes: an odd number, at least 3 (node " + std::to_string(nodes) + ")");
+    if (bad >= 0)
+        return fail(me + "the parent of node " + std::to_string(bad) + " is " + std::to_string(tree[bad]) + " (a higher id inside the tree, -1 at the last node)");
+    const size_t N = (size_t)nodes;
+    std::vector<int32_t> w32(4 * N);
+    const VgxInWork w{w32.data(), w32.data() + N, w32.data() + 2 * N, w32.data() + 3 * N};
+    int64_t arg = 0;
+    const int st = vgx_in_sweep(tree, pop, nodes, pops, w, clade, local, tips_by_pop, imports, into, spectrum, stats, &arg);
+    if (st == VGX_GW_BAD_TREE) return fail(me + "node " + std::to_string(arg) + " has " + std::to_string(w.kids[arg]) + " children (none or two)");
+    if (st == VGX_GW_BAD_LABEL)
+        return fail(me + "the label of node " + std::to_string(arg) + " is " + std::to_string(pop[arg]) + ", outside the model of " + std::to_string(pops) +
+                    " populations");
     return VGX_OK;
 }

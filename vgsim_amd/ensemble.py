@@ -591,6 +591,99 @@ class MutationSpectrum:
             return self._ratio(d, np.sqrt(np.where(good, var, 1.0)), where=good & np.isfinite(d))
 
 
+class Introductions:
+    """What ``Ensemble.introductions`` returns: the population labels of every selected replicate's sampled tree reduced to its
+    transmission lineages: how many introductions every population received, from where, and how large the lineage is that each
+    one seeded.
+
+    The branch above a node crosses when the node's population differs from its parent's: it is then one NET introduction from
+    the parent's population (src) into the node's (dst).  Moves along a branch that left no node are invisible: a lineage that went
+    0 -> 2 -> 1 between two nodes counts as 0 -> 1, one that went 0 -> 1 -> 0 does not count.  The root and every node below a
+    crossing branch head a transmission lineage; its size (``local``) is the number of tips reached from it without passing another
+    crossing branch, possibly 0; every tip lies in exactly one lineage.  With ``pops`` = P: ``tips_by_pop`` [n, P] int64;
+    ``imports`` [n, P, P] indexed ``[r, src, dst]``; ``into`` [n, P, 6] per destination over its introductions in the order of
+    ``INTO``: ``count``, ``clade_sum`` (all tips below), ``local_sum``, ``local_sumsq``, ``empty`` (size 0), ``max_local``;
+    ``spectrum`` [n, P, 32], introductions into dst with ``floor(log2 local) == b`` (the empty ones are in ``into`` alone);
+    ``stats`` [n, 8] in the order of ``STATS``, each column also an attribute: ``tips``, ``introductions``, ``root_pop``,
+    ``root_local``, ``max_local`` (the root's lineage included), ``max_clade``, ``empty``, ``pops_with_tips``.  All exact integers:
+    the same bits on every path.  ``replicates`` [n]; ``status``, ``status_arg``, ``ok``, ``message(i)``, ``rng_raw`` as
+    :class:`GenealogyBatch`: the row of a replicate whose walk failed holds zeros, and the ratios are NaN there and wherever a
+    denominator is 0.  ``passes``, ``kernel_ms`` (walk, lineages), ``wall_ms``."""
+
+    INTO = _capi.INTRODUCTIONS_INTO
+    STATS = _capi.INTRODUCTIONS_STATS
+    BINS = _capi.INTRODUCTIONS_BINS
+
+    def __getattr__(self, name):   # one attribute per column of stats
+        if name in Introductions.STATS:
+            return self.stats[:, Introductions.STATS.index(name)]
+        raise AttributeError(name)
+
+    @property
+    def ok(self):
+        return self.status == 0
+
+    def message(self, i):
+        """Text of row i's status: what ``Ensemble.genealogy`` raises for that replicate ('' when its walk succeeded)."""
+        return _capi.genealogy_message(int(self.status[i]), int(self.status_arg[i]))
+
+    def _ratio(self, num, den):   # [n, P] / [n, P]: one float64 division per cell
+        num, den = np.asarray(num, dtype=np.float64), np.asarray(den, dtype=np.float64)
+        ok = np.broadcast_to(self.ok[:, None], num.shape) & (den != 0)
+        out = np.full(num.shape, np.nan, dtype=np.float64)
+        np.divide(num, den, out=out, where=ok)
+        return out
+
+    @staticmethod
+    def bin_edges():
+        """The lower edges of the 32 bins, ``2 ** b``: bin b holds the lineage sizes ``2 ** b <= local < 2 ** (b + 1)``."""
+        return 2 ** np.arange(Introductions.BINS, dtype=np.int64)
+
+    def imports_into(self):
+        """Introductions every population received, int64 [n, P]: ``imports`` summed over src (= ``into[:, :, 0]``)."""
+        return self.imports.sum(axis=1)
+
+    def exports_from(self):
+        """Introductions every population seeded elsewhere, int64 [n, P]: ``imports`` summed over dst."""
+        return self.imports.sum(axis=2)
+
+    def net_flow(self):
+        """``imports_into() - exports_from()``, int64 [n, P]."""
+        return self.imports_into() - self.exports_from()
+
+    def lineages(self):
+        """Transmission lineages per population, int64 [n, P]: its introductions and, in the root's population, the root's
+        lineage; zeros for a replicate that is not ok."""
+        out = self.into[:, :, 0].copy()
+        rows = np.nonzero(self.ok)[0]
+        out[rows, self.root_pop[rows]] += 1
+        return out
+
+    def mean_lineage_size(self):
+        """``local_sum / count`` per destination, [n, P]: the mean size of the lineages its introductions seeded."""
+        return self._ratio(self.into[:, :, 2], self.into[:, :, 0])
+
+    def size_weighted_mean(self):
+        """``local_sumsq / local_sum`` per destination, [n, P]: the size of the introduced lineage a random introduced tip lies in."""
+        return self._ratio(self.into[:, :, 3], self.into[:, :, 2])
+
+    def singleton_share(self):
+        """``spectrum[:, :, 0] / count`` per destination, [n, P]: introductions that seeded one sampled tip."""
+        return self._ratio(self.spectrum[:, :, 0], self.into[:, :, 0])
+
+    def empty_share(self):
+        """``empty / count`` per destination, [n, P]: introductions all of whose tips lie behind further crossings."""
+        return self._ratio(self.into[:, :, 4], self.into[:, :, 0])
+
+    def observed_share(self, flows):
+        """Tree introductions over the true cross-population infections per destination, [n, P]: ``imports_into()`` over
+        ``flows.imports()`` (a :class:`Flows` of the same replicates in the same order) summed over its bins and variant classes,
+        so the classes should cover every haplotype and the bins the whole run for the ratio to mean the sampled share."""
+        if not np.array_equal(np.asarray(flows.replicates), np.asarray(self.replicates)):
+            raise ValueError("observed_share() needs the Flows of the same replicates in the same order")
+        return self._ratio(self.imports_into(), flows.imports().sum(axis=(1, 3), dtype=np.int64))
+
+
 class Susceptibles:
     """What ``Ensemble.susceptibles`` returns: susceptible hosts per selected replicate, grid time, population and class of
     susceptibility groups.
@@ -1923,6 +2016,99 @@ class Ensemble:
         ms.passes, ms.kernel_ms = int(io.passes), (io.kernel_ms[0] + io.kernel_ms[1], io.kernel_ms[2])
         ms.host_ms, ms.wall_ms = io.ms[1], io.ms[2]
         return ms
+
+    def _introduction_blocks(self, io, n, reps, rng, words):
+        """The output blocks of an Introductions behind ``io`` (either of the two io structs); returns (it, per, rng_out)."""
+        P = int(self.engine.dims.popNum)
+        it = Introductions()
+        it.replicates, it.pops = reps.copy(), P
+        it.tips_by_pop, it.imports, it.into, it.spectrum, it.stats = _capi._introductions_blocks(max(n, 1), P)
+        per = {k: np.zeros(max(n, 1), dtype=np.int64) for k in ("status", "status_arg")}
+        rng_out = np.zeros((max(n, 1), words), dtype=np.uint64)
+        u64 = C.POINTER(C.c_uint64)
+        io.n, io.replicates, io.rng_state = n, _capi._p(reps), rng.ctypes.data_as(u64)
+        io.tips_by_pop, io.imports, io.into = _capi._p(it.tips_by_pop), _capi._p(it.imports), _capi._p(it.into)
+        io.spectrum, io.stats = _capi._p(it.spectrum), _capi._p(it.stats)
+        io.status, io.status_arg, io.rng_out = _capi._p(per["status"]), _capi._p(per["status_arg"]), rng_out.ctypes.data_as(u64)
+        return it, per, rng_out
+
+    @staticmethod
+    def _introduction_rows(it, per, n):
+        it.tips_by_pop, it.imports, it.into, it.spectrum, it.stats = it.tips_by_pop[:n], it.imports[:n], it.into[:n], it.spectrum[:n], it.stats[:n]
+        it.status, it.status_arg = per["status"][:n], per["status_arg"][:n]
+
+    def introductions(self, seed=None, replicates=None):
+        """The transmission lineages of every selected replicate's sampled tree after the last direct
+        ``simulate(record_events=True)`` call, on the device (``vgx_get_introductions``): the walk of
+        ``genealogies(seed, replicates)`` with the same draws, status and generator afterwards, then one kernel that counts, below
+        every node, all tips and the tips reached without a change of population, and bins every branch whose two ends differ in
+        population as one net introduction.  No node time is needed, so no host clock runs: only the rows cross to the host.
+        Returns an :class:`Introductions`, whose rows are what the ``tree`` and ``tree_pop`` of ``genealogies(seed).replicate(r)``
+        give.
+
+        ``seed`` and ``replicates`` as ``genealogies()``.  A replicate whose walk fails (fewer than two samples, lineages that never
+        coalesce, ...) gets its status and zeros and does not fail the call.  Direct chains only; at most 1024 populations."""
+        if self._last_call is None:
+            raise ValueError("introductions() needs a direct simulate(record_events=True) call first")
+        if self._last_call[0] != 'direct':
+            raise ValueError("introductions() walks direct chains only: the last call was simulate_tau")
+        if not self._last_call[1]:
+            raise ValueError("introductions() needs the event log: the last call had record_events=False")
+        eng = self.engine
+        reps = np.arange(self.R, dtype=np.int64) if replicates is None else np.ascontiguousarray(replicates, dtype=np.int64).ravel()
+        n = len(reps)
+        if n and (reps.min() < 0 or reps.max() >= self.R):
+            raise ValueError("replicate index out of range")
+        if len(np.unique(reps)) != n:
+            raise ValueError("replicates must be distinct")
+        counters = [eng.counters(int(r)) for r in reps]
+        for r, c in zip(reps, counters):
+            if c.ev_first_new != 0:
+                raise ValueError("replicate %d: its chain does not start in the last call's device log (the model held %d events "
+                                 "when the ensemble started)" % (r, c.ev_first_new))
+        rng = self._walk_starts(reps, counters, seed)
+        io = _capi.VgxIntroductionsIO()
+        it, per, rng_out = self._introduction_blocks(io, n, reps, rng, 4)
+        eng._check(eng.lib.vgx_get_introductions(eng.handle, C.byref(io)))
+        self._introduction_rows(it, per, n)
+        it.rng_raw = np.zeros((n, 6), dtype=np.uint64)
+        it.rng_raw[:, :4] = rng_out[:n]
+        it.passes, it.kernel_ms, it.wall_ms = int(io.passes), (io.ms[0], io.ms[1]), io.ms[2]
+        return it
+
+    def tau_introductions(self, seed=None, replicates=None):
+        """``introductions()`` for the replicates of the last ``simulate_tau(record_events=True)`` call
+        (``vgx_get_tau_introductions``): the walk of ``tau_genealogies(seed, replicates)`` over the same chain with the same draws,
+        status and six generator words afterwards, then the lineage kernel of ``introductions()``; nothing of a tree or a label
+        crosses to the host.  Returns an :class:`Introductions` whose rows are what the ``tree`` and ``tree_pop`` of
+        ``tau_genealogies(seed).replicate(r)`` give.
+
+        ``seed`` and ``replicates`` as ``tau_genealogies()``.  A replicate whose walk fails gets its status and zeros and does not
+        fail the call.  ``kernel_ms``: (canonicalise + walk, lineages); ``stage_ms``: the three kernels apart; ``host_ms``: the
+        host's descriptors."""
+        self._check_tau_genealogy_call("tau_introductions()")
+        eng, lib = self.engine, self.engine.lib
+        reps = self._selected_replicates(replicates)
+        n = len(reps)
+        if seed is not None and not np.isscalar(seed):
+            seeds = np.ascontiguousarray(seed, dtype=np.int64).ravel()
+            if len(seeds) != n:
+                raise ValueError("one seed per selected replicate: got %d for %d" % (len(seeds), n))
+        rng = np.zeros((max(n, 1), 6), dtype=np.uint64)
+        pos = (C.c_uint64 * 4)()
+        for i, r in enumerate(reps):
+            lib.vgx_rng_position(int(self.seeds[r]) if seed is None else int(seed) if np.isscalar(seed) else int(seeds[i]), 0, 0, C.byref(pos))
+            rng[i, :4] = list(pos)
+        pre = self._tau_genealogy_prefix_struct()
+        io = _capi.VgxTauIntroductionsIO()
+        it, per, rng_out = self._introduction_blocks(io, n, reps, rng, 6)
+        eng._check(lib.vgx_get_tau_introductions(eng.handle, C.byref(io), C.byref(pre)))
+        self._introduction_rows(it, per, n)
+        it.rng_raw = rng_out[:n]
+        it.stage_ms = tuple(io.kernel_ms)
+        it.passes, it.kernel_ms = int(io.passes), (io.kernel_ms[0] + io.kernel_ms[1], io.kernel_ms[2])
+        it.host_ms, it.wall_ms = io.ms[1], io.ms[2]
+        return it
 
     def milestones(self, variants=None, thresholds=(), replicates=None):
         """Peaks, first passages and extinctions of every selected replicate of the last direct ``simulate(record_events=True)``
